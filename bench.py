@@ -8,7 +8,10 @@ uniform hex cells in blockMesh numbering, all six patches zeroGradient, fvsc Gau
 step (one cell plane + its patch faces per neighbour).
 
 A step = one pass of the QGDFoam loop body (flux assembly + cell update + BC refresh), inputs resident in HBM.
-Prints ONE JSON line on rank 0.  Beside the contract's keys the line carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the configuration, `setup_s`, `min_rho`); --dump-outputs DIR also writes the cell fields the last
+timed step left (dump_outputs).  With --full the line also carries `roofline`, `other_kernels` and `kernels_ms_avg` (from a second pass with
+per-launch events) and
   N = 1: `secondary` {qhd_n200, qhd_implicit_n200, implicit_n200, qhd_c5} -- the QHDFoam step (both branches of implicitDiffusion), QGDFoam's
          implicitDiffusion step at 200^3 and the QHDFoam step on BASELINE config 5's 16 M-cell irregular mesh, 20 timed steps each, as
          child processes after the headline (--no-secondary skips them; skipped by themselves under a profiler), `dropin_fvsc`,
@@ -56,6 +59,10 @@ FUSED_BYTES_PER_POINT = 100
 STEP_BYTES_PER_CELL = 1084
 POINT_BYTES_PER_CELL = 196
 CELL_BYTES_PER_CELL = 240
+# --dump-outputs: seven float64 components per cell (rho, U, p, T, e) for at most this many cells keep the files under 32 MB
+DUMP_FIELDS = ("rho", "U", "p", "T", "e")
+DUMP_MAX_CELLS = 500_000
+DUMP_SEED = 2024
 
 
 def parse():
@@ -90,6 +97,13 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=24)
     ap.add_argument("--cpu-only", action="store_true", help="only time the CPU baseline (no GPU needed) and print it")
     ap.add_argument("--cpu-ranks", type=int, default=0, help="CPU-baseline ranks (0 = one per physical core, at most 128)")
+    ap.add_argument("--full", action="store_true",
+                    help="qgd workload: everything beside the headline as well -- per-kernel times and the roofline (a second pass of "
+                         "min(steps, 20) steps with HIP events), the secondary workloads, the fvsc drop-in line, the CPU baseline and, N > 1, "
+                         "the native-transport line (the --no-* switches still leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="qgd workload, one GPU: after the timed steps write the cell fields the last timed step left (rho, U, p, T, e) as "
+                         f"DIR/<name>.npy, float64; boxes of more than {DUMP_MAX_CELLS} cells are sampled at a fixed, seeded set of cells")
     return ap.parse_args()
 
 
@@ -326,6 +340,37 @@ def qgd_env():
     """every QGD_* variable set in this process's environment: they select code paths inside the library and the bench, so the line
     records them (a stray variable on the GPU box would otherwise change what is measured without a trace)"""
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith("QGD_")}
+
+
+def initial_U_p(box_initial_fields, C):
+    """U and p of box_initial_fields on the cell centres C, computed on slices of the cells in threads (numpy releases the GIL): every
+    value is a function of its own cell's centre alone, so the result is the one call's bit for bit.  The slices' T is not used: the
+    caller draws T from the global cell labels."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    U, p = np.empty_like(C), np.empty(C.shape[0])
+    parts = max(1, min(int(os.environ.get("OMP_NUM_THREADS") or 0) or host_cpu_quota(), host_cpu_quota(), C.shape[0] // 65536))
+    bounds = [C.shape[0] * i // parts for i in range(parts + 1)]
+
+    def one(i):
+        a, b = bounds[i], bounds[i + 1]
+        U[a:b], _, p[a:b] = box_initial_fields(C[a:b])
+
+    with ThreadPoolExecutor(parts) as ex:
+        list(ex.map(one, range(parts)))
+    return U, p
+
+
+def dump_outputs(case, n_cells, out_dir):
+    """--dump-outputs: the cell fields the last timed step left, as a caller of the step reads them back (QGDFoamCase.field), float64.
+    Beyond DUMP_MAX_CELLS cells, a fixed sample: the same sorted set of cell labels, drawn with DUMP_SEED, on every run of the same box."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    if n_cells > DUMP_MAX_CELLS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_cells, size=DUMP_MAX_CELLS, replace=False))
+    for name in DUMP_FIELDS:
+        a = case.field(name)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a if idx is None else a[idx], dtype=np.float64))
 
 
 def bench_deadline_s():
@@ -930,6 +975,9 @@ def qhd_line_sharded(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.workload != "qgd" or args.gpus != 1):
+        print("bench.py: --dump-outputs writes the fields of the one-GPU qgd workload only", file=sys.stderr)
+        sys.exit(2)
     if args.workload == "implicit":
         if "QGD_BENCH_N" not in os.environ and "--edge" not in " ".join(sys.argv):
             args.n = 200
@@ -1015,7 +1063,13 @@ def main():
     opt = q.default_options(stencil="GaussVolPoint", deltaT=0.1 * h / 1.3)  # fixed deltaT = 0.1 h / (c+|U|)_max
     case = q.QGDFoamCase(dev, opt)
     C = mesh.array("C").reshape(-1, 3)
-    U, T, p = box_initial_fields(C)
+    n_if, n_c, n_p = mesh.nInternalFaces, mesh.nCells, mesh.nPoints
+    # the device no longer needs the host mesh (tens of GB at 400^3): it is released in the background (the library releases the GIL)
+    # while the initial fields are drawn and the device finishes its set-up
+    import threading
+    closing = threading.Thread(target=mesh.close)
+    closing.start()
+    U, p = initial_U_p(box_initial_fields, C)
     # the noise must be a function of the GLOBAL cell label so that shards agree with the unsharded run
     rng = np.random.Generator(np.random.MT19937(12345))
     noise = rng.uniform(-1e-3, 1e-3, size=n * n * n)
@@ -1024,10 +1078,9 @@ def main():
     case.set_fields(U, T, p)
     init_fields = (U, T, p) if world > 1 else None
     del U, T, p, C
-    n_if, n_c, n_p = mesh.nInternalFaces, mesh.nCells, mesh.nPoints
-    mesh.close()
     stream = torch.cuda.current_stream()
     case.set_stream(stream.cuda_stream)
+    closing.join()
     t_setup = time.perf_counter() - t_setup
 
     # one RCCL send/recv pair per neighbour per step; buffers live in HBM, pack/unpack run on the same stream
@@ -1135,7 +1188,7 @@ def main():
     init_fields = None
     for _ in range(args.warmup):
         step()
-    case.timing(False)  # the headline runs without per-launch events; kernel times come from a second pass below
+    case.timing(False)  # the headline runs without per-launch events; with --full, kernel times come from a second pass below
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -1160,21 +1213,8 @@ def main():
             dist.all_reduce(cs, op=dist.ReduceOp.SUM)
         checksum = [float(x) for x in cs]
 
-    # second pass, not part of the headline: HIP events around every launch on the kernels' own stream
-    case.timing(True)
-    case.timing_reset()
-    for _ in range(min(args.steps, 20)):
-        step()
-    torch.cuda.synchronize()
-    kt = {}
-    for name, k in (("point", L.K_POINT), ("bpoint", L.K_BPOINT), ("face", L.K_FACE), ("bface", L.K_BFACE), ("cell", L.K_CELL),
-                    ("bc", L.K_BC)):
-        ms, cnt = case.kernel_time(k)
-        kt[name] = {"ms_total": ms, "launches": cnt, "ms_avg": (ms / cnt if cnt else None)}
-    info = case.info()
-    face_bytes = FACE_BYTES_PER_FACE * n_if + FACE_BYTES_PER_CELL * n_c + FACE_BYTES_PER_POINT * n_p
-    face_ms = kt["face"]["ms_avg"]
-    ft = dev.face_tiles()
+    if args.dump_outputs:
+        dump_outputs(case, n_c, args.dump_outputs)
     fused = case.fused_info()
     if fused["fused"]:
         fused["mean_cells_per_block"] = owned_cells / fused["blocks"]
@@ -1193,35 +1233,51 @@ def main():
                      "mean_cells_per_block": (float(e[2]) / float(e[0])) if float(e[0]) else None, "setup_s": float(e[3]),
                      "faces_computed_per_cell": float(e[4]) / float(e[2]), "cell_records_staged_per_cell": float(e[5]) / float(e[2])}
                     for e in (x.cpu() for x in every)]
-    if fused["fused"] and kt["face"]["launches"]:
-        # per STEP: on a shard the fused kernel runs as two launches (the boundary-layer blocks, then the rest)
-        face_ms = kt["face"]["ms_total"] / min(args.steps, 20)
-    unfused_bytes = None
-    if fused["fused"]:
-        # ONE launch does the work of all three rows of SURVEY 8(d) -- vertex interpolation (P), face kernel (F), cell update (C).  Its
-        # ALGORITHMIC bytes are those rows' bytes WITHOUT what the rows hand each other through HBM, because that is exactly what the fusion
-        # removes and never moves: F: 144 B per face in (its 40 B of net fluxes stay in LDS) + every cell record once 48 B; P: 8 weights 64 +
-        # 8 labels 32 + offset 4 = 100 B per vertex (the cell records are the ones F counts; the 48 B vertex record is neither written nor read
-        # back); C: face ids + signs 24 + V 8 + 5 old conserved 40 + 6 primitives written 48 = 120 B per cell (the 120 B of fluxes come out of LDS).
-        # 3 x 144 + 48 + 100 + 120 = 700 B per cell-step on a hex box; the three-kernel figure (1084 B, rounds 1-5's `achieved`) stays beside
-        # it as `equivalent_unfused_*`: how fast the STEP is against the reference's own data flow at 8 TB/s -- not a statement about HBM.
-        unfused_bytes = face_bytes + (CELL_BYTES_PER_CELL + POINT_BYTES_PER_CELL) * n_c
-        face_bytes = FUSED_BYTES_PER_FACE * n_if + FUSED_BYTES_PER_CELL * n_c + FUSED_BYTES_PER_POINT * n_p
-        face_kernel_name = (f"fusedFaceCellKernel ({fused['blocks']} blocks of <= 128 cells; {fused['facesComputed']} faces computed for "
-                            f"{n_if} internal faces, {fused['verticesFormed']} vertex values formed for {n_p} vertices; vertex values, faces and "
-                            "cell update are ONE launch)")
-        # its own compulsory bytes, from what its blocks stage: per computed face 16 B of block list + weight 8 + hQGDf 8 + kind 1; per staged
-        # cell RecA 48 + label 4, for own cells and cells across a face also RecB 32 + centre 24; per own cell rhoE 8 + V 8 + hQGD 8 read,
-        # 88 + 8 written, 25 B of face entries; per vertex formed 8 positions 16 + 8 weights 64 + count 1 + label 4 + coordinates 24
-        # round 6: the per-face positions (12 B), the own cells' face entries (25 B per cell) and the vertices' cell positions (16 B) come out of the
-        # block's TEMPLATE, which blocks that are alike share (L2-resident on a structured mesh): counted once per template, not per block
-        own_bytes = (21 * fused["facesComputed"] + 52 * fused["cellsStaged"] + 56 * fused["cellsStagedFull"] + 120 * n_c +
-                     93 * fused["verticesFormed"] + fb["templateBytes"] * fb["templates"])
-    else:
-        face_kernel_name = (f"faceFluxGvp3TileKernel<{ft['facesPerTile']}> (+ faceFluxGvp3Kernel on {ft['gatherTiles']} of {ft['tiles']} tiles; "
-                            "avg_launch_ms covers both launches)") if ft["facesPerTile"] else "faceFluxGvp3Kernel"
-        own_bytes = OWN_BYTES_PER_FACE * n_if + OWN_BYTES_PER_CELL * n_c + OWN_BYTES_PER_POINT * n_p
-    achieved = face_bytes / (face_ms * 1e-3) / 1e9 if face_ms else None
+    if args.full:
+        # --full: a second pass, not part of the headline: HIP events around every launch on the kernels' own stream
+        case.timing(True)
+        case.timing_reset()
+        for _ in range(min(args.steps, 20)):
+            step()
+        torch.cuda.synchronize()
+        kt = {}
+        for name, k in (("point", L.K_POINT), ("bpoint", L.K_BPOINT), ("face", L.K_FACE), ("bface", L.K_BFACE), ("cell", L.K_CELL),
+                        ("bc", L.K_BC)):
+            ms, cnt = case.kernel_time(k)
+            kt[name] = {"ms_total": ms, "launches": cnt, "ms_avg": (ms / cnt if cnt else None)}
+        face_bytes = FACE_BYTES_PER_FACE * n_if + FACE_BYTES_PER_CELL * n_c + FACE_BYTES_PER_POINT * n_p
+        face_ms = kt["face"]["ms_avg"]
+        ft = dev.face_tiles()
+        if fused["fused"] and kt["face"]["launches"]:
+            # per STEP: on a shard the fused kernel runs as two launches (the boundary-layer blocks, then the rest)
+            face_ms = kt["face"]["ms_total"] / min(args.steps, 20)
+        unfused_bytes = None
+        if fused["fused"]:
+            # ONE launch does the work of all three rows of SURVEY 8(d) -- vertex interpolation (P), face kernel (F), cell update (C).  Its
+            # ALGORITHMIC bytes are those rows' bytes WITHOUT what the rows hand each other through HBM, because that is exactly what the fusion
+            # removes and never moves: F: 144 B per face in (its 40 B of net fluxes stay in LDS) + every cell record once 48 B; P: 8 weights 64 +
+            # 8 labels 32 + offset 4 = 100 B per vertex (the cell records are the ones F counts; the 48 B vertex record is neither written nor read
+            # back); C: face ids + signs 24 + V 8 + 5 old conserved 40 + 6 primitives written 48 = 120 B per cell (the 120 B of fluxes come out of LDS).
+            # 3 x 144 + 48 + 100 + 120 = 700 B per cell-step on a hex box; the three-kernel figure (1084 B, rounds 1-5's `achieved`) stays beside
+            # it as `equivalent_unfused_*`: how fast the STEP is against the reference's own data flow at 8 TB/s -- not a statement about HBM.
+            unfused_bytes = face_bytes + (CELL_BYTES_PER_CELL + POINT_BYTES_PER_CELL) * n_c
+            face_bytes = FUSED_BYTES_PER_FACE * n_if + FUSED_BYTES_PER_CELL * n_c + FUSED_BYTES_PER_POINT * n_p
+            face_kernel_name = (f"fusedFaceCellKernel ({fused['blocks']} blocks of <= 128 cells; {fused['facesComputed']} faces computed for "
+                                f"{n_if} internal faces, {fused['verticesFormed']} vertex values formed for {n_p} vertices; vertex values, faces and "
+                                "cell update are ONE launch)")
+            # its own compulsory bytes, from what its blocks stage: per computed face 16 B of block list + weight 8 + hQGDf 8 + kind 1; per staged
+            # cell RecA 48 + label 4, for own cells and cells across a face also RecB 32 + centre 24; per own cell rhoE 8 + V 8 + hQGD 8 read,
+            # 88 + 8 written, 25 B of face entries; per vertex formed 8 positions 16 + 8 weights 64 + count 1 + label 4 + coordinates 24
+            # round 6: the per-face positions (12 B), the own cells' face entries (25 B per cell) and the vertices' cell positions (16 B) come out of the
+            # block's TEMPLATE, which blocks that are alike share (L2-resident on a structured mesh): counted once per template, not per block
+            own_bytes = (21 * fused["facesComputed"] + 52 * fused["cellsStaged"] + 56 * fused["cellsStagedFull"] + 120 * n_c +
+                         93 * fused["verticesFormed"] + fb["templateBytes"] * fb["templates"])
+        else:
+            face_kernel_name = (f"faceFluxGvp3TileKernel<{ft['facesPerTile']}> (+ faceFluxGvp3Kernel on {ft['gatherTiles']} of {ft['tiles']} tiles; "
+                                "avg_launch_ms covers both launches)") if ft["facesPerTile"] else "faceFluxGvp3Kernel"
+            own_bytes = OWN_BYTES_PER_FACE * n_if + OWN_BYTES_PER_CELL * n_c + OWN_BYTES_PER_POINT * n_p
+        achieved = face_bytes / (face_ms * 1e-3) / 1e9 if face_ms else None
+    info = case.info()
 
     if rank == 0:
         total_cells = n ** 3
@@ -1257,7 +1313,18 @@ def main():
                 "fused_step": fused if fused["fused"] else False,
                 "env": qgd_env(),
             },
-            "roofline": {
+            "step_roofline_frac": STEP_BYTES_PER_CELL * owned_cells * args.steps / elapsed / (HBM_PEAK_GBS * 1e9),
+            "device_bytes": case.device_bytes(),
+            "setup_s": t_setup if per_rank is None else max(r["setup_s"] for r in per_rank),   # N > 1: the slowest rank's (they share the host's cores)
+            "per_rank": per_rank,
+            "min_rho": info["minRho"],
+        }
+        if checksum is not None:
+            out["checksum_rho"] = checksum
+        if selfcheck is not None:
+            out["overlap_selfcheck_rel"] = selfcheck
+        if args.full:
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": face_kernel_name + " (rank 0 shard)",
                 "achieved": achieved,
@@ -1274,46 +1341,36 @@ def main():
                 "equivalent_unfused_bytes_per_launch": unfused_bytes,
                 "equivalent_unfused_frac": (unfused_bytes / (face_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (unfused_bytes and face_ms) else None,
                 "moved_frac": None,   # traffic / avg_launch_ms / peak: filled in below when counters of this workload exist
-            },
-            "other_kernels": {
+            }
+            out["other_kernels"] = {
                 "pointInterpRecKernel": {"algorithmic_bytes_per_launch": POINT_BYTES_PER_CELL * n_c, "avg_launch_ms": kt["point"]["ms_avg"],
                                          "frac": (POINT_BYTES_PER_CELL * n_c / (kt["point"]["ms_avg"] * 1e-3) / 1e9 / HBM_PEAK_GBS)
                                          if kt["point"]["ms_avg"] else None},
                 "cellUpdateKernel": {"algorithmic_bytes_per_launch": CELL_BYTES_PER_CELL * n_c, "avg_launch_ms": kt["cell"]["ms_avg"],
                                      "frac": (CELL_BYTES_PER_CELL * n_c / (kt["cell"]["ms_avg"] * 1e-3) / 1e9 / HBM_PEAK_GBS)
                                      if kt["cell"]["ms_avg"] else None},
-            },
-            "step_roofline_frac": STEP_BYTES_PER_CELL * owned_cells * args.steps / elapsed / (HBM_PEAK_GBS * 1e9),
-            "kernels_ms_avg": {k: v["ms_avg"] for k, v in kt.items()},
-            "device_bytes": case.device_bytes(),
-            "setup_s": t_setup if per_rank is None else max(r["setup_s"] for r in per_rank),   # N > 1: the slowest rank's (they share the host's cores)
-            "per_rank": per_rank,
-            "min_rho": info["minRho"],
-        }
-        if checksum is not None:
-            out["checksum_rho"] = checksum
-        if selfcheck is not None:
-            out["overlap_selfcheck_rel"] = selfcheck
-        traffic_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(traffic_file):
-            try:
-                tr = json.load(open(traffic_file))
-                key = f"n{n}_gpus{world}"
-                if key in tr and ("fusedFaceCell" in tr[key].get("kernel", "")) == bool(fused["fused"]):   # counters of the kernel that ran
-                    out["roofline"]["traffic"] = tr[key]["bytes_per_launch"]
-                    out["roofline"]["traffic_source"] = tr[key].get("source")
-                    # a constant read from profiles/pmc_traffic.json (counters of the builder's profiling run of this
-                    # workload), not counters of THIS run
-                    out["roofline"]["traffic_is_static"] = True
-                    if face_ms:   # bytes the memory system really moved per launch (L2 <-> fabric) over the launch time, against the peak
-                        out["roofline"]["moved_frac"] = tr[key]["bytes_per_launch"] / (face_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                    # measured HBM-side bytes / algorithmic bytes, per kernel (1.0 = nothing fetched twice)
-                    out["roofline"]["kernel_traffic_ratio"] = {
-                        "face": tr[key]["bytes_per_launch"] / face_bytes,
-                        **{k: v / (b * n_c) for k, v, b in (("point", tr[key].get("point_bytes_per_launch"), POINT_BYTES_PER_CELL),
-                                                             ("cell", tr[key].get("cell_bytes_per_launch"), CELL_BYTES_PER_CELL)) if v}}
-            except Exception:
-                pass
+            }
+            out["kernels_ms_avg"] = {k: v["ms_avg"] for k, v in kt.items()}
+            traffic_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(traffic_file):
+                try:
+                    tr = json.load(open(traffic_file))
+                    key = f"n{n}_gpus{world}"
+                    if key in tr and ("fusedFaceCell" in tr[key].get("kernel", "")) == bool(fused["fused"]):   # counters of the kernel that ran
+                        out["roofline"]["traffic"] = tr[key]["bytes_per_launch"]
+                        out["roofline"]["traffic_source"] = tr[key].get("source")
+                        # a constant read from profiles/pmc_traffic.json (counters of the builder's profiling run of this
+                        # workload), not counters of THIS run
+                        out["roofline"]["traffic_is_static"] = True
+                        if face_ms:   # bytes the memory system really moved per launch (L2 <-> fabric) over the launch time, against the peak
+                            out["roofline"]["moved_frac"] = tr[key]["bytes_per_launch"] / (face_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                        # measured HBM-side bytes / algorithmic bytes, per kernel (1.0 = nothing fetched twice)
+                        out["roofline"]["kernel_traffic_ratio"] = {
+                            "face": tr[key]["bytes_per_launch"] / face_bytes,
+                            **{k: v / (b * n_c) for k, v, b in (("point", tr[key].get("point_bytes_per_launch"), POINT_BYTES_PER_CELL),
+                                                                 ("cell", tr[key].get("cell_bytes_per_launch"), CELL_BYTES_PER_CELL)) if v}}
+                except Exception:
+                    pass
     case.close()
     dev.close()
     if native:
@@ -1322,35 +1379,36 @@ def main():
         dist.barrier()
         dist.destroy_process_group()   # the other ranks leave now; rank 0 may still start the second set of ranks below
     if rank == 0:
-        if world > 1 and not native and not staged and not args.no_native_line and under_profiler():
-            out["native_transport"] = {"skipped": "a profiler's tool library is preloaded into this process tree"}
-        elif world > 1 and not native and not staged and not args.no_native_line:
-            left = bench_deadline_s() - (time.perf_counter() - T_START)
-            try:
-                out["native_transport"] = (native_transport_line(args, world, min(420.0, left - 30.0)) if left > 90.0
-                                           else {"error": "no time left before QGD_BENCH_DEADLINE_S"})
-            except Exception as e:   # the second set of ranks must never cost the first line
-                out["native_transport"] = {"error": repr(e)}
-        elif world > 1 and staged and not args.no_native_line:
-            out["native_transport"] = {"skipped": "gloo debugging mode: every rank sits on GPU 0 and RCCL refuses two ranks of one communicator on one device"}
-        # the headline is known from here on: say so on stderr before any child workload starts (stdout carries ONE line, at the end)
-        print(f"bench.py: headline {out['value']:.1f} {out['unit']}, {out['ms_per_step']:.3f} ms per step; secondary lines next", file=sys.stderr, flush=True)
-        if world == 1 and not args.no_secondary and args.workload == "qgd":
-            if under_profiler():
-                out["secondary"] = {"skipped": "a profiler's tool library is preloaded into this process tree: child workloads would run under it too"}
-            else:
+        if args.full:
+            if world > 1 and not native and not staged and not args.no_native_line and under_profiler():
+                out["native_transport"] = {"skipped": "a profiler's tool library is preloaded into this process tree"}
+            elif world > 1 and not native and not staged and not args.no_native_line:
+                left = bench_deadline_s() - (time.perf_counter() - T_START)
                 try:
-                    out["secondary"] = secondary_lines(args)
-                except Exception as e:
-                    out["secondary"] = {"error": repr(e)}
-        if world == 1 and not args.no_dropin:
-            try:
-                out["dropin_fvsc"] = dropin_fvsc_line(q, args.dropin_n, 3)
-            except Exception as e:  # the second line must never cost the headline
-                out["dropin_fvsc"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            ranks = args.cpu_ranks or cpu_rank_budget(args.cpu_n)
-            out["cpu_baseline"] = cpu_baseline(args.cpu_n, args.cpu_steps, ranks)
+                    out["native_transport"] = (native_transport_line(args, world, min(420.0, left - 30.0)) if left > 90.0
+                                               else {"error": "no time left before QGD_BENCH_DEADLINE_S"})
+                except Exception as e:   # the second set of ranks must never cost the first line
+                    out["native_transport"] = {"error": repr(e)}
+            elif world > 1 and staged and not args.no_native_line:
+                out["native_transport"] = {"skipped": "gloo debugging mode: every rank sits on GPU 0 and RCCL refuses two ranks of one communicator on one device"}
+            # the headline is known from here on: say so on stderr before any child workload starts (stdout carries ONE line, at the end)
+            print(f"bench.py: headline {out['value']:.1f} {out['unit']}, {out['ms_per_step']:.3f} ms per step; secondary lines next", file=sys.stderr, flush=True)
+            if world == 1 and not args.no_secondary and args.workload == "qgd":
+                if under_profiler():
+                    out["secondary"] = {"skipped": "a profiler's tool library is preloaded into this process tree: child workloads would run under it too"}
+                else:
+                    try:
+                        out["secondary"] = secondary_lines(args)
+                    except Exception as e:
+                        out["secondary"] = {"error": repr(e)}
+            if world == 1 and not args.no_dropin:
+                try:
+                    out["dropin_fvsc"] = dropin_fvsc_line(q, args.dropin_n, 3)
+                except Exception as e:  # the second line must never cost the headline
+                    out["dropin_fvsc"] = {"error": repr(e)}
+            if world == 1 and not args.no_cpu_baseline:
+                ranks = args.cpu_ranks or cpu_rank_budget(args.cpu_n)
+                out["cpu_baseline"] = cpu_baseline(args.cpu_n, args.cpu_steps, ranks)
         print(json.dumps(out), flush=True)
 
 

@@ -8,7 +8,7 @@ timeout 600 python scripts/fused_launch_shape_check.py 128 7 QGD_FU_OVERLAP 1 2>
 for N in 400 200; do
 for V in 0 1 0 1; do
   echo "== n $N QGD_FU_OVERLAP=$V" >> $OUT
-  QGD_FU_OVERLAP=$V timeout 400 python bench.py --edge $N --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
+  QGD_FU_OVERLAP=$V timeout 400 python bench.py --full --edge $N --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ OUT=gpurun_out/r06pf/ab2.txt
 : > $OUT
 for V in "QGD_X=0" "QGD_FU_ROTATE=1" "QGD_FU_ROTATE=2" "QGD_X=0" "QGD_FU_ROTATE=3" "QGD_FU_PREFETCH=64 QGD_FU_PREFETCH_RECORDS=32" "QGD_FU_PREFETCH=32 QGD_FU_PREFETCH_RECORDS=12" "QGD_X=0" "QGD_FU_ROTATE=1"; do
   echo "== $V" >> $OUT
-  env $V timeout 400 python bench.py --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
+  env $V timeout 400 python bench.py --full --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ OUT=gpurun_out/r06prev/ab.txt
 timeout 900 python -m pytest tests/test_fused_step_gpu.py tests/test_case_parity_gpu.py tests/test_golden.py -q -m gpu -x 2>&1 | tail -3 >> $OUT
 for V in "QGD_AMD_LIB=$PWD/ab_libs/libqgd_prev.so" "QGD_X=0" "QGD_AMD_LIB=$PWD/ab_libs/libqgd_prev.so" "QGD_X=0"; do
   echo "== $V" >> $OUT
-  env $V timeout 400 python bench.py --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
+  env $V timeout 400 python bench.py --full --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

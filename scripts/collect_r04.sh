@@ -23,5 +23,5 @@ done
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_qhd_implicit" -- python3 "$REPO/bench.py" --workload qhd --implicit-diffusion --steps 20 --warmup 5 > "$KEEP/r04_qhd_implicit_n200_bench_under_rocprof.log" 2>&1
 cp $(find "$OUT/stats_qhd_implicit" -name "*kernel_stats.csv" | head -1) "$KEEP/r04_qhd_implicit_n200_kernel_stats.csv"
 cd "$REPO"
-python3 bench.py > "$KEEP/r04_bench_default.json" 2> "$KEEP/bench_default.err"
+python3 bench.py --full > "$KEEP/r04_bench_default.json" 2> "$KEEP/bench_default.err"
 ls -la "$KEEP"; du -sh gpurun_out

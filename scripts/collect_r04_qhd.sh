@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$REPO"
 KEEP=$REPO/gpurun_out/r04_summaries2
 mkdir -p "$KEEP"
-python3 bench.py > "$KEEP/r04_bench_default.json" 2> "$KEEP/bench_default.err"
+python3 bench.py --full > "$KEEP/r04_bench_default.json" 2> "$KEEP/bench_default.err"
 python3 bench.py --workload qhd --irregular --steps 20 --warmup 5 > "$KEEP/r04_bench_qhd_c5.json" 2> "$KEEP/bench_c5.err"
 python3 bench.py --workload qhd --irregular --implicit-diffusion --steps 20 --warmup 5 > "$KEEP/r04_bench_qhd_c5_implicit.json" 2> "$KEEP/bench_c5i.err"
 cd /tmp && export TMPDIR=/tmp

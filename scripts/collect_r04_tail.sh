@@ -15,5 +15,5 @@ rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_implicit" --
 cp $(find "$OUT/stats_implicit" -name "*kernel_stats.csv" | head -1) "$KEEP/r04_implicit_n200_kernel_stats.csv"
 ls -la "$KEEP"
 cd "$REPO"
-python3 bench.py > "$KEEP/r04_bench_default.json" 2> "$KEEP/bench_default.err"
+python3 bench.py --full > "$KEEP/r04_bench_default.json" 2> "$KEEP/bench_default.err"
 ls -la "$KEEP"

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$REPO"
 KEEP=$REPO/gpurun_out/r05_summaries
 mkdir -p "$KEEP"
-python3 bench.py > "$KEEP/r05_bench_default.json" 2> "$KEEP/bench_default.err"
+python3 bench.py --full > "$KEEP/r05_bench_default.json" 2> "$KEEP/bench_default.err"
 python3 bench.py --workload implicit > "$KEEP/r05_bench_implicit_n200.json" 2> "$KEEP/bench_implicit.err"
 python3 bench.py --workload qhd > "$KEEP/r05_bench_qhd_n200.json" 2> "$KEEP/bench_qhd.err"
 python3 bench.py --workload qhd --irregular > "$KEEP/r05_bench_qhd_c5.json" 2> "$KEEP/bench_c5.err"

@@ -14,5 +14,5 @@ for N in 400 200; do
   bash scripts/ab_variants.sh $N QGD_FUSED=0 QGD_FUSED=1 QGD_FUSED=0 QGD_FUSED=1 > /dev/null 2>&1
   cp gpurun_out/ab_$N.txt "$KEEP/ab_fused_n$N.txt"
 done
-python3 bench.py > "$KEEP/r05_bench_default.json" 2> "$KEEP/bench_default.err"
+python3 bench.py --full > "$KEEP/r05_bench_default.json" 2> "$KEEP/bench_default.err"
 tail -3 "$KEEP/collect_profiles.log"; cat "$KEEP/ab_fused_n400.txt" "$KEEP/ab_fused_n200.txt"; head -c 600 "$KEEP/r05_bench_default.json"

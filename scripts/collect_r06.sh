@@ -11,7 +11,7 @@ mkdir -p "$KEEP"
 bash scripts/collect_profiles.sh r06 > "$KEEP/collect_profiles.log" 2>&1
 cp gpurun_out/prof_r06/summaries/* "$KEEP/" 2>/dev/null
 for N in 400 200; do cp gpurun_out/prof_r06/bench_stats_n$N.log "$KEEP/r06_n${N}_bench_under_rocprof.log" 2>/dev/null; done
-python3 bench.py > "$KEEP/r06_bench_default.json" 2> "$KEEP/bench_default.err"
+python3 bench.py --full > "$KEEP/r06_bench_default.json" 2> "$KEEP/bench_default.err"
 python3 bench.py --workload implicit > "$KEEP/r06_bench_implicit_n200.json" 2> "$KEEP/bench_implicit.err"
 python3 bench.py --workload qhd > "$KEEP/r06_bench_qhd_n200.json" 2> "$KEEP/bench_qhd.err"
 python3 bench.py --workload qhd --edge 126 > "$KEEP/r06_bench_qhd_n126.json" 2> "$KEEP/bench_qhd126.err"

@@ -106,6 +106,42 @@ def test_native_transport_is_attached_from_a_second_set_of_ranks(monkeypatch):
     assert "error" in nt and "5 s" in nt["error"] and nt["stderr"] == ["stuck"]
 
 
+def test_dump_outputs_is_a_one_gpu_qgd_option():
+    """--dump-outputs writes the one-GPU qgd workload's fields; elsewhere it is refused before anything starts"""
+    for args in (["--gpus", "2", "--dump-outputs", "unused"], ["--workload", "qhd", "--dump-outputs", "unused"]):
+        pr, _ = run_bench(args + ["--steps", "1"], 120)
+        assert pr.returncode == 2 and "--dump-outputs" in pr.stderr, (args, pr.returncode, pr.stderr[-300:])
+
+
+def test_dump_outputs_samples_a_fixed_set_of_cells(tmp_path):
+    """beyond DUMP_MAX_CELLS cells the dump is the same seeded, sorted sample every time; float64 files under 64 MB in all"""
+    import numpy as np
+    import bench
+
+    class Case:
+        def __init__(self, n):
+            self.n = n
+
+        def field(self, name):
+            a = np.arange(self.n, dtype=np.float64) + 0.5
+            return np.repeat(a[:, None], 3, axis=1) if name == "U" else a
+
+    n = bench.DUMP_MAX_CELLS + 12345
+    bench.dump_outputs(Case(n), n, str(tmp_path / "a"))
+    bench.dump_outputs(Case(n), n, str(tmp_path / "b"))
+    total = 0
+    for name in bench.DUMP_FIELDS:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape[0] == bench.DUMP_MAX_CELLS and np.array_equal(a, b)
+        cells = (a[:, 0] if a.ndim == 2 else a) - 0.5
+        assert np.all(np.diff(cells) > 0) and cells[0] >= 0 and cells[-1] < n
+        total += (tmp_path / "a" / f"{name}.npy").stat().st_size
+    assert total <= 64 * 2 ** 20
+    small = tmp_path / "small"
+    bench.dump_outputs(Case(1000), 1000, str(small))
+    assert np.array_equal(np.load(small / "rho.npy"), np.arange(1000) + 0.5)
+
+
 def test_env_switches_are_echoed(monkeypatch):
     import bench
     monkeypatch.setenv("QGD_XCD_RUN", "16")
@@ -116,7 +152,7 @@ def test_env_switches_are_echoed(monkeypatch):
 
 @pytest.mark.gpu
 def test_two_ranks_self_launched_match_one_rank():
-    common = ["--backend", "gloo", "--edge", "48", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-dropin", "--no-secondary", "--check"]
+    common = ["--full", "--backend", "gloo", "--edge", "48", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-dropin", "--no-secondary", "--check"]
     one, _ = run_bench(["--gpus", "1"] + common, 900)
     assert one.returncode == 0, one.stderr[-800:]
     two, _ = run_bench(["--gpus", "2"] + common, 900)
@@ -134,6 +170,30 @@ def test_two_ranks_self_launched_match_one_rank():
 
 
 @pytest.mark.gpu
+def test_plain_line_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """python bench.py --steps K --warmup W (the driver's command): the headline's keys, K timed steps, none of what --full adds;
+    --dump-outputs writes the fields the last timed step left, the same on every run with the same arguments, and a different number
+    of steps leaves different fields"""
+    runs = {}
+    for tag, steps in (("a", "3"), ("b", "3"), ("c", "4")):
+        pr, _ = run_bench(["--gpus", "1", "--edge", "24", "--steps", steps, "--warmup", "1", "--dump-outputs", str(tmp_path / tag)], 600)
+        assert pr.returncode == 0, pr.stderr[-800:]
+        runs[tag] = json.loads([ln for ln in pr.stdout.splitlines() if ln.startswith("{")][-1])
+    d = runs["a"]
+    assert d["metric"] == "Mcell-steps/s (QGDFoam explicit step)" and d["unit"] == "Mcell-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 3 and runs["c"]["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["value"] - 24 ** 3 / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-9 * d["value"]
+    assert not {"roofline", "other_kernels", "kernels_ms_avg", "secondary", "dropin_fvsc", "cpu_baseline", "native_transport"} & set(d)
+    import numpy as np
+    for name, shape in (("rho", (24 ** 3,)), ("U", (24 ** 3, 3)), ("p", (24 ** 3,)), ("T", (24 ** 3,)), ("e", (24 ** 3,))):
+        a, b, c = (np.load(tmp_path / tag / f"{name}.npy") for tag in "abc")
+        assert a.dtype == np.float64 and a.shape == shape and np.all(np.isfinite(a))
+        assert np.array_equal(a, b), name
+    for name in ("rho", "U", "p", "T", "e"):   # --steps sets the timed steps: one more step moves every field
+        assert not np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "c" / f"{name}.npy")), name
+
+
+@pytest.mark.gpu
 def test_native_halo_refuses_the_one_gpu_stand_in():
     pr, _ = run_bench(["--gpus", "2", "--backend", "gloo", "--halo", "native", "--edge", "16", "--steps", "1", "--warmup", "0",
                        "--no-cpu-baseline", "--no-dropin", "--no-secondary"], 600)
@@ -142,12 +202,12 @@ def test_native_halo_refuses_the_one_gpu_stand_in():
 
 @pytest.mark.gpu
 def test_default_line_carries_the_secondary_workloads_and_the_env():
-    """python bench.py --gpus 1 (the driver's command) appends `secondary` {qhd, implicit} from child processes, 20 timed steps each,
+    """python bench.py --gpus 1 --full appends `secondary` {qhd, implicit} from child processes, 20 timed steps each,
     and echoes every QGD_* variable; shrunk here through QGD_BENCH_SECONDARY_N, which the echo then shows"""
     env = dict(os.environ, QGD_BENCH_SECONDARY_N="24", QGD_BENCH_C5_N="20")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    pr = subprocess.run([sys.executable, BENCH, "--edge", "32", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-dropin"], env=env,
+    pr = subprocess.run([sys.executable, BENCH, "--full", "--edge", "32", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-dropin"], env=env,
                         capture_output=True, text=True, timeout=1200)
     assert pr.returncode == 0, pr.stderr[-800:]
     d = json.loads([ln for ln in pr.stdout.splitlines() if ln.startswith("{")][-1])
