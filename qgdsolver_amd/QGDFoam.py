@@ -102,7 +102,8 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         mesh = gmesh.unroll_cyclic(gmesh.cyclic_pairs)
         cells = mesh.array("cellGlobal")
         owned = np.arange(mesh.nCells) < n_global
-    # only a fixed-deltaT case with one GaussVolPoint stencil uses the cell blocks: no block tables otherwise
+    # this driver builds the block tables for a fixed-deltaT case with one GaussVolPoint stencil only: an adjustTimeStep case, which the library
+    # can step on the blocks as well (QGD_FUSED_ADJUST, include/qgd_amd.h qgd_case_fused_info), runs the separate kernels here
     # (the blocks serve the explicit branch's one-launch step, shards included, and the implicitDiffusion branch's assembly of the U systems on one rank)
     eligible = (not (opt.get("adjustTimeStep") or opt.get("termStencils")) and opt["stencil"] == "GaussVolPoint"
                 and not (opt.get("implicitDiffusion") and world > 1))

@@ -303,7 +303,7 @@ struct qgd_case_s {
     bool fusedAdj = false;      // adjustTimeStep: the blocks run up to their flux sums + Courant partials, cellFinishKernel advances once deltaT is known (QGD_FUSED_ADJUST)
     bool fusedImpl = false;     // implicitDiffusion: vertex values, QGD fluxes, tauMC and the U systems' rows are one launch on the same blocks (QGD_IMPL_FUSED)
     std::vector<double*> selfBuf;   // cyclic pairs served by ghost cells: one message buffer per halo slot (selfHaloExchange)
-    bool ghostsCurrent = false;     // ... and whether the copies hold their originals' records (reset by set_fields / set_bc)
+    bool ghostsCurrent = false;     // ... and whether the copies hold their originals' records (reset by set_fields only; set by qgd_case_step alone)
     bool hasQgdFlux = false;
     bool phiwRegistered = false;
     bool fieldsSet = false;
@@ -714,7 +714,7 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
         v.ie1 = s.ie1; v.ie2 = s.ie2; v.ie3 = s.ie3;
         v.nGeomD = m.nGeometricD;
         for (int k = 0; k < 3; ++k) v.emptyDir[k] = m.geometricD[k] < 0 ? 1 : 0;
-        static const int kBlocks[] = {64, 128, 256}, kWaves[] = {2, 3, 4};
+        static const int kBlocks[] = {64, 128, 256};
         v.xcdRun = envChoice("QGD_XCD_RUN", 16, nullptr, 0, 0, 1 << 20);   // 0: one contiguous eighth of the tiles per XCD
         v.fuXcdRun = envChoice("QGD_FU_XCD_RUN", 64, nullptr, 0, 0, 1 << 20);   // (measured at 64 M cells: 4: 9.63, 16: 9.51-9.53, 64: 9.44, 256: 9.35-9.38 on one box; 16: 9.39, 64: 9.29-9.36, 1024: 9.38 on another)
         v.fblock = envChoice("QGD_FBLOCK", 128, kBlocks, 3);
@@ -723,10 +723,7 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
         // Sf of a quadrilateral = (p3-p1) x (p4-p2) / 2 exactly (the triangle fan about any centre sums to it), and the
         // kernel holds those differences already: 24 B per face less to stream.  Not when the caller supplied its own Sf.
         static const int kOnOff[] = {0, 1};
-        v.tileWaves = envChoice("QGD_FT_WAVES", 3, kWaves, 3);
-        v.sGeo = (envChoice("QGD_SGEO", 1, kOnOff, 2) != 0 && !m.userGeometry && v.fblock == 128 && v.tileWaves == 3) ? 1 : 0;
-        v.cblock = envChoice("QGD_CBLOCK", 256, kBlocks, 3);
-        v.pblock = envChoice("QGD_PBLOCK", 256, kBlocks, 3);
+        v.sGeo = (envChoice("QGD_SGEO", 1, kOnOff, 2) != 0 && !m.userGeometry && v.fblock == 128) ? 1 : 0;
         // upload + free each table in turn so the host peak stays at one table
         auto up = [&](auto& vec) { auto* p = a.upload(vec); std::decay_t<decltype(vec)>().swap(vec); return p; };
         {
@@ -743,7 +740,7 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                 v.tileMaxC = t.maxCells; v.tileMaxV = t.maxVerts;
                 v.qhdTiles = envChoice("QGD_QHD_TILES", 1, kOnOff, 2);
                 v.implTiles = envChoice("QGD_IMPL_TILES", 1, kOnOff, 2);
-                if (v.fblock == 128 && v.tileWaves == 3 && envChoice("QGD_FTILE_FIXED", 1, kOnOff, 2) != 0 &&
+                if (v.fblock == 128 && envChoice("QGD_FTILE_FIXED", 1, kOnOff, 2) != 0 &&
                     (int64_t)nTiles * std::max(t.maxCells, t.maxVerts) < (int64_t)INT32_MAX) {
                     // the lists once more at a fixed stride (built and uploaded one after the other: the host peak stays at one table)
                     std::vector<uint8_t> flag((size_t)nTiles, 0);

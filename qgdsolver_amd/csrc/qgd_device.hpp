@@ -19,7 +19,6 @@ struct MeshView {
     int32_t ie1, ie2, ie3;
     int32_t nGeomD;          // mesh.nGeometricD()
     int32_t emptyDir[3];     // 1 for the directions of empty patches (vector components the segregated solves skip)
-    int32_t cblock, pblock;  // tiles of the cell-update and vertex kernels (64, 128 or 256)
     int32_t fblock;          // face tile of the 3-D GaussVolPoint kernel: 64, 128 or 256 faces per workgroup
     int32_t hasOther;        // 1: some internal face has more than four vertices (FK_OTHER)
     int32_t xcdRun;          // tiles per XCD run of the workgroup->tile map (0: one contiguous eighth per XCD)
@@ -64,7 +63,6 @@ struct MeshView {
     const int32_t* tileCellsFix; const int32_t* tileVertsFix; const uint8_t* tileFlag;
     int32_t qhdTiles;        // QGD_QHD_TILES (default 1): QHD's two face passes use the tiles too (qgd_qhd.hip qhdFace{1,2}TileKernel)
     int32_t implTiles;       // QGD_IMPL_TILES (default 1): so does the face kernel of QGDFoam's implicit branch (qgd_implicit.hip implFaceTileKernel)
-    int32_t tileWaves;       // waves per SIMD the staged kernel is compiled for (2, 3 or 4)
     int32_t sGeo;            // 1: the 3-D GaussVolPoint kernels rebuild Sf of quadrilateral faces from the vertices (no Sf stream)
     const double* V; const double* hQGD; const uint8_t* ghost;
     const int32_t* bPatch; const double* hQGDb;

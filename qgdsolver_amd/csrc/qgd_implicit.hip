@@ -8,8 +8,9 @@
 // The face-flux kernels of qgd_kernels.hip run with GasModel::implicitDiffusion = 1 (Pi without its Navier-Stokes part, q
 // without its Fourier part); what is here sits between them and the boundary refresh.  L0 pieces: fvc::grad (Gauss linear +
 // gaussGrad::correctBoundaryConditions), fvm::laplacian (Gauss, uncorrected snGrad; patch coefficients of fixedValue,
-// zeroGradient and basicSymmetry patches), segregated component solves.  Not a benchmark path: generic one-thread-per-item
-// kernels, the two linear solves by the reproducible Jacobi-PCG of qgd_poisson.hip.
+// zeroGradient and basicSymmetry patches), segregated component solves: Chebyshev iteration on the Jacobi-preconditioned system by
+// default (QGD_IMPL_SOLVER=pcg keeps the Jacobi-preconditioned conjugate gradients), the U systems assembled by the fused block kernel
+// of qgd_kernels.hip where the case has cell blocks (QGD_IMPL_FUSED).  Measured by its own line of the benchmark (bench.py --workload implicit).
 #include <algorithm>
 #include <stdexcept>
 #include <string>
@@ -564,9 +565,8 @@ __global__ __launch_bounds__(QGD_BLOCK) void iApplyKernel(const MeshView m, cons
 // One Chebyshev step (see the head of this section).  FIRST: x_1 = x_0 + D^-1 r_0 from the residual phase 0 left (no product);
 // otherwise the product on the current iterate (buffer step & 1), the new d and the next iterate into the other buffer, and the
 // partial sums of |b - A x_i|.  Components that are done are not touched; all others have made the same number of steps.
-#ifndef QGD_CHEB_DF
-#define QGD_CHEB_DF 1   // 0: the recurrence's d in double (A/B: profiles/r05_ab_implicit_direction_f32.txt)
-#endif
+// The recurrence's direction d is kept in single precision (ISolveView::df): 0.338 against 0.364-0.375 ms per kernel in
+// double, 10.76 against 11.06-11.17 ms per implicit step, same iteration counts (profiles/r05_ab_implicit_direction_f32.txt).
 template <int NR, int FIRST>
 __global__ __launch_bounds__(QGD_BLOCK) void iChebKernel(const MeshView m, const ISolveView v) {
     const int blk = FIRST ? (int)blockIdx.x : xcdRunBlock(v.xrun);
@@ -619,20 +619,12 @@ __global__ __launch_bounds__(QGD_BLOCK) void iChebKernel(const MeshView m, const
             if (FIRST) { rc = v.r[j]; dn = rc / dg; }
             else {
                 rc = v.rhs[j] - (dg * xv - v.gam[k] * acc[k]);
-#if QGD_CHEB_DF
                 dn = v.ctl[ICTL(I_C1, k)] * (double)v.df[j] + v.ctl[ICTL(I_C2, k)] * (rc / dg);
-#else
-                dn = v.ctl[ICTL(I_C1, k)] * v.d[j] + v.ctl[ICTL(I_C2, k)] * (rc / dg);
-#endif
             }
             // the update x_{i+1} = x_i + d_i is made with d_i in double; what the NEXT step's recurrence reads back is d_i rounded to single
             // precision (4 + 4 instead of 8 + 8 B per component and step).  z is the true residual of the iterate every step, so the rounding
             // (6e-8 of a term that c1 < 1 damps) perturbs the polynomial, not the fixed point: same solution to the same tolerance
-#if QGD_CHEB_DF
             v.df[j] = (float)dn;
-#else
-            v.d[j] = dn;
-#endif
             dst[j] = xv + dn;
             s0[k] = fabs(rc);
         }

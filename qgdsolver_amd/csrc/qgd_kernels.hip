@@ -397,12 +397,6 @@ __global__ __launch_bounds__(QGD_BLOCK) void faceFluxMixedKernel(const MeshView 
 // (2) the 2 cell and 4 vertex records; then ~600 fp64 operations out of registers.  One memory round trip per
 // dependency level instead of one per gradient component; the register budget is traded for that on purpose.
 // ---------------------------------------------------------------------------
-#ifndef QGD_F_WAVES_MIN
-#define QGD_F_WAVES_MIN 2
-#endif
-#ifndef QGD_F_WAVES_MAX
-#define QGD_F_WAVES_MAX 3
-#endif
 // Gauss coefficients of one internal face from the geometry records alone (so that a kernel holding its records in LDS can
 // let go of the geometry before it touches the field values).  Quad [GaussVolPointBase3D_8C L346-389, L488-513] in difference
 // form: with a2=-a0, a3=-a1, a4=-a5,
@@ -438,17 +432,6 @@ __device__ __forceinline__ void gvp3Coefs(const int kind, const double4& cO, con
     }
 }
 
-// QGD_F_PRIO: wave priority inside the staged face kernel.  Its rate is tiles in flight / length of a tile's chain of dependent round
-// trips (profiles/r04_ab_face_latency_chain.txt), and the instructions between those round trips -- address arithmetic, LDS stores, the
-// barrier -- compete for issue with the flux algebra of the other waves of the SIMD: 0 never raised, 1 raised until the piece loads are
-// out, 2 until the tile is in LDS (default: F 6.75 / 6.63 / 6.50 ms for 0 / 1 / 2; kept up until the records are in registers -- with the
-// Gauss coefficients' arithmetic inside the window -- 7.0-7.3 ms).
-#ifndef QGD_F_PRIO
-#define QGD_F_PRIO 2
-#endif
-#ifndef QGD_P_PRIO
-#define QGD_P_PRIO 1   // the same in the vertex kernel, until its gathers are out: P 2.53 -> 2.48 ms (nothing in the cell kernel: not kept there)
-#endif
 // everything after the loads of one internal face: gradient coefficients from the geometry, the 6-component gradient, the 13
 // interpolations, the flux algebra, the five net fluxes (slot-major position fp), the face's share of the Courant number
 // component k of the quadrilateral's gradient [GaussVolPointBase3D_8C L346-389, L488-513 in difference form, gvp3Coefs]: one definition for the
@@ -576,7 +559,7 @@ __device__ __forceinline__ void gvp3FaceBody(const MeshView& m, const CaseView& 
 }
 
 template <bool DBG, int FB, bool SGEO = false, bool UPW = false>
-__global__ __launch_bounds__(FB) __attribute__((amdgpu_waves_per_eu(QGD_F_WAVES_MIN, QGD_F_WAVES_MAX)))
+__global__ __launch_bounds__(FB) __attribute__((amdgpu_waves_per_eu(2, 3)))
 void faceFluxGvp3Kernel(const MeshView m, const CaseView c, const GasModel gm, const int adjustDt, const int32_t* __restrict__ tileList) {
     // tileList: the tiles the staged kernel below leaves to this one (nullptr: every tile)
     const int tile = tileList ? tileList[blockIdx.x] : xcdTile((int)gridDim.x, m.xcdRun * (QGD_BLOCK / FB));
@@ -624,27 +607,22 @@ void faceFluxGvp3Kernel(const MeshView m, const CaseView c, const GasModel gm, c
 // ---------------------------------------------------------------------------
 typedef double v2d __attribute__((ext_vector_type(2)));   // one 16-B piece
 constexpr int kFusedCapCDev = 320, kFusedCapVDev = 256, kFusedCapFDev = 512, kFusedCapTotDev = 384;   // = kFusedCap{C,V,F,Tot} of qgd_setup.hpp
-#ifndef QGD_F_BUF
-#define QGD_F_BUF 0
-#endif
-#ifndef QGD_FT_WAVES_MIN
-#define QGD_FT_WAVES_MIN 2
-#endif
-#ifndef QGD_FT_WAVES_MAX
-#define QGD_FT_WAVES_MAX 3
-#endif
 // FIXED: the tile lists at a fixed stride (MeshView::tileCellsFix / tileVertsFix: every tile's list padded to the longest one by
 // repeating its last label, tileFlag = 1 for the tiles left to the gather kernel).  A tile's life is a chain of dependent memory
 // round trips -- list offsets -> labels -> pieces -> LDS -> algebra -- and with 6 workgroups per CU in flight the kernel's rate is
 // tiles in flight / length of that chain, not bytes (29 % fewer L2 misses under a pencil order: -1.6 % time,
 // profiles/r04_ab_pencil_xcd_matched.txt).  With computed offsets the chain is one round trip shorter.
-template <int FB, int WAVES, bool SGEO = false, bool FIXED = false, bool UPW = false>
-__global__ __launch_bounds__(FB) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
+// Wave priority: the instructions between those round trips -- address arithmetic, LDS stores, the barrier -- compete for issue with
+// the flux algebra of the other waves of the SIMD (profiles/r04_ab_face_latency_chain.txt), so the priority is raised from the start
+// until the tile is in LDS.  Measured: F 6.75 ms never raised / 6.63 raised until the piece loads are out / 6.50 as here; kept up until
+// the records are in registers -- with the Gauss coefficients' arithmetic inside the window -- 7.0-7.3 ms.
+// Three waves per SIMD: compiled for two the 128-face kernel measured 8.37 against 7.35 ms, for four it spills (52 VGPRs: 14.3 ms) -- the
+// flux algebra holds ~100 live doubles -- and a lean four-wave variant without scratch ran 2 % slower (profiles/r05_ab_face_four_waves.txt).
+template <int FB, bool SGEO = false, bool FIXED = false, bool UPW = false>
+__global__ __launch_bounds__(FB) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void faceFluxGvp3TileKernel(const MeshView m, const CaseView c, const GasModel gm, const int adjustDt) {
     extern __shared__ v2d tileLds[];
-#if QGD_F_PRIO
     __builtin_amdgcn_s_setprio(3);   // the address arithmetic in front of the loads ahead of the other waves' flux algebra
-#endif
     constexpr int KC = 4, KB2 = 3, KV = 5;   // piece loads per thread: ceil(3 capC / FB), ceil(2 capC / FB), ceil(3 capV / FB) (faceTileCap*)
     static_assert(3 * (FB + FB / 16) <= KC * FB && 2 * (FB + FB / 16) <= KB2 * FB && 3 * (((FB * 23) / 16 + 7) / 8 * 8) <= KV * FB, "caps");
     const int tile = xcdTile((int)gridDim.x, m.xcdRun * (QGD_BLOCK / FB));
@@ -702,40 +680,14 @@ void faceFluxGvp3TileKernel(const MeshView m, const CaseView c, const GasModel g
     const v2d* __restrict__ gP = reinterpret_cast<const v2d*>(c.P);
     v2d dA[KC], dB[KB2], dP[KV];
     double dC[KC], dX[KV];
-#if QGD_F_BUF
-    // QGD_F_BUF (compile-time experiment): the piece gathers as raw buffer loads -- a 32-bit byte offset per
-    // load instead of a 64-bit address (one v_lshlrev_b32 in place of v_ashrrev + v_lshl_add_u64); needs every array below 4 GiB
-    (void)gA; (void)gB; (void)gP;
-    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)c.A, 0, (int)0xffffffffu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)c.B, 0, (int)0xffffffffu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)c.P, 0, (int)0xffffffffu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc((void*)m.Cc, 0, (int)0xffffffffu, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)m.X, 0, (int)0xffffffffu, 0x00020000);
-#pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        dA[k] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rA, (int)((unsigned)idC[k] << 4), 0, 0));
-        dC[k] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rC, (int)((unsigned)idC[k] << 3), 0, 0));
-    }
-#pragma unroll
-    for (int k = 0; k < KB2; ++k) dB[k] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rB, (int)((unsigned)idB[k] << 4), 0, 0));
-#pragma unroll
-    for (int k = 0; k < KV; ++k) {
-        dP[k] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rP, (int)((unsigned)idV[k] << 4), 0, 0));
-        dX[k] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rX, (int)((unsigned)idV[k] << 3), 0, 0));
-    }
-#else
+    // (the same gathers as raw buffer loads with 32-bit offsets instead of 64-bit addresses: 14 VALU instructions fewer, F 7.35 ms either
+    // way -- not kept, profiles/r04_ab_face_instruction_diet.txt)
 #pragma unroll
     for (int k = 0; k < KC; ++k) { dA[k] = gA[idC[k]]; dC[k] = m.Cc[idC[k]]; }
 #pragma unroll
     for (int k = 0; k < KB2; ++k) dB[k] = gB[idB[k]];
 #pragma unroll
     for (int k = 0; k < KV; ++k) { dP[k] = gP[idV[k]]; dX[k] = m.X[idV[k]]; }
-#endif
-#if QGD_F_PRIO == 1
-    __builtin_amdgcn_s_setprio(0);
-#endif
     double msO = 1.0, dnO = 0.0;
     if (SGEO && kind != 0) { S[0] = ldStream(m.Sx + fl); S[1] = ldStream(m.Sy + fl); S[2] = ldStream(m.Sz + fl); }
     if (m.hasOther) { msO = m.magSf[fl]; dnO = m.dn[fl]; }
@@ -748,9 +700,7 @@ void faceFluxGvp3TileKernel(const MeshView m, const CaseView c, const GasModel g
 #pragma unroll
     for (int k = 0; k < KV; ++k) { const int q = tid + k * FB; if (q < 3 * nUv) { sP[q] = dP[k]; sX[q] = dX[k]; } }
     __syncthreads();
-#if QGD_F_PRIO == 2
     __builtin_amdgcn_s_setprio(0);
-#endif
     // (2) every face picks its records out of LDS
     double cof = -1e300, tauMin = 1e300;
     if (active) {
@@ -919,18 +869,12 @@ __global__ __launch_bounds__(QGD_BLOCK) void pointInterpKernel(const MeshView m,
 
 // The case's vertex kernel: the gather list of a wave is read as contiguous runs (sliced ELL), the cell records
 // as whole 48-B records (3 x dwordx4), all gathers of a point are issued before the first use.
-#ifndef QGD_P_WAVES_MIN
-#define QGD_P_WAVES_MIN 3
-#endif
-#ifndef QGD_P_WAVES_MAX
-#define QGD_P_WAVES_MAX 4
-#endif
+// Wave priority raised until the gathers are out, as in the staged face kernel: P 2.53 -> 2.48 ms (nothing in the cell kernel: not
+// kept there).
 template <int PB>
-__global__ __launch_bounds__(PB) __attribute__((amdgpu_waves_per_eu(QGD_P_WAVES_MIN, QGD_P_WAVES_MAX)))
+__global__ __launch_bounds__(PB) __attribute__((amdgpu_waves_per_eu(3, 4)))
 void pointInterpRecKernel(const MeshView m, const RecA* __restrict__ A, RecA* __restrict__ P) {
-#if QGD_P_PRIO
     __builtin_amdgcn_s_setprio(3);
-#endif
     const int p = xcdTile((int)gridDim.x, m.xcdRun * (QGD_BLOCK / PB)) * PB + threadIdx.x;
     if (p >= m.nP) return;
     const int n = m.pcCount[p];
@@ -948,9 +892,7 @@ void pointInterpRecKernel(const MeshView m, const RecA* __restrict__ A, RecA* __
         for (int q = 0; q < 8; ++q) { id[q] = m.pcCell[base + (size_t)q * 64]; w[q] = m.pcW[base + (size_t)q * 64]; }
 #pragma unroll
         for (int q = 0; q < 8; ++q) r[q] = A[id[q]];
-#if QGD_P_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -1019,14 +961,8 @@ __device__ __forceinline__ void advanceCell(const CaseView& c, const GasModel& g
 // cell update: gather of the net face fluxes in ascending face order (the
 // summation order of fvc::surfaceIntegrate), explicit Euler, thermo, QGD coeffs
 // ---------------------------------------------------------------------------
-#ifndef QGD_C_WAVES_MIN
-#define QGD_C_WAVES_MIN 3
-#endif
-#ifndef QGD_C_WAVES_MAX
-#define QGD_C_WAVES_MAX 4
-#endif
 template <int CB>
-__global__ __launch_bounds__(CB) __attribute__((amdgpu_waves_per_eu(QGD_C_WAVES_MIN, QGD_C_WAVES_MAX)))
+__global__ __launch_bounds__(CB) __attribute__((amdgpu_waves_per_eu(3, 4)))
 void cellUpdateKernel(const MeshView m, const CaseView c, const GasModel gm, const int mode,
                       const int32_t* __restrict__ list, const int nList, const int slotBase) {
     // mode 0: every cell but the ghosts; mode 1: the cells of `list` (boundary layer of a shard: its records are what the
@@ -1127,13 +1063,8 @@ void cellUpdateKernel(const MeshView m, const CaseView c, const GasModel gm, con
 // no debug fields (everything else keeps the three kernels); UPW = `Gauss upwind` fluxes; shards run it too (the boundary-layer blocks first,
 // stepAdvance).
 // ---------------------------------------------------------------------------
-#ifndef QGD_FU_WAVES
-#define QGD_FU_WAVES 3
-#endif
-// wave priority raised from the kernel's start: 0 never, 1 until the loads are out, 2 until the block is staged, 3 until its vertex values are formed
-#ifndef QGD_FU_PRIO
-#define QGD_FU_PRIO 3
-#endif
+// Wave priority is raised from the kernel's start until the block's vertex values are formed.  Never raising it, or dropping it once
+// the loads are out or once the block is staged, measured the same: what was worth 4 % in the face kernel changes nothing here.
 // IMPL = the implicitDiffusion branch [QGDUEqn.H L36-68, updateFluxes.H L95-111]: the same block forms its vertex values and the QGD fluxes of
 // its faces (without the Navier-Stokes / Fourier parts), then -- with fvc::grad(U) of its own and across-a-face cells staged where the vertex
 // records were -- tauMC, phiTauMC and the laplacian coefficients of every face (implInternalFace: implFaceTileKernel's expressions), and instead
@@ -1147,17 +1078,11 @@ void cellUpdateKernel(const MeshView m, const CaseView c, const GasModel gm, con
 // cell in cellSum; cellFinishKernel advances the cells from there.  Vertex values and face fluxes still never reach device memory.
 template <bool SGEO, bool UPW = false, bool IMPL = false, bool ADJ = false>
 // (IMPL with `Gauss upwind` fluxes needs a few registers more than three waves per SIMD leave: that instantiation is compiled for two -- no scratch)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((IMPL && UPW) ? 2 : QGD_FU_WAVES, (IMPL && UPW) ? 2 : QGD_FU_WAVES)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((IMPL && UPW) ? 2 : 3, (IMPL && UPW) ? 2 : 3)))
 void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, const int firstBlock, const ImplView iv,
                          const PatchBCDev* __restrict__ bcs) {
     extern __shared__ v2d tileLds[];
-#if QGD_FU_CLOCK   // timing probe (scripts/fused_phase_clock.py): where a block's lifetime goes, in shader-clock ticks, left in its cells' new records
-    const uint64_t tk0 = __builtin_readcyclecounter();
-    uint64_t tk1 = 0, tk2 = 0, tk3 = 0, tk4 = 0, tk5 = 0;
-#endif
-#if QGD_FU_PRIO
     __builtin_amdgcn_s_setprio(3);
-#endif
     constexpr int NT = 256, KC = 5, KCC = 4, KB2 = 3, KV = 3, KF = 2, KE = 6, KP = 8, KG = 12;
     static_assert(9 * kFusedCapCDev <= KG * NT, "caps");
     // piece loads per thread: RecA of <= 384 staged cells, centres and RecB of the <= 320 own + across-a-face cells, coordinates of <= 256
@@ -1208,10 +1133,6 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // block's local topology out of its TEMPLATE (hdr2.y; qgd_setup.hpp FusedBlocks: the interior bricks of a structured region share a few
     // hundred templates, which stay in L2): the positions of this thread's two faces' cells and vertices in the staged lists, its cell's face
     // entries, its vertex's cell positions.  None of it is needed before the records are staged, so the template costs no round trip.
-#if QGD_FU_CLOCK
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (probe only: the two rounds one after the other, to time them apart)
-    tk1 = __builtin_readcyclecounter();
-#endif
     const size_t tpl = (size_t)hdr2.y;
     struct Pos3 { uint32_t c, va, vb; };
     const Pos3* __restrict__ tFacePos = reinterpret_cast<const Pos3*>(m.fuFacePos) + tpl * capF;
@@ -1251,9 +1172,6 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         for (int k = 0; k < 3; ++k) dPt[k] = gP[(size_t)myVert * 3 + k];
     }
     __builtin_amdgcn_sched_barrier(0);
-#if QGD_FU_PRIO == 1
-    __builtin_amdgcn_s_setprio(0);
-#endif
     const int nOwn = hdr.x, nUc = hdr.y, nUv = hdr.z, nFc = hdr.w;
     // LDS, laid out by THIS block's counts (the launch reserves what the block that needs most takes): RecA of every staged cell and RecB of
     // the own + across-a-face cells stay to the end (an own cell's old record is read by its update); the vertex records -- formed HERE, from
@@ -1280,13 +1198,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     for (int k = 0; k < KB2; ++k) { const int q = tid + k * NT; if (q < 2 * nUc) sB[q] = dB[k]; }
 #pragma unroll
     for (int k = 0; k < KV; ++k) { const int q = tid + k * NT; if (q < 3 * nUv) sX[q] = dX[k]; }
-#if QGD_FU_CLOCK
-    tk2 = __builtin_readcyclecounter();
-#endif
     __syncthreads();
-#if QGD_FU_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
     // (1b) the vertex values [volPointInterpolation: inverse-distance weights over pointCells, in their order -- pointInterpRecKernel's
     // arithmetic, out of the staged cell records]
     if (tid < nUv) {
@@ -1322,13 +1234,8 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             for (int k = 0; k < 3; ++k) sP[3 * tid + k] = dPt[k];
         }
     }
-#if QGD_FU_CLOCK
-    tk3 = __builtin_readcyclecounter();
-#endif
     __syncthreads();
-#if QGD_FU_PRIO == 3
     __builtin_amdgcn_s_setprio(0);
-#endif
     // (2) the faces: fluxes into registers
     auto l3 = [](const double* p, int i) { return make_double4(p[3 * i], p[3 * i + 1], p[3 * i + 2], 0.0); };
     double out[KF][5];
@@ -1423,9 +1330,6 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-#if QGD_FU_CLOCK
-    tk4 = __builtin_readcyclecounter();
-#endif
     __syncthreads();   // every face has read its vertex records and coordinates
     if constexpr (IMPL) {
         // The implicitDiffusion branch keeps the explicit step's LDS (three blocks per CU) by using the dead vertex region three times:
@@ -1547,9 +1451,6 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         }
     }
     __syncthreads();
-#if QGD_FU_CLOCK
-    tk5 = __builtin_readcyclecounter();
-#endif
     // (3) the block's own cells out of LDS
     double rmin = 1e300, emin = 1e300;
     if (tid < nOwn) {
@@ -1599,15 +1500,6 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             RecB Bn;
             double rEnew;
             advanceCell(c, gm, ci, A, rEold, Vc, hq, sum, An, Bn, rEnew);
-#if QGD_FU_CLOCK
-            {
-                asm volatile("" ::"v"(An.rho), "v"(An.e), "v"(Bn.muQGD), "v"(rEnew));
-                const uint64_t tk6 = __builtin_readcyclecounter();
-                // lists (round 0) | records (round 1) + staging | barrier + vertex values | barrier + faces | barriers + flux planes | sums + advanceCell
-                An.rho = (double)(tk1 - tk0); An.ux = (double)(tk2 - tk1); An.uy = (double)(tk3 - tk2); An.uz = (double)(tk4 - tk3);
-                An.p = (double)(tk5 - tk4); An.e = (double)(tk6 - tk5);
-            }
-#endif
             c.A2[ci] = An;
             c.B2[ci] = Bn;
             c.rE[ci] = rEnew;
@@ -2130,9 +2022,7 @@ static inline int gridFor(int64_t n) { return (int)((n + QGD_BLOCK - 1) / QGD_BL
 
 void launchPointInterp(const Launcher& L, const MeshView& m, const CaseView& c) {
     if (m.nP == 0) return;
-    if (m.pblock == 64) QGD_TIMED(L, QGD_K_POINT, (pointInterpRecKernel<64><<<(m.nP + 63) / 64, 64, 0, L.stream>>>(m, c.A, c.P)));
-    else if (m.pblock == 128) QGD_TIMED(L, QGD_K_POINT, (pointInterpRecKernel<128><<<(m.nP + 127) / 128, 128, 0, L.stream>>>(m, c.A, c.P)));
-    else QGD_TIMED(L, QGD_K_POINT, (pointInterpRecKernel<256><<<gridFor(m.nP), QGD_BLOCK, 0, L.stream>>>(m, c.A, c.P)));
+    QGD_TIMED(L, QGD_K_POINT, (pointInterpRecKernel<256><<<gridFor(m.nP), QGD_BLOCK, 0, L.stream>>>(m, c.A, c.P)));
 }
 void launchBoundaryPoints(const Launcher& L, const MeshView& m, const CaseView& c, bool pOnly) {
     if (m.nBP == 0) return;
@@ -2143,6 +2033,47 @@ void launchBoundaryPoints(const Launcher& L, const MeshView& m, const CaseView& 
         QGD_TIMED(L, QGD_K_BPOINT, (boundaryPointKernel<6><<<gridFor(m.nBP), QGD_BLOCK, 0, L.stream>>>(
             m, reinterpret_cast<const double*>(c.bA), 6, reinterpret_cast<double*>(c.P), 6, 0, m.nGeomD == 3 ? 1 : -1)));   // U of the records: a pointVectorField in 3-D only
 }
+// The 3-D GaussVolPoint internal faces, FB = m.fblock faces per workgroup.  SGEO (Sf from the quadrilateral's diagonals) and FIXED (tile lists at
+// a fixed stride) exist at FB = 128 only (qgd_device_create sets m.sGeo / m.tileFlag there alone), and `Gauss upwind` tiles only in the default
+// configuration <128, SGEO, FIXED>: every other upwind case takes the gather kernel, which streams Sf.
+// (1) the staged kernel over every tile
+template <int FB, bool UPW>
+static void launchGvp3Tiles(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, bool adj) {
+    const int grid = (m.nIF + FB - 1) / FB;
+    if constexpr (FB != 128) faceFluxGvp3TileKernel<FB><<<grid, FB, m.tileLds, L.stream>>>(m, c, g, adj);
+    else if constexpr (UPW) faceFluxGvp3TileKernel<128, true, true, true><<<grid, 128, m.tileLds, L.stream>>>(m, c, g, adj);
+    else if (m.sGeo && m.tileFlag) faceFluxGvp3TileKernel<128, true, true><<<grid, 128, m.tileLds, L.stream>>>(m, c, g, adj);
+    else if (m.tileFlag) faceFluxGvp3TileKernel<128, false, true><<<grid, 128, m.tileLds, L.stream>>>(m, c, g, adj);
+    else if (m.sGeo) faceFluxGvp3TileKernel<128, true><<<grid, 128, m.tileLds, L.stream>>>(m, c, g, adj);
+    else faceFluxGvp3TileKernel<128><<<grid, 128, m.tileLds, L.stream>>>(m, c, g, adj);
+}
+// (2) the gather kernel over the tiles the staged kernel leaves out (m.tileSpill)
+template <int FB, bool UPW>
+static void launchGvp3Spill(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, bool adj) {
+    if (m.nTileSpill == 0) return;
+    if constexpr (FB == 128)
+        if (m.sGeo) { faceFluxGvp3Kernel<false, 128, true, UPW><<<m.nTileSpill, 128, 0, L.stream>>>(m, c, g, adj, m.tileSpill); return; }
+    faceFluxGvp3Kernel<false, FB, false, UPW><<<m.nTileSpill, FB, 0, L.stream>>>(m, c, g, adj, m.tileSpill);
+}
+// (3) the gather kernel over every face: meshes without tiles (QGD_FTILE=0, numberings whose tiles do not fit), debug fields
+template <bool DBG, int FB, bool UPW>
+static void launchGvp3Gather(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, bool adj) {
+    const int grid = (m.nIF + FB - 1) / FB;
+    if constexpr (FB == 128 && !UPW)
+        if (m.sGeo) { faceFluxGvp3Kernel<DBG, 128, true><<<grid, 128, 0, L.stream>>>(m, c, g, adj, nullptr); return; }
+    faceFluxGvp3Kernel<DBG, FB, false, UPW><<<grid, FB, 0, L.stream>>>(m, c, g, adj, nullptr);
+}
+template <bool DBG, int FB, bool UPW>
+static void launchGvp3(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, bool adj) {
+    if constexpr (!DBG && (!UPW || FB == 128)) {
+        if (m.tileOff != nullptr && (!UPW || (m.sGeo && m.tileFlag))) {
+            launchGvp3Tiles<FB, UPW>(L, m, c, g, adj);
+            launchGvp3Spill<FB, UPW>(L, m, c, g, adj);
+            return;
+        }
+    }
+    launchGvp3Gather<DBG, FB, UPW>(L, m, c, g, adj);
+}
 template <bool DBG, bool UPW>
 static void launchFaceFluxT(const Launcher& L, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, bool adj) {
     const int grid = gridFor(m.nIF);
@@ -2151,35 +2082,9 @@ static void launchFaceFluxT(const Launcher& L, int stencil, const MeshView& m, c
         case ST_REDUCED: faceFluxReducedKernel<DBG, UPW><<<grid, QGD_BLOCK, 0, L.stream>>>(m, c, g, adj); break;
         case ST_LSQ: faceFluxLsqKernel<DBG, UPW><<<grid, QGD_BLOCK, 0, L.stream>>>(m, c, g, adj); break;
         case ST_GVP3:
-            if constexpr (UPW) {
-                // `Gauss upwind` fluxes: the default tile configuration has its upwind instantiation, every other one takes the gather kernel
-                if (!DBG && m.tileOff != nullptr && m.fblock == 128 && m.tileWaves == 3 && m.sGeo && m.tileFlag) {
-                    faceFluxGvp3TileKernel<128, 3, true, true, true><<<(m.nIF + 127) / 128, 128, m.tileLds, L.stream>>>(m, c, g, adj);
-                    if (m.nTileSpill > 0) faceFluxGvp3Kernel<false, 128, true, true><<<m.nTileSpill, 128, 0, L.stream>>>(m, c, g, adj, m.tileSpill);
-                } else if (m.fblock == 64) faceFluxGvp3Kernel<DBG, 64, false, true><<<(m.nIF + 63) / 64, 64, 0, L.stream>>>(m, c, g, adj, nullptr);
-                else if (m.fblock == 128) faceFluxGvp3Kernel<DBG, 128, false, true><<<(m.nIF + 127) / 128, 128, 0, L.stream>>>(m, c, g, adj, nullptr);
-                else faceFluxGvp3Kernel<DBG, 256, false, true><<<grid, QGD_BLOCK, 0, L.stream>>>(m, c, g, adj, nullptr);
-                break;
-            }
-            if (!DBG && m.tileOff != nullptr) {
-                if (m.fblock == 64) faceFluxGvp3TileKernel<64, 3><<<(m.nIF + 63) / 64, 64, m.tileLds, L.stream>>>(m, c, g, adj);
-                else if (m.fblock == 256) faceFluxGvp3TileKernel<256, 3><<<grid, QGD_BLOCK, m.tileLds, L.stream>>>(m, c, g, adj);
-                else if (m.tileWaves == 2) faceFluxGvp3TileKernel<128, 2><<<(m.nIF + 127) / 128, 128, m.tileLds, L.stream>>>(m, c, g, adj);
-                else if (m.tileWaves == 4) faceFluxGvp3TileKernel<128, 4><<<(m.nIF + 127) / 128, 128, m.tileLds, L.stream>>>(m, c, g, adj);
-                else if (m.sGeo && m.tileFlag) faceFluxGvp3TileKernel<128, 3, true, true><<<(m.nIF + 127) / 128, 128, m.tileLds, L.stream>>>(m, c, g, adj);
-                else if (m.tileFlag) faceFluxGvp3TileKernel<128, 3, false, true><<<(m.nIF + 127) / 128, 128, m.tileLds, L.stream>>>(m, c, g, adj);
-                else if (m.sGeo) faceFluxGvp3TileKernel<128, 3, true><<<(m.nIF + 127) / 128, 128, m.tileLds, L.stream>>>(m, c, g, adj);
-                else faceFluxGvp3TileKernel<128, 3><<<(m.nIF + 127) / 128, 128, m.tileLds, L.stream>>>(m, c, g, adj);
-                if (m.nTileSpill > 0) {
-                    if (m.sGeo && m.fblock == 128 && m.tileWaves == 3) faceFluxGvp3Kernel<false, 128, true><<<m.nTileSpill, 128, 0, L.stream>>>(m, c, g, adj, m.tileSpill);
-                    else if (m.fblock == 64) faceFluxGvp3Kernel<false, 64><<<m.nTileSpill, 64, 0, L.stream>>>(m, c, g, adj, m.tileSpill);
-                    else if (m.fblock == 256) faceFluxGvp3Kernel<false, 256><<<m.nTileSpill, 256, 0, L.stream>>>(m, c, g, adj, m.tileSpill);
-                    else faceFluxGvp3Kernel<false, 128><<<m.nTileSpill, 128, 0, L.stream>>>(m, c, g, adj, m.tileSpill);
-                }
-            } else if (m.fblock == 64) faceFluxGvp3Kernel<DBG, 64><<<(m.nIF + 63) / 64, 64, 0, L.stream>>>(m, c, g, adj, nullptr);
-            else if (m.fblock == 128 && m.sGeo && m.tileWaves == 3) faceFluxGvp3Kernel<DBG, 128, true><<<(m.nIF + 127) / 128, 128, 0, L.stream>>>(m, c, g, adj, nullptr);
-            else if (m.fblock == 128) faceFluxGvp3Kernel<DBG, 128><<<(m.nIF + 127) / 128, 128, 0, L.stream>>>(m, c, g, adj, nullptr);
-            else faceFluxGvp3Kernel<DBG, 256><<<grid, QGD_BLOCK, 0, L.stream>>>(m, c, g, adj, nullptr);
+            if (m.fblock == 64) launchGvp3<DBG, 64, UPW>(L, m, c, g, adj);
+            else if (m.fblock == 128) launchGvp3<DBG, 128, UPW>(L, m, c, g, adj);
+            else launchGvp3<DBG, 256, UPW>(L, m, c, g, adj);
             break;
         default: faceFluxGvp2Kernel<DBG, UPW><<<grid, QGD_BLOCK, 0, L.stream>>>(m, c, g, adj); break;
     }
@@ -2262,7 +2167,7 @@ void launchCellFinish(const Launcher& L, const MeshView& m, const CaseView& c, c
     const int n = (mode == 1) ? nList : m.nC;
     if (n == 0) return;
     // (mode 1 uses the monitor slots behind the fused kernel's / the cell kernel's, like launchCellUpdate)
-    const int slotBase = (mode == 1) ? std::max((m.nC + m.cblock - 1) / m.cblock, m.fuBlocks) : 0;
+    const int slotBase = (mode == 1) ? std::max((m.nC + 255) / 256, m.fuBlocks) : 0;
     QGD_TIMED(L, QGD_K_CELL, (cellFinishKernel<256><<<(n + 255) / 256, 256, 0, L.stream>>>(m, c, g, mode, list, nList, slotBase)));
 }
 // the implicitDiffusion branch's block-fused assembly of the U systems (fusedFaceCellKernel<..., IMPL = true>): more dynamic LDS than the
@@ -2292,9 +2197,7 @@ void launchCellUpdate(const Launcher& L, const MeshView& m, const CaseView& c, c
     const int n = (mode == 1) ? nList : m.nC;
     if (n == 0) return;
     const int slotBase = (mode == 1) ? cellBlocks(m) : 0;  // the list launch monitors min(rho), min(e) in its own slots
-    if (m.cblock == 64) QGD_TIMED(L, QGD_K_CELL, (cellUpdateKernel<64><<<(n + 63) / 64, 64, 0, L.stream>>>(m, c, g, mode, list, nList, slotBase)));
-    else if (m.cblock == 128) QGD_TIMED(L, QGD_K_CELL, (cellUpdateKernel<128><<<(n + 127) / 128, 128, 0, L.stream>>>(m, c, g, mode, list, nList, slotBase)));
-    else QGD_TIMED(L, QGD_K_CELL, (cellUpdateKernel<256><<<gridFor(n), QGD_BLOCK, 0, L.stream>>>(m, c, g, mode, list, nList, slotBase)));
+    QGD_TIMED(L, QGD_K_CELL, (cellUpdateKernel<256><<<gridFor(n), QGD_BLOCK, 0, L.stream>>>(m, c, g, mode, list, nList, slotBase)));
 }
 void launchBoundaryUpdate(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, const PatchBCDev* bc,
                           bool init, bool phiwRegistered, int mode, const int32_t* list, int nList) {
@@ -2319,7 +2222,7 @@ void launchResetReductions(const Launcher& L, const CaseView& c) { resetReductio
 void launchCellMinReduce(const Launcher& L, const CaseView& c) { cellMinReduceKernel<<<1, QGD_BLOCK, 0, L.stream>>>(c); }
 int faceBlocks(const MeshView& m) { return (m.nIF + 63) / 64; }
 int bfaceBlocks(const MeshView& m) { return gridFor(m.nBF); }
-int cellBlocks(const MeshView& m) { return (m.nC + 63) / 64; }  // slots laid out for the smallest cell tile
+int cellBlocks(const MeshView& m) { return (m.nC + 63) / 64; }  // (one slot per 64 cells: more than the 256-cell workgroups fill)
 // the message in the middle of the flux assembly: mid-step patch pressure and qgdFlux gradient of patch faces (2 doubles each)
 __global__ __launch_bounds__(QGD_BLOCK) void midHaloKernel(const CaseView c, const int32_t* __restrict__ bfaces, const int n,
                                                           double* __restrict__ buf, const int pack) {

@@ -836,11 +836,6 @@ struct PressureSolver {
         dist.buf = alloc<double>((size_t)n);      // the old one stays in `owned` until the solver goes (set-up only grows it twice)
         dist.bufCap = n;
     }
-    // the V-cycle is a fixed sequence of ~75 small launches on fixed buffers (r -> z); with QGD_MG_GRAPH=1 it is captured once into
-    // a hipGraph and replayed per CG iteration.  Measured: 5.11 -> 5.03 ms per step at 64^3, nothing at 128^3 / 200^3 (the
-    // asynchronous launches were already hidden), and rocprofv3 crashes on the captured graph -- hence opt-in.
-    hipGraphExec_t cycleGraph = nullptr;
-    bool cycleGraphTried = false;
 
     template <class T>
     T* alloc(size_t n, const T* host = nullptr) {
@@ -859,7 +854,6 @@ struct PressureSolver {
         return (T*)p;
     }
     ~PressureSolver() {
-        if (cycleGraph) (void)hipGraphExecDestroy(cycleGraph);
         for (void* p : owned) (void)hipFree(p);
         if (hostCtl) (void)hipHostFree(hostCtl);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -945,21 +939,10 @@ struct PressureSolver {
         tailZ = fused && rzPart ? z + ob : nullptr; tailR = r + ob; tailPart = rzPart;
         struct Reset { PressureSolver* s; ~Reset() { s->headDone = false; s->tailZ = nullptr; } } reset{this};
         if (precond == 1 && !L.empty()) {
-            if (!cycleGraphTried) {
-                cycleGraphTried = true;
-                hipGraph_t g = nullptr;
-                if (std::getenv("QGD_MG_GRAPH") && hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    bool ok = true;
-                    try { vcycle(0, r + ob, z + ob); } catch (...) { ok = false; }
-                    if (hipStreamEndCapture(stream, &g) != hipSuccess || !ok || !g) { g = nullptr; (void)hipGetLastError(); }
-                    if (g) {
-                        if (hipGraphInstantiate(&cycleGraph, g, nullptr, nullptr, 0) != hipSuccess) { cycleGraph = nullptr; (void)hipGetLastError(); }
-                        (void)hipGraphDestroy(g);
-                    }
-                }
-            }
-            if (cycleGraph) PCHECK(hipGraphLaunch(cycleGraph, stream));
-            else vcycle(0, r + ob, z + ob);
+            // the V-cycle is a fixed sequence of ~75 small launches on fixed buffers (r -> z), launched one by one: replayed as a captured
+            // graph it measured 5.11 -> 5.03 ms per step at 64^3 and nothing at 128^3 / 200^3 (the asynchronous launches were already
+            // hidden), and the profiler crashed on the replay -- not kept
+            vcycle(0, r + ob, z + ob);
         } else {
             MgLevelDev jl; jl.n = n; jl.diag = diag + ob;
             const double* none = nullptr; double* noOut = nullptr;
@@ -1456,7 +1439,7 @@ PressureSolver* pressureSolverCreate(hipStream_t stream, const MeshView& m, cons
         };
         S->nu = (int)knob("QGD_MG_NU", S->nu, 1, 8);
         S->nu0 = (int)knob("QGD_MG_NU0", 0, 0, 8);
-        S->fuse = knob("QGD_MG_FUSE", 1, 0, 1) != 0 && !std::getenv("QGD_MG_GRAPH");
+        S->fuse = knob("QGD_MG_FUSE", 1, 0, 1) != 0;
         if (S->nu0 == 0) S->nu0 = S->nu;
         S->oc = knob("QGD_MG_OC", S->oc, 0.5, 3.0);
         S->omega = knob("QGD_MG_OMEGA", S->omega, 0.1, 1.0);

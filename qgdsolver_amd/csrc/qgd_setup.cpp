@@ -558,7 +558,6 @@ StaticData buildStaticData(const HostMesh& m) {
                 rank[f] = r;
                 maxRank = std::max(maxRank, r);
             }
-            const bool labelOrder = std::getenv("QGD_FLUX_LABEL_ORDER") != nullptr;  // experiment switch
             const int64_t nChunks = std::max<int64_t>(1, std::min<int64_t>(1024, nIF / 4096));
             const size_t nR = (size_t)maxRank + 1;
             std::vector<int64_t> cnt((size_t)nChunks * nR, 0);
@@ -573,7 +572,7 @@ StaticData buildStaticData(const HostMesh& m) {
             }
 #pragma omp parallel for schedule(static)
             for (int64_t ch = 0; ch < nChunks; ++ch)
-                for (int64_t f = chunkLo(ch); f < chunkLo(ch + 1); ++f) s.fpos[f] = labelOrder ? (int32_t)f : (int32_t)(cnt[(size_t)ch * nR + rank[f]]++);
+                for (int64_t f = chunkLo(ch); f < chunkLo(ch + 1); ++f) s.fpos[f] = (int32_t)(cnt[(size_t)ch * nR + rank[f]]++);
 #pragma omp parallel for schedule(static)
             for (int64_t k = 0; k < (int64_t)cfItemCsr.size(); ++k) {
                 const int32_t it = cfItemCsr[k], f = it >= 0 ? it : ~it;

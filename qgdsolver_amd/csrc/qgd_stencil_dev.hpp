@@ -53,24 +53,13 @@ __device__ __forceinline__ double4 ld3(const double* __restrict__ base, const in
 
 // Streamed-once data (per-face geometry, gather lists) is loaded non-temporally so it does not push the
 // re-used cell/vertex records out of the 4 MiB L2 of the XCD.
-#ifndef QGD_NT
-#define QGD_NT 1
-#endif
 template <class T>
 __device__ __forceinline__ T ldStream(const T* p) {
-#if QGD_NT
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 template <class T>
 __device__ __forceinline__ void stStream(T* p, T v) {
-#if QGD_NT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 template <int NC>

@@ -1,8 +1,14 @@
-"""Where a block's lifetime goes inside fusedFaceCellKernel: the -DQGD_FU_CLOCK=1 build of the library (make -C qgdsolver_amd/csrc
-BUILD=/tmp/bclk OUT=ab_libs/libqgd_clock.so EXTRA=-DQGD_FU_CLOCK=1) reads s_memtime at the kernel's phase boundaries and leaves the
-differences in the new records of the block's own cells; ONE step, then the fields are read back as tick counts.
+"""Where a block's lifetime goes inside fusedFaceCellKernel.  The instrumentation is a patch, not a switch of the library: apply
+scripts/probes/fused_phase_clock_probe.patch, build the patched source next to the product with BUILD= / OUT=, take the patch off again,
+then run this script on that build:
 
+    git apply scripts/probes/fused_phase_clock_probe.patch
+    make -C qgdsolver_amd/csrc BUILD=/tmp/bclk OUT=$PWD/ab_libs/libqgd_clock.so
+    git apply -R scripts/probes/fused_phase_clock_probe.patch
     QGD_AMD_LIB=ab_libs/libqgd_clock.so python scripts/fused_phase_clock.py [n=200]
+
+The patched kernel reads the shader clock at its phase boundaries and leaves the differences in the new records of the block's own cells;
+ONE step, then the fields are read back as tick counts.
 
 rho: start -> the block's lists are there (round 0) | Ux: -> records loaded and staged in LDS (round 1) | Uy: first barrier + vertex values |
 Uz: second barrier + the faces | p: third barrier, flux planes into LDS, fourth barrier | e: the cell's sums and advanceCell.
