@@ -191,7 +191,10 @@ int qgd_mesh_shard(qgd_mesh_t global, int32_t nRanks, const int32_t* cellStart, 
  * packed message it unpacks.  pairs = 2 * nPairs patch indices {A, B} with face i of A = face i of B shifted by one vector (checked:
  * rotational pairs are refused with QGD_ERR_NOT_IMPLEMENTED); nPairs = 0 pairs consecutive cyclic patches.  Real cells, points and patch
  * faces keep their labels ("cellGlobal" = the original of every cell).  A case on such a mesh steps with plain qgd_case_step (explicit branch):
- * the library refreshes the copies from their originals after every step, on the case's stream. */
+ * the library refreshes the copies from their originals after every step, on the case's stream.  The copies belong to the library: what
+ * qgd_case_set_fields is handed for them is never computed on -- qgd_case_step and qgd_case_update_fluxes give them their originals' records
+ * first.  qgd_case_step_phase is refused on such a device (QGD_ERR_INVALID, "periodic device"): between two phases nothing would refresh
+ * the copies.  qgd_case_set_bc asks for a new qgd_case_set_fields, as on every mesh, and the copies are refreshed again after it. */
 int qgd_mesh_unroll_cyclic(qgd_mesh_t mesh, int32_t nPairs, const int32_t* pairs, qgd_mesh_t* out);
 /* number of halo slots (neighbouring shards) of a mesh; 0 when unsharded, 2 for a qgd_mesh_box slab */
 int qgd_mesh_halo_slots(qgd_mesh_t m, int32_t* nSlots);

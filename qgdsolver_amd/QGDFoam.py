@@ -99,6 +99,8 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         if world > 1 or opt.get("implicitDiffusion") or renumber != "none":
             raise ff.FoamFileError(f"{case_dir}: a case with cyclic patches runs on one rank, explicit branch (QGD {{ implicitDiffusion false; }}), "
                                    "in the case's own cell order")
+        if "alphaQGD" in fields or "ScQGD" in fields:   # (foamfile.load_case refuses the same case; before any device exists)
+            raise ff.FoamFileError(f"{case_dir}: a case with cyclic patches runs with uniform alphaQGD / ScQGD (no alphaQGD or ScQGD field file)")
         mesh = gmesh.unroll_cyclic(gmesh.cyclic_pairs)
         cells = mesh.array("cellGlobal")
         owned = np.arange(mesh.nCells) < n_global

@@ -303,7 +303,8 @@ struct qgd_case_s {
     bool fusedAdj = false;      // adjustTimeStep: the blocks run up to their flux sums + Courant partials, cellFinishKernel advances once deltaT is known (QGD_FUSED_ADJUST)
     bool fusedImpl = false;     // implicitDiffusion: vertex values, QGD fluxes, tauMC and the U systems' rows are one launch on the same blocks (QGD_IMPL_FUSED)
     std::vector<double*> selfBuf;   // cyclic pairs served by ghost cells: one message buffer per halo slot (selfHaloExchange)
-    bool ghostsCurrent = false;     // ... and whether the copies hold their originals' records (reset by set_fields only; set by qgd_case_step alone)
+    bool ghostsCurrent = false;     // ... and whether the copies hold their originals' records: reset by set_fields (the only way on after set_bc / set_qgd_coeffs, which
+                                    //     clear fieldsSet), set by qgd_case_step and qgd_case_update_fluxes, which refresh the copies first; qgd_case_step_phase is refused
     bool hasQgdFlux = false;
     bool phiwRegistered = false;
     bool fieldsSet = false;
@@ -1571,7 +1572,10 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
         cv.bA = a.alloc<RecA>(v.nBF); cv.bB = a.alloc<RecB>(v.nBF);
         cv.bG = a.alloc<double>(v.nBF); cv.bPhiw = a.alloc<double>(v.nBF); cv.bPmid = a.alloc<double>(v.nBF);
         cv.bRhoLag = a.alloc<double>(v.nBF);
-        cv.nBlkFace = faceBlocks(v) + bfaceBlocks(v);
+        // (the cell blocks under Courant-number control get slots of their own behind the patch kernel's: a mesh of small blocks has more
+        // blocks than 64-face tiles, and a block that wrote into the tiles' slots would overwrite the patch faces' partials and run past the table)
+        cv.fuBlkFace = faceBlocks(v) + bfaceBlocks(v);
+        cv.nBlkFace = cv.fuBlkFace + (c->fusedAdj ? v.fuBlocks : 0);
         cv.nBlkCell = std::max(cellBlocks(v), v.fuBlocks) + (d->nSendAll + 63) / 64;   // (the fused kernel monitors min(rho), min(e) per block)
         cv.blkFace = a.alloc<double>(2 * (size_t)std::max(1, cv.nBlkFace));
         cv.blkFace2 = a.alloc<double>(2 * (size_t)QGD_FACE_REDUCE_PARTIALS);
@@ -1705,6 +1709,7 @@ static void assembleFluxes(qgd_case_s* c, bool adjust, int part = 0, bool intern
     if (c->fusedAdj && !internalFaces && !c->view.dbg) launchFusedAdjust(L, m, v, c->gas);
 }
 static bool midExchangeNeeded(const qgd_case_s* c) { return c->dev->sharded() && c->pRefresh && c->hasQgdFlux; }
+static void selfHaloExchange(qgd_case_s* c, bool mid);
 
 int qgd_case_set_fields(qgd_case_t c, const double* U, const double* T, const double* p) {
     QGD_TRY
@@ -1759,7 +1764,13 @@ int qgd_case_update_fluxes(qgd_case_t c) {
     if (!c->dbgBuf) c->dbgBuf = c->arena.alloc<double>((size_t)DBG_COUNT * m.nF);
     HIP_CHECK(hipMemsetAsync(c->dbgBuf, 0, sizeof(double) * (size_t)DBG_COUNT * m.nF, c->stream()));
     c->view.dbg = c->dbgBuf;
-    assembleFluxes(c, false);
+    if (c->dev->periodic()) {
+        // cyclic pairs served by ghost cells: the copies belong to the library, whatever the caller put into them with set_fields -- they take
+        // their originals' records before anything is computed from them (and the mid-step message where qgd_case_step has one)
+        if (!c->ghostsCurrent) { selfHaloExchange(c, false); c->ghostsCurrent = true; }
+        if (midExchangeNeeded(c)) { assembleFluxes(c, false, 1); selfHaloExchange(c, true); assembleFluxes(c, false, 2); }
+        else assembleFluxes(c, false);
+    } else assembleFluxes(c, false);
     c->view.dbg = nullptr;
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream()));
@@ -1974,6 +1985,9 @@ int qgd_case_step_phase(qgd_case_t c, int phase) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_case_step_phase: call qgd_case_set_fields first");
+    if (c->dev->periodic())
+        return fail(QGD_ERR_INVALID, "qgd_case_step_phase: a periodic device (cyclic patches served by ghost copies, qgd_mesh_unroll_cyclic) is stepped with "
+                                     "qgd_case_step, which refreshes the copies after every step; a phase would compute on stale copies");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
     if (c->opt.implicitDiffusion && (phase == 10 || phase == 11))
         return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_step_phase: the implicitDiffusion branch has no boundary-layer-first order (its linear "

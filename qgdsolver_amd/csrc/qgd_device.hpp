@@ -112,10 +112,12 @@ struct CaseView {
     double* cellSum;                // 5*nC, fused step under Courant-number control only: the ordered net flux sums of every owned cell (the blocks stop there until deltaT is known)
     double* flux;                   // 5*nF net face fluxes, SoA: flux[k*nF + fpos[f]] (boundary faces: their label)
     double* red;                    // [0]=max Co, [1]=min tauQGDf, [2]=min rho, [3]=min e
-    double* blkFace;                // 2 per face-kernel workgroup (internal then boundary): max Cof, min tauQGDf
+    double* blkFace;                // 2 per face-kernel workgroup (internal, then boundary, then the cell blocks of the fused step under
+                                    //     Courant-number control): max Cof, min tauQGDf
     double* blkFace2;               // 2 x QGD_FACE_REDUCE_PARTIALS: the first level of their fold (launchFaceReduce)
     double* blkCell;                // 2 per cell-kernel workgroup: min rho, min e since the last query
     int32_t nBlkFace, nBlkCell;
+    int32_t fuBlkFace;              // first slot of the cell blocks in blkFace (behind the face kernels' and the patch kernel's: a block never shares one)
     double* dt;                     // [0]=deltaT (device resident so adjustTimeStep needs no host round trip)
     double* dbg;                    // optional debug face fields (nullptr in the product path)
     // non-uniform alphaQGD / ScQGD (the READ_IF_PRESENT fields of QGDCoeffs_8C L119-160, constScPrModel1_8C L66-79);

@@ -1074,7 +1074,7 @@ void cellUpdateKernel(const MeshView m, const CaseView c, const GasModel gm, con
 // QGD face kernel, implFaceTileKernel and implCellUKernel are this one launch, in the explicit step's LDS (three blocks per CU).  Unsharded cases.
 // ADJ = Courant-number control [QGDCourantNo.H L36-53, setDeltaT-QGDQHD.H L41-61]: the new deltaT needs every face's Courant number and
 // tauQGDf before the first cell may advance, so the block stops after its ordered sums: it leaves max Cof / min tauQGDf of its faces in its
-// slot of blkFace (the three kernels' partial slots; faceReduceKernel folds them, deltaTKernel follows) and the five net flux sums of each own
+// slot of blkFace (slot fuBlkFace + block, behind the face kernels' and the patch kernel's; faceReduceKernel folds them all, deltaTKernel follows) and the five net flux sums of each own
 // cell in cellSum; cellFinishKernel advances the cells from there.  Vertex values and face fluxes still never reach device memory.
 template <bool SGEO, bool UPW = false, bool IMPL = false, bool ADJ = false>
 // (IMPL with `Gauss upwind` fluxes needs a few registers more than three waves per SIMD leave: that instantiation is compiled for two -- no scratch)
@@ -1507,7 +1507,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             emin = (An.e == An.e) ? An.e : -1e300;
         }
     }
-    if constexpr (ADJ) blockMaxMin<NT>(cofMax, tauMinAll, c.blkFace + 2 * (size_t)blk, false);
+    if constexpr (ADJ) blockMaxMin<NT>(cofMax, tauMinAll, c.blkFace + 2 * ((size_t)c.fuBlkFace + blk), false);
     else blockMaxMin<NT>(-rmin, emin, c.blkCell + 2 * (size_t)blk, true);
 }
 

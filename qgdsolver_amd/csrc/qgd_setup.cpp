@@ -749,7 +749,11 @@ struct OneBlock {
         for (size_t lf = 0; lf < face.size() / 4; ++lf) { mix((uint32_t)face[4 * lf + 1]); mix((uint32_t)face[4 * lf + 2]); mix((uint32_t)face[4 * lf + 3]); }
         for (size_t j = 0; j < (size_t)nOwn; ++j) { mix(nEntry[j]); for (int k = 0; k < nEntry[j]; ++k) mix((uint32_t)entry[j * (size_t)maxE + k]); }
         for (size_t lv = 0; lv < verts.size(); ++lv) { mix(vCount[lv]); for (int k = 0; k < vCount[lv]; ++k) mix(vPos[lv * (size_t)maxPE + k]); }
+#ifdef QGD_TEST_TOPOHASH_BITS   // host tests only: a fingerprint of a few bits, so that unlike blocks are certain to share one
+        return {h1 & ((1ull << QGD_TEST_TOPOHASH_BITS) - 1), 0};
+#else
         return {h1, h2};
+#endif
     }
 };
 }  // namespace
@@ -1134,7 +1138,7 @@ FusedBlocks buildFusedBlocks(const StaticData& s) {
     B.capE = maxE;
     B.capPE = maxPE; B.maxTot = maxC; B.maxAll = maxAll; B.maxLds = maxLds; B.maxLdsImpl = maxLdsImpl;
     // templates: the distinct topology fingerprints in ascending order (deterministic); a block's template = its fingerprint's rank; the
-    // template's tables are written by the first block (in launch order) that has it.  QGD_FUSED_TEMPLATES=0: one template per block.
+    // template's tables are written by the first block (in launch order) that has it, and every other block compares its own with them.  QGD_FUSED_TEMPLATES=0: one template per block.
     std::vector<int32_t> tplOf((size_t)nBlocks, 0);      // by launch position
     std::vector<int64_t> tplWriter;                       // range-order index of the block that writes template t
     int64_t nTemplates = nBlocks;
@@ -1176,40 +1180,84 @@ FusedBlocks buildFusedBlocks(const StaticData& s) {
     B.vPos.resize((size_t)nTemplates * B.capPE * B.capV);
     B.facePos.resize((size_t)nTemplates * B.capF * 3);
     B.entry.resize((size_t)nTemplates * B.capE * kFusedCells);
+    // a template's tables as block `o` wants them, at template slot t: written (the template's writer), or compared with what is there
+    // (every other block of the template: equal fingerprints are no proof of equal topologies)
+    auto templateTables = [&](const OneBlock& o, size_t t, bool write) {
+        const int32_t nV = (int32_t)o.verts.size(), nF = (int32_t)o.face.size() / 4;
+        bool same = true;
+        auto put = [&](auto& slot, auto v) { if (write) slot = v; else same = same && slot == v; };
+        for (int32_t i = 0; i < B.capV; ++i) {
+            const int32_t n = i < nV ? o.vCount[i] : 0;
+            for (int32_t e = 0; e < B.capPE; ++e) put(B.vPos[(t * B.capPE + e) * B.capV + i], e < n ? o.vPos[(size_t)i * o.maxPE + e] : (uint16_t)0);
+        }
+        for (int32_t i = 0; i < B.capF; ++i)
+            for (int q = 0; q < 3; ++q) put(B.facePos[(t * B.capF + i) * 3 + q], nF ? (uint32_t)o.face[4 * (size_t)std::min(i, nF - 1) + 1 + q] : 0u);
+        for (int32_t j = 0; j < kFusedCells; ++j) {
+            const int32_t nE = j < o.nOwn ? o.nEntry[j] : 0;
+            for (int32_t e = 0; e < B.capE; ++e) put(B.entry[(t * B.capE + e) * kFusedCells + j], e < nE ? o.entry[(size_t)j * o.maxE + e] : 0);
+        }
+        return same;
+    };
+    // the counts a block reads its template's tables with: the block's own against those of the template's writer (at launch position w)
+    auto sameCounts = [&](size_t b, size_t w) {
+        for (int q = 0; q < 4; ++q) if (B.hdr[4 * b + q] != B.hdr[4 * w + q]) return false;
+        if (B.hdr2[4 * b] != B.hdr2[4 * w]) return false;
+        return std::equal(&B.nEntry[b * kFusedCells], &B.nEntry[b * kFusedCells] + kFusedCells, &B.nEntry[w * kFusedCells]) &&
+               std::equal(&B.vCount[b * B.capV], &B.vCount[b * B.capV] + B.capV, &B.vCount[w * B.capV]);
+    };
+    // Pass 2 in two sweeps when blocks share templates: the writers first, then the others, which find their template's tables complete and
+    // compare their own with them once.  A block whose tables differ (two topologies, one fingerprint) gets a template of its own below.
+    std::vector<int64_t> mismatched;
+    for (int sweep = 0; sweep < (templated ? 2 : 1); ++sweep) {
 #pragma omp parallel
-    {
-        std::vector<SmallMap> maps(3);
-        OneBlock o;
+        {
+            std::vector<SmallMap> maps(3);
+            OneBlock o;
 #pragma omp for schedule(dynamic, 64)
-        for (int64_t ib = 0; ib < nBlocks; ++ib) {
-            const auto [b0, b1] = blk[ib];
-            tryBlock(b0, b1, o, maps[0], maps[1], maps[2]);
-            const size_t b = (size_t)first[ib];
-            const int32_t nTot = (int32_t)o.cells.size(), nV = (int32_t)o.verts.size(), nF = (int32_t)o.face.size() / 4;
-            const size_t t = (size_t)tplOf[b];
-            B.hdr[4 * b] = o.nOwn; B.hdr[4 * b + 1] = o.nAll; B.hdr[4 * b + 2] = nV; B.hdr[4 * b + 3] = nF;
-            B.hdr2[4 * b] = nTot; B.hdr2[4 * b + 1] = (int32_t)t; B.hdr2[4 * b + 2] = B.hdr2[4 * b + 3] = 0;
-            for (int32_t i = 0; i < B.capC; ++i) B.cells[b * B.capC + i] = o.cells[std::min(i, nTot - 1)];
-            for (int32_t i = 0; i < B.capV; ++i) {
-                const int32_t n = i < nV ? o.vCount[i] : 0;
-                B.vCount[b * B.capV + i] = (uint8_t)n;
-                for (int32_t e = 0; e < B.capPE; ++e) B.vW[(b * B.capPE + e) * B.capV + i] = e < n ? o.vW[(size_t)i * o.maxPE + e] : 0.0;
-            }
-            for (int32_t i = 0; i < B.capV; ++i) B.verts[b * B.capV + i] = nV ? o.verts[std::min(i, nV - 1)] : 0;
-            for (int32_t i = 0; i < B.capF; ++i) B.faceLabel[b * B.capF + i] = nF ? o.face[4 * (size_t)std::min(i, nF - 1)] : 0;
-            for (int32_t j = 0; j < kFusedCells; ++j) B.nEntry[b * kFusedCells + j] = (uint8_t)(j < o.nOwn ? o.nEntry[j] : 0);
-            if (templated && tplWriter[t] != ib) continue;   // the template's tables are another block's to write
-            for (int32_t i = 0; i < B.capV; ++i) {
-                const int32_t n = i < nV ? o.vCount[i] : 0;
-                for (int32_t e = 0; e < B.capPE; ++e) B.vPos[(t * B.capPE + e) * B.capV + i] = e < n ? o.vPos[(size_t)i * o.maxPE + e] : (uint16_t)0;
-            }
-            for (int32_t i = 0; i < B.capF; ++i)
-                for (int q = 0; q < 3; ++q) B.facePos[(t * B.capF + i) * 3 + q] = nF ? (uint32_t)o.face[4 * (size_t)std::min(i, nF - 1) + 1 + q] : 0u;
-            for (int32_t j = 0; j < kFusedCells; ++j) {
-                const int32_t nE = j < o.nOwn ? o.nEntry[j] : 0;
-                for (int32_t e = 0; e < B.capE; ++e) B.entry[(t * B.capE + e) * kFusedCells + j] = e < nE ? o.entry[(size_t)j * o.maxE + e] : 0;
+            for (int64_t ib = 0; ib < nBlocks; ++ib) {
+                const size_t b = (size_t)first[ib];
+                const size_t t = (size_t)tplOf[b];
+                const bool writer = !templated || tplWriter[t] == ib;
+                if (writer != (sweep == 0)) continue;
+                const auto [b0, b1] = blk[ib];
+                tryBlock(b0, b1, o, maps[0], maps[1], maps[2]);
+                const int32_t nTot = (int32_t)o.cells.size(), nV = (int32_t)o.verts.size(), nF = (int32_t)o.face.size() / 4;
+                B.hdr[4 * b] = o.nOwn; B.hdr[4 * b + 1] = o.nAll; B.hdr[4 * b + 2] = nV; B.hdr[4 * b + 3] = nF;
+                B.hdr2[4 * b] = nTot; B.hdr2[4 * b + 1] = (int32_t)t; B.hdr2[4 * b + 2] = B.hdr2[4 * b + 3] = 0;
+                for (int32_t i = 0; i < B.capC; ++i) B.cells[b * B.capC + i] = o.cells[std::min(i, nTot - 1)];
+                for (int32_t i = 0; i < B.capV; ++i) {
+                    const int32_t n = i < nV ? o.vCount[i] : 0;
+                    B.vCount[b * B.capV + i] = (uint8_t)n;
+                    for (int32_t e = 0; e < B.capPE; ++e) B.vW[(b * B.capPE + e) * B.capV + i] = e < n ? o.vW[(size_t)i * o.maxPE + e] : 0.0;
+                }
+                for (int32_t i = 0; i < B.capV; ++i) B.verts[b * B.capV + i] = nV ? o.verts[std::min(i, nV - 1)] : 0;
+                for (int32_t i = 0; i < B.capF; ++i) B.faceLabel[b * B.capF + i] = nF ? o.face[4 * (size_t)std::min(i, nF - 1)] : 0;
+                for (int32_t j = 0; j < kFusedCells; ++j) B.nEntry[b * kFusedCells + j] = (uint8_t)(j < o.nOwn ? o.nEntry[j] : 0);
+                if (writer) { templateTables(o, t, true); continue; }
+                if (sameCounts(b, (size_t)first[tplWriter[t]]) && templateTables(o, t, false)) continue;
+#pragma omp critical(qgdTemplateMismatch)
+                mismatched.push_back(ib);
             }
         }
+    }
+    if (!mismatched.empty()) {
+        std::sort(mismatched.begin(), mismatched.end(), [&](int64_t a, int64_t b) { return first[a] < first[b]; });   // (deterministic template ids)
+        const int64_t nT = nTemplates + (int64_t)mismatched.size();
+        if (nT * (int64_t)std::max({B.capV * B.capPE, 3 * B.capF, B.capE * kFusedCells}) > (int64_t)INT32_MAX) return FusedBlocks{};
+        B.vPos.resize((size_t)nT * B.capPE * B.capV);
+        B.facePos.resize((size_t)nT * B.capF * 3);
+        B.entry.resize((size_t)nT * B.capE * kFusedCells);
+        std::vector<SmallMap> maps(3);
+        OneBlock o;
+        for (size_t k = 0; k < mismatched.size(); ++k) {
+            const int64_t ib = mismatched[k];
+            const size_t t = (size_t)nTemplates + k;
+            tryBlock(blk[ib].first, blk[ib].second, o, maps[0], maps[1], maps[2]);
+            templateTables(o, t, true);
+            B.hdr2[4 * (size_t)first[ib] + 1] = (int32_t)t;
+        }
+        B.nTemplates = (int32_t)nT;
+        B.templateMismatches = (int32_t)mismatched.size();
     }
     B.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
     return B;

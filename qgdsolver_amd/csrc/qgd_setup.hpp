@@ -158,6 +158,7 @@ struct FusedBlocks {
     // in round 5 stay in L2 instead.  Blocks with a patch face (its entry is the face's own label) and the blocks of a jittered, renumbered mesh
     // (no two bricks list their cells alike) have templates of their own: the same bytes as before, read through the template id.
     int32_t nTemplates = 0, templated = 0;
+    int32_t templateMismatches = 0;   // blocks whose fingerprint matched a template that their tables did not: each got a template of its own (a collision; 0 in practice)
     RawVec<uint32_t> facePos;    // 3 per face, capF faces per template: lo | ln << 16, v0 | v1 << 16, v2 | v3 << 16 (positions in the staged lists)
     // the vertex values formed inside the block (volPointInterpolation's inverse-distance weights, pointCells order): the cells around the
     // block's vertices that are neither its own nor across one of its faces ("extra": edge and corner neighbours) are staged too, behind

@@ -6,7 +6,15 @@
 //     labels; every list is padded to its stride with its last entry;
 //   * the face entries of an own cell are the cell's faces in ascending label with the right side bit, patch faces as ~label;
 //   * a vertex's cell positions are its pointCells in order, with the weights of the vertex kernel's table; patch points have count 0;
-//   * the maxima are the maxima, and no block of more than 32 cells needs more LDS than lets three blocks share a CU.
+//   * the maxima are the maxima, and no block of more than 32 cells needs more LDS than lets three blocks share a CU;
+//   * blocks that share a template have the same tables: the builder compares them once and counts the blocks whose fingerprint matched
+//     a template that their tables did not (FusedBlocks::templateMismatches; each gets a template of its own).  With the full fingerprint
+//     the count is zero and the template counts are what they were before the comparison existed.  Compiled a second time with
+//     -DQGD_TEST_TOPOHASH_BITS=1 -- a fingerprint of one bit: unlike blocks are certain to share one -- the count must be positive, and
+//     every block's tables, read through its template, must still be what the mesh dictates (the entry-by-entry checks above);
+//   * thin meshes, whose blocks are small, have more blocks than 64-face tiles of internal faces -- the premise of
+//     tests/test_courant_small_blocks_gpu.py: under Courant-number control a block needs a partial slot that is neither a face tile's
+//     nor the patch kernel's.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -27,7 +35,10 @@ static int fails = 0;
         }                                                  \
     } while (0)
 
-static void checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, int maxTemplates = -1) {
+static int mismatchesSeen = 0;
+
+// wantTemplates: the template count of the full fingerprint, as it was before the builder compared tables (-1: not pinned)
+static FusedBlocks checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, int maxTemplates = -1, int wantTemplates = -1) {
     if (m.magSf.empty()) m.computeGeometry();
     m.computeDerived();
     const StaticData s = buildStaticData(m);
@@ -35,7 +46,7 @@ static void checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, i
     std::printf("%s: %d cells, %d blocks (%d boundary-layer), strides %d %d %d %d %d, faces computed %lld of %d\n", tag, s.nC, B.nBlocks, B.nLayerBlocks, B.capC,
                 B.capV, B.capF, B.capE, B.capPE, (long long)B.facesComputed, s.nIF);
     CHECK(B.nBlocks > 0, "%s: no blocks", tag);
-    if (B.nBlocks == 0) return;
+    if (B.nBlocks == 0) return B;
     {
         int64_t owned = 0;
         for (int32_t c = 0; c < s.nC; ++c) owned += (s.ghost.empty() || s.ghost[c] != 1) ? 1 : 0;
@@ -47,7 +58,13 @@ static void checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, i
     std::vector<int> ownerBlock((size_t)s.nC, -1);
     std::vector<int> tplUsed((size_t)std::max(B.nTemplates, 1), 0);
     std::printf("    %d templates for %d blocks (%s)\n", B.nTemplates, B.nBlocks, B.templated ? "shared" : "one per block");
+    std::printf("    %d blocks matched a template by fingerprint and not by their tables\n", B.templateMismatches);
+    mismatchesSeen += B.templateMismatches;
+#ifndef QGD_TEST_TOPOHASH_BITS
     CHECK(maxTemplates < 0 || B.nTemplates <= maxTemplates, "%s: %d templates, at most %d wanted", tag, B.nTemplates, maxTemplates);
+    CHECK(B.templateMismatches == 0, "%s: %d template mismatches with the full fingerprint", tag, B.templateMismatches);
+    CHECK(wantTemplates < 0 || B.nTemplates == wantTemplates, "%s: %d templates, %d before the tables were compared", tag, B.nTemplates, wantTemplates);
+#endif
     int32_t maxTot = 0, maxAll = 0, maxV = 0, maxF = 0, maxLds = 0;
     int64_t faces = 0;
     for (int32_t b = 0; b < B.nBlocks; ++b) {
@@ -89,7 +106,8 @@ static void checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, i
         CHECK((int32_t)want.size() == nF, "block %d: %d faces listed, %d wanted", b, nF, (int)want.size());
         // the block's local topology sits in its template (hdr2[1]); blocks that share one must expand to their own labels all the same
         const int32_t tpl = B.hdr2[4 * b + 1];
-        CHECK(tpl >= 0 && tpl < B.nTemplates && (B.templated || tpl == b) && (B.templated == (B.nTemplates < B.nBlocks)), "block %d template %d of %d", b, tpl, B.nTemplates);
+        CHECK(tpl >= 0 && tpl < B.nTemplates && (B.templated || tpl == b) &&
+              (B.templateMismatches > 0 || B.templated == (B.nTemplates < B.nBlocks)), "block %d template %d of %d", b, tpl, B.nTemplates);
         tplUsed[tpl]++;
         const int32_t* face = &B.faceLabel[(size_t)b * B.capF];
         const uint32_t* fpos = &B.facePos[(size_t)tpl * B.capF * 3];
@@ -147,31 +165,62 @@ static void checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, i
           maxF, B.maxTot, B.maxAll, B.maxV, B.maxF);
     CHECK(maxLds == B.maxLds, "%s: LDS %d vs %d", tag, maxLds, B.maxLds);
     CHECK(faces == B.facesComputed && faces >= 0, "%s: faces computed", tag);
+    return B;
+}
+
+// A chain of cells (one internal face and four vertices of its own per cell: the 256 vertices a block stages hold 50 to 60 cells) has
+// more blocks than 64-face tiles of internal faces.  Under Courant-number control the blocks once wrote their partials into slots
+// [0, nBlocks) of a table whose slots [faceBlocks, faceBlocks + bfaceBlocks) belong to the patch kernel's 256-face workgroups: blocks
+// faceBlocks .. nBlocks-1 then overwrote the partials of the first 256 * (nBlocks - faceBlocks) patch faces.  inletOverwritten: patch 0
+// (xMin, the inlet of tests/test_courant_small_blocks_gpu.py) lies among those faces entirely.
+// (No mesh of hexahedra goes past the END of that table: a cell has 6 = patchFaces + 2 * internalFaces faces, so the table holds at least
+// (2 f + 6) / 256 slots per cell (f = internal faces per cell), and a block is cut only when it is over a cap of the kernel -- 128 cells, or
+// 256 vertices at no more than 4 per face -- which leaves at most max(1 / 64, f / 32) blocks per cell even when every cut halves a block
+// that was just over; the two meet at f > 1 only, where faces share vertices and the blocks grow again.  The chains below have
+// 19 blocks against 16 + 17 slots.)
+static void checkSmallBlocks(const char* tag, HostMesh& m, bool inletOverwritten) {
+    const FusedBlocks B = checkMesh(tag, m);
+    const int32_t nIF = m.nInternalFaces, nBF = m.nFaces - m.nInternalFaces;
+    const int32_t faceBlocks = (nIF + 63) / 64, bfaceBlocks = (nBF + 255) / 256;
+    std::printf("    %d blocks, %d face tiles, %d patch workgroups\n", B.nBlocks, faceBlocks, bfaceBlocks);
+    CHECK(B.nBlocks > faceBlocks, "%s: %d blocks, %d face tiles", tag, B.nBlocks, faceBlocks);
+    const int32_t inletEnd = m.patches[0].start - nIF + m.patches[0].size;
+    CHECK(!inletOverwritten || (m.patches[0].size > 0 && inletEnd <= 256 * (B.nBlocks - faceBlocks)), "%s: patch 0 ends at patch face %d, blocks cover %d", tag,
+          inletEnd, 256 * (B.nBlocks - faceBlocks));
 }
 
 int main() {
     const double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
     const int32_t pt[6] = {0, 0, 0, 0, 0, 0};
-    { HostMesh m = makeBox(16, 8, 8, 0, 8, lo, hi, pt); checkMesh("box 16x8x8 (bricks)", m); }
-    { HostMesh m = makeBox(13, 7, 5, 0, 5, lo, hi, pt); checkMesh("box 13x7x5 (ragged)", m); }
-    { HostMesh m = makeBox(3, 2, 2, 0, 2, lo, hi, pt); checkMesh("box 3x2x2", m); }
+    { HostMesh m = makeBox(16, 8, 8, 0, 8, lo, hi, pt); checkMesh("box 16x8x8 (bricks)", m, 0.0, -1, 8); }
+    { HostMesh m = makeBox(13, 7, 5, 0, 5, lo, hi, pt); checkMesh("box 13x7x5 (ragged)", m, 0.0, -1, 5); }
+    { HostMesh m = makeBox(3, 2, 2, 0, 2, lo, hi, pt); checkMesh("box 3x2x2", m, 0.0, -1, 1); }
     {
         HostMesh m = makeBox(11, 9, 7, 0, 7, lo, hi, pt);
         jitterPoints(m, 0.15, 7);
         splitQuads(m, 3);
         splitEdges(m, 5);
-        checkMesh("jittered, every third quad split, every fifth edge split (triangles, polygons)", m);
+        checkMesh("jittered, every third quad split, every fifth edge split (triangles, polygons)", m, 0.0, -1, 7);
     }
-    { HostMesh m = makeBox(12, 6, 12, 3, 9, lo, hi, pt); checkMesh("slab 3..9 of a 12x6x12 box (two cuts)", m); }
+    { HostMesh m = makeBox(12, 6, 12, 3, 9, lo, hi, pt); checkMesh("slab 3..9 of a 12x6x12 box (two cuts)", m, 0.0, -1, 3); }
     // what a cut must not cost: a 50-plane slab between two cuts keeps brick-shaped blocks -- 13 brick layers of 3 or 4
     // planes, 123 cells per block -- and the blocks of the planes a neighbour waits for are whole bricks, not flat one-plane ones
-    { HostMesh m = makeBox(80, 80, 150, 49, 101, lo, hi, pt); checkMesh("planes 50..100 of an 80x80x150 box (50 owned planes between two ghost planes)", m, 120.0, 2600 - 8 * 18 * 11 + 40); }   // the 8 x 18 x 11 bricks without a patch face or a ghost plane share a handful of templates
-    { HostMesh m = makeBox(50, 50, 50, 0, 50, lo, hi, pt); checkMesh("box 50x50x50 (extents 8x4x4 bricks do not divide: 5x5x5 ones)", m, 120.0, 1000 - 8 * 8 * 8 + 1); }   // 512 interior cubes, ONE template
+    { HostMesh m = makeBox(80, 80, 150, 49, 101, lo, hi, pt); checkMesh("planes 50..100 of an 80x80x150 box (50 owned planes between two ghost planes)", m, 120.0, 2600 - 8 * 18 * 11 + 40, 730); }   // the 8 x 18 x 11 bricks without a patch face or a ghost plane share a handful of templates
+    { HostMesh m = makeBox(50, 50, 50, 0, 50, lo, hi, pt); checkMesh("box 50x50x50 (extents 8x4x4 bricks do not divide: 5x5x5 ones)", m, 120.0, 1000 - 8 * 8 * 8 + 1, 489); }   // 512 interior cubes, ONE template
     {   // a jittered, Morton-renumbered mesh: no two blocks list their cells alike -> one template per block, the kernel's untemplated path
         HostMesh m = makeBox(24, 16, 16, 0, 16, lo, hi, pt);
         jitterPoints(m, 0.15, 7);
         splitQuads(m, 7);
-        checkMesh("jittered 24x16x16, every seventh quad split", m, 0.0, -1); }
+        checkMesh("jittered 24x16x16, every seventh quad split", m, 0.0, -1, 52); }
+    {   // the thin meshes of tests/test_courant_small_blocks_gpu.py (PolyMesh.box takes the same arguments): six generic patches, three solved directions
+        const double lo2[3] = {0.0, 0.45, 0.45}, hi2[3] = {7.0, 0.55, 0.55};
+        { HostMesh m = makeBox(1024, 1, 1, 0, 1, lo, hi, pt); checkSmallBlocks("thin 1024x1x1", m, true); }
+        { HostMesh m = makeBox(700, 1, 1, 0, 1, lo2, hi2, pt); checkSmallBlocks("thin 700x1x1, cells of 0.01 x 0.1 x 0.1", m, true); }
+        { HostMesh m = makeBox(1, 1, 700, 0, 700, lo, hi, pt); checkSmallBlocks("thin 1x1x700", m, false); }
+    }
+#ifdef QGD_TEST_TOPOHASH_BITS
+    CHECK(mismatchesSeen > 0, "a fingerprint of %d bits and no block whose tables differ from its template's", (int)QGD_TEST_TOPOHASH_BITS);
+#endif
     if (fails) { std::printf("%d checks failed\n", fails); return 1; }
     std::printf("ok\n");
     return 0;

@@ -1,6 +1,9 @@
 """Host logic of the fused step (CPU): the block tables of qgd_setup.cpp buildFusedBlocks checked entry by entry against the mesh tables they are
 made from, on bricks, ragged boxes, a jittered mesh with triangles and polygons, and a slab shard with two cuts (tests/cpp/fused_blocks_test.cpp,
-compiled with plain g++ from the library's own host sources -- no HIP, no oracle)."""
+compiled with plain g++ from the library's own host sources -- no HIP, no oracle).  The same program checks that thin meshes have more
+blocks than 64-face tiles (the premise of tests/test_courant_small_blocks_gpu.py), and that blocks which share a template share its
+tables: a second build truncates the topology fingerprint to one bit (QGD_TEST_TOPOHASH_BITS, a macro the library's own build never
+defines), so that unlike blocks are certain to meet in one template unless the builder compares their tables."""
 import os
 import subprocess
 
@@ -8,11 +11,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "qgdsolver_amd", "csrc")
 
 
-def test_block_tables_are_consistent_with_the_mesh(tmp_path):
-    exe = str(tmp_path / "fused_blocks_test")
-    cmd = ["g++", "-std=c++17", "-O2", "-fopenmp", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "fused_blocks_test.cpp")] + \
+def build_and_run(tmp_path, name, defines=()):
+    exe = str(tmp_path / name)
+    cmd = ["g++", "-std=c++17", "-O2", "-fopenmp", "-I", CSRC, *defines, os.path.join(ROOT, "tests", "cpp", "fused_blocks_test.cpp")] + \
           [os.path.join(CSRC, f) for f in ("qgd_mesh.cpp", "qgd_partition.cpp", "qgd_setup.cpp")] + ["-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, OMP_NUM_THREADS="4"))
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-4000:] + r.stderr[-2000:]
+    return r.stdout
+
+
+def test_block_tables_are_consistent_with_the_mesh(tmp_path):
+    """... with the full fingerprint: no block differs from its template, the template counts are the pinned ones, and the thin meshes have
+    more blocks than face tiles"""
+    out = build_and_run(tmp_path, "fused_blocks_test")
+    assert "thin 1024x1x1" in out and "thin 1x1x700" in out
+
+
+def test_blocks_that_collide_in_a_template_get_their_own(tmp_path):
+    """a fingerprint of one bit: every mesh with three unlike blocks puts two of them into one template.  The builder must notice (the
+    program asserts a positive mismatch count) and every block's tables, read through its template, must still be the mesh's"""
+    out = build_and_run(tmp_path, "fused_blocks_test_collide", ["-DQGD_TEST_TOPOHASH_BITS=1"])
+    assert "matched a template by fingerprint and not by their tables" in out
