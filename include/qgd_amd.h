@@ -541,6 +541,50 @@ int qgd_qhd_case_halo_count(qgd_qhd_case_t c, int slot, int kind, int64_t* sendC
 int qgd_qhd_case_halo_pack(qgd_qhd_case_t c, int slot, int kind, double* sendBufDevice);
 int qgd_qhd_case_halo_unpack(qgd_qhd_case_t c, int slot, int kind, const double* recvBufDevice);
 
+/* ---- scalarTransportQHDFoam case resident on the device ---------------------------------------------------------------- */
+/* The loop body of scalarTransportQHDFoam [scalarTransportQHDFoam_8C_source.html L86-125]: U is read and never advanced, thermo.correct()
+ * runs once, so Uf, phiu, tauQGDf, hQGDf and Hif = alphaf/rhof are constants of the run; per step gradTf = fvsc::grad(T), Tf =
+ * qgdInterpolate(T), phiTf = qgdFlux(phiu,T,Tf), phiTauTReg = tauQGDf phiu (Uf & gradTf) and, ONLY with implicitDiffusion,
+ *   solve(fvm::ddt(T) + fvc::div(phiTf) - fvc::Sp(fvc::div(phiu),T) - fvm::laplacian(Hif,T) - fvc::div(phiTauTReg) == TSu), TSu = 0.
+ * The listing has no else: with implicitDiffusion 0 T stays as it is and only time advances (reproduced as listed).  Thermo and L0
+ * discretisation are the QHDFoam case's (rhoConst + constTransport, uniform rho0, mu, Pr; Euler, Gauss linear uncorrected).  The solve is
+ * the implicitDiffusion solver of the other cases (Chebyshev, QGD_IMPL_SOLVER=pcg: conjugate gradients), started from the old T.
+ * adjustTimeStep [setDeltaT-QGDQHD_8H L41-61]: CoNum = deltaT max(|Uf|/hQGDf), deltaTFact = min(min(maxCo/(CoNum + SMALL),
+ * 1 + 0.1 maxCo/(CoNum + SMALL)), 1.2), deltaT = min(deltaTFact deltaT, min(maxDeltaT, cTau min(tauQGDf))); both extrema are constants of
+ * the run (reduced once on the device by qgd_scalar_case_set_fields), so a step waits for nothing.
+ * One device: a sharded or periodic (qgd_mesh_unroll_cyclic) device is refused with QGD_ERR_NOT_IMPLEMENTED. */
+typedef struct qgd_scalar_options {
+    int32_t stencil;          /* QGD_FVSC_*                                                                    */
+    int32_t implicitDiffusion;/* 1 (the reference's default): the T equation is solved; 0: T is left unchanged, as listed */
+    int32_t tauModel;         /* 0 constTau (Tau), 1 HbyUQHD (aQGD, UQHD), 2 T0byGr (T0, Gr), 3 H2bynuQHD (aQGD; nu = mu/rho0) */
+    int32_t adjustTimeStep;
+    int32_t fluxSchemeT;      /* QGD_FLUX_* of qgdFlux(phiu,T,Tf) [.C L110], entry `div(phiu,T)`                 */
+    int32_t implicitMaxIter;  /* iteration limit of the T solve (1000)                                         */
+    double rho0, mu, Pr, deltaT;
+    double Tau, aQGD, UQHD, T0, Gr;
+    double maxCo, maxDeltaT, cTau;   /* controlDict maxCo, maxDeltaT; cTau (default 0.75)                       */
+    double implicitTol;       /* tolerance (OpenFOAM's normalised residual) of the T solve (1e-10)             */
+} qgd_scalar_options;
+typedef struct qgd_scalar_case_s* qgd_scalar_case_t;
+int qgd_scalar_options_default(qgd_scalar_options* opt);
+int qgd_scalar_case_create(qgd_device_t d, const qgd_scalar_options* opt, qgd_scalar_case_t* out);
+int qgd_scalar_case_free(qgd_scalar_case_t c);
+/* per patch: U zeroGradient | fixedValue (valueU) | slip; T zeroGradient | fixedValue (valueT); symmetryPlane / symmetry / empty patches
+ * keep their own field types whatever is asked for, as in the QHDFoam case */
+int qgd_scalar_case_set_bc(qgd_scalar_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT);
+/* U (3 nCells), T (nCells): forms everything that does not depend on T and resets time, steps and the solver statistics */
+int qgd_scalar_case_set_fields(qgd_scalar_case_t c, const double* U, const double* T);
+int qgd_scalar_case_step(qgd_scalar_case_t c, int32_t nSteps);
+/* "T", "T.boundary"; face fields (nFaces) "phiu", "tauQGDf", "hQGDf", "Uf" (3 per face), and, evaluated on the CURRENT T (what the next
+ * step's updateFields.H would form), "gradTf" (3 per face), "phiTf", "phiTauTReg" */
+int qgd_scalar_case_get_field(qgd_scalar_case_t c, const char* name, double* out, int64_t outDoubles);
+/* info[0]=time, [1]=deltaT of the last step, [2]=CoNum the last step's time-step control saw (deltaT BEFORE it, times max(|Uf|/hQGDf);
+ * fixed deltaT: that deltaT), [3]=steps, [4..6]= iterations / initial / final normalised residual of the last T solve, [7]=steps since
+ * set_fields in which the solve stopped above implicitTol, [8]=steps in which a Chebyshev solve ended at the rounding floor of its
+ * residual above implicitTol, [9]=0 no solve | 1 conjugate gradients | 2 Chebyshev, [10]=max(|Uf|/hQGDf), [11]=min(tauQGDf) */
+int qgd_scalar_case_info(qgd_scalar_case_t c, double info[12]);
+int qgd_scalar_case_sync(qgd_scalar_case_t c);
+
 /* ---- QGDFoam case ----------------------------------------------------------- */
 
 typedef struct qgd_case_options {

@@ -59,6 +59,15 @@ class QhdOptions(C.Structure):
                 ("fluxSchemeU", C.c_int32), ("fluxSchemeT", C.c_int32), ("pad_", C.c_int32)]
 
 
+class ScalarOptions(C.Structure):
+    """qgd_scalar_options"""
+    _fields_ = [("stencil", C.c_int32), ("implicitDiffusion", C.c_int32), ("tauModel", C.c_int32), ("adjustTimeStep", C.c_int32),
+                ("fluxSchemeT", C.c_int32), ("implicitMaxIter", C.c_int32),
+                ("rho0", C.c_double), ("mu", C.c_double), ("Pr", C.c_double), ("deltaT", C.c_double),
+                ("Tau", C.c_double), ("aQGD", C.c_double), ("UQHD", C.c_double), ("T0", C.c_double), ("Gr", C.c_double),
+                ("maxCo", C.c_double), ("maxDeltaT", C.c_double), ("cTau", C.c_double), ("implicitTol", C.c_double)]
+
+
 # every symbol include/qgd_amd.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "qgd_version": (C.c_char_p, []),
@@ -141,6 +150,15 @@ SIGNATURES = {
     "qgd_qhd_case_halo_unpack": (C.c_int, [handle, C.c_int, C.c_int, C.c_void_p]),
     "qgd_qhd_case_halo_exchange": (C.c_int, [handle, handle, c_int32_p, C.c_int, C.c_int]),
     "qgd_qhd_case_step_sharded": (C.c_int, [handle, handle, c_int32_p, C.c_int, C.c_int32]),
+    "qgd_scalar_options_default": (C.c_int, [C.POINTER(ScalarOptions)]),
+    "qgd_scalar_case_create": (C.c_int, [handle, C.POINTER(ScalarOptions), handle_p]),
+    "qgd_scalar_case_free": (C.c_int, [handle]),
+    "qgd_scalar_case_set_bc": (C.c_int, [handle, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_double]),
+    "qgd_scalar_case_set_fields": (C.c_int, [handle, c_double_p, c_double_p]),
+    "qgd_scalar_case_step": (C.c_int, [handle, C.c_int32]),
+    "qgd_scalar_case_get_field": (C.c_int, [handle, C.c_char_p, c_double_p, C.c_int64]),
+    "qgd_scalar_case_info": (C.c_int, [handle, c_double_p]),
+    "qgd_scalar_case_sync": (C.c_int, [handle]),
     "qgd_case_options_default": (C.c_int, [C.POINTER(CaseOptions)]),
     "qgd_case_create": (C.c_int, [handle, C.POINTER(CaseOptions), handle_p]),
     "qgd_case_free": (C.c_int, [handle]),

@@ -2665,6 +2665,237 @@ int qgd_qhd_case_fused_info(qgd_qhd_case_t c, int64_t info[4]) {
     return QGD_OK;
 }
 
+// ---- scalarTransportQHDFoam case resident on the device (qgd_scalar.hip) -------------------------------------------------
+struct qgd_scalar_case_s {
+    qgd_device_s* dev = nullptr;
+    qgd_scalar_options opt{};
+    int stencil = ST_GVP3;
+    bool usesPoints = true, fieldsSet = false;
+    std::vector<PatchBCDev> bc;
+    PatchBCDev* bcDev = nullptr;
+    DeviceArena arena;
+    ScalarView view{};
+    double *work = nullptr, *red = nullptr;
+    ImplicitSolver* solver = nullptr;
+    // the two extrema the time-step control reads are constants of the run (U, tauQGDf and the mesh do not change): reduced once on the
+    // device at set_fields, the rule itself is then host arithmetic on them and no step waits for the device
+    double maxUh = 0, minTau = 0;
+    double dt = 0, dtDiag = 0, CoNum = 0, time = 0;   // dtDiag: the deltaT view.diag was built with
+    int64_t steps = 0;
+};
+
+int qgd_scalar_options_default(qgd_scalar_options* o) {
+    if (!o) return fail(QGD_ERR_INVALID, "null argument");
+    std::memset(o, 0, sizeof(*o));
+    o->stencil = QGD_FVSC_GAUSSVOLPOINT;
+    o->implicitDiffusion = 1; o->tauModel = 0; o->fluxSchemeT = QGD_FLUX_LINEAR; o->implicitMaxIter = 1000;
+    o->rho0 = 1.0; o->mu = 0.0; o->Pr = 1.0; o->deltaT = 1e-3;
+    o->Tau = 1e-3; o->aQGD = 0.5; o->UQHD = 1.0; o->T0 = 1.0; o->Gr = 1e3;
+    o->maxCo = 0.5; o->maxDeltaT = 1e300; o->cTau = 0.75;
+    o->implicitTol = 1e-10;
+    return QGD_OK;
+}
+int qgd_scalar_case_create(qgd_device_t d, const qgd_scalar_options* opt, qgd_scalar_case_t* out) {
+    QGD_TRY
+    if (!d || !opt || !out) return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: null argument");
+    if (d->periodic())
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_scalar_case_create: a mesh whose cyclic patches were unrolled into ghost cells (qgd_mesh_unroll_cyclic) is "
+                                             "not served: the implicit laplacian would need the coupled rows of the periodic pairs");
+    if (d->sharded())
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_scalar_case_create: a sharded device is not served: the scalarTransportQHDFoam case runs on one device "
+                                             "(no halo exchange of T, no reductions across shards)");
+    if (!(opt->implicitTol > 0) || opt->implicitMaxIter < 1)
+        return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: implicitTol must be positive, implicitMaxIter >= 1");
+    if (!(opt->rho0 > 0) || !(opt->Pr > 0) || !(opt->deltaT > 0) || !(opt->mu >= 0) || opt->tauModel < 0 || opt->tauModel > 3)
+        return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: rho0, Pr, deltaT must be positive, mu >= 0, tauModel in 0..3");
+    if (opt->tauModel == 3 && !(opt->mu > 0)) return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: H2bynuQHD needs mu > 0");
+    if (opt->fluxSchemeT != QGD_FLUX_LINEAR && opt->fluxSchemeT != QGD_FLUX_UPWIND)
+        return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: fluxSchemeT must be QGD_FLUX_LINEAR or QGD_FLUX_UPWIND");
+    if (opt->adjustTimeStep && (!(opt->maxCo > 0) || !(opt->maxDeltaT > 0) || !(opt->cTau > 0)))
+        return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: adjustTimeStep needs maxCo, maxDeltaT, cTau > 0");
+    if (!d->caseRefusal.empty()) return fail(d->caseRefusalCode, "qgd_scalar_case_create: " + d->caseRefusal);
+    int st = 0;
+    int rc = deviceStencil(d, opt->stencil, &st);
+    if (rc) return rc;
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    qgd_scalar_case_s* c = new qgd_scalar_case_s();
+    try {
+        c->dev = d; c->opt = *opt; c->stencil = st;
+        c->usesPoints = (st == ST_GVP3 || st == ST_GVP2);
+        const MeshView& v = d->view;
+        DeviceArena& a = c->arena;
+        ScalarView& q = c->view;
+        const size_t nC = (size_t)v.nC, nB = (size_t)std::max(v.nBF, 1), nF = (size_t)std::max(v.nF, 1), nP = (size_t)std::max(v.nP, 1);
+        q.T = a.alloc<double>(nC); q.Tb = a.alloc<double>(nB); q.ptT = a.alloc<double>(c->usesPoints ? nP : 1);
+        q.tauF = a.alloc<double>(nF); q.Uf = a.alloc<double>(3 * nF); q.phiu = a.alloc<double>(nF); q.tpu = a.alloc<double>(3 * nF); q.a = a.alloc<double>(nF);
+        q.divPhiu = a.alloc<double>(nC); q.diagBase = a.alloc<double>(nC); q.srcB = a.alloc<double>(nC);
+        q.F = a.alloc<double>(nF); q.diag = a.alloc<double>(nC); q.rhs = a.alloc<double>(nC);
+        q.dbg = nullptr;
+        c->work = a.alloc<double>(2 * ((nF + 255) / 256) + 2);   // two partials per workgroup of the set-up face kernel
+        c->red = a.alloc<double>(2);
+        q.Hi = (opt->mu / opt->Pr) / opt->rho0;
+        q.upwindT = opt->fluxSchemeT == QGD_FLUX_UPWIND ? 1 : 0;
+        q.tauModel = opt->tauModel; q.Tau = opt->Tau; q.aQGD = opt->aQGD; q.UQHD = opt->UQHD; q.T0 = opt->T0; q.Gr = opt->Gr; q.nu = opt->mu / opt->rho0;
+        if (opt->implicitDiffusion) c->solver = implicitSolverCreate(d->stream, v, 0, v.nC);
+        c->bc.resize(d->patches.size());
+        for (size_t i = 0; i < d->patches.size(); ++i) initPatchBC(c->bc[i], d->patches[i]);
+        c->bcDev = a.alloc<PatchBCDev>(std::max<size_t>(1, c->bc.size()));
+    } catch (...) { if (c->solver) implicitSolverFree(c->solver); c->arena.release(); delete c; throw; }
+    d->liveCases++;
+    *out = c;
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_scalar_case_free(qgd_scalar_case_t c) {
+    if (!c) return QGD_OK;
+    (void)hipSetDevice(c->dev->deviceId);
+    (void)hipStreamSynchronize(c->dev->stream);
+    if (c->solver) implicitSolverFree(c->solver);
+    c->arena.release();
+    c->dev->liveCases--;
+    delete c;
+    return QGD_OK;
+}
+int qgd_scalar_case_set_bc(qgd_scalar_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT) {
+    QGD_TRY
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, "qgd_scalar_case_set_bc: patch out of range");
+    auto okU = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_SLIP || k == QGD_BC_NONE; };
+    auto okT = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_NONE; };
+    if (!okU(bcU) || !okT(bcT)) return fail(QGD_ERR_INVALID, "qgd_scalar_case_set_bc: unsupported boundary-condition kind");
+    PatchBCDev& b = c->bc[patch];
+    int32_t bcP = QGD_BC_ZEROGRADIENT;
+    constraintKinds(b.ptype, bcU, bcT, bcP);   // a constraint patch keeps its own field type whatever the caller asks for
+    b.bcU = bcU; b.bcT = bcT; b.vT = valueT;
+    if (valueU) for (int k = 0; k < 3; ++k) b.vU[k] = valueU[k];
+    c->fieldsSet = false;
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_scalar_case_set_fields(qgd_scalar_case_t c, const double* U, const double* T) {
+    QGD_TRY
+    if (!c || !U || !T) return fail(QGD_ERR_INVALID, "qgd_scalar_case_set_fields: null argument");
+    qgd_device_s* d = c->dev;
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    const MeshView& m = d->view;
+    if (!c->bc.empty()) HIP_CHECK(hipMemcpy(c->bcDev, c->bc.data(), sizeof(PatchBCDev) * c->bc.size(), hipMemcpyHostToDevice));
+    Workspace& ws = d->ws;
+    double* dU = ws.get<double>(WS_CELL, 3 * (size_t)m.nC);
+    double* dT = ws.get<double>(WS_A, (size_t)m.nC);
+    ws.h2d(dU, U, sizeof(double) * 3 * (size_t)m.nC, d->stream);
+    ws.h2d(dT, T, sizeof(double) * (size_t)m.nC, d->stream);
+    (void)hipGetLastError();
+    launchScalarSetup(d->stream, m, c->view, c->bcDev, dU, dT, c->work, c->red);
+    HIP_CHECK(hipGetLastError());
+    double red[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(red, c->red, sizeof(red), hipMemcpyDeviceToHost, d->stream));
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    c->maxUh = std::max(red[0], 0.0); c->minTau = red[1];
+    c->dt = c->opt.deltaT; c->dtDiag = 0; c->CoNum = c->dt * c->maxUh; c->time = 0; c->steps = 0;
+    if (c->solver) implicitStatsReset(c->solver);
+    c->fieldsSet = true;
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_scalar_case_step(qgd_scalar_case_t c, int32_t nSteps) {
+    QGD_TRY
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_scalar_case_step: call qgd_scalar_case_set_fields first");
+    qgd_device_s* d = c->dev;
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    const MeshView& m = d->view;
+    const qgd_scalar_options& o = c->opt;
+    for (int i = 0; i < nSteps; ++i) {
+        c->CoNum = c->dt * c->maxUh;                                         // .C L88-92 (fixed deltaT: what the application prints)
+        if (o.adjustTimeStep) {                                             // setDeltaT-QGDQHD.H L41-61
+            const double maxDeltaTFact = o.maxCo / (c->CoNum + 1e-15);
+            const double deltaTFact = std::min(std::min(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
+            c->dt = std::min(deltaTFact * c->dt, std::min(o.maxDeltaT, o.cTau * c->minTau));
+        }
+        c->time += c->dt;                                                   // runTime++
+        c->steps++;
+        if (!o.implicitDiffusion) continue;                                 // .C L113: there is no else -- T stays as it is
+        (void)hipGetLastError();
+        if (c->dt != c->dtDiag) { launchScalarDiag(d->stream, m, c->view, c->dt); c->dtDiag = c->dt; }
+        implicitStepMark(c->solver, true);
+        launchScalarAssemble(d->stream, c->stencil, c->usesPoints, m, c->view, c->bcDev, c->dt, true);
+        HIP_CHECK(hipGetLastError());
+        implicitSolveSetup(c->solver, 1, 1, c->view.a, c->view.diag, c->view.rhs, c->view.T, o.implicitTol, o.implicitMaxIter);
+        implicitSolveRun(c->solver, nullptr);
+        implicitSolveEnd(c->solver, 1);
+        implicitStepMark(c->solver, false);
+        launchScalarPatchValues(d->stream, m, c->view, c->bcDev);            // solve() ends in correctBoundaryConditions()
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_scalar_case_get_field(qgd_scalar_case_t c, const char* name, double* out, int64_t outDoubles) {
+    QGD_TRY
+    if (!c || !name || !out) return fail(QGD_ERR_INVALID, "qgd_scalar_case_get_field: null argument");
+    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_scalar_case_get_field: call qgd_scalar_case_set_fields first");
+    qgd_device_s* d = c->dev;
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    const MeshView& m = d->view;
+    const ScalarView& q = c->view;
+    const std::string s(name);
+    const size_t nF = (size_t)m.nF;
+    const double* src = nullptr;
+    int64_t count = 0;
+    int nc = 1;          // > 1: src is SoA with stride nF, the caller gets nc per face
+    if (s == "T") { src = q.T; count = m.nC; }
+    else if (s == "T.boundary") { src = q.Tb; count = m.nBF; }
+    else if (s == "phiu") { src = q.phiu; count = m.nF; }
+    else if (s == "tauQGDf") { src = q.tauF; count = m.nF; }
+    else if (s == "hQGDf") { src = m.hf; count = m.nF; }
+    else if (s == "Uf") { src = q.Uf; count = m.nF; nc = 3; }
+    else if (s == "gradTf" || s == "phiTf" || s == "phiTauTReg") {
+        ScalarView qd = q;
+        qd.dbg = d->ws.get<double>(WS_B, 5 * std::max<size_t>(nF, 1));
+        (void)hipGetLastError();
+        launchScalarAssemble(d->stream, c->stencil, c->usesPoints, m, qd, c->bcDev, c->dt, false);
+        HIP_CHECK(hipGetLastError());
+        count = m.nF;
+        if (s == "gradTf") { src = qd.dbg; nc = 3; } else src = qd.dbg + (s == "phiTf" ? 3 : 4) * nF;
+    } else return fail(QGD_ERR_INVALID, "qgd_scalar_case_get_field: unknown field " + s);
+    if (count * nc > outDoubles) return fail(QGD_ERR_INVALID, "output too small");
+    if (count == 0) return QGD_OK;
+    if (nc == 1) { d->ws.d2h(out, src, sizeof(double) * (size_t)count, d->stream); return QGD_OK; }
+    double* tmp = d->ws.get<double>(WS_OUT, (size_t)count * nc);
+    launchSoaToAos(d->stream, count, nc, src, tmp);
+    HIP_CHECK(hipGetLastError());
+    d->ws.d2h(out, tmp, sizeof(double) * (size_t)count * nc, d->stream);
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_scalar_case_info(qgd_scalar_case_t c, double info[12]) {
+    QGD_TRY
+    if (!c || !info) return fail(QGD_ERR_INVALID, "null argument");
+    for (int k = 0; k < 12; ++k) info[k] = 0.0;
+    info[0] = c->time; info[1] = c->dt > 0 ? c->dt : c->opt.deltaT; info[2] = c->CoNum; info[3] = (double)c->steps;
+    info[10] = c->maxUh; info[11] = c->minTau;
+    if (c->solver && c->fieldsSet) {
+        HIP_CHECK(hipSetDevice(c->dev->deviceId));
+        int it[4] = {0, 0, 0, 0};
+        double r0[4] = {0, 0, 0, 0}, r1[4] = {0, 0, 0, 0}, un = 0, stalled = 0;
+        implicitSolverInfo(c->solver, it, r0, r1, &un, &stalled);   // the case's solve is kept in the second block (implicitSolveEnd(S, 1))
+        info[4] = it[3]; info[5] = r0[3]; info[6] = r1[3]; info[7] = un; info[8] = stalled;
+        info[9] = implicitSolverChebyshev(c->solver) ? 2.0 : 1.0;
+    }
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_scalar_case_sync(qgd_scalar_case_t c) {
+    QGD_TRY
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    HIP_CHECK(hipStreamSynchronize(c->dev->stream));
+    return QGD_OK;
+    QGD_CATCH
+}
+
 // ---- native halo transport: RCCL send/recv inside the library -----------------------------------------------------------
 // Replaces, for a C++/MPI host, what the reference does per gradient call with PstreamBuffers
 // [extendedFaceStencilScalarGrad_8C L145-233] and with processor-patch evaluation [GaussVolPointStencil_8C L73]:

@@ -325,6 +325,38 @@ void launchQhdHalo(hipStream_t s, const QhdView& q, double* direction, int kind,
 void launchQhdHaloFloat(hipStream_t s, float* vec, const int32_t* cells, int nCells, double* buf, bool pack);
 void launchQhdExtract(hipStream_t s, int64_t n, const double* rec4, int field, double* out);
 
+// ---- scalarTransportQHDFoam case resident on the device (qgd_scalar.hip) ------------------------------------------------
+// U, rho and tauQGDf never change [scalarTransportQHDFoam.C L86-125: thermo.correct() and updateFluxes.H run once], so everything that
+// does not depend on T is formed at set_fields time (the `static` members); a step reads T and those.
+struct ScalarView {
+    double* T; double* Tb; double* ptT;        // T: cells (nC; also the solve's vector), patch faces (nBF), vertices (nP, GaussVolPoint only)
+    // static per face
+    double* tauF;                              // nF tauQGDf
+    double* Uf;                                // 3*nF SoA qgdInterpolate(U)
+    double* phiu;                              // nF Sf & Uf
+    double* tpu;                               // 3*nF SoA tauQGDf * phiu * Uf
+    double* a;                                 // nF Hif |Sf| delta_f at the faces' slot-major positions (MeshView::fpos)
+    // static per cell
+    double* divPhiu;                           // nC volume-integrated fvc::div(phiu)
+    double* diagBase;                          // nC sum of a over the cell's internal and fixedValue patch faces
+    double* srcB;                              // nC sum of a_b T_b over the cell's fixedValue patch faces
+    // per step
+    double* F;                                 // nF net face flux phiu Tf - (tau phiu Uf) & gradTf at the faces' slot-major positions
+    double *diag, *rhs;                        // nC
+    double* dbg;                               // 5*nF SoA {gradTf(3), phiTf, phiTauTReg}: filled for qgd_scalar_case_get_field only (nullptr in a step)
+    double Hi;                                 // alphaf/rhof = mu/(Pr rho0)
+    int32_t upwindT;
+    int32_t tauModel; double Tau, aQGD, UQHD, T0, Gr, nu;
+};
+// cell records -> Uf, phiu, tpu, a, divPhiu, diagBase, srcB, T, Tb; red (2 doubles) = {max |Uf|/hQGDf, min tauQGDf} over the non-empty faces
+void launchScalarSetup(hipStream_t s, const MeshView& m, const ScalarView& q, const PatchBCDev* bc, const double* U, const double* T, double* work,
+                       double* red);
+void launchScalarDiag(hipStream_t s, const MeshView& m, const ScalarView& q, double dt);                 // diag = V/deltaT + diagBase
+// patch values, vertex values (usesPoints), the face kernel, the right-hand side; the solve on (a, diag, rhs, T) follows
+void launchScalarAssemble(hipStream_t s, int stencil, bool usesPoints, const MeshView& m, const ScalarView& q, const PatchBCDev* bc, double dt,
+                          bool rhs);
+void launchScalarPatchValues(hipStream_t s, const MeshView& m, const ScalarView& q, const PatchBCDev* bc);   // T.correctBoundaryConditions() after the solve
+
 // persistent pressure solver: PCG preconditioned by aggregation multigrid (precond 1) or Jacobi (0); qgd_poisson.hip
 struct PressureSolver;
 // ownedBegin/ownedEnd: the rows of the system, i.e. the owned cells of a shard (0, -1: every cell)

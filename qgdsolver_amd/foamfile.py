@@ -908,6 +908,125 @@ def read_qhd_case_setup(case_dir, time="0"):
     return mesh, opt, {"U": U, "T": T[:, 0], "p": p[:, 0]}, bcs
 
 
+def read_scalar_case_setup(case_dir, time="0"):
+    """Read an OpenFOAM scalarTransportQHDFoam case directory [scalarTransportQHDFoam.C L60-84, its createFields.H].
+
+    Returns (mesh, options dict for ``scalarfoam.scalar_options``, {'U','T'} internal arrays, per-patch BC pairs, run control dict
+    {endTime, writeInterval}).  Entries read: constant/polyMesh; constant/thermophysicalProperties -- thermoType (equationOfState
+    rhoConst, transport const), mixture.equationOfState.rho, mixture.transport.{mu, Pr}, QGD{implicitDiffusion (default true,
+    QGDThermo.C L70-82), QGDCoeffs constTau | HbyUQHD | T0byGr | H2bynuQHD with the keys of <model>Dict or of QGD itself}; <time>/alphaQGD
+    when present and uniform; system/fvSchemes fvsc (grad(T), else default), divSchemes `div(phiu,T)`, interpolationSchemes, ddt /
+    laplacian schemes; system/controlDict deltaT, endTime, writeInterval, adjustTimeStep, maxCo, maxDeltaT, cTau (default 0.75,
+    setDeltaT-QGDQHD.H L48); system/fvSolution solvers.T {tolerance, maxIter}; <time>/{U,T}.  What the path would compute differently
+    is refused by name."""
+    mesh = read_polymesh(os.path.join(case_dir, "constant", "polyMesh"))
+    _refuse_unserved_patches(mesh, case_dir)
+    opt = {}
+    tp = read_dict(os.path.join(case_dir, "constant", "thermophysicalProperties"))
+    tt = tp.get("thermoType", {})
+    for key, want in (("equationOfState", "rhoConst"), ("transport", "const")):
+        if isinstance(tt, dict) and key in tt and str(tt[key]) != want:
+            raise FoamFileError(f"thermoType.{key} '{tt[key]}' is not supported by the scalarTransportQHDFoam path (only {want})")
+    mix = tp["mixture"]
+    opt["rho0"] = float(mix["equationOfState"]["rho"])
+    tr = mix["transport"]
+    opt["mu"], opt["Pr"] = float(tr["mu"]), float(tr["Pr"])
+    qgd = tp["QGD"]
+    opt["implicitDiffusion"] = 1 if _truthy(qgd.get("implicitDiffusion", "true")) else 0
+    model = str(qgd["QGDCoeffs"])
+    if model not in ("constTau", "HbyUQHD", "T0byGr", "H2bynuQHD"):
+        raise FoamFileError(f"QGDCoeffs '{model}' is not a closure of the scalarTransportQHDFoam path (constTau, HbyUQHD, T0byGr, H2bynuQHD)")
+    opt["tauModel"] = model
+    md = qgd.get(model + "Dict", qgd)
+    for key, needed in (("Tau", model == "constTau"), ("UQHD", model == "HbyUQHD"), ("T0", model == "T0byGr"), ("Gr", model == "T0byGr")):
+        if needed:
+            if key not in md:
+                raise FoamFileError(f"QGD.{model}: entry '{key}' is missing")
+            opt[key] = float(md[key])
+    tdir = os.path.join(case_dir, str(time))
+    opt["aQGD"] = 0.5
+    apath = os.path.join(tdir, "alphaQGD")
+    if _exists(apath):
+        vals, _ = read_field(apath, mesh)
+        if not np.all(vals == vals[0]):
+            raise FoamFileError(f"{apath}: a non-uniform alphaQGD is not supported by the scalarTransportQHDFoam path")
+        opt["aQGD"] = float(vals[0, 0])
+    fs_path = os.path.join(case_dir, "system", "fvSchemes")
+    fs = read_dict(fs_path)
+    words, flux = read_face_schemes(fs, ("div(phiu,T)",), ("grad(T)",), fs_path)   # fvsc::grad(T) [updateFields.H L1], qgdFlux(phiu,T,Tf) [.C L110]
+    opt["stencil"] = words["grad(T)"]
+    opt["fluxSchemeT"] = 1 if flux["div(phiu,T)"] == "upwind" else 0
+    _check_fv_schemes(fs, mesh, need_laplacian=True, need_grad=False, what=fs_path)
+    cd = read_dict(os.path.join(case_dir, "system", "controlDict"))
+    opt["deltaT"] = float(cd["deltaT"])
+    opt["adjustTimeStep"] = 1 if _truthy(cd.get("adjustTimeStep", "no")) else 0
+    if opt["adjustTimeStep"]:
+        opt["maxCo"] = float(cd.get("maxCo", 1.0))                 # runTime.controlDict().lookupOrDefault [readTimeControls.H, L0]
+        opt["maxDeltaT"] = float(cd.get("maxDeltaT", 1e300))       # GREAT
+        opt["cTau"] = float(cd.get("cTau", 0.75))
+    control = {"endTime": float(cd["endTime"]), "writeInterval": float(cd.get("writeInterval", 1)),
+               "writeControl": str(cd.get("writeControl", "timeStep")), "timePrecision": int(cd.get("timePrecision", 6))}
+    fsol_path = os.path.join(case_dir, "system", "fvSolution")
+    if _exists(fsol_path):
+        solvers = read_dict(fsol_path).get("solvers", {})
+        for key, entry in solvers.items() if isinstance(solvers, dict) else ():
+            names = str(key).strip('"()').replace("|", " ").split()
+            if isinstance(entry, dict) and "T" in names:
+                opt["implicitTol"] = float(entry.get("tolerance", 1e-6))
+                opt["implicitMaxIter"] = int(float(entry.get("maxIter", 1000)))
+    U, bU = read_field(os.path.join(tdir, "U"), mesh)
+    T, bT = read_field(os.path.join(tdir, "T"), mesh)
+    ptw = [PATCH_WORDS.get(int(t), "patch") for t in mesh.array("patchType")]
+    bcs = []
+    for i, name in enumerate(mesh.patch_names):
+        bu, bt = _bc(bU[name], True, ptw[i], f"U.{name}"), _bc(bT[name], False, ptw[i], f"T.{name}")
+        if bu[0] == "qgdFlux" or bt[0] in ("qgdFlux", "slip"):
+            raise FoamFileError(f"patch {name}: boundary condition not supported for U / T of a scalarTransportQHDFoam case")
+        bcs.append({"U": bu, "T": bt})
+    return mesh, opt, {"U": U, "T": T[:, 0]}, bcs, control
+
+
+def load_scalar_case(case_dir, time="0", device_id=0):
+    """Case directory -> (Device, ScalarTransportQHDCase) ready to ``step()``"""
+    from .fvsc import Device
+    from .scalarfoam import ScalarTransportQHDCase, scalar_options
+
+    mesh, opt, fields, bcs, _ = read_scalar_case_setup(case_dir, time)
+    dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}}, fused_tables=False)
+    case = ScalarTransportQHDCase(dev, scalar_options(**opt))
+    for i, bc in enumerate(bcs):
+        case.set_bc(i, U=bc["U"], T=bc["T"])
+    case.set_fields(fields["U"], fields["T"])
+    return dev, case
+
+
+def write_scalar_time(case, case_dir, time_name, U, bcs=None, rho0=None):
+    """T of a ScalarTransportQHDCase, the frozen U it was started with and the uniform rho into <case_dir>/<time_name>/ (the AUTO_WRITE
+    fields of scalarTransportQHDFoam); T's patch entries carry the patch values as ``value``"""
+    mesh = case.mesh
+    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
+    ps, pz, pt = mesh.array("patchStart"), mesh.array("patchSize"), mesh.array("patchType")
+    nIF = mesh.nInternalFaces
+    Tb = case.field("T.boundary")
+    rho = float(rho0 if rho0 is not None else case.options.rho0)
+    pT, pU, pR = {}, {}, {}
+    for i, pn in enumerate(names):
+        word = PATCH_WORDS.get(int(pt[i]), "patch")
+        if word in _CONSTRAINT_BCS:
+            pT[pn] = pU[pn] = pR[pn] = (word, None)
+            continue
+        b0 = int(ps[i]) - nIF
+        kT = bcs[i]["T"][0] if bcs is not None else "calculated"
+        pT[pn] = ("calculated" if kT == "none" else kT, Tb[b0:b0 + int(pz[i])])
+        kU, vU = bcs[i]["U"] if bcs is not None else ("zeroGradient", None)
+        pU[pn] = (kU, np.asarray(vU, dtype=np.float64)) if kU == "fixedValue" else (kU, None)
+        pR[pn] = ("calculated", np.float64(rho))
+    d = os.path.join(case_dir, str(time_name))
+    write_field(os.path.join(d, "T"), mesh, "T", case.field("T"), pT, "[0 0 0 1 0 0 0]")
+    write_field(os.path.join(d, "U"), mesh, "U", np.asarray(U, dtype=np.float64).reshape(-1, 3), pU, "[0 1 -1 0 0 0 0]")
+    write_field(os.path.join(d, "rho"), mesh, "rho", np.full(mesh.nCells, rho), pR, "[1 -3 0 0 0 0 0]")
+
+
 def load_qhd_case(case_dir, time="0", device_id=0):
     """Case directory -> (Device, QHDFoamCase) ready to ``step()``: the createFields.H sequence of QHDFoam over the C-ABI."""
     from .fvsc import Device
