@@ -1041,13 +1041,19 @@ void cellUpdateKernel(const MeshView m, const CaseView c, const GasModel gm, con
     blockMaxMin<CB>(-rmin, emin, c.blkCell + 2 * (size_t)(slotBase + tile), true);
 }
 
+// a value loaded under a lane mask passes through here before its first use: the compiler then cannot move arithmetic on it up into the
+// masked block, where it would put a wait for the load between the loads of a round (no instruction is emitted)
+template <class T> __device__ __forceinline__ void fuPin(T& v) { asm volatile("" : "+v"(v)); }
+
 // ---------------------------------------------------------------------------
 // QGD_FUSED: the explicit step of a BLOCK of cells in one workgroup (qgd_setup.hpp FusedBlocks) -- vertex values, internal faces, cell update.
 // The three kernels of the explicit step (P, F, C above) run at what the memory system delivers (profiles/r05_ab_face_four_waves.txt), and
 // most of the step's bytes are what they hand each other through HBM: 48 B per vertex written by P and read back by F, 40 B per face written
 // by F and read back twice by C.  Here a workgroup (256 threads) takes <= 128 cells that are compact in space -- an 8x4x4 brick on a box --
 // and
-//   (0) reads its lists (no address depends on a loaded value: they are padded to fixed strides) and, one round trip later, stages in LDS
+//   (0) reads its lists (no address depends on a loaded value: they are padded to fixed strides, so round 0 needs no count) and, one round
+//       trip later -- every lane loading only what it keeps: the counts have arrived with the lists (see "which lanes load what" in the
+//       body) -- stages in LDS
 //       RecA of its own cells, of the cells across its surface and of the edge / corner cells around its vertices (360 on a box), RecB and
 //       the centres of the first two groups (288), the coordinates of its vertices (225);
 //   (1) thread v forms vertex v: volPointInterpolation's weighted sum over pointCells, in their order (pointInterpRecKernel's arithmetic,
@@ -1095,11 +1101,16 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     const int32_t* __restrict__ tCells = m.fuCells + (size_t)blk * capC;
     const int32_t* __restrict__ tVerts = m.fuVerts + (size_t)blk * capV;
     const int32_t* __restrict__ tFaceLabel = m.fuFaceLabel + (size_t)blk * capF;
-    // (0) everything whose address does not depend on a loaded value: the counts and the template id, the lists (padded to their strides with
-    // their last entry, so no count is needed to read them), the labels of this thread's two faces, its vertex's weights
-    const int4 hdr = m.fuHdr[blk];
-    const int4 hdr2 = m.fuHdr2[blk];
-    const int nTot = hdr2.x;
+    // (0) everything whose address does not depend on a loaded value: the counts and the template id, the piece labels out of the lists (padded
+    // to their strides with their last entry, so no count is needed to read them), the labels of this thread's two faces, its vertex and its
+    // cell.  Nothing in this round waits for the counts: they arrive with it.
+    // WHICH LANES LOAD WHAT, from round 1 on: a lane loads only what it keeps.  The own-cell data (label and entry count already in round 0,
+    // face entries, rhoE, V, hQGD) under tid < 128 -- waves 2 and 3 branch round it; a record piece under the condition of its LDS store; a
+    // vertex's weights, cell positions and patch-point record under tid < nUv; a face's positions and streams under lf < nFc.  A wavefront
+    // whose whole slot range is empty branches round the instruction (wv0 + k NT is the wavefront's first slot: a scalar compare).  A value
+    // loaded under a mask is used under that mask only; it passes an empty asm first where the compiler would otherwise move integer
+    // arithmetic on it into the masked block, behind a wait for the load (fuPin).
+    const int wv0 = __builtin_amdgcn_readfirstlane(tid & ~63);
     int fl[KF];
 #pragma unroll
     for (int j = 0; j < KF; ++j) fl[j] = tFaceLabel[min(tid + j * NT, capF - 1)];
@@ -1119,60 +1130,99 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         const int q = tid + k * NT, r = (q * 43691) >> 17;
         idV[k] = tVerts[min(r, capV - 1)] * 3 + (q - 3 * r);
     }
-    const int ci = tCells[min(tid & 127, capC - 1)];   // (threads beyond the block's cells repeat its last label: loads stay inside the lists)
-    const int nEraw = (int)m.fuNEntry[(size_t)blk * 128 + (tid & 127)];
-    // this thread's vertex (thread v forms vertex v of the block's list)
+    // this thread's own cell (threads 0..127; those beyond the block's cells repeat its last label: the list is padded)
+    const bool cellLane = wv0 < 128;
+    int ci, nEraw;
+    if (cellLane) {
+        ci = tCells[min(tid, capC - 1)];
+        nEraw = (int)m.fuNEntry[(size_t)blk * 128 + tid];
+    }
+    // (the counts: block-uniform, but loaded through the vector path and broadcast -- asked for behind the branch above, or the broadcast,
+    // and with it a wait for them, lands in front of that branch and of the loads behind it)
+    const int4 hdr = m.fuHdr[blk];
+    const int4 hdr2 = m.fuHdr2[blk];
+    const int nTot = hdr2.x;
+    // this thread's vertex (thread v forms vertex v of the block's list; threads beyond the block's vertices repeat its last one)
     const int vt = min(tid, capV - 1);
     const int myVert = tVerts[vt];
     const int nPc = (int)m.fuVCount[(size_t)blk * capV + vt];
-    const double* __restrict__ vW = m.fuVW + (size_t)blk * capPE * capV + vt;
-    double pcW[KP];
-#pragma unroll
-    for (int i = 0; i < KP; ++i) pcW[i] = vW[(size_t)min(i, capPE - 1) * capV];
-    // (1) one round trip later: the records, piece by piece; the faces' streams; the cell's own scalars; a patch point's record -- and the
-    // block's local topology out of its TEMPLATE (hdr2.y; qgd_setup.hpp FusedBlocks: the interior bricks of a structured region share a few
+    // The round ends HERE, for everything at once (s_waitcnt vmcnt(0): the loads above went out back to back and return together).  The
+    // memory counter counts in order, and behind a masked block the compiler no longer knows how many loads are outstanding: left to
+    // itself it waits for a label of this round by waiting for masked loads of the next one as well -- a third round trip.
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __builtin_amdgcn_sched_barrier(0);
+    // (1) one round trip later: the records, piece by piece; the faces' streams; the cell's own scalars; the vertex's weights; a patch
+    // point's record -- and the block's local topology out of its TEMPLATE (hdr2.y; qgd_setup.hpp FusedBlocks: the interior bricks of a structured region share a few
     // hundred templates, which stay in L2): the positions of this thread's two faces' cells and vertices in the staged lists, its cell's face
     // entries, its vertex's cell positions.  None of it is needed before the records are staged, so the template costs no round trip.
+    const int nOwn = hdr.x, nUc = hdr.y, nUv = hdr.z, nFc = hdr.w;
+    const bool vertWave = wv0 < nUv, vertLane = tid < nUv;
     const size_t tpl = (size_t)hdr2.y;
     struct Pos3 { uint32_t c, va, vb; };
     const Pos3* __restrict__ tFacePos = reinterpret_cast<const Pos3*>(m.fuFacePos) + tpl * capF;
     const int32_t* __restrict__ ent = m.fuEntry + tpl * m.fuCapE * 128 + (tid & 127);
     const uint16_t* __restrict__ vPos = m.fuVPos + tpl * capPE * capV + vt;
+    const double* __restrict__ vW = m.fuVW + (size_t)blk * capPE * capV + vt;
     Pos3 fp[KF];
 #pragma unroll
-    for (int j = 0; j < KF; ++j) fp[j] = tFacePos[min(tid + j * NT, capF - 1)];
+    for (int j = 0; j < KF; ++j) {
+        if (wv0 + j * NT < nFc) { if (tid + j * NT < nFc) fp[j] = tFacePos[tid + j * NT]; }
+    }
     int e6[KE];
+    if (cellLane) {
 #pragma unroll
-    for (int i = 0; i < KE; ++i) e6[i] = ent[(size_t)min(i, m.fuCapE - 1) * 128];
+        for (int i = 0; i < KE; ++i) e6[i] = ent[(size_t)min(i, m.fuCapE - 1) * 128];
+    }
     int pcPos[KP];
+    double pcW[KP];
+    if (vertWave) {
+        if (vertLane) {
 #pragma unroll
-    for (int i = 0; i < KP; ++i) pcPos[i] = (int)vPos[(size_t)min(i, capPE - 1) * capV];
+            for (int i = 0; i < KP; ++i) pcPos[i] = (int)vPos[(size_t)min(i, capPE - 1) * capV];
+#pragma unroll
+            for (int i = 0; i < KP; ++i) pcW[i] = vW[(size_t)min(i, capPE - 1) * capV];
+        }
+    }
     const v2d* __restrict__ gA = reinterpret_cast<const v2d*>(c.A);
     const v2d* __restrict__ gB = reinterpret_cast<const v2d*>(c.B);
     const v2d* __restrict__ gP = reinterpret_cast<const v2d*>(c.P);
     v2d dA[KC], dB[KB2];
     double dC[KCC], dX[KV];
 #pragma unroll
-    for (int k = 0; k < KC; ++k) dA[k] = gA[idC[k]];
+    for (int k = 0; k < KC; ++k) {
+        if (wv0 + k * NT < 3 * nTot) { if (tid + k * NT < 3 * nTot) dA[k] = gA[idC[k]]; }
+    }
 #pragma unroll
-    for (int k = 0; k < KCC; ++k) dC[k] = m.Cc[idC[k]];
+    for (int k = 0; k < KCC; ++k) {
+        if (wv0 + k * NT < 3 * nUc) { if (tid + k * NT < 3 * nUc) dC[k] = m.Cc[idC[k]]; }
+    }
 #pragma unroll
-    for (int k = 0; k < KB2; ++k) dB[k] = gB[idB[k]];
+    for (int k = 0; k < KB2; ++k) {
+        if (wv0 + k * NT < 2 * nUc) { if (tid + k * NT < 2 * nUc) dB[k] = gB[idB[k]]; }
+    }
 #pragma unroll
-    for (int k = 0; k < KV; ++k) dX[k] = m.X[idV[k]];
+    for (int k = 0; k < KV; ++k) {
+        if (wv0 + k * NT < 3 * nUv) { if (tid + k * NT < 3 * nUv) dX[k] = m.X[idV[k]]; }
+    }
     double fw[KF], fh[KF];
     int fk[KF];
 #pragma unroll
-    for (int j = 0; j < KF; ++j) { fw[j] = ldStream(m.w + fl[j]); fh[j] = ldStream(m.hf + fl[j]); fk[j] = m.fkind[fl[j]]; }
-    const double rEold = c.rE[ci], Vc = m.V[ci], hq = m.hQGD[ci];
+    for (int j = 0; j < KF; ++j) {
+        if (wv0 + j * NT < nFc) {
+            if (tid + j * NT < nFc) { fw[j] = ldStream(m.w + fl[j]); fh[j] = ldStream(m.hf + fl[j]); fk[j] = m.fkind[fl[j]]; }
+        }
+    }
+    fuPin(ci);
+    double rEold, Vc, hq;
+    if (cellLane) { rEold = c.rE[ci]; Vc = m.V[ci]; hq = m.hQGD[ci]; }
     v2d dPt[3];
     dPt[0] = dPt[1] = dPt[2] = v2d{0.0, 0.0};
-    if (nPc == 0) {   // a patch point: the patch-point kernel has put its value into the vertex records
+    if (vertLane && nPc == 0) {   // a patch point: the patch-point kernel has put its value into the vertex records
 #pragma unroll
         for (int k = 0; k < 3; ++k) dPt[k] = gP[(size_t)myVert * 3 + k];
     }
     __builtin_amdgcn_sched_barrier(0);
-    const int nOwn = hdr.x, nUc = hdr.y, nUv = hdr.z, nFc = hdr.w;
     // LDS, laid out by THIS block's counts (the launch reserves what the block that needs most takes): RecA of every staged cell and RecB of
     // the own + across-a-face cells stay to the end (an own cell's old record is read by its update); the vertex records -- formed HERE, from
     // the staged cells -- and all coordinates are dead once every face has its fluxes in registers, and the fluxes take their place.  The
@@ -1199,6 +1249,12 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
 #pragma unroll
     for (int k = 0; k < KV; ++k) { const int q = tid + k * NT; if (q < 3 * nUv) sX[q] = dX[k]; }
     __syncthreads();
+    // (every load of the two rounds has arrived: from here on the values loaded under a mask may be computed with)
+    fuPin(nEraw);
+#pragma unroll
+    for (int i = 0; i < KP; ++i) fuPin(pcPos[i]);
+#pragma unroll
+    for (int j = 0; j < KF; ++j) { fuPin(fk[j]); fuPin(fp[j].c); fuPin(fp[j].va); fuPin(fp[j].vb); }
     // (1b) the vertex values [volPointInterpolation: inverse-distance weights over pointCells, in their order -- pointInterpRecKernel's
     // arithmetic, out of the staged cell records]
     if (tid < nUv) {
@@ -1337,7 +1393,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         // tauMC, phiTauMC, the laplacian coefficients of every face; (c) the phiTauMC / coefficient planes -> the cells' second sums and
         // their rows of the U systems.  The gradients and the faces' streamed data are requested before (a) and arrive behind it.
         const size_t nF = (size_t)m.nF;
-        double dG[KG], fgsd[KF], fS[KF][3];
+        double dG[KG], fms[KF], fdn[KF], fS[KF][3];
         int fps[KF];
 #pragma unroll
         for (int k = 0; k < KG; ++k) {
@@ -1346,10 +1402,14 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         }
 #pragma unroll
         for (int j = 0; j < KF; ++j) {
-            fps[j] = ldStream(m.fpos + fl[j]);
-            fgsd[j] = ldStream(m.magSf + fl[j]) * ldStream(m.dn + fl[j]);   // |Sf| * nonOrthDeltaCoeffs
-            // the STREAMED Sf: implFaceTileKernel multiplies with that one, the QGD fluxes above with the Sf rebuilt from the vertices
-            fS[j][0] = ldStream(m.Sx + fl[j]); fS[j][1] = ldStream(m.Sy + fl[j]); fS[j][2] = ldStream(m.Sz + fl[j]);
+            if (wv0 + j * NT < nFc) {
+                if (tid + j * NT < nFc) {
+                    fps[j] = ldStream(m.fpos + fl[j]);
+                    fms[j] = ldStream(m.magSf + fl[j]); fdn[j] = ldStream(m.dn + fl[j]);   // |Sf|, nonOrthDeltaCoeffs: multiplied where the face uses them (no wait in here)
+                    // the STREAMED Sf: implFaceTileKernel multiplies with that one, the QGD fluxes above with the Sf rebuilt from the vertices
+                    fS[j][0] = ldStream(m.Sx + fl[j]); fS[j][1] = ldStream(m.Sy + fl[j]); fS[j][2] = ldStream(m.Sz + fl[j]);
+                }
+            }
         }
 #pragma unroll
         for (int j = 0; j < KF; ++j) {
@@ -1393,7 +1453,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
                 const double muQo = reinterpret_cast<const RecB*>(sB + 2 * lo)->muQGD, muQn = reinterpret_cast<const RecB*>(sB + 2 * ln)->muQGD;
                 const double uo[3] = {Ao.ux, Ao.uy, Ao.uz}, un[3] = {An.ux, An.uy, An.uz};
                 ImplFaceOut r;
-                implInternalFace(gm, fw[j], muQo, muQn, uo, un, sG + 9 * lo, sG + 9 * ln, fS[j], fgsd[j], r);
+                implInternalFace(gm, fw[j], muQo, muQn, uo, un, sG + 9 * lo, sG + 9 * ln, fS[j], fms[j] * fdn[j], r);
                 oxi[j][0] = r.phiTau[0]; oxi[j][1] = r.phiTau[1]; oxi[j][2] = r.phiTau[2]; oxi[j][3] = r.aU;
                 if (lo < nOwn) {   // the block that owns the face's owner writes what the solves and the energy equation read later
                     const size_t pos = (size_t)fps[j];
