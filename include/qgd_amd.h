@@ -105,7 +105,7 @@ typedef struct qgd_case_s* qgd_case_t;     /* a QGDFoam case on one device      
 
 /* ---- library ---------------------------------------------------------------- */
 /* Bumped whenever an options struct grows or an entry changes its meaning (3: round 3). */
-#define QGD_ABI_VERSION 7
+#define QGD_ABI_VERSION 8
 const char* qgd_version(void);
 /* sizes[0..2] = sizeof(qgd_case_options), sizeof(qgd_qhd_options), sizeof(qgd_poisson_control) as THIS library was built,
  * sizes[3] = its QGD_ABI_VERSION: a host compiled against another header compares before it passes a struct (the structs
@@ -537,6 +537,26 @@ int qgd_qhd_case_sync(qgd_qhd_case_t c);
 /* measurement: `reps` smoothing sweeps of multigrid level 0 (the kernel the pressure solve spends most of its time in) between two
  * HIP events; info = {average ms per sweep, rows, ELL width, bytes per matrix value and vector entry (4: single-precision cycle)} */
 int qgd_qhd_case_sweep_time(qgd_qhd_case_t c, int reps, double info[4]);
+/* The pressure preconditioner z = M r (one multigrid V-cycle) as an observable operator: three entries for tests, none of which
+ * changes a solve.  QGD_ERR_INVALID before qgd_qhd_case_set_fields; QGD_ERR_NOT_IMPLEMENTED on a sharded device, with precond = 0
+ * and for the hierarchy that spans the ranks.
+ * mg_info: info[0..32) = {levels, single-precision cycle, smoothed aggregation, omega, oc, nu, nu0, coarseSweeps, cr[8], cm[8],
+ *   fused hand-over possible (mode 1 of mg_apply), rows per r.z partial, QGD_MG_PT_ELL_MIN, 0...}, then 8 per level: {rows, layout
+ *   (0 sliced ELL, 1 CSR rows), dense inverse, smoothed prolongator, P^T sliced, smootherScale, widest row, stored entries};
+ *   cap >= 32 + 8 levels (128 always suffices).
+ * mg_get: one array of one level copied BACK FROM DEVICE MEMORY (lengths from the start arrays read back, not from the builder's
+ *   host copies); *n = its elements, buf == NULL: size query, 0: the level has no such array.  what: 0 diag, 1 sliceStart / rowStart,
+ *   2 col, 3 val, 4 pS, 5 pCol, 6 pVal, 7 ptS, 8 ptCol, 9 ptVal, 10 agg, 11 aggStart, 12 aggItems, 13 inverse, 14 / 15 diag / val of
+ *   the double-precision level.  Elements: int32_t (1, 2, 4, 5, 7, 8, 10, 11, 12), double (14, 15), otherwise the cycle's precision
+ *   (float for a single-precision cycle, else double); cap counts elements.  Sliced ELL: entry k of row i at
+ *   (sliceStart[i >> 6] + k) * 64 + (i & 63), col < 0 = padding; val holds a_ij = -A_ij, diag A_ii.
+ * mg_apply: z = M r for host vectors over the rows (cells), through the solver's own preconditioner call.  mode 0: the separate
+ *   passes; mode 1: the fused tail (the last level-0 sweep writes z in double and the partial sums of r.z per block of info[25]
+ *   rows into rzPart, ceil(rows / info[25]) doubles; QGD_ERR_INVALID when info[24] == 0).  Runs with the control block's "done"
+ *   flag cleared and puts the control block, r and z back as it found them. */
+int qgd_qhd_case_mg_info(qgd_qhd_case_t c, double* info, int32_t cap);
+int qgd_qhd_case_mg_get(qgd_qhd_case_t c, int32_t level, int32_t what, void* buf, int64_t cap, int64_t* n);
+int qgd_qhd_case_mg_apply(qgd_qhd_case_t c, const double* r, double* z, int32_t mode, double* rzPart);
 int qgd_qhd_case_halo_count(qgd_qhd_case_t c, int slot, int kind, int64_t* sendCount, int64_t* recvCount);
 int qgd_qhd_case_halo_pack(qgd_qhd_case_t c, int slot, int kind, double* sendBufDevice);
 int qgd_qhd_case_halo_unpack(qgd_qhd_case_t c, int slot, int kind, const double* recvBufDevice);

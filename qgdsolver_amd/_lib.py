@@ -144,6 +144,9 @@ SIGNATURES = {
     "qgd_qhd_case_control": (C.c_int, [handle, c_double_p, C.c_int]),
     "qgd_qhd_case_sync": (C.c_int, [handle]),
     "qgd_qhd_case_sweep_time": (C.c_int, [handle, C.c_int, c_double_p]),
+    "qgd_qhd_case_mg_info": (C.c_int, [handle, c_double_p, C.c_int32]),
+    "qgd_qhd_case_mg_get": (C.c_int, [handle, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, c_int64_p]),
+    "qgd_qhd_case_mg_apply": (C.c_int, [handle, c_double_p, c_double_p, C.c_int32, c_double_p]),
     "qgd_case_implicit_apply_time": (C.c_int, [handle, C.c_int, c_double_p]),
     "qgd_qhd_case_halo_count": (C.c_int, [handle, C.c_int, C.c_int, c_int64_p, c_int64_p]),
     "qgd_qhd_case_halo_pack": (C.c_int, [handle, C.c_int, C.c_int, C.c_void_p]),

@@ -2469,6 +2469,47 @@ int qgd_qhd_case_sweep_time(qgd_qhd_case_t c, int reps, double info[4]) {
     return QGD_OK;
     QGD_CATCH
 }
+// the three read-only entries on the pressure preconditioner: 0 when the cycle is observable, else the status (last error set)
+static int qhdMgRefused(qgd_qhd_case_t c, const char* who) {
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    if (!c->solver) return fail(QGD_ERR_INVALID, std::string(who) + ": call qgd_qhd_case_set_fields first");
+    if (c->dev->sharded() || !pressureSolverMgObservable(c->solver))
+        return fail(QGD_ERR_NOT_IMPLEMENTED, std::string(who) + ": the multigrid cycle of an unsharded case with precond = 1 only");
+    return QGD_OK;
+}
+int qgd_qhd_case_mg_info(qgd_qhd_case_t c, double* info, int32_t cap) {
+    QGD_TRY
+    if (const int rc = qhdMgRefused(c, "qgd_qhd_case_mg_info")) return rc;
+    if (!info || cap < 1) return fail(QGD_ERR_INVALID, "qgd_qhd_case_mg_info: bad argument");
+    const int need = pressureSolverMgInfo(c->solver, info, cap);
+    if (need > cap) return fail(QGD_ERR_INVALID, "qgd_qhd_case_mg_info: info needs " + std::to_string(need) + " doubles");
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_qhd_case_mg_get(qgd_qhd_case_t c, int32_t level, int32_t what, void* buf, int64_t cap, int64_t* n) {
+    QGD_TRY
+    if (const int rc = qhdMgRefused(c, "qgd_qhd_case_mg_get")) return rc;
+    if (!n) return fail(QGD_ERR_INVALID, "qgd_qhd_case_mg_get: null argument");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    const int64_t count = pressureSolverMgGet(c->solver, level, what, nullptr, 0);
+    if (count < 0) return fail(QGD_ERR_INVALID, "qgd_qhd_case_mg_get: no such level or array");
+    *n = count;
+    if (!buf) return QGD_OK;
+    if (cap < count) return fail(QGD_ERR_INVALID, "qgd_qhd_case_mg_get: buf holds " + std::to_string(cap) + " of " + std::to_string(count) + " elements");
+    pressureSolverMgGet(c->solver, level, what, buf, cap);
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_qhd_case_mg_apply(qgd_qhd_case_t c, const double* r, double* z, int32_t mode, double* rzPart) {
+    QGD_TRY
+    if (const int rc = qhdMgRefused(c, "qgd_qhd_case_mg_apply")) return rc;
+    if (!r || !z || mode < 0 || mode > 1 || (mode == 1 && !rzPart)) return fail(QGD_ERR_INVALID, "qgd_qhd_case_mg_apply: bad argument");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    if (!pressureSolverMgApply(c->solver, r, z, mode == 1, rzPart))
+        return fail(QGD_ERR_INVALID, "qgd_qhd_case_mg_apply: mode 1 needs the fused hand-over of a single-precision cycle (QGD_MG_F32, QGD_MG_FUSE)");
+    return QGD_OK;
+    QGD_CATCH
+}
 int qgd_qhd_case_control(qgd_qhd_case_t c, double control[16], int set) {
     QGD_TRY
     if (!c || !control) return fail(QGD_ERR_INVALID, "null argument");

@@ -392,6 +392,11 @@ void pressureSolveFlux(PressureSolver* S, double* phi);
 void pressureSolveStatus(PressureSolver* S, double out[4]);
 double pressureSolverSweepMs(PressureSolver* S, int reps, int* rows, double* width);   // measurement: one level-0 smoothing sweep
 bool pressureSolverSinglePrecisionCycle(const PressureSolver* S);
+// the multigrid cycle as an observable operator (tests; qgd_poisson.hip): an unsharded hierarchy of precond 1 only
+bool pressureSolverMgObservable(const PressureSolver* S);
+int pressureSolverMgInfo(const PressureSolver* S, double* info, int cap);                          // returns the doubles needed
+int64_t pressureSolverMgGet(PressureSolver* S, int level, int what, void* buf, int64_t cap);     // elements (0 none, -1 bad level / what)
+bool pressureSolverMgApply(PressureSolver* S, const double* r, double* z, bool tail, double* rzPart);   // false: no fused tail in this cycle
 double* pressureSolverCtl(PressureSolver* S);         // control block: slots [0,3) [3] [4] [5] [6,8) [8] are the sums a sharded run reduces
 double* pressureSolverDirection(PressureSolver* S);   // nC doubles by local cell label
 

@@ -786,6 +786,8 @@ struct PressureSolver {
     int passes = 2;
     double saTheta = 0.08;
     int denseMax = 2048;                   // QGD_MG_DENSE_MAX
+    int ptEllMin = 300000;                 // QGD_MG_PT_ELL_MIN: P^T of a transfer to more coarse rows than this is stored as sliced ELL (mgRestrictEllKernel)
+    double* hookBuf = nullptr;             // pressureSolverMgApply: what it puts back (r, z, the control block) and its own r.z partials
     int64_t distMaxCells = 20000000;       // QGD_MG_DIST_MAX_CELLS: above it a sharded solve keeps the rank-local hierarchy (distSetupStep)
     int rowRun = 0;                        // QGD_ROW_XCD_RUN: row blocks per XCD run of the sliced-ELL sweeps (xcdRunBlock), 0: plain order (measured: runs of 16 make the f32 sweeps 1 % slower)
     // ---- a hierarchy that SPANS THE RANKS of a sharded solve (QGD_MG_DIST, default on; 0: the rank-local block hierarchy) ----------------
@@ -1379,12 +1381,12 @@ static void mgBuildHierarchy(PressureSolver* S, int n, std::vector<int>& I, std:
             } else if (S->f32) {
                 MgLevelT<float>& ff = S->Lf.back();
                 mgUploadEll<float>(S, n, P, &ff.pS, &ff.pCol, &ff.pVal);
-                if (cur > 300000) { mgUploadEll<float>(S, cur, PT, &ff.ptS, &ff.ptCol, &ff.ptVal); ff.ptSliced = 1; }
+                if (cur > S->ptEllMin) { mgUploadEll<float>(S, cur, PT, &ff.ptS, &ff.ptCol, &ff.ptVal); ff.ptSliced = 1; }
                 else mgUploadCsr<float>(S, cur, PT, &ff.ptS, &ff.ptCol, &ff.ptVal);
                 fine.pS = ff.pS;   // marks the level; the double arrays of the levels below 0 are not used with the f32 cycle
             } else {
                 mgUploadEll<double>(S, n, P, &fine.pS, &fine.pCol, &fine.pVal);
-                if (cur > 300000) { mgUploadEll<double>(S, cur, PT, &fine.ptS, &fine.ptCol, &fine.ptVal); fine.ptSliced = 1; }
+                if (cur > S->ptEllMin) { mgUploadEll<double>(S, cur, PT, &fine.ptS, &fine.ptCol, &fine.ptVal); fine.ptSliced = 1; }
                 else mgUploadCsr<double>(S, cur, PT, &fine.ptS, &fine.ptCol, &fine.ptVal);
             }
             I.swap(cI); J.swap(cJ); w.swap(cw); diag.swap(cdiag);
@@ -1452,6 +1454,7 @@ PressureSolver* pressureSolverCreate(hipStream_t stream, const MeshView& m, cons
         S->saTheta = knob("QGD_MG_SA_THETA", 0.08, 0.0, 0.9);             // strength threshold on level 0, halved per level
         S->rowRun = (int)knob("QGD_ROW_XCD_RUN", 0, 0, 4096);
         S->denseMax = (int)knob("QGD_MG_DENSE_MAX", MG_DENSE_MAX, 64, 8192);  // the last level (solved exactly) has at most this many rows
+        S->ptEllMin = (int)knob("QGD_MG_PT_ELL_MIN", S->ptEllMin, 0, 2.0e9);
         if (sa) S->oc = knob("QGD_MG_OC", 1.0, 0.5, 3.0);
         S->distMaxCells = (int64_t)knob("QGD_MG_DIST_MAX_CELLS", (double)S->distMaxCells, 0, 2.0e9);
         // a shard with smoothed aggregation and the single-precision cycle builds the hierarchy that spans the ranks, at its first solve
@@ -2199,6 +2202,119 @@ double pressureSolverSweepMs(PressureSolver* S, int reps, int* rows, double* wid
     return (double)ms / reps;
 }
 bool pressureSolverSinglePrecisionCycle(const PressureSolver* S) { return !S->Lf.empty(); }
+
+// ---- the cycle as an observable operator (tests): its parameters, its arrays as the device holds them, one application z = M r.
+// None of the three changes a solve: they read, or they put back what they touched.
+bool pressureSolverMgObservable(const PressureSolver* S) { return S->precond == 1 && !S->dist.wanted && !S->L.empty(); }
+// info[0..32): levels, f32, sa, omega, oc, nu, nu0, coarseSweeps, cr[8], cm[8], fused hand-over possible, rows per block of the r.z
+// partials, QGD_MG_PT_ELL_MIN, 0...;  then 8 per level: n, layout (0 sliced ELL, 1 CSR rows), dense inverse, smoothed prolongator,
+// ptSliced, smootherScale, widest row, stored entries.  Returns the doubles needed (nothing is written when cap is smaller).
+int pressureSolverMgInfo(const PressureSolver* S, double* info, int cap) {
+    const int nL = (int)S->L.size(), need = 32 + 8 * nL;
+    if (cap < need) return need;
+    std::fill(info, info + need, 0.0);
+    info[0] = nL; info[1] = S->f32 ? 1 : 0; info[2] = S->sa ? 1 : 0; info[3] = S->omega; info[4] = S->oc; info[5] = S->nu; info[6] = S->nu0;
+    info[7] = S->coarseSweeps;
+    for (int k = 0; k < 8; ++k) { info[8 + k] = S->cr[k]; info[16 + k] = S->cm[k]; }
+    info[24] = S->fusedCycle() ? 1 : 0; info[25] = PB; info[26] = (double)S->ptEllMin;
+    for (int l = 0; l < nL; ++l) {
+        double* o = info + 32 + 8 * l;
+        const MgLevelDev& lv = S->L[l];
+        const bool f = S->f32;
+        o[0] = lv.n; o[1] = lv.rowStart ? 1 : 0;
+        o[2] = (f ? S->Lf[l].inverse != nullptr : lv.inverse != nullptr) ? 1 : 0;
+        o[3] = lv.pS ? 1 : 0; o[4] = f ? S->Lf[l].ptSliced : lv.ptSliced;
+        o[5] = (size_t)l < S->smootherScale.size() ? S->smootherScale[l] : 1.0;
+        o[6] = lv.width; o[7] = (double)lv.entries;
+    }
+    return need;
+}
+// one array of one level, copied back from device memory; every length is derived from the level sizes and from the start arrays
+// READ BACK from the device, never from what the builder had on the host.  what: 0 diag, 1 sliceStart / rowStart, 2 col, 3 val,
+// 4 pS, 5 pCol, 6 pVal, 7 ptS, 8 ptCol, 9 ptVal, 10 agg, 11 aggStart, 12 aggItems, 13 inverse, 14 diag and 15 val of the
+// double-precision level (they exist next to a single-precision cycle too).  Elements: int32 (1, 2, 4, 5, 7, 8, 10-12), double (14, 15),
+// else the cycle's precision.  Returns the element count (0: the level has no such array), -1: bad level / what; copies when
+// buf != nullptr && cap >= count.
+int64_t pressureSolverMgGet(PressureSolver* S, int level, int what, void* buf, int64_t cap) {
+    if (level < 0 || level >= (int)S->L.size() || what < 0 || what > 15) return -1;
+    const bool f = S->f32;
+    const MgLevelDev& lv = S->L[level];
+    const MgLevelT<float>* lf = f ? &S->Lf[level] : nullptr;
+    const int n = lv.n, nNext = level + 1 < (int)S->L.size() ? S->L[level + 1].n : 0;
+    hipStream_t stream = S->stream;
+    auto lastOf = [&](const int* start, int64_t at) {   // start[at], from the device
+        int v = 0;
+        PCHECK(hipMemcpyAsync(&v, start + at, sizeof(int), hipMemcpyDeviceToHost, stream));
+        PCHECK(hipStreamSynchronize(stream));
+        return (int64_t)v;
+    };
+    auto slices = [](int rows) { return (int64_t)(rows + 63) / 64; };
+    const void* src = nullptr;
+    int64_t count = 0;
+    size_t elem = f ? sizeof(float) : sizeof(double);
+    const int* mStart = lv.rowStart ? lv.rowStart : lv.sliceStart;
+    // (a level without couplings still stores one padding element: the arrays are never empty)
+    auto matrixEntries = [&]() { return std::max<int64_t>(lv.rowStart ? lastOf(mStart, n) : lastOf(mStart, slices(n)) * 64, 1); };
+    const int *pS = f ? lf->pS : lv.pS, *pCol = f ? lf->pCol : lv.pCol, *ptS = f ? lf->ptS : lv.ptS, *ptCol = f ? lf->ptCol : lv.ptCol;
+    const int ptSliced = f ? lf->ptSliced : lv.ptSliced;
+    const bool hasP = pS != nullptr && pCol != nullptr;   // (the distributed level 0 marks pS only; it is not observable here)
+    auto pEntries = [&]() { return std::max<int64_t>(lastOf(pS, slices(n)) * 64, 1); };
+    auto ptEntries = [&]() { return ptSliced ? lastOf(ptS, slices(nNext)) * 64 : lastOf(ptS, nNext); };
+    switch (what) {
+        case 0: src = f ? (const void*)lf->diag : (const void*)lv.diag; count = n; break;
+        case 1: src = mStart; count = lv.rowStart ? (int64_t)n + 1 : slices(n) + 2; elem = sizeof(int); break;
+        case 2: src = lv.col; count = matrixEntries(); elem = sizeof(int); break;
+        case 3: src = f ? (const void*)lf->val : (const void*)lv.val; count = matrixEntries(); break;
+        case 4: if (hasP) { src = pS; count = slices(n) + 2; } elem = sizeof(int); break;
+        case 5: if (hasP) { src = pCol; count = pEntries(); } elem = sizeof(int); break;
+        case 6: if (hasP) { src = f ? (const void*)lf->pVal : (const void*)lv.pVal; count = pEntries(); } break;
+        case 7: if (hasP) { src = ptS; count = ptSliced ? slices(nNext) + 2 : (int64_t)nNext + 1; } elem = sizeof(int); break;
+        case 8: if (hasP) { src = ptCol; count = ptEntries(); } elem = sizeof(int); break;
+        case 9: if (hasP) { src = f ? (const void*)lf->ptVal : (const void*)lv.ptVal; count = ptEntries(); } break;
+        case 10: if (lv.agg) { src = lv.agg; count = n; } elem = sizeof(int); break;
+        case 11: if (lv.aggStart) { src = lv.aggStart; count = (int64_t)nNext + 1; } elem = sizeof(int); break;
+        case 12: if (lv.aggItems) { src = lv.aggItems; count = n; } elem = sizeof(int); break;
+        case 13: src = f ? (const void*)lf->inverse : (const void*)lv.inverse; count = src ? (int64_t)n * n : 0; break;
+        case 14: src = lv.diag; count = n; elem = sizeof(double); break;
+        case 15: src = lv.val; count = matrixEntries(); elem = sizeof(double); break;
+    }
+    if (!src) return 0;
+    if (buf && cap >= count && count > 0) {
+        PCHECK(hipMemcpyAsync(buf, src, (size_t)count * elem, hipMemcpyDeviceToHost, stream));
+        PCHECK(hipStreamSynchronize(stream));
+    }
+    return count;
+}
+// z = M r through PressureSolver::precondition, host vectors over the owned rows.  tail: the fused hand-over (mgSmoothLastKernel writes z in
+// double and the block partials of r.z, returned in rzPart: one per PB rows); false when the cycle has no such tail.  The control block
+// (its "done" flag cleared for the application), r and z are put back as they were; the partials go to a buffer of their own.
+bool pressureSolverMgApply(PressureSolver* S, const double* r, double* z, bool tail, double* rzPart) {
+    if (tail && !S->fusedCycle()) return false;
+    const int n = S->oe - S->ob, nb = blocksOf(n);
+    hipStream_t stream = S->stream;
+    if (!S->hookBuf) {
+        // (outside `bytes`: what a step needs does not grow by looking at it)
+        PCHECK(hipMalloc((void**)&S->hookBuf, sizeof(double) * (2 * (size_t)n + (size_t)nb + C_COUNT)));
+        S->owned.push_back(S->hookBuf);
+    }
+    double *keepR = S->hookBuf, *keepZ = keepR + n, *part = keepZ + n, *keepCtl = part + nb;
+    const double zero = 0.0;
+    PCHECK(hipMemcpyAsync(keepR, S->r + S->ob, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
+    PCHECK(hipMemcpyAsync(keepZ, S->z + S->ob, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
+    PCHECK(hipMemcpyAsync(keepCtl, S->ctl, sizeof(double) * C_COUNT, hipMemcpyDeviceToDevice, stream));
+    PCHECK(hipMemcpyAsync(S->r + S->ob, r, sizeof(double) * n, hipMemcpyHostToDevice, stream));
+    PCHECK(hipMemcpyAsync(S->ctl + C_DONE, &zero, sizeof(double), hipMemcpyHostToDevice, stream));
+    PCHECK(hipStreamSynchronize(stream));   // `zero` and a pageable r are read by now
+    S->precondition(false, tail ? part : nullptr);
+    PCHECK(hipGetLastError());
+    PCHECK(hipMemcpyAsync(z, S->z + S->ob, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
+    if (tail && rzPart) PCHECK(hipMemcpyAsync(rzPart, part, sizeof(double) * nb, hipMemcpyDeviceToHost, stream));
+    PCHECK(hipMemcpyAsync(S->r + S->ob, keepR, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
+    PCHECK(hipMemcpyAsync(S->z + S->ob, keepZ, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
+    PCHECK(hipMemcpyAsync(S->ctl, keepCtl, sizeof(double) * C_COUNT, hipMemcpyDeviceToDevice, stream));
+    PCHECK(hipStreamSynchronize(stream));
+    return true;
+}
 
 // single rank, everything: rhs, solve, flux
 int pressureSolve(PressureSolver* S, const double* phiu, const double* phiwo, const double* pb, const double* gb, double tolerance,

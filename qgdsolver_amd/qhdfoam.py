@@ -280,6 +280,54 @@ class QHDFoamCase:
         L.check(L.lib.qgd_qhd_case_sweep_time(self._h, int(reps), a), "qgd_qhd_case_sweep_time")
         return dict(ms=a[0], rows=int(a[1]), width=float(a[2]), value_bytes=int(a[3]))
 
+    # ---- the pressure preconditioner as an observable operator (qgd_qhd_case_mg_*; none of them changes a solve) ----
+    _MG_ARRAYS = ("diag", "start", "col", "val", "pS", "pCol", "pVal", "ptS", "ptCol", "ptVal", "agg", "aggStart", "aggItems", "inverse",
+                  "diag64", "val64")
+    _MG_INT = {"start", "col", "pS", "pCol", "ptS", "ptCol", "agg", "aggStart", "aggItems"}
+
+    def mg_info(self):
+        """parameters of the multigrid V-cycle: levels, f32, sa, omega, oc, nu, nu0, coarseSweeps, cr, cm, fused, partRows, ptEllMin and,
+        per level, n, layout ('ell' | 'csr'), dense, smoothed, ptSliced, smootherScale, width, entries"""
+        a = np.zeros(128)
+        L.check(L.lib.qgd_qhd_case_mg_info(self._h, a.ctypes.data_as(L.c_double_p), a.size), "qgd_qhd_case_mg_info")
+        nl = int(a[0])
+        levels = [dict(n=int(o[0]), layout="csr" if o[1] else "ell", dense=bool(o[2]), smoothed=bool(o[3]), ptSliced=bool(o[4]),
+                       smootherScale=float(o[5]), width=int(o[6]), entries=int(o[7])) for o in a[32:32 + 8 * nl].reshape(nl, 8)]
+        return dict(levels=levels, f32=bool(a[1]), sa=bool(a[2]), omega=float(a[3]), oc=float(a[4]), nu=int(a[5]), nu0=int(a[6]),
+                    coarseSweeps=int(a[7]), cr=a[8:16].copy(), cm=a[16:24].copy(), fused=bool(a[24]), partRows=int(a[25]), ptEllMin=int(a[26]))
+
+    def mg_level(self, level):
+        """the arrays of one level as the device holds them (copied back from device memory): a dict of numpy arrays, in the
+        precision of the cycle ('diag64' / 'val64': the double-precision level); arrays the level does not have are left out"""
+        real = np.float32 if self.mg_info()["f32"] else np.float64
+        out = {}
+        for what, name in enumerate(self._MG_ARRAYS):
+            n = C.c_int64()
+            L.check(L.lib.qgd_qhd_case_mg_get(self._h, int(level), what, None, 0, C.byref(n)), f"qgd_qhd_case_mg_get({name})")
+            if n.value == 0:
+                continue
+            a = np.zeros(n.value, dtype=np.int32 if name in self._MG_INT else (np.float64 if name.endswith("64") else real))
+            L.check(L.lib.qgd_qhd_case_mg_get(self._h, int(level), what, a.ctypes.data_as(C.c_void_p), a.size, C.byref(n)),
+                    f"qgd_qhd_case_mg_get({name})")
+            out[name] = a
+        return out
+
+    def mg_apply(self, r, tail=False):
+        """z = M r: one application of the pressure preconditioner to a host vector over the cells.  tail=True: through the fused
+        hand-over; returns (z, the block partial sums of r.z)"""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.size == self.mesh.nCells
+        z = np.zeros(r.size)
+        if not tail:
+            L.check(L.lib.qgd_qhd_case_mg_apply(self._h, r.ctypes.data_as(L.c_double_p), z.ctypes.data_as(L.c_double_p), 0, None),
+                    "qgd_qhd_case_mg_apply")
+            return z
+        rows = self.mg_info()["partRows"]
+        part = np.zeros((r.size + rows - 1) // rows)
+        L.check(L.lib.qgd_qhd_case_mg_apply(self._h, r.ctypes.data_as(L.c_double_p), z.ctypes.data_as(L.c_double_p), 1,
+                                            part.ctypes.data_as(L.c_double_p)), "qgd_qhd_case_mg_apply")
+        return z, part
+
     def halo_count(self, slot, kind):
         s, r = C.c_int64(), C.c_int64()
         L.check(L.lib.qgd_qhd_case_halo_count(self._h, int(slot), int(kind), C.byref(s), C.byref(r)), "qgd_qhd_case_halo_count")
