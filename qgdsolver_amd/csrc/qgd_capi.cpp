@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -288,6 +289,35 @@ struct TimedLaunch {
     hipEvent_t a, b;
 };
 
+// One halo message of a case (QGD case: kind 0 state, 1 grad U, 2 U, 3 search direction, 4 guess, 5 mid-assembly; QHD case: kinds 0..4,
+// include/qgd_amd.h): its length per cell / per patch face of a slot's lists, and the launch that packs it into, or unpacks it from, a buffer
+struct HaloMessage {
+    int perCell = 0, perFace = 0;
+    std::function<int(int slot, double* buf, bool pack, hipStream_t stream)> move;   // QGD_OK, or what fail() returned
+    size_t sendCount(const qgd_device_s::HaloSlot& h) const { return (size_t)perCell * h.nSend + (size_t)perFace * h.nSendBF; }
+    size_t recvCount(const qgd_device_s::HaloSlot& h) const { return (size_t)perCell * h.nGhost + (size_t)perFace * h.nGhostBF; }
+};
+// The message buffers of a case's own transport (exchangeOn), per halo slot, sized on first use for the widest message of the case.
+// ONE pair serves every message kind, the cyclic self-exchange included, because no two exchanges of a case are ever in flight together:
+// all of them are enqueued on the case's stream, in program order, except the state exchange of the overlapped step
+// (qgd_case_step_sharded), which runs on the library's halo stream -- and there the compute stream waits on evUnpacked, the event
+// behind that exchange's last unpack, before the step returns, so whatever could issue the next message (the next step's
+// mid-assembly exchange at the earliest) is ordered after the buffers' last use.  (qgd_case_set_stream waits for the old stream first.)
+struct HaloBuffers {
+    DeviceArena* arena = nullptr;
+    HaloMessage widest;   // its widths only
+    std::vector<double*> send, recv;
+    void ensure(const qgd_device_s* d) {
+        if (send.size() == d->halo.size()) return;
+        send.assign(d->halo.size(), nullptr);
+        recv.assign(d->halo.size(), nullptr);
+        for (size_t s = 0; s < d->halo.size(); ++s) {
+            send[s] = arena->alloc<double>(widest.sendCount(d->halo[s]));
+            recv[s] = arena->alloc<double>(widest.recvCount(d->halo[s]));
+        }
+    }
+};
+
 struct qgd_case_s {
     qgd_device_s* dev = nullptr;
     qgd_case_options opt{};
@@ -302,8 +332,7 @@ struct qgd_case_s {
     bool fused = false;         // qgd_case_step advances with fusedFaceCellKernel (QGD_FUSED)
     bool fusedAdj = false;      // adjustTimeStep: the blocks run up to their flux sums + Courant partials, cellFinishKernel advances once deltaT is known (QGD_FUSED_ADJUST)
     bool fusedImpl = false;     // implicitDiffusion: vertex values, QGD fluxes, tauMC and the U systems' rows are one launch on the same blocks (QGD_IMPL_FUSED)
-    std::vector<double*> selfBuf;   // cyclic pairs served by ghost cells: one message buffer per halo slot (selfHaloExchange)
-    bool ghostsCurrent = false;     // ... and whether the copies hold their originals' records: reset by set_fields (the only way on after set_bc / set_qgd_coeffs, which
+    bool ghostsCurrent = false;     // cyclic pairs served by ghost cells (selfHaloExchange): whether the copies hold their originals' records: reset by set_fields (the only way on after set_bc / set_qgd_coeffs, which
                                     //     clear fieldsSet), set by qgd_case_step and qgd_case_update_fluxes, which refresh the copies first; qgd_case_step_phase is refused
     bool hasQgdFlux = false;
     bool phiwRegistered = false;
@@ -318,8 +347,6 @@ struct qgd_case_s {
     int implSolveIndex = 0;                 // 0: the U solve is the one in flight, 1: the e solve
     bool reuseGradU = true;                 // QGD_IMPL_REUSE_GRADU (default 1)
     bool gradUValid = false;                // implicit branch, unsharded: fvc::grad(U) of phase 29 is still that of the records (phase 20 of the next step skips it)
-    std::vector<double*> implSendBuf, implRecvBuf;   // native transport of the branch's own halo messages
-    std::vector<double*> midSendBuf, midRecvBuf;     // the mid-assembly message (midExchangeOn)
     double* coef[4] = {nullptr, nullptr, nullptr, nullptr};  // device copies of non-uniform alphaQGD / ScQGD (cells, patch faces)
     double time = 0;
     int64_t steps = 0;
@@ -336,8 +363,8 @@ struct qgd_case_s {
     hipStream_t stream() const { return useUserStream ? userStream : dev->stream; }
     hipStream_t haloStream = nullptr;  // pack/unpack stream (defaults to stream())
     bool useHaloStream = false;
-    // native halo transport (qgd_case_halo_exchange): message buffers per halo slot, events ordering the two streams
-    std::vector<double*> sendBuf, recvBuf;
+    // native halo transport (qgd_case_halo_exchange, qgd_case_step_sharded, selfHaloExchange): message buffers, events ordering the two streams
+    HaloBuffers haloBuf;
     hipStream_t ownHaloStream = nullptr;
     hipEvent_t evLayerDone = nullptr, evUnpacked = nullptr;
 };
@@ -395,7 +422,6 @@ static Launcher launcherOf(qgd_case_s* c) {
 __attribute__((constructor)) static void qgdInitOpenMP() { setenv("KMP_BLOCKTIME", "0", 0); }
 
 static bool hasWedgeAndPrism(const HostMesh& m);
-static int implHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pack, hipStream_t stream);
 
 // Tuning knobs of the measurement scripts (QGD_*): a value outside the supported set is an error, not a silent change of
 // code path.  allowed == nullptr: any integer in [lo, hi].
@@ -1917,38 +1943,6 @@ static void stepAdvance(qgd_case_s* c, int part) {
     }
 }
 
-// cyclic pairs served by ghost cells: every slot packs into the case's own buffers, every slot unpacks what its partner slot packed
-// (mid = the 2-double message in the middle of the assembly, see assembleFluxes)
-static void selfHaloExchange(qgd_case_s* c, bool mid) {
-    qgd_device_s* d = c->dev;
-    const size_t nSlots = d->halo.size();
-    if (c->selfBuf.size() != nSlots) {
-        c->selfBuf.assign(nSlots, nullptr);
-        for (size_t k = 0; k < nSlots; ++k) {
-            const qgd_device_s::HaloSlot& h = d->halo[k];
-            const size_t n = std::max<size_t>(1, QGD_HALO_CELL_DOUBLES_HOST * (size_t)h.nSend + 12 * (size_t)h.nSendBF);
-            c->selfBuf[k] = c->arena.alloc<double>(n);
-        }
-    }
-    Launcher L = launcherOf(c);
-    L.pre = nullptr; L.post = nullptr;
-    (void)hipGetLastError();
-    for (size_t k = 0; k < nSlots; ++k) {
-        const qgd_device_s::HaloSlot& h = d->halo[k];
-        if (mid) { if (h.nSendBF) launchMidHalo(L.stream, c->view, h.sendBF, h.nSendBF, c->selfBuf[k], true); }
-        else if (h.nSend) launchHaloPack(L, c->view, c->gas, h.send, h.nSend, h.sendBF, h.nSendBF, c->selfBuf[k], true);
-    }
-    for (size_t k = 0; k < nSlots; ++k) {
-        const qgd_device_s::HaloSlot& h = d->halo[k];
-        const qgd_device_s::HaloSlot& from = d->halo[(size_t)d->haloSelf[k]];
-        if (from.nSend != h.nGhost || from.nSendBF != h.nGhostBF) throw std::runtime_error("cyclic self-exchange: a slot's ghosts do not match its partner's message");
-        double* buf = c->selfBuf[(size_t)d->haloSelf[k]];
-        if (mid) { if (h.nGhostBF) launchMidHalo(L.stream, c->view, h.ghostBF, h.nGhostBF, buf, false); }
-        else if (h.nGhost) launchHaloPack(L, c->view, c->gas, h.ghost, h.nGhost, h.ghostBF, h.nGhostBF, buf, false);
-    }
-    HIP_CHECK(hipGetLastError());
-}
-
 int qgd_case_step(qgd_case_t c, int32_t nSteps) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
@@ -2064,57 +2058,76 @@ int qgd_device_release(qgd_device_t d, void* devicePtr) {
     QGD_CATCH
 }
 
-// halo message layout: 10 doubles per cell (RecA, RecB), 12 per boundary face (RecA, RecB, p gradient, lagged rho)
-int qgd_case_halo_count(qgd_case_t c, int slot, int64_t* count) {
-    if (!c || !count || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    *count = 0;
-    if (slot >= (int)c->dev->halo.size()) return QGD_OK;  // an unsharded mesh has no slots: nothing to exchange
-    *count = QGD_HALO_CELL_DOUBLES_HOST * (int64_t)c->dev->halo[slot].nSend + 12 * (int64_t)c->dev->halo[slot].nSendBF;
+// ---- the halo messages of the QGD case -------------------------------------------------------------------------------------
+// kind 0: the state message, QGD_HALO_CELL_DOUBLES_HOST doubles per cell (RecA, RecB), 12 per boundary face (RecA, RecB, p gradient, lagged rho);
+// kinds 1..4: the implicitDiffusion branch's own (1 grad U, 2 U, 3 search direction, 4 guess: implicitHaloWidth doubles per cell);
+// kind 5: the message between step phases 5 and 6 (see assembleFluxes), 2 doubles per patch face of the slot's boundary-layer cells
+static int caseHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pack, hipStream_t stream) {
+    qgd_device_s* d = c->dev;
+    if (slot >= (int)d->halo.size()) return QGD_OK;  // an unsharded mesh has no slots: nothing to exchange
+    const qgd_device_s::HaloSlot& h = d->halo[slot];
+    const int32_t *cells = pack ? h.send : h.ghost, *faces = pack ? h.sendBF : h.ghostBF;
+    const int32_t nCells = pack ? h.nSend : h.nGhost, nFaces = pack ? h.nSendBF : h.nGhostBF;
+    if ((kind == 5 ? nFaces : nCells) == 0) return QGD_OK;
+    if (!buf) return fail(QGD_ERR_INVALID, "null buffer");
+    (void)hipGetLastError();   // a stale error of an earlier, refused call must not be taken for this launch's
+    if (kind == 0) {
+        Launcher L = launcherOf(c);
+        L.pre = nullptr; L.post = nullptr; L.stream = stream;
+        launchHaloPack(L, c->view, c->gas, cells, nCells, faces, nFaces, buf, pack);
+    } else if (kind == 5) launchMidHalo(stream, c->view, faces, nFaces, buf, pack);
+    else launchImplicitHalo(stream, d->view, c->view, c->impl, c->implSolver, kind, cells, nCells, buf, pack);
+    HIP_CHECK(hipGetLastError());
     return QGD_OK;
+}
+// forCount: kinds 3 and 4 with room for the widest solve (what a caller sizes its buffers by); what is SENT has the width of the solve in flight
+static HaloMessage haloMessage(qgd_case_s* c, int kind, bool forCount = false) {
+    HaloMessage m;
+    if (kind == 0) { m.perCell = QGD_HALO_CELL_DOUBLES_HOST; m.perFace = 12; }
+    else if (kind == 5) m.perFace = 2;
+    else m.perCell = (forCount && kind >= 3) ? 3 : implicitHaloWidth(c->implSolver, kind);
+    m.move = [c, kind](int slot, double* buf, bool pack, hipStream_t stream) { return caseHaloMove(c, slot, kind, buf, pack, stream); };
+    return m;
+}
+static HaloBuffers& haloBuffers(qgd_case_s* c) {
+    c->haloBuf.arena = &c->arena;
+    c->haloBuf.widest.perCell = c->implSolver ? 9 : QGD_HALO_CELL_DOUBLES_HOST;   // grad U: 9 per cell; state: 8 per cell and ...
+    c->haloBuf.widest.perFace = 12;                                               // ... 12 per face
+    return c->haloBuf;
+}
+static int caseHaloCount(qgd_case_s* c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
+    *sendCount = *recvCount = 0;
+    if (slot >= (int)c->dev->halo.size()) return QGD_OK;
+    const HaloMessage m = haloMessage(c, kind, true);
+    *sendCount = (int64_t)m.sendCount(c->dev->halo[slot]);
+    *recvCount = (int64_t)m.recvCount(c->dev->halo[slot]);
+    return QGD_OK;
+}
+// the public pack / unpack of message `kind`: the state message honours qgd_case_set_halo_stream, the others run on the case's stream
+static int caseHaloMovePublic(qgd_case_s* c, int slot, int kind, const double* buf, bool pack) {
+    QGD_TRY
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    return caseHaloMove(c, slot, kind, const_cast<double*>(buf), pack, kind == 0 && c->useHaloStream ? c->haloStream : c->stream());
+    QGD_CATCH
+}
+int qgd_case_halo_count(qgd_case_t c, int slot, int64_t* count) {
+    int64_t recv;
+    if (!c || !count || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
+    return caseHaloCount(c, slot, 0, count, &recv);
 }
 int qgd_case_halo_recv_count(qgd_case_t c, int slot, int64_t* count) {
+    int64_t send;
     if (!c || !count || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    *count = 0;
-    if (slot >= (int)c->dev->halo.size()) return QGD_OK;
-    *count = QGD_HALO_CELL_DOUBLES_HOST * (int64_t)c->dev->halo[slot].nGhost + 12 * (int64_t)c->dev->halo[slot].nGhostBF;
-    return QGD_OK;
+    return caseHaloCount(c, slot, 0, &send, count);
 }
 int qgd_case_halo_pack(qgd_case_t c, int slot, double* sendBufDevice) {
-    QGD_TRY
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    qgd_device_s* d = c->dev;
-    if (slot >= (int)d->halo.size() || !d->halo[slot].nSend) return QGD_OK;
-    if (!sendBufDevice) return fail(QGD_ERR_INVALID, "null buffer");
-    const qgd_device_s::HaloSlot& h = d->halo[slot];
-    HIP_CHECK(hipSetDevice(d->deviceId));
-    Launcher L = launcherOf(c);
-    L.pre = nullptr; L.post = nullptr;
-    if (c->useHaloStream) L.stream = c->haloStream;
-    (void)hipGetLastError();
-    launchHaloPack(L, c->view, c->gas, h.send, h.nSend, h.sendBF, h.nSendBF, sendBufDevice, true);
-    HIP_CHECK(hipGetLastError());
-    return QGD_OK;
-    QGD_CATCH
+    return caseHaloMovePublic(c, slot, 0, sendBufDevice, true);
 }
 int qgd_case_halo_unpack(qgd_case_t c, int slot, const double* recvBufDevice) {
-    QGD_TRY
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    qgd_device_s* d = c->dev;
-    if (slot >= (int)d->halo.size() || !d->halo[slot].nGhost) return QGD_OK;
-    if (!recvBufDevice) return fail(QGD_ERR_INVALID, "null buffer");
-    const qgd_device_s::HaloSlot& h = d->halo[slot];
-    HIP_CHECK(hipSetDevice(d->deviceId));
-    Launcher L = launcherOf(c);
-    L.pre = nullptr; L.post = nullptr;
-    if (c->useHaloStream) L.stream = c->haloStream;
-    (void)hipGetLastError();
-    launchHaloPack(L, c->view, c->gas, h.ghost, h.nGhost, h.ghostBF, h.nGhostBF, const_cast<double*>(recvBufDevice), false);
-    HIP_CHECK(hipGetLastError());
-    return QGD_OK;
-    QGD_CATCH
+    return caseHaloMovePublic(c, slot, 0, recvBufDevice, false);
 }
-
-// the message between step phases 5 and 6 (see assembleFluxes): 2 doubles per patch face of the slot's boundary-layer cells
 int qgd_case_mid_exchange_needed(qgd_case_t c, int32_t* needed) {
     if (!c || !needed) return fail(QGD_ERR_INVALID, "bad argument");
     *needed = midExchangeNeeded(c) ? 1 : 0;
@@ -2122,37 +2135,30 @@ int qgd_case_mid_exchange_needed(qgd_case_t c, int32_t* needed) {
 }
 int qgd_case_mid_halo_count(qgd_case_t c, int slot, int64_t* sendCount, int64_t* recvCount) {
     if (!c || slot < 0 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
-    *sendCount = *recvCount = 0;
-    if (slot >= (int)c->dev->halo.size()) return QGD_OK;
-    *sendCount = 2 * (int64_t)c->dev->halo[slot].nSendBF;
-    *recvCount = 2 * (int64_t)c->dev->halo[slot].nGhostBF;
-    return QGD_OK;
-}
-static int midHaloMove(qgd_case_s* c, int slot, double* buf, bool pack, hipStream_t stream) {
-    qgd_device_s* d = c->dev;
-    if (slot >= (int)d->halo.size()) return QGD_OK;
-    const qgd_device_s::HaloSlot& h = d->halo[slot];
-    const int32_t n = pack ? h.nSendBF : h.nGhostBF;
-    if (n == 0) return QGD_OK;
-    if (!buf) return fail(QGD_ERR_INVALID, "null buffer");
-    (void)hipGetLastError();
-    launchMidHalo(stream, c->view, pack ? h.sendBF : h.ghostBF, n, buf, pack);
-    HIP_CHECK(hipGetLastError());
-    return QGD_OK;
+    return caseHaloCount(c, slot, 5, sendCount, recvCount);
 }
 int qgd_case_mid_halo_pack(qgd_case_t c, int slot, double* sendBufDevice) {
-    QGD_TRY
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return midHaloMove(c, slot, sendBufDevice, true, c->stream());
-    QGD_CATCH
+    return caseHaloMovePublic(c, slot, 5, sendBufDevice, true);
 }
 int qgd_case_mid_halo_unpack(qgd_case_t c, int slot, const double* recvBufDevice) {
-    QGD_TRY
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return midHaloMove(c, slot, const_cast<double*>(recvBufDevice), false, c->stream());
-    QGD_CATCH
+    return caseHaloMovePublic(c, slot, 5, recvBufDevice, false);
+}
+// the branch's own messages on a shard (kinds 1 grad U, 2 U, 3 search direction, 4 guess): counts in doubles
+int qgd_case_implicit_halo_count(qgd_case_t c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
+    if (!c || slot < 0 || kind < 1 || kind > 4 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
+    *sendCount = *recvCount = 0;
+    if (!c->implSolver) return fail(QGD_ERR_INVALID, "qgd_case_implicit_halo_count: not an implicitDiffusion case");
+    return caseHaloCount(c, slot, kind, sendCount, recvCount);
+}
+int qgd_case_implicit_halo_pack(qgd_case_t c, int slot, int kind, double* sendBufDevice) {
+    if (!c || slot < 0 || kind < 1 || kind > 4 || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
+    return caseHaloMovePublic(c, slot, kind, sendBufDevice, true);
+}
+int qgd_case_implicit_halo_unpack(qgd_case_t c, int slot, int kind, const double* recvBufDevice) {
+    if (!c || slot < 0 || kind < 1 || kind > 4 || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
+    return caseHaloMovePublic(c, slot, kind, recvBufDevice, false);
 }
 
 // ---- QHDFoam case resident on the device -------------------------------------------------------------------------------
@@ -2176,7 +2182,7 @@ struct qgd_qhd_case_s {
     bool needRef = false;
     int localRefCell = -1;                 // local label of pRefCell when this shard owns it
     std::vector<int32_t> bcPRequested;     // p kinds as the caller set them (a box slab's cut plane hides the patch's own kind)
-    std::vector<double*> sendBuf, recvBuf; // native transport: message buffers per halo slot (sized for the largest kind)
+    HaloBuffers haloBuf;                   // native transport (qgd_qhd_case_halo_exchange, qgd_qhd_case_step_sharded)
     double time = 0, lastIter = 0, lastRes0 = 0, lastRes = 0, lastSolveMs = 0;
     int64_t steps = 0;
 };
@@ -2584,12 +2590,6 @@ int qgd_qhd_case_sync(qgd_qhd_case_t c) {
     return QGD_OK;
     QGD_CATCH
 }
-// halo messages: doubles per listed cell / per listed patch face of message kind 0 (state), 1 (p), 2 (search direction), 3 (the iterate of
-// the multigrid level that spans the ranks)
-static void qhdHaloWidths(int kind, int& perCell, int& perFace) {
-    perCell = kind == 0 ? 4 : (kind == 1 ? 10 : (kind == 4 ? 4 : 1));   // kind 4: the iterate of the implicit solve, {Ux, Uy, Uz, T}
-    perFace = kind == 0 ? 4 : (kind == 1 ? 2 : 0);
-}
 // what the phase in flight waits for before qgd_qhd_case_step_phase(c, 9): see include/qgd_amd.h
 int qgd_qhd_case_pending(qgd_qhd_case_t c, int32_t* action, void** devicePtr, int64_t* count) {
     if (!c || !action) return fail(QGD_ERR_INVALID, "bad argument");
@@ -2600,18 +2600,9 @@ int qgd_qhd_case_pending(qgd_qhd_case_t c, int32_t* action, void** devicePtr, in
     if (count) *count = n;
     return QGD_OK;
 }
-int qgd_qhd_case_halo_count(qgd_qhd_case_t c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
-    if (!c || slot < 0 || kind < 0 || kind > 4 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
-    *sendCount = *recvCount = 0;
-    if (slot >= (int)c->dev->halo.size()) return QGD_OK;
-    int pc, pf;
-    qhdHaloWidths(kind, pc, pf);
-    const qgd_device_s::HaloSlot& h = c->dev->halo[slot];
-    *sendCount = (int64_t)pc * h.nSend + (int64_t)pf * h.nSendBF;
-    *recvCount = (int64_t)pc * h.nGhost + (int64_t)pf * h.nGhostBF;
-    return QGD_OK;
-}
-static int qhdHaloMove(qgd_qhd_case_t c, int slot, int kind, double* buf, bool pack, hipStream_t stream) {
+// ---- the halo messages of the QHD case: kind 0 (state), 1 (p), 2 (search direction), 3 (the iterate of the multigrid level that spans the
+// ranks), 4 (the iterate of the implicit solve, {Ux, Uy, Uz, T}) ------------------------------------------------------------------------
+static int caseHaloMove(qgd_qhd_case_s* c, int slot, int kind, double* buf, bool pack, hipStream_t stream) {
     qgd_device_s* d = c->dev;
     if (slot >= (int)d->halo.size()) return QGD_OK;
     const qgd_device_s::HaloSlot& h = d->halo[slot];
@@ -2619,37 +2610,51 @@ static int qhdHaloMove(qgd_qhd_case_t c, int slot, int kind, double* buf, bool p
     if (nCells + nFaces == 0) return QGD_OK;
     if (!buf) return fail(QGD_ERR_INVALID, "null buffer");
     if (kind >= 2 && !c->solver) return fail(QGD_ERR_INVALID, "no solve in flight");
-    (void)hipGetLastError();
-    if (kind == 4) {
-        if (!c->implSolver) return fail(QGD_ERR_INVALID, "message kind 4 belongs to the implicitDiffusion branch");
-        launchSolverHalo(stream, c->implSolver, pack ? h.send : h.ghost, nCells, buf, pack);
-        HIP_CHECK(hipGetLastError());
-        return QGD_OK;
-    }
-    if (kind == 3) {
-        float* vec = pressureSolverMgHaloVec(c->solver);
-        if (!vec) return fail(QGD_ERR_INVALID, "message kind 3: no multigrid iterate is waiting for its ghost entries (qgd_qhd_case_pending)");
-        launchQhdHaloFloat(stream, vec, pack ? h.send : h.ghost, nCells, buf, pack);
-        HIP_CHECK(hipGetLastError());
-        return QGD_OK;
-    }
-    launchQhdHalo(stream, c->view, c->solver ? pressureSolverDirection(c->solver) : nullptr, kind, pack ? h.send : h.ghost, nCells,
-                  pack ? h.sendBF : h.ghostBF, nFaces, buf, pack);
+    if (kind == 4 && !c->implSolver) return fail(QGD_ERR_INVALID, "message kind 4 belongs to the implicitDiffusion branch");
+    float* vec = kind == 3 ? pressureSolverMgHaloVec(c->solver) : nullptr;
+    if (kind == 3 && !vec) return fail(QGD_ERR_INVALID, "message kind 3: no multigrid iterate is waiting for its ghost entries (qgd_qhd_case_pending)");
+    (void)hipGetLastError();   // a stale error of an earlier, refused call must not be taken for this launch's
+    if (kind == 4) launchSolverHalo(stream, c->implSolver, pack ? h.send : h.ghost, nCells, buf, pack);
+    else if (kind == 3) launchQhdHaloFloat(stream, vec, pack ? h.send : h.ghost, nCells, buf, pack);
+    else launchQhdHalo(stream, c->view, c->solver ? pressureSolverDirection(c->solver) : nullptr, kind, pack ? h.send : h.ghost, nCells,
+                       pack ? h.sendBF : h.ghostBF, nFaces, buf, pack);
     HIP_CHECK(hipGetLastError());
+    return QGD_OK;
+}
+static HaloMessage haloMessage(qgd_qhd_case_s* c, int kind) {
+    HaloMessage m;
+    m.perCell = kind == 0 ? 4 : (kind == 1 ? 10 : (kind == 4 ? 4 : 1));
+    m.perFace = kind == 0 ? 4 : (kind == 1 ? 2 : 0);
+    m.move = [c, kind](int slot, double* buf, bool pack, hipStream_t stream) { return caseHaloMove(c, slot, kind, buf, pack, stream); };
+    return m;
+}
+static HaloBuffers& haloBuffers(qgd_qhd_case_s* c) {
+    c->haloBuf.arena = &c->arena;
+    c->haloBuf.widest.perCell = 10;   // p
+    c->haloBuf.widest.perFace = 4;    // state
+    return c->haloBuf;
+}
+int qgd_qhd_case_halo_count(qgd_qhd_case_t c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
+    if (!c || slot < 0 || kind < 0 || kind > 4 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
+    *sendCount = *recvCount = 0;
+    if (slot >= (int)c->dev->halo.size()) return QGD_OK;
+    const HaloMessage m = haloMessage(c, kind);
+    *sendCount = (int64_t)m.sendCount(c->dev->halo[slot]);
+    *recvCount = (int64_t)m.recvCount(c->dev->halo[slot]);
     return QGD_OK;
 }
 int qgd_qhd_case_halo_pack(qgd_qhd_case_t c, int slot, int kind, double* sendBufDevice) {
     QGD_TRY
     if (!c || slot < 0 || kind < 0 || kind > 4) return fail(QGD_ERR_INVALID, "bad argument");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return qhdHaloMove(c, slot, kind, sendBufDevice, true, c->dev->stream);
+    return caseHaloMove(c, slot, kind, sendBufDevice, true, c->dev->stream);
     QGD_CATCH
 }
 int qgd_qhd_case_halo_unpack(qgd_qhd_case_t c, int slot, int kind, const double* recvBufDevice) {
     QGD_TRY
     if (!c || slot < 0 || kind < 0 || kind > 4) return fail(QGD_ERR_INVALID, "bad argument");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return qhdHaloMove(c, slot, kind, const_cast<double*>(recvBufDevice), false, c->dev->stream);
+    return caseHaloMove(c, slot, kind, const_cast<double*>(recvBufDevice), false, c->dev->stream);
     QGD_CATCH
 }
 int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int64_t outDoubles) {
@@ -3054,17 +3059,6 @@ int qgd_comm_info(qgd_comm_t c, int32_t info[3]) {
     QGD_CATCH
 }
 
-static void ensureHaloBuffers(qgd_case_s* c) {
-    qgd_device_s* d = c->dev;
-    if (c->sendBuf.size() == d->halo.size()) return;
-    c->sendBuf.assign(d->halo.size(), nullptr);
-    c->recvBuf.assign(d->halo.size(), nullptr);
-    for (size_t s = 0; s < d->halo.size(); ++s) {
-        const qgd_device_s::HaloSlot& h = d->halo[s];
-        c->sendBuf[s] = c->arena.alloc<double>(QGD_HALO_CELL_DOUBLES_HOST * (size_t)h.nSend + 12 * (size_t)h.nSendBF);
-        c->recvBuf[s] = c->arena.alloc<double>(QGD_HALO_CELL_DOUBLES_HOST * (size_t)h.nGhost + 12 * (size_t)h.nGhostBF);
-    }
-}
 // RCCL matches the messages of one peer in issue order, and both sides issue in their own slot order: two slots towards
 // the same rank (two ranks on a periodic cut, two disjoint interfaces with one neighbour) would land in each other's
 // ghost lists.  Refused; a rank exchanging with itself (the one-GPU test of this path) is the one ordered exception.
@@ -3079,49 +3073,52 @@ static void checkHaloPeers(const qgd_comm_s* comm, const int32_t* peers, int n) 
     for (int s = 0; s < n; ++s)
         if (peers[s] >= comm->nRanks) throw std::invalid_argument("halo exchange: peer rank out of range");
 }
-// pack -> grouped send/recv -> unpack on `stream`
-static void haloExchangeOn(qgd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots, hipStream_t stream) {
-    qgd_device_s* d = c->dev;
+// THE halo exchange of both case types and every message kind, on `stream`: every slot with a neighbour packs its message into the case's
+// send buffer, the messages travel, every such slot unpacks what arrived.  comm != nullptr: a grouped ncclSend / ncclRecv pair per slot
+// towards peers[slot] (< 0: no neighbour).  comm == nullptr: the cyclic pairs of a periodic device, where slot s takes what its partner
+// slot haloSelf[s] of the same case packed (peers is not read).
+static void exchangeOn(qgd_device_s* d, qgd_comm_s* comm, const int32_t* peers, int nSlots, hipStream_t stream, const HaloMessage& msg,
+                       HaloBuffers& bufs) {
     const int n = std::min<int>(nSlots, (int)d->halo.size());
-    checkHaloPeers(comm, peers, n);
-    ensureHaloBuffers(c);
-    Launcher L = launcherOf(c);
-    L.pre = nullptr; L.post = nullptr; L.stream = stream;
-    (void)hipGetLastError();
-    for (int s = 0; s < n; ++s) {
-        const qgd_device_s::HaloSlot& h = d->halo[s];
-        if (peers[s] < 0 || !h.nSend) continue;
-        launchHaloPack(L, c->view, c->gas, h.send, h.nSend, h.sendBF, h.nSendBF, c->sendBuf[s], true);
-    }
-    HIP_CHECK(hipGetLastError());
-    RCCL_CHECK(rcclRef().groupStart());
-    try {
-        for (int s = 0; s < n; ++s) {
-            const qgd_device_s::HaloSlot& h = d->halo[s];
-            if (peers[s] < 0) continue;
-            const size_t ns = QGD_HALO_CELL_DOUBLES_HOST * (size_t)h.nSend + 12 * (size_t)h.nSendBF, nr = QGD_HALO_CELL_DOUBLES_HOST * (size_t)h.nGhost + 12 * (size_t)h.nGhostBF;
-            if (ns) RCCL_CHECK(rcclRef().send(c->sendBuf[s], ns, ncclFloat64, peers[s], comm->comm, stream));
-            if (nr) RCCL_CHECK(rcclRef().recv(c->recvBuf[s], nr, ncclFloat64, peers[s], comm->comm, stream));
+    if (comm) checkHaloPeers(comm, peers, n);
+    bufs.ensure(d);
+    auto move = [&](int s, double* buf, bool pack) {
+        if ((!comm || peers[s] >= 0) && msg.move(s, buf, pack, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
+    };
+    for (int s = 0; s < n; ++s) move(s, bufs.send[s], true);
+    if (comm) {
+        RCCL_CHECK(rcclRef().groupStart());
+        try {
+            for (int s = 0; s < n; ++s) {
+                if (peers[s] < 0) continue;
+                const size_t ns = msg.sendCount(d->halo[s]), nr = msg.recvCount(d->halo[s]);
+                if (ns) RCCL_CHECK(rcclRef().send(bufs.send[s], ns, ncclFloat64, peers[s], comm->comm, stream));
+                if (nr) RCCL_CHECK(rcclRef().recv(bufs.recv[s], nr, ncclFloat64, peers[s], comm->comm, stream));
+            }
+        } catch (...) {
+            (void)rcclRef().groupEnd();   // never leave the group open behind a failed call: the next collective would join it
+            throw;
         }
-    } catch (...) {
-        (void)rcclRef().groupEnd();   // never leave the group open behind a failed call: the next collective would join it
-        throw;
+        RCCL_CHECK(rcclRef().groupEnd());
+    } else {
+        for (int s = 0; s < n; ++s)
+            if (d->halo[(size_t)d->haloSelf[s]].nSend != d->halo[s].nGhost || d->halo[(size_t)d->haloSelf[s]].nSendBF != d->halo[s].nGhostBF)
+                throw std::runtime_error("cyclic self-exchange: a slot's ghosts do not match its partner's message");
     }
-    RCCL_CHECK(rcclRef().groupEnd());
-    for (int s = 0; s < n; ++s) {
-        const qgd_device_s::HaloSlot& h = d->halo[s];
-        if (peers[s] < 0 || !h.nGhost) continue;
-        launchHaloPack(L, c->view, c->gas, h.ghost, h.nGhost, h.ghostBF, h.nGhostBF, c->recvBuf[s], false);
-    }
-    HIP_CHECK(hipGetLastError());
+    for (int s = 0; s < n; ++s) move(s, comm ? bufs.recv[s] : bufs.send[(size_t)d->haloSelf[s]], false);
 }
+static void exchangeOn(qgd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots, hipStream_t stream, int kind) {
+    exchangeOn(c->dev, comm, peers, nSlots, stream, haloMessage(c, kind), haloBuffers(c));
+}
+// cyclic pairs served by ghost cells: what a rank does with its neighbours, with itself (mid = the message in the middle of the assembly)
+static void selfHaloExchange(qgd_case_s* c, bool mid) { exchangeOn(c, nullptr, nullptr, (int)c->dev->halo.size(), c->stream(), mid ? 5 : 0); }
 int qgd_case_halo_exchange(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, int nSlots) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (c->dev->halo.empty() || nSlots <= 0) return QGD_OK;  // unsharded: nothing to exchange
     if (!comm || !peers) return fail(QGD_ERR_INVALID, "qgd_case_halo_exchange: null argument");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    haloExchangeOn(c, comm, peers, nSlots, c->stream());
+    exchangeOn(c, comm, peers, nSlots, c->stream(), 0);
     return QGD_OK;  // stream-ordered on the case's stream
     QGD_CATCH
 }
@@ -3134,65 +3131,6 @@ int qgd_case_allreduce_max(qgd_case_t c, qgd_comm_t comm) {
     return QGD_OK;
     QGD_CATCH
 }
-// the implicit branch's own messages (kind 1 grad U, 2 U, 3 search direction) over the library's transport, on the case's stream
-static void implHaloExchangeOn(qgd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots, int kind) {
-    qgd_device_s* d = c->dev;
-    const int n = std::min<int>(nSlots, (int)d->halo.size());
-    checkHaloPeers(comm, peers, n);
-    if (c->implSendBuf.size() != d->halo.size()) {
-        c->implSendBuf.assign(d->halo.size(), nullptr);
-        c->implRecvBuf.assign(d->halo.size(), nullptr);
-        for (size_t s2 = 0; s2 < d->halo.size(); ++s2) {
-            c->implSendBuf[s2] = c->arena.alloc<double>(9 * (size_t)d->halo[s2].nSend);
-            c->implRecvBuf[s2] = c->arena.alloc<double>(9 * (size_t)d->halo[s2].nGhost);
-        }
-    }
-    hipStream_t stream = c->stream();
-    const size_t w = (size_t)implicitHaloWidth(c->implSolver, kind);
-    for (int s2 = 0; s2 < n; ++s2)
-        if (peers[s2] >= 0 && implHaloMove(c, s2, kind, c->implSendBuf[s2], true, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
-    RCCL_CHECK(rcclRef().groupStart());
-    try {
-        for (int s2 = 0; s2 < n; ++s2) {
-            const qgd_device_s::HaloSlot& h = d->halo[s2];
-            if (peers[s2] < 0) continue;
-            if (h.nSend) RCCL_CHECK(rcclRef().send(c->implSendBuf[s2], w * h.nSend, ncclFloat64, peers[s2], comm->comm, stream));
-            if (h.nGhost) RCCL_CHECK(rcclRef().recv(c->implRecvBuf[s2], w * h.nGhost, ncclFloat64, peers[s2], comm->comm, stream));
-        }
-    } catch (...) { (void)rcclRef().groupEnd(); throw; }
-    RCCL_CHECK(rcclRef().groupEnd());
-    for (int s2 = 0; s2 < n; ++s2)
-        if (peers[s2] >= 0 && implHaloMove(c, s2, kind, c->implRecvBuf[s2], false, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
-}
-// the mid-assembly message over the library's transport, on the case's stream
-static void midExchangeOn(qgd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots) {
-    qgd_device_s* d = c->dev;
-    const int n = std::min<int>(nSlots, (int)d->halo.size());
-    checkHaloPeers(comm, peers, n);
-    if (c->midSendBuf.size() != d->halo.size()) {
-        c->midSendBuf.assign(d->halo.size(), nullptr);
-        c->midRecvBuf.assign(d->halo.size(), nullptr);
-        for (size_t s2 = 0; s2 < d->halo.size(); ++s2) {
-            c->midSendBuf[s2] = c->arena.alloc<double>(2 * (size_t)d->halo[s2].nSendBF);
-            c->midRecvBuf[s2] = c->arena.alloc<double>(2 * (size_t)d->halo[s2].nGhostBF);
-        }
-    }
-    hipStream_t stream = c->stream();
-    for (int s2 = 0; s2 < n; ++s2)
-        if (peers[s2] >= 0 && midHaloMove(c, s2, c->midSendBuf[s2], true, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
-    RCCL_CHECK(rcclRef().groupStart());
-    try {
-        for (int s2 = 0; s2 < n; ++s2) {
-            const qgd_device_s::HaloSlot& h = d->halo[s2];
-            if (peers[s2] < 0) continue;
-            if (h.nSendBF) RCCL_CHECK(rcclRef().send(c->midSendBuf[s2], 2 * (size_t)h.nSendBF, ncclFloat64, peers[s2], comm->comm, stream));
-            if (h.nGhostBF) RCCL_CHECK(rcclRef().recv(c->midRecvBuf[s2], 2 * (size_t)h.nGhostBF, ncclFloat64, peers[s2], comm->comm, stream));
-        }
-    } catch (...) { (void)rcclRef().groupEnd(); throw; }
-    RCCL_CHECK(rcclRef().groupEnd());
-    for (int s2 = 0; s2 < n; ++s2)
-        if (peers[s2] >= 0 && midHaloMove(c, s2, c->midRecvBuf[s2], false, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
-}
 int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, int nSlots, int overlapped) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
@@ -3204,7 +3142,7 @@ int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, i
     if (sharded) checkHaloPeers(comm, peers, std::min<int>(nSlots, (int)c->dev->halo.size()));   // before the first message of the step
     if (sharded && midExchangeNeeded(c)) {
         stepAssemble(c, 1);
-        midExchangeOn(c, comm, peers, nSlots);
+        exchangeOn(c, comm, peers, nSlots, c->stream(), 5);
         stepAssemble(c, 2);
     } else stepAssemble(c);
     if (adjust && comm && comm->nRanks > 1)
@@ -3222,16 +3160,17 @@ int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, i
                 RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, op == 3 ? ncclMax : ncclSum, comm->comm, st));
             };
         }
-        hooks.haloDirection = [&]() { implHaloExchangeOn(c, comm, peers, nSlots, 3); };
-        hooks.haloGuess = [&]() { implHaloExchangeOn(c, comm, peers, nSlots, 4); };
-        implicitAdvanceWith(c, &hooks, [&](int kind) { implHaloExchangeOn(c, comm, peers, nSlots, kind); });
-        haloExchangeOn(c, comm, peers, nSlots, st);
+        auto halo = [&](int kind) { exchangeOn(c, comm, peers, nSlots, st, kind); };
+        hooks.haloDirection = [&]() { halo(3); };
+        hooks.haloGuess = [&]() { halo(4); };
+        implicitAdvanceWith(c, &hooks, halo);
+        halo(0);
         HIP_CHECK(hipGetLastError());
         return QGD_OK;
     }
     if (!overlapped) {
         stepAdvance(c, 0);
-        haloExchangeOn(c, comm, peers, nSlots, c->stream());
+        exchangeOn(c, comm, peers, nSlots, c->stream(), 0);
     } else {
         // boundary layer first; pack / send / recv / unpack on the library's halo stream while the compute stream
         // updates the remaining cells; the next assembly waits for the unpack
@@ -3243,7 +3182,7 @@ int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, i
         stepAdvance(c, 1);
         HIP_CHECK(hipEventRecord(c->evLayerDone, c->stream()));
         HIP_CHECK(hipStreamWaitEvent(c->ownHaloStream, c->evLayerDone, 0));
-        haloExchangeOn(c, comm, peers, nSlots, c->ownHaloStream);
+        exchangeOn(c, comm, peers, nSlots, c->ownHaloStream, 0);
         HIP_CHECK(hipEventRecord(c->evUnpacked, c->ownHaloStream));
         stepAdvance(c, 2);
         HIP_CHECK(hipStreamWaitEvent(c->stream(), c->evUnpacked, 0));
@@ -3254,39 +3193,9 @@ int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, i
 }
 
 // ---- the QHD case over the library's own transport ----------------------------------------------------------------------
-// pack -> grouped send/recv -> unpack of message kind 0 (state), 1 (p) or 2 (search direction of the pressure solve) on the
-// device's stream; buffers owned by the case, sized once for the widest kind
-static void qhdHaloExchangeOn(qgd_qhd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots, int kind) {
-    qgd_device_s* d = c->dev;
-    const int n = std::min<int>(nSlots, (int)d->halo.size());
-    checkHaloPeers(comm, peers, n);
-    if (c->sendBuf.size() != d->halo.size()) {
-        c->sendBuf.assign(d->halo.size(), nullptr);
-        c->recvBuf.assign(d->halo.size(), nullptr);
-        for (size_t s2 = 0; s2 < d->halo.size(); ++s2) {
-            const qgd_device_s::HaloSlot& h = d->halo[s2];
-            c->sendBuf[s2] = c->arena.alloc<double>(10 * (size_t)h.nSend + 4 * (size_t)h.nSendBF);
-            c->recvBuf[s2] = c->arena.alloc<double>(10 * (size_t)h.nGhost + 4 * (size_t)h.nGhostBF);
-        }
-    }
-    int pc, pf;
-    qhdHaloWidths(kind, pc, pf);
-    hipStream_t stream = d->stream;
-    for (int s2 = 0; s2 < n; ++s2)
-        if (peers[s2] >= 0 && qhdHaloMove(c, s2, kind, c->sendBuf[s2], true, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
-    RCCL_CHECK(rcclRef().groupStart());
-    try {
-        for (int s2 = 0; s2 < n; ++s2) {
-            const qgd_device_s::HaloSlot& h = d->halo[s2];
-            if (peers[s2] < 0) continue;
-            const size_t ns = (size_t)pc * h.nSend + (size_t)pf * h.nSendBF, nr = (size_t)pc * h.nGhost + (size_t)pf * h.nGhostBF;
-            if (ns) RCCL_CHECK(rcclRef().send(c->sendBuf[s2], ns, ncclFloat64, peers[s2], comm->comm, stream));
-            if (nr) RCCL_CHECK(rcclRef().recv(c->recvBuf[s2], nr, ncclFloat64, peers[s2], comm->comm, stream));
-        }
-    } catch (...) { (void)rcclRef().groupEnd(); throw; }
-    RCCL_CHECK(rcclRef().groupEnd());
-    for (int s2 = 0; s2 < n; ++s2)
-        if (peers[s2] >= 0 && qhdHaloMove(c, s2, kind, c->recvBuf[s2], false, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
+// every message kind on the device's stream
+static void exchangeOn(qgd_qhd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots, int kind) {
+    exchangeOn(c->dev, comm, peers, nSlots, c->dev->stream, haloMessage(c, kind), haloBuffers(c));
 }
 int qgd_qhd_case_halo_exchange(qgd_qhd_case_t c, qgd_comm_t comm, const int32_t* peers, int nSlots, int kind) {
     QGD_TRY
@@ -3294,7 +3203,7 @@ int qgd_qhd_case_halo_exchange(qgd_qhd_case_t c, qgd_comm_t comm, const int32_t*
     if (c->dev->halo.empty() || nSlots <= 0) return QGD_OK;
     if (!comm || !peers) return fail(QGD_ERR_INVALID, "qgd_qhd_case_halo_exchange: null argument");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    qhdHaloExchangeOn(c, comm, peers, nSlots, kind);
+    exchangeOn(c, comm, peers, nSlots, kind);
     return QGD_OK;
     QGD_CATCH
 }
@@ -3313,14 +3222,14 @@ int qgd_qhd_case_step_sharded(qgd_qhd_case_t c, qgd_comm_t comm, const int32_t* 
     SolveHooks hooks;
     if (comm && comm->nRanks > 1)
         hooks.allreduce = [&](double* ptr, int n) { RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, ncclSum, comm->comm, d->stream)); };
-    if (sharded) hooks.haloDirection = [&]() { qhdHaloExchangeOn(c, comm, peers, nSlots, 2); };
-    if (sharded) hooks.haloMg = [&]() { qhdHaloExchangeOn(c, comm, peers, nSlots, 3); };
+    if (sharded) hooks.haloDirection = [&]() { exchangeOn(c, comm, peers, nSlots, 2); };
+    if (sharded) hooks.haloMg = [&]() { exchangeOn(c, comm, peers, nSlots, 3); };
     if (comm && comm->nRanks > 1)
         hooks.allreduceBuf = [&](double* ptr, int64_t n, int op) {
             RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, op == 3 ? ncclMax : ncclSum, comm->comm, d->stream));
         };
     std::function<void(int)> haloState;
-    if (sharded) haloState = [&](int kind) { qhdHaloExchangeOn(c, comm, peers, nSlots, kind); };
+    if (sharded) haloState = [&](int kind) { exchangeOn(c, comm, peers, nSlots, kind); };
     for (int i = 0; i < nSteps; ++i) qhdStepWith(c, &hooks, haloState);
     HIP_CHECK(hipStreamSynchronize(d->stream));
     return QGD_OK;
@@ -3473,42 +3382,6 @@ int qgd_case_implicit_apply_time(qgd_case_t c, int reps, double info[2]) {
     info[0] = implicitApplyMs(c->implSolver, c->impl, reps, &rows);
     info[1] = rows;
     return QGD_OK;
-    QGD_CATCH
-}
-// the branch's own halo messages and control block on a shard (kinds 1 grad U, 2 U, 3 search direction; the state message is
-// qgd_case_halo_*): counts in doubles
-int qgd_case_implicit_halo_count(qgd_case_t c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
-    if (!c || slot < 0 || kind < 1 || kind > 4 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
-    *sendCount = *recvCount = 0;
-    if (!c->implSolver) return fail(QGD_ERR_INVALID, "qgd_case_implicit_halo_count: not an implicitDiffusion case");
-    if (slot >= (int)c->dev->halo.size()) return QGD_OK;
-    const int w = kind >= 3 ? 3 : implicitHaloWidth(c->implSolver, kind);   // kinds 3, 4: room for the widest solve
-    *sendCount = (int64_t)w * c->dev->halo[slot].nSend;
-    *recvCount = (int64_t)w * c->dev->halo[slot].nGhost;
-    return QGD_OK;
-}
-static int implHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pack, hipStream_t stream) {
-    qgd_device_s* d = c->dev;
-    if (slot >= (int)d->halo.size()) return QGD_OK;
-    const qgd_device_s::HaloSlot& h = d->halo[slot];
-    const int32_t n = pack ? h.nSend : h.nGhost;
-    if (n == 0) return QGD_OK;
-    if (!buf) return fail(QGD_ERR_INVALID, "null buffer");
-    launchImplicitHalo(stream, d->view, c->view, c->impl, c->implSolver, kind, pack ? h.send : h.ghost, n, buf, pack);
-    return QGD_OK;
-}
-int qgd_case_implicit_halo_pack(qgd_case_t c, int slot, int kind, double* sendBufDevice) {
-    QGD_TRY
-    if (!c || slot < 0 || kind < 1 || kind > 4 || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return implHaloMove(c, slot, kind, sendBufDevice, true, c->stream());
-    QGD_CATCH
-}
-int qgd_case_implicit_halo_unpack(qgd_case_t c, int slot, int kind, const double* recvBufDevice) {
-    QGD_TRY
-    if (!c || slot < 0 || kind < 1 || kind > 4 || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return implHaloMove(c, slot, kind, const_cast<double*>(recvBufDevice), false, c->stream());
     QGD_CATCH
 }
 // control block of the solve in flight: 68 doubles, slot-major (control[slot * 4 + component]); a sharded run SUM-reduces

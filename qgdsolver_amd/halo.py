@@ -9,7 +9,35 @@ transport (backend "nccl" == RCCL on ROCm, "gloo" on CPU); pack/unpack are the l
 
 import ctypes as C
 
+import numpy as np
+
 from . import _lib as L
+
+
+def _send_recv(dist, messages):
+    """one waited-for batch of point-to-point operations: (send tensor, recv tensor, peer rank) per halo slot in slot order (None or
+    empty: nothing that way), per slot the isend before the irecv"""
+    ops = []
+    for send, recv, peer in messages:
+        ops += [dist.P2POp(op, t, peer) for op, t in ((dist.isend, send), (dist.irecv, recv)) if t is not None and len(t)]
+    if ops:
+        for w in dist.batch_isend_irecv(ops):
+            w.wait()
+
+
+def _serve_pending(exchange, cases, pending, reduce):
+    """the comm points inside a phase (the multigrid hierarchy that spans the ranks, qgd_qhd_case_pending): while ``pending()`` =
+    (action, pointer(s), count) is not 0, message kind 3 (action 1) or ``reduce(action, pointers, count)`` (2: SUM, 3: MAX), then phase 9"""
+    while True:
+        action, ptr, count = pending()
+        if action == 0:
+            return
+        if action == 1:
+            exchange(QHD_MG_ITERATE)
+        else:
+            reduce(action, ptr, count)
+        for c in cases:
+            c.step_phase(9)
 
 
 def slab_range(n, rank, world):
@@ -56,15 +84,7 @@ class SlabHalo:
         for s in self.sides:
             if len(send[s]):
                 pack(s, self.arg(send[s]))
-        ops = []
-        for s in self.sides:
-            if len(send[s]):
-                ops.append(self.dist.P2POp(self.dist.isend, send[s], self.peer[s]))
-            if len(recv[s]):
-                ops.append(self.dist.P2POp(self.dist.irecv, recv[s], self.peer[s]))
-        if ops:
-            for w in self.dist.batch_isend_irecv(ops):
-                w.wait()
+        _send_recv(self.dist, [(send[s], recv[s], self.peer[s]) for s in self.sides])
         for s in self.sides:
             if len(recv[s]):
                 unpack(s, self.arg(recv[s]))
@@ -158,15 +178,7 @@ class HostStaged:
         for s in self.sides:
             if send[s].numel():
                 send[s].copy_(dev_s[s][:send[s].numel()])
-        ops = []
-        for s in self.sides:
-            if send[s].numel():
-                ops.append(self.dist.P2POp(self.dist.isend, send[s], self.peer[s]))
-            if recv[s].numel():
-                ops.append(self.dist.P2POp(self.dist.irecv, recv[s], self.peer[s]))
-        if ops:
-            for w in self.dist.batch_isend_irecv(ops):
-                w.wait()
+        _send_recv(self.dist, [(send[s], recv[s], self.peer[s]) for s in self.sides])
         for s in self.sides:
             if recv[s].numel():
                 dev_r[s][:recv[s].numel()].copy_(recv[s])
@@ -189,9 +201,6 @@ class NativeComm:
     broadcast standing in for MPI_Bcast (``bcast(bytes_or_None) -> bytes`` on every rank; identity on one rank)."""
 
     def __init__(self, device_id, rank=0, world=1, bcast=None):
-        import ctypes as C
-        from . import _lib as L
-        self._L, self._C = L, C
         uid = (C.c_char * 128)()
         if rank == 0:
             L.check(L.lib.qgd_comm_unique_id(uid), "qgd_comm_unique_id")
@@ -205,40 +214,39 @@ class NativeComm:
 
     def info(self):
         """{rank, ranks, device} as RCCL itself reports them for the communicator (qgd_comm_info)"""
-        v = (self._C.c_int32 * 3)()
-        self._L.check(self._L.lib.qgd_comm_info(self._h, v), "qgd_comm_info")
+        v = (C.c_int32 * 3)()
+        L.check(L.lib.qgd_comm_info(self._h, v), "qgd_comm_info")
         return {"rank": int(v[0]), "ranks": int(v[1]), "device": int(v[2])}
 
     def _peers(self, peers):
-        import numpy as np
         a = np.ascontiguousarray(peers, dtype=np.int32)
-        return a, a.ctypes.data_as(self._L.c_int32_p), int(a.size)
+        return a, a.ctypes.data_as(L.c_int32_p), int(a.size)
 
     def exchange(self, case, peers):
         a, p, n = self._peers(peers)
-        self._L.check(self._L.lib.qgd_case_halo_exchange(case._h, self._h, p, n), "qgd_case_halo_exchange")
+        L.check(L.lib.qgd_case_halo_exchange(case._h, self._h, p, n), "qgd_case_halo_exchange")
 
     def step(self, case, peers, overlapped=False):
         a, p, n = self._peers(peers)
-        self._L.check(self._L.lib.qgd_case_step_sharded(case._h, self._h, p, n, 1 if overlapped else 0), "qgd_case_step_sharded")
+        L.check(L.lib.qgd_case_step_sharded(case._h, self._h, p, n, 1 if overlapped else 0), "qgd_case_step_sharded")
 
     def allreduce_max(self, case):
-        self._L.check(self._L.lib.qgd_case_allreduce_max(case._h, self._h), "qgd_case_allreduce_max")
+        L.check(L.lib.qgd_case_allreduce_max(case._h, self._h), "qgd_case_allreduce_max")
 
     def qhd_exchange(self, case, peers, kind=0):
         """message kind 0 (state), 1 (p) ... of a sharded QHDFoam case over RCCL (qgd_qhd_case_halo_exchange)"""
         a, p, n = self._peers(peers)
-        self._L.check(self._L.lib.qgd_qhd_case_halo_exchange(case._h, self._h, p, n, int(kind)), "qgd_qhd_case_halo_exchange")
+        L.check(L.lib.qgd_qhd_case_halo_exchange(case._h, self._h, p, n, int(kind)), "qgd_qhd_case_halo_exchange")
 
     def qhd_step(self, case, peers, n_steps=1):
         """whole QHDFoam steps of a sharded case with the transport inside the library (qgd_qhd_case_step_sharded): halo messages,
         the all-reduced scalars of the pressure solve and the comm points of its multigrid hierarchy, all on the device's stream"""
         a, p, n = self._peers(peers)
-        self._L.check(self._L.lib.qgd_qhd_case_step_sharded(case._h, self._h, p, n, int(n_steps)), "qgd_qhd_case_step_sharded")
+        L.check(L.lib.qgd_qhd_case_step_sharded(case._h, self._h, p, n, int(n_steps)), "qgd_qhd_case_step_sharded")
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.lib.qgd_comm_free(self._h)
+            L.lib.qgd_comm_free(self._h)
             self._h = None
 
 
@@ -335,31 +343,27 @@ class LocalWorld:
         """the comm points inside a phase (the multigrid hierarchy that spans the ranks: qgd_qhd_case_pending)"""
         if not hasattr(self.cases[0], "pending"):
             return
-        import numpy as np
-        while True:
+
+        def pending():
             pend = [c.pending() for c in self.cases]
             assert len({p[0] for p in pend}) == 1 and len({p[2] for p in pend}) == 1, pend
-            action, _, count = pend[0]
-            if action == 0:
-                return
-            if action == 1:
-                self.exchange(QHD_MG_ITERATE)
-            else:
-                for c in self.cases:
-                    c.sync()                      # the buffers are written by kernels on the cases' streams
-                host = [c.dev.to_host(p[1], (count,)) for c, p in zip(self.cases, pend)]
-                total = np.sum(host, axis=0) if action == 2 else np.max(host, axis=0)
-                for c, p in zip(self.cases, pend):
-                    L.check(L.lib.qgd_device_copy(c.dev._h, C.c_void_p(p[1]), total.ctypes.data_as(C.c_void_p), total.nbytes, 1), "qgd_device_copy")
+            return pend[0][0], [p[1] for p in pend], pend[0][2]
+
+        def reduce(action, ptrs, count):
             for c in self.cases:
-                c.step_phase(9)
+                c.sync()                      # the buffers are written by kernels on the cases' streams
+            host = [c.dev.to_host(p, (count,)) for c, p in zip(self.cases, ptrs)]
+            total = np.sum(host, axis=0) if action == 2 else np.max(host, axis=0)
+            for c, p in zip(self.cases, ptrs):
+                L.check(L.lib.qgd_device_copy(c.dev._h, C.c_void_p(p), total.ctypes.data_as(C.c_void_p), total.nbytes, 1), "qgd_device_copy")
+
+        _serve_pending(self.exchange, self.cases, pending, reduce)
 
     def implicit(self):
         return bool(getattr(self.cases[0], "implicit", False))
 
     def allreduce(self, first, count, op="sum", block=None):
         """block="implicit": the control block of a QHD case's implicitDiffusion solve instead of the pressure solve's"""
-        import numpy as np
         get = (lambda c: c.implicit_control()) if block == "implicit" else (lambda c: c.control())
         ctl = [get(c) for c in self.cases]
         total = sum(a[first:first + count] for a in ctl) if op == "sum" else np.max([a[first:first + count] for a in ctl], axis=0)
@@ -410,22 +414,19 @@ class DistWorld:
         self.case.step_phase(k)
         if not hasattr(self.case, "pending"):
             return
-        while True:                       # the comm points inside a phase (qgd_qhd_case_pending)
-            action, ptr, count = self.case.pending()
-            if action == 0:
-                return
-            if action == 1:
-                self.exchange(QHD_MG_ITERATE)
-            elif self.device_reduce:
-                t = device_tensor(self.torch, ptr, count)
-                self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM if action == 2 else self.dist.ReduceOp.MAX)
+
+        def reduce(action, ptr, count):
+            op = self.dist.ReduceOp.SUM if action == 2 else self.dist.ReduceOp.MAX
+            if self.device_reduce:
+                self.dist.all_reduce(device_tensor(self.torch, ptr, count), op=op)
             else:
                 self.case.sync()                  # the buffer is written by kernels on the case's stream
                 t = self.to_transport(ptr, count)
-                self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM if action == 2 else self.dist.ReduceOp.MAX)
+                self.dist.all_reduce(t, op=op)
                 self.from_transport(t, ptr)
                 self.case.sync()
-            self.case.step_phase(9)
+
+        _serve_pending(self.exchange, [self.case], self.case.pending, reduce)
 
     def implicit(self):
         return bool(getattr(self.case, "implicit", False))
@@ -446,21 +447,13 @@ class DistWorld:
     def exchange(self, kind):
         if not self.slots:
             return
-        ops, recv = [], {}
         for s in self.slots:
-            ns, nr = self.case.halo_count(s, kind)
             self.case.halo_pack(s, kind, self.sbuf[s])
         self.case.sync()
-        for s in self.slots:
-            ns, nr = self.case.halo_count(s, kind)
-            if ns:
-                ops.append(self.dist.P2POp(self.dist.isend, self.to_transport(self.sbuf[s], ns), self.peers[s]))
-            if nr:
-                recv[s] = self.to_transport(self.rbuf[s], nr)
-                ops.append(self.dist.P2POp(self.dist.irecv, recv[s], self.peers[s]))
-        if ops:
-            for w in self.dist.batch_isend_irecv(ops):
-                w.wait()
+        counts = {s: self.case.halo_count(s, kind) for s in self.slots}
+        send = {s: self.to_transport(self.sbuf[s], n) for s, (n, _) in counts.items() if n}
+        recv = {s: self.to_transport(self.rbuf[s], n) for s, (_, n) in counts.items() if n}
+        _send_recv(self.dist, [(send.get(s), recv.get(s), self.peers[s]) for s in self.slots])
         for s, t in recv.items():
             self.from_transport(t, self.rbuf[s])
             self.case.halo_unpack(s, kind, self.rbuf[s])
