@@ -659,6 +659,21 @@ int qgd_case_free(qgd_case_t c);
 int qgd_case_set_bc(qgd_case_t c, int32_t patch, int32_t bcU, const double* valueU,
                     int32_t bcT, double valueT, int32_t bcP, double valueP);
 
+/* Per-face values of a fixedValue entry (`value nonuniform List<...>`): field 0 = U (3 * nFaces doubles), 1 = T, 2 = p
+ * (nFaces doubles), HOST pointers, in the patch's face order on THIS device's mesh -- nFaces is the patch's size there: on a
+ * shard that includes the patch faces of ghost cells, on a mesh from qgd_mesh_unroll_cyclic the faces of the copies, which
+ * follow the real ones.  (Such a face's record comes from its original with the halo message; its entry is read only by the
+ * start-up evaluation of qgd_case_set_fields, so give it the original's value.)  Call after qgd_case_set_bc, which returns
+ * the patch to its uniform values, and before qgd_case_set_fields.  values == NULL drops the list: the entry reads its
+ * uniform value again.  Refused (QGD_ERR_INVALID, by name) when the field's entry on that patch is not QGD_BC_FIXEDVALUE,
+ * when the patch is a constraint (empty / symmetryPlane / symmetry / wedge), halo or cyclic patch, and when nFaces is not
+ * the patch's size.  Every kernel that evaluates a fixedValue face reads the list; the implicitDiffusion branch assembles
+ * the U systems of a case with per-face velocities with its separate kernels (qgd_case_fused_info reports 0, not 2).
+ * qgd_case_get_bc_values returns what the entry prescribes per face (the list, or the uniform value repeated);
+ * isList (may be NULL) tells which. */
+int qgd_case_set_bc_values(qgd_case_t c, int32_t patch, int32_t field, const double* values, int64_t nFaces);
+int qgd_case_get_bc_values(qgd_case_t c, int32_t patch, int32_t field, double* values, int64_t nFaces, int32_t* isList);
+
 /* Non-uniform alphaQGD / ScQGD: the READ_IF_PRESENT volScalarFields "alphaQGD" [QGDCoeffs_8C_source.html L119-160] and
  * "ScQGD" [constScPrModel1_8C_source.html L66-79] of the time directory, cell values (nCells) and patch values
  * (nBoundaryFaces) as the files' own boundary conditions evaluate them.  NULL keeps the uniform value of the options.

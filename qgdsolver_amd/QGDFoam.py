@@ -111,7 +111,9 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
                 and not (opt.get("implicitDiffusion") and world > 1))
     dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}}, fused_tables=eligible)
     case = QGDFoamCase(dev, default_options(**opt))
-    for i, bc in enumerate(bcs):
+    # value lists of fixedValue entries follow the device mesh's patch faces (a shard's through faceGlobal, the copies behind cyclic halves
+    # take their originals' values); the case files keep theirs for the writer
+    for i, bc in enumerate(ff.device_bcs(gmesh, mesh, bcs)):
         case.set_bc(i, U=bc["U"], T=bc["T"], p=bc["p"])
     if "alphaQGD" in fields or "ScQGD" in fields:
         # non-uniform alphaQGD / ScQGD files: cell values follow the relabelling; boundary faces keep their labels under

@@ -166,6 +166,8 @@ SIGNATURES = {
     "qgd_case_create": (C.c_int, [handle, C.POINTER(CaseOptions), handle_p]),
     "qgd_case_free": (C.c_int, [handle]),
     "qgd_case_set_bc": (C.c_int, [handle, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_double, C.c_int32, C.c_double]),
+    "qgd_case_set_bc_values": (C.c_int, [handle, C.c_int32, C.c_int32, c_double_p, C.c_int64]),
+    "qgd_case_get_bc_values": (C.c_int, [handle, C.c_int32, C.c_int32, c_double_p, C.c_int64, c_int32_p]),
     "qgd_case_set_fields": (C.c_int, [handle, c_double_p, c_double_p, c_double_p]),
     "qgd_case_set_qgd_coeffs": (C.c_int, [handle, c_double_p, c_double_p, c_double_p, c_double_p]),
     "qgd_case_update_fluxes": (C.c_int, [handle]),

@@ -339,6 +339,11 @@ struct qgd_case_s {
     bool fieldsSet = false;
     std::vector<PatchBCDev> bc;
     PatchBCDev* bcDev = nullptr;
+    // per-face values of fixedValue patches (qgd_case_set_bc_values), field 0 U (3 per boundary face), 1 T, 2 p: the host copy serves
+    // qgd_case_get_bc_values, the device copy is CaseView::bValU / bValT / bValP while some patch's valList names the field; both empty /
+    // nullptr until the first list arrives
+    std::vector<double> bcValHost[3];
+    double* bcValDev[3] = {nullptr, nullptr, nullptr};
     DeviceArena arena;
     CaseView view{};
     double* dbgBuf = nullptr;
@@ -1661,6 +1666,18 @@ int qgd_case_free(qgd_case_t c) {
     return QGD_OK;
 }
 
+// CaseView::bValU / bValT / bValP follow the patches' flags: a field no patch has a list for reads nothing (nullptr)
+static void bcValuePointers(qgd_case_s* c) {
+    int32_t any = 0;
+    for (const PatchBCDev& b : c->bc) any |= b.valList;
+    c->view.bValU = (any & QGD_BC_LIST_U) ? c->bcValDev[0] : nullptr;
+    c->view.bValT = (any & QGD_BC_LIST_T) ? c->bcValDev[1] : nullptr;
+    c->view.bValP = (any & QGD_BC_LIST_P) ? c->bcValDev[2] : nullptr;
+}
+// the block-fused assembly of the U systems reads a fixedValue patch's one velocity out of the table (implCellU inside
+// fusedFaceCellKernel<..., IMPL>): a case with per-face velocities assembles with implCellUKernel, which reads the list
+static bool implFusedNow(const qgd_case_s* c) { return c->fusedImpl && !c->view.bValU; }
+
 int qgd_case_set_bc(qgd_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT, int32_t bcP, double valueP) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
@@ -1673,8 +1690,81 @@ int qgd_case_set_bc(qgd_case_t c, int32_t patch, int32_t bcU, const double* valu
     constraintKinds(b.ptype, bcU, bcT, bcP);   // a constraint patch keeps its own field type whatever the caller asks for
     b.bcU = bcU; b.bcT = bcT; b.bcP = bcP; b.vT = valueT; b.vP = valueP;
     if (valueU) for (int k = 0; k < 3; ++k) b.vU[k] = valueU[k];
+    b.valList = 0;   // the patch is uniform again: a value list follows its entry (qgd_case_set_bc_values comes after this call)
+    bcValuePointers(c);
     c->fieldsSet = false;
     c->gradUValid = false;
+    return QGD_OK;
+    QGD_CATCH
+}
+
+// field 0 U, 1 T, 2 p of a patch's table entry
+static int32_t bcKindOf(const PatchBCDev& b, int field) { return field == 0 ? b.bcU : (field == 1 ? b.bcT : b.bcP); }
+static int bcValuesCheck(qgd_case_t c, const char* who, int32_t patch, int32_t field, int64_t nFaces) {
+    const std::string w(who);
+    if (!c) return fail(QGD_ERR_INVALID, w + ": null case");
+    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, w + ": patch out of range");
+    if (field < 0 || field > 2) return fail(QGD_ERR_INVALID, w + ": field must be 0 (U), 1 (T) or 2 (p)");
+    const Patch& pt = c->dev->patches[patch];
+    const PatchBCDev& b = c->bc[patch];
+    static const char* kFieldName[3] = {"U", "T", "p"};
+    if (pt.type == QGD_PATCH_HALO) return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a halo patch (its faces carry no boundary condition)");
+    if (pt.type == QGD_PATCH_CYCLIC) return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a cyclic patch (its faces carry no boundary condition)");
+    if (pt.type != QGD_PATCH_GENERIC)
+        return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a constraint patch (empty / symmetryPlane / symmetry / wedge): it keeps its own field type");
+    if (bcKindOf(b, field) != QGD_BC_FIXEDVALUE)
+        return fail(QGD_ERR_INVALID, w + ": the " + kFieldName[field] + " entry of patch '" + pt.name + "' is not fixedValue (per-face values belong to fixedValue entries only)");
+    if (nFaces != (int64_t)pt.size)
+        return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' has " + std::to_string(pt.size) + " faces on this device's mesh, nFaces = " + std::to_string(nFaces));
+    return QGD_OK;
+}
+
+int qgd_case_set_bc_values(qgd_case_t c, int32_t patch, int32_t field, const double* values, int64_t nFaces) {
+    QGD_TRY
+    const int rc = bcValuesCheck(c, "qgd_case_set_bc_values", patch, field, values ? nFaces : (c && patch >= 0 && patch < (int32_t)c->bc.size() ? (int64_t)c->dev->patches[patch].size : nFaces));
+    if (rc) return rc;
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    const MeshView& m = c->dev->view;
+    const Patch& pt = c->dev->patches[patch];
+    const int32_t bit = 1 << field;
+    if (!values) c->bc[patch].valList &= ~bit;
+    else {
+        const size_t w = field == 0 ? 3 : 1, nB = (size_t)m.nBF, first = (size_t)(pt.start - m.nIF);
+        if (first + (size_t)pt.size > nB) return fail(QGD_ERR_INVALID, "qgd_case_set_bc_values: the patch's faces lie outside the device's boundary faces");
+        if (c->bcValHost[field].empty()) c->bcValHost[field].assign(w * std::max<size_t>(nB, 1), 0.0);
+        if (!c->bcValDev[field]) c->bcValDev[field] = c->arena.alloc<double>(w * std::max<size_t>(nB, 1));   // (zero-filled)
+        if (pt.size > 0) {
+            std::memcpy(c->bcValHost[field].data() + w * first, values, sizeof(double) * w * (size_t)pt.size);
+            HIP_CHECK(hipStreamSynchronize(c->stream()));   // (no kernel of an earlier step still reads the old values)
+            HIP_CHECK(hipMemcpy(c->bcValDev[field] + w * first, values, sizeof(double) * w * (size_t)pt.size, hipMemcpyHostToDevice));
+        }
+        c->bc[patch].valList |= bit;
+    }
+    bcValuePointers(c);
+    c->fieldsSet = false;      // like qgd_case_set_bc: the patch records are evaluated again by qgd_case_set_fields,
+    c->ghostsCurrent = false;  // and the copies behind cyclic halves take their originals' records after it
+    c->gradUValid = false;
+    return QGD_OK;
+    QGD_CATCH
+}
+
+int qgd_case_get_bc_values(qgd_case_t c, int32_t patch, int32_t field, double* values, int64_t nFaces, int32_t* isList) {
+    QGD_TRY
+    const int rc = bcValuesCheck(c, "qgd_case_get_bc_values", patch, field, nFaces);
+    if (rc) return rc;
+    if (!values && nFaces > 0) return fail(QGD_ERR_INVALID, "qgd_case_get_bc_values: null argument");
+    const MeshView& m = c->dev->view;
+    const Patch& pt = c->dev->patches[patch];
+    const PatchBCDev& b = c->bc[patch];
+    const bool list = (b.valList & (1 << field)) != 0;
+    const size_t w = field == 0 ? 3 : 1, first = (size_t)(pt.start - m.nIF);
+    if (list) std::memcpy(values, c->bcValHost[field].data() + w * first, sizeof(double) * w * (size_t)pt.size);
+    else
+        for (int64_t i = 0; i < nFaces; ++i) {
+            if (field == 0) for (int k = 0; k < 3; ++k) values[3 * i + k] = b.vU[k];
+            else values[i] = field == 1 ? b.vT : b.vP;
+        }
+    if (isList) *isList = list ? 1 : 0;
     return QGD_OK;
     QGD_CATCH
 }
@@ -1808,7 +1898,7 @@ int qgd_case_update_fluxes(qgd_case_t c) {
 // phase 1: deltaT, cell update, boundary refresh
 static void stepAssemble(qgd_case_s* c, int part = 0) {
     const bool adjust = c->opt.adjustTimeStep != 0;
-    assembleFluxes(c, adjust, part, !(c->fused || c->fusedImpl || c->fusedAdj));   // a fused case computes its internal faces inside the advance (stepAdvance / phase 21)
+    assembleFluxes(c, adjust, part, !(c->fused || implFusedNow(c) || c->fusedAdj));   // a fused case computes its internal faces inside the advance (stepAdvance / phase 21)
     if (adjust && part != 1) launchFaceReduce(launcherOf(c), c->view);
 }
 // ---- the implicitDiffusion branch [QGDUEqn.H L54-75, QGDEEqn.H L53-64] as stream-ordered phases ---------------------------------
@@ -1845,7 +1935,7 @@ static void implicitPhase(qgd_case_s* c, int phase) {
             c->gradUValid = false;
             break;
         }
-        case 21: c->implSolveIndex = 0; launchImplicitPart(st, m, c->view, c->impl, c->gas, c->bcDev, S, tol, maxIter, 1, c->fusedImpl); break;
+        case 21: c->implSolveIndex = 0; launchImplicitPart(st, m, c->view, c->impl, c->gas, c->bcDev, S, tol, maxIter, 1, implFusedNow(c)); break;
         case 22: case 23: case 24: case 25: case 26: case 27: implicitSolvePhase(S, phase - 22); break;
         case 28:
             implicitSolveEnd(S, 0);
@@ -3343,10 +3433,11 @@ int qgd_case_info(qgd_case_t c, double info[6]) {
 int qgd_case_fused_info(qgd_case_t c, int64_t info[8]) {
     if (!c || !info) return fail(QGD_ERR_INVALID, "null argument");
     const MeshView& v = c->dev->view;
-    info[0] = c->fused ? 1 : (c->fusedImpl ? 2 : (c->fusedAdj ? 3 : 0));   // 2: the implicitDiffusion branch's block-fused assembly of the U systems; 3: Courant-number control (blocks up to their sums + a cell kernel)
-    info[1] = (c->fused || c->fusedImpl || c->fusedAdj) ? v.fuBlocks : 0;
+    const bool fusedImpl = implFusedNow(c);   // (off while the case carries per-face velocities on a fixedValue patch)
+    info[0] = c->fused ? 1 : (fusedImpl ? 2 : (c->fusedAdj ? 3 : 0));   // 2: the implicitDiffusion branch's block-fused assembly of the U systems; 3: Courant-number control (blocks up to their sums + a cell kernel)
+    info[1] = (c->fused || fusedImpl || c->fusedAdj) ? v.fuBlocks : 0;
     info[2] = c->fused ? c->dev->fusedFacesComputed : 0;
-    info[3] = (c->fused || c->fusedAdj) ? v.fuLds : (c->fusedImpl ? v.fuLdsImpl : 0);
+    info[3] = (c->fused || c->fusedAdj) ? v.fuLds : (fusedImpl ? v.fuLdsImpl : 0);
     info[4] = c->fused ? c->dev->fusedCellsStaged : 0;
     info[5] = c->fused ? c->dev->fusedCellsStagedFull : 0;
     info[6] = c->fused ? c->dev->fusedVertsStaged : 0;

@@ -82,9 +82,15 @@ struct PatchBCDev {
     int32_t bcU, bcT, bcP, ptype; double vU[3]; double vT, vP;
     // symmetryPlane patches: the one normal of the patch (qgd_mesh.hpp Patch::nHat), used on every face where basicSymmetry (slip,
     // symmetry) uses the face's own normal (L0: symmetryPlaneFvPatchField::evaluate / snGrad / snGradTransformDiag)
-    double nHat[3]; int32_t planeN, pad_;
+    double nHat[3]; int32_t planeN;
+    // which of the patch's fixedValue fields take one value per face out of CaseView::bValU / bValT / bValP instead of vU / vT / vP
+    // (QGD_BC_LIST_U | _T | _P; qgd_case_set_bc_values); 0: the patch is uniform in all three
+    int32_t valList;
 };
 #define QGD_MAX_PATCHES 64
+#define QGD_BC_LIST_U 1
+#define QGD_BC_LIST_T 2
+#define QGD_BC_LIST_P 4
 
 struct GasModel {
     double R, Cv, mu0, Pr, ScQGD, PrQGD, alphaQGD;
@@ -123,7 +129,23 @@ struct CaseView {
     // non-uniform alphaQGD / ScQGD (the READ_IF_PRESENT fields of QGDCoeffs_8C L119-160, constScPrModel1_8C L66-79);
     // nullptr = the uniform value of GasModel
     const double* aQ; const double* aQb; const double* sc; const double* scb;
+    // per-face values of fixedValue patches (qgd_case_set_bc_values), indexed by boundary face (bValU: 3 per face); read only on the faces of
+    // a patch whose PatchBCDev::valList names the field; nullptr = no patch of the case has a list for that field
+    const double* bValU; const double* bValT; const double* bValP;
 };
+#if defined(__HIPCC__)
+// the prescribed value of a fixedValue patch face: the face's own entry where the patch carries a list, the patch's one value otherwise
+__device__ __forceinline__ void fixedValueU(const CaseView& c, const PatchBCDev& bc, const int b, double& ux, double& uy, double& uz) {
+    if (bc.valList & QGD_BC_LIST_U) { ux = c.bValU[3 * (size_t)b]; uy = c.bValU[3 * (size_t)b + 1]; uz = c.bValU[3 * (size_t)b + 2]; }
+    else { ux = bc.vU[0]; uy = bc.vU[1]; uz = bc.vU[2]; }
+}
+__device__ __forceinline__ double fixedValueT(const CaseView& c, const PatchBCDev& bc, const int b) {
+    return (bc.valList & QGD_BC_LIST_T) ? c.bValT[b] : bc.vT;
+}
+__device__ __forceinline__ double fixedValueP(const CaseView& c, const PatchBCDev& bc, const int b) {
+    return (bc.valList & QGD_BC_LIST_P) ? c.bValP[b] : bc.vP;
+}
+#endif
 
 enum DebugSlot : int {
     DBG_PHIJM = 0, DBG_PHIJMU = 1, DBG_PHIP = 4, DBG_PHIPI = 7, DBG_PHIJMH = 10, DBG_PHIQ = 11, DBG_PHIPIU = 12,

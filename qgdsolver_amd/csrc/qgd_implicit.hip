@@ -245,7 +245,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void implCellUKernel(const MeshView m, c
         }
     }
     const RecA A = c.A[ci];
-    implCellU(m, c, iv, bcs, ci, A, m.V[ci], sum, dTau, diagBase, n, [&](int i) { return m.cfItem[base + (size_t)i * 64]; });   // (qgd_implicit_dev.hpp)
+    implCellU(m, c, iv, bcs, ci, A, m.V[ci], sum, dTau, diagBase, n, [&](int i) { return m.cfItem[base + (size_t)i * 64]; }, c.bValU);   // (qgd_implicit_dev.hpp)
 }
 
 // after the U solve: rho and U of the records (p and e stay those of the old time level), patch values of U
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void implBcUKernel(const MeshView m, con
     if (bc.ptype == QGD_PATCH_HALO) return;
     const RecA Ao = c.A[m.own[f]];
     RecA Ab = c.bA[b];
-    if (bc.bcU == QGD_BC_FIXEDVALUE) { Ab.ux = bc.vU[0]; Ab.uy = bc.vU[1]; Ab.uz = bc.vU[2]; }
+    if (bc.bcU == QGD_BC_FIXEDVALUE) fixedValueU(c, bc, b, Ab.ux, Ab.uy, Ab.uz);
     else if (bc.bcU == QGD_BC_SLIP) {
         double n[3];
         symmNormal(m, bc, f, n);
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void implCellEKernel(const MeshView m, c
             const PatchBCDev bc = bcs[m.bPatch[f - m.nIF]];
             if (bc.ptype != QGD_PATCH_HALO && bc.ptype != QGD_PATCH_CYCLIC && bc.bcT == QGD_BC_FIXEDVALUE) {
                 diag += a;                       // fixedEnergy = fixedValue
-                rhs += a * (gm.Cv * bc.vT);
+                rhs += a * (gm.Cv * fixedValueT(c, bc, f - m.nIF));
             }
         }
     };

@@ -112,7 +112,7 @@ __device__ __forceinline__ void implInternalFace(const GasModel& gm, const doubl
 template <class PatchFaceFn>
 __device__ __forceinline__ void implCellU(const MeshView& m, const CaseView& c, const ImplView& iv, const PatchBCDev* __restrict__ bcs, const int ci,
                                           const RecA& A, const double V, const double sum[4], const double dTau[3], const double diagBase,
-                                          const int nPatchFaces, PatchFaceFn patchFace) {
+                                          const int nPatchFaces, PatchFaceFn patchFace, const double* __restrict__ bValU) {
 #pragma clang fp contract(off)   // (no fusing left to the compiler: inlined into different kernels it would fuse different products, see implInternalFace)
     const size_t nC = (size_t)m.nC;
     const double dt = c.dt[0], dtV = dt / V, rDeltaT = 1.0 / dt;
@@ -136,7 +136,9 @@ __device__ __forceinline__ void implCellU(const MeshView& m, const CaseView& c, 
         if (bc.ptype == QGD_PATCH_HALO || bc.ptype == QGD_PATCH_CYCLIC) continue;
         const double a = iv.aU[f];
         if (bc.bcU == QGD_BC_FIXEDVALUE) {
-            for (int k = 0; k < 3; ++k) { diag[k] += a; rhs[k] += a * bc.vU[k]; }
+            // bValU: the per-face values of the case's list patches (CaseView::bValU), or nullptr from a caller that serves no list case
+            const bool list = bValU && (bc.valList & QGD_BC_LIST_U);
+            for (int k = 0; k < 3; ++k) { diag[k] += a; rhs[k] += a * (list ? bValU[3 * (size_t)b + k] : bc.vU[k]); }
         } else if (bc.bcU == QGD_BC_SLIP) {
             const double ms = m.magSf[f], dc = m.dn[f], gs = iv.mufS[f] * ms;
             double nv[3];

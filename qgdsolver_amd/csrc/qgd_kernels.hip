@@ -1498,7 +1498,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             implCellU(m, c, iv, bcs, ci, A, Vc, sum, dTau, diagBase, nE, [&](int i) {
                 const int e = (i < KE) ? sE[i * 128 + tid] : ent[(size_t)i * 128];
                 return e < 0 ? ~e : -1;   // a patch face's label; internal faces carry no patch coefficient
-            });
+            }, nullptr);   // (no per-face U values here: a case that has them assembles its U systems with implCellUKernel, qgd_capi.cpp implFusedNow)
         }
         return;
     }
@@ -1650,7 +1650,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void boundaryUpdateKernel(const MeshView
     const RecA Ao = c.A[o];
     RecA Ab;
     // U
-    if (bc.bcU == QGD_BC_FIXEDVALUE) { Ab.ux = bc.vU[0]; Ab.uy = bc.vU[1]; Ab.uz = bc.vU[2]; }
+    if (bc.bcU == QGD_BC_FIXEDVALUE) fixedValueU(c, bc, b, Ab.ux, Ab.uy, Ab.uz);
     else if (bc.bcU == QGD_BC_SLIP) {
         double n[3];
         symmNormal(m, bc, f, n);
@@ -1666,7 +1666,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void boundaryUpdateKernel(const MeshView
     } else { Ab.ux = Ao.ux; Ab.uy = Ao.uy; Ab.uz = Ao.uz; }
     // e / T
     double Tb;
-    if (bc.bcT == QGD_BC_FIXEDVALUE) { Tb = bc.vT; Ab.e = gm.Cv * Tb; }
+    if (bc.bcT == QGD_BC_FIXEDVALUE) { Tb = fixedValueT(c, bc, b); Ab.e = gm.Cv * Tb; }
     else { Ab.e = Ao.e; Tb = Ab.e / gm.Cv; }
     const double psi = 1.0 / (gm.R * Tb);
     const double cs = sqrt(gm.gamma / psi);
@@ -1675,11 +1675,11 @@ __global__ __launch_bounds__(QGD_BLOCK) void boundaryUpdateKernel(const MeshView
     Bb.c = cs;
     Bb.aOc = aq / cs;
     // pressure seen by constScPrModel1 at thermo.correct(): the patch value before p's BC update
-    const double pOld = init ? ((bc.bcP == QGD_BC_FIXEDVALUE) ? bc.vP : Ao.p) : c.bPmid[b];
+    const double pOld = init ? ((bc.bcP == QGD_BC_FIXEDVALUE) ? fixedValueP(c, bc, b) : Ao.p) : c.bPmid[b];
     const double tauQGD = aq * m.hQGDb[b] / cs;
     Bb.muQGD = pOld * scq * tauQGD;
     // p
-    if (bc.bcP == QGD_BC_FIXEDVALUE) Ab.p = bc.vP;
+    if (bc.bcP == QGD_BC_FIXEDVALUE) Ab.p = fixedValueP(c, bc, b);
     else if (bc.bcP == QGD_BC_QGDFLUX) {
         double grad = init ? 0.0 : c.bG[b];
         if (phiwRegistered) {

@@ -99,6 +99,8 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdPressureBcKernel(const MeshView 
     const PatchBCDev bc = bcs[m.bPatch[b]];
     const double po = q.p[m.own[f]];
     double pb = po, gb = 0.0;
+    // (vU / vT / vP throughout this file: a QHDFoam case has one value per patch and entry; per-face lists, PatchBCDev::valList, belong to
+    // the QGDFoam case, whose set_bc_values is the only entry that raises the flag)
     if (bc.bcP == QGD_BC_FIXEDVALUE) pb = bc.vP;
     else if (bc.bcP == QGD_BC_QGDFLUX) { gb = bc.vP; pb = po + gb / m.dn[f]; }
     else if (bc.bcP == QGD_BC_QHDFLUX) { gb = -(q.phiwo[f] / q.tauF[f] * q.rho0 / m.magSf[f]); pb = po + gb / m.dn[f]; }

@@ -57,6 +57,8 @@ __global__ __launch_bounds__(QGD_BLOCK) void scalarSetupFaceKernel(const MeshVie
             } else {
                 const int b = f - m.nIF;
                 const PatchBCDev bc = bcs[m.bPatch[b]];
+                // (vU / vT throughout this file: the scalar case has one value per patch and entry; per-face lists, PatchBCDev::valList,
+                // belong to the QGDFoam case)
                 if (bc.bcU == QGD_BC_FIXEDVALUE) { uf[0] = bc.vU[0]; uf[1] = bc.vU[1]; uf[2] = bc.vU[2]; }
                 else if (bc.bcU == QGD_BC_SLIP) {   // basicSymmetry::evaluate = (pif + transform(I - 2 nn, pif))/2
                     double n[3];

@@ -502,8 +502,12 @@ def write_field(path, mesh, name, internal, patches, dimensions="[0 0 0 0 0 0 0]
 # ---------------------------------------------------------------------------------------------------------------------
 # case set-up (what QGDFoam's createFields.H reads)
 # ---------------------------------------------------------------------------------------------------------------------
-def _bc(rec, vector, patch_type_word, what):
+def _bc(rec, vector, patch_type_word, what, lists=False):
     """boundaryField entry -> the (kind, value) pair QGDFoamCase.set_bc takes.
+
+    lists (the QGDFoam reader): a fixedValue entry written as `nonuniform List<scalar|vector>` comes back as the array of its values in
+    patch-face order ((nFaces, 3) or (nFaces,)), `noSlip` on U is fixedValue (0 0 0); a value list on any other kind of entry is refused
+    (the resident case would not evaluate it).  The QHDFoam and scalar readers keep to one value per patch.
 
     Constraint patches (L0: fvPatchField<Type>::New(p, iF, dict)): the entry's type must be the patch's own constraint type --
     OpenFOAM stops with "inconsistent patch and patchField types" otherwise -- and the field then IS that constraint field:
@@ -523,15 +527,24 @@ def _bc(rec, vector, patch_type_word, what):
     if t in _CONSTRAINT_BCS:
         raise FoamFileError(f"{what}: boundary condition '{t}' needs a patch of that type (the patch is '{patch_type_word}')")
     if t in ("zeroGradient", "slip", "qgdFlux"):
+        v = rec.get("value")
+        if lists and v is not None and len(v) and np.any(v != v[0]):
+            raise FoamFileError(f"{what}: a value list on a '{t}' entry is not supported (per-face values belong to fixedValue entries)")
         if t == "slip" and not vector:
             return ("zeroGradient", None)  # slip on a scalar is zeroGradient (basicSymmetry, L0)
         return (t, None)
+    if t == "noSlip" and vector and lists:
+        return ("fixedValue", np.zeros(3))   # noSlipFvPatchVectorField: fixedValue (0 0 0) without a value entry (L0)
     if t == "fixedValue":
         v = rec["value"]
         if v is None:
             raise FoamFileError(f"{what}: fixedValue needs a value")
-        if np.any(v != v[0]):
-            raise FoamFileError(f"{what}: only uniform fixedValue patches are supported")
+        if len(v) and np.any(v != v[0]):
+            if not lists:
+                raise FoamFileError(f"{what}: only uniform fixedValue patches are supported")
+            return ("fixedValue", np.array(v if vector else v[:, 0], dtype=np.float64))
+        if not len(v):
+            return ("fixedValue", np.zeros(3) if vector else 0.0)   # a patch without faces
         return ("fixedValue", v[0] if vector else float(v[0, 0]))
     raise FoamFileError(f"{what}: boundary condition '{t}' is not supported")
 
@@ -765,8 +778,8 @@ def read_case_setup(case_dir, time="0"):
     ptw = [PATCH_WORDS.get(int(t), "patch") for t in mesh.array("patchType")]
     bcs = []
     for i, name in enumerate(mesh.patch_names):
-        bcs.append({"U": _bc(bU[name], True, ptw[i], f"U.{name}"), "T": _bc(bT[name], False, ptw[i], f"T.{name}"),
-                    "p": _bc(bP[name], False, ptw[i], f"p.{name}")})
+        bcs.append({"U": _bc(bU[name], True, ptw[i], f"U.{name}", lists=True), "T": _bc(bT[name], False, ptw[i], f"T.{name}", lists=True),
+                    "p": _bc(bP[name], False, ptw[i], f"p.{name}", lists=True)})
     fields = {"U": U, "T": T[:, 0], "p": p[:, 0]}
     fields.update(coeff_fields)
     return mesh, opt, fields, bcs
@@ -1095,6 +1108,36 @@ def _patch_values(mesh, internal, patches, what):
     return out
 
 
+def _is_value_list(field, value):
+    """whether a fixedValue entry's value is one value per face ((nFaces, 3) for U, (nFaces,) for T and p) and not the patch's one value"""
+    return value is not None and np.ndim(value) == (2 if field == "U" else 1)
+
+
+def device_bcs(file_mesh, mesh, bcs):
+    """the per-patch BC triples of the case files for a device mesh cut or unrolled from file_mesh: value lists of fixedValue entries follow
+    the device mesh's patch faces.  A shard's patch faces (those of its ghost cells included) are found through faceGlobal; on a mesh from
+    unroll_cyclic the real faces keep their order and a copy's face (faceGlobal = -1 - label) takes the value of the face it copies -- its
+    record is its original's anyway (the library refreshes it), the entry only serves the start-up evaluation."""
+    if mesh is file_mesh or not any(_is_value_list(f, bc[f][1]) for bc in bcs for f in ("U", "T", "p") if bc[f][0] == "fixedValue"):
+        return bcs
+    fg = mesh.array("faceGlobal")
+    ps, pz = mesh.array("patchStart"), mesh.array("patchSize")
+    gps, gpz = file_mesh.array("patchStart"), file_mesh.array("patchSize")
+    out = []
+    for i, bc in enumerate(bcs):
+        rec = dict(bc)
+        for f in ("U", "T", "p"):
+            kind, val = bc[f]
+            if kind == "fixedValue" and _is_value_list(f, val):
+                g = fg[int(ps[i]): int(ps[i]) + int(pz[i])].astype(np.int64)
+                g = np.where(g < 0, -1 - g, g) - int(gps[i])
+                if g.size and (g.min() < 0 or g.max() >= int(gpz[i])):
+                    raise FoamFileError(f"patch {i}: a face of the device mesh does not belong to the same patch of the case's mesh")
+                rec[f] = (kind, np.asarray(val, dtype=np.float64)[g])
+        out.append(rec)
+    return out
+
+
 def load_case(case_dir, time="0", device_id=0):
     """Case directory -> (Device, QGDFoamCase) ready to ``step()``: the createFields.H sequence of QGDFoam over the
     C-ABI.  Needs the HIP device (there is no CPU fallback)."""
@@ -1112,6 +1155,7 @@ def load_case(case_dir, time="0", device_id=0):
         mesh.file_mesh = file_mesh
         cg = mesh.array("cellGlobal")
         fields = {k: v[cg] for k, v in fields.items()}
+        bcs = device_bcs(file_mesh, mesh, bcs)
     dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}})
     case = QGDFoamCase(dev, default_options(**opt))
     for i, bc in enumerate(bcs):
@@ -1124,7 +1168,9 @@ def load_case(case_dir, time="0", device_id=0):
 
 def write_time(case, case_dir, time_name, bcs=None):
     """Write U, T, p, rho of a QGDFoamCase into <case_dir>/<time_name>/ (what runTime.write() leaves for QGDFoam's
-    AUTO_WRITE fields); patch entries carry the patch values as ``value``."""
+    AUTO_WRITE fields); patch entries carry the patch values as ``value`` -- a fixedValue entry what the case prescribes there
+    (``uniform`` for one value per patch, ``nonuniform List<...>`` for a value list: what the reader takes back), zeroGradient / slip /
+    qgdFlux entries none (the case evaluates them at start-up; the reader refuses a value list there)."""
     mesh = case.mesh
     if hasattr(mesh, "file_mesh"):
         raise FoamFileError("write_time: a case with cyclic patches carries copies of its cells; python -m qgdsolver_amd.QGDFoam writes its time directories")
@@ -1147,5 +1193,11 @@ def write_time(case, case_dir, time_name, bcs=None):
                 if kind == "none":
                     kind = "calculated"
             b0 = int(ps[i]) - nIF
-            patches[pn] = (kind, bvals[b0:b0 + int(pz[i])])
+            if kind == "fixedValue" and fname != "rho":
+                vals, is_list = case.get_bc_values(i, fname)
+                patches[pn] = (kind, vals if is_list or not len(vals) else vals[0])
+            elif kind in ("zeroGradient", "slip", "qgdFlux"):
+                patches[pn] = (kind, None)
+            else:
+                patches[pn] = (kind, bvals[b0:b0 + int(pz[i])])
         write_field(os.path.join(case_dir, str(time_name), fname), mesh, fname, internal, patches, dims[fname])

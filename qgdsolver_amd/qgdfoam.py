@@ -92,9 +92,45 @@ class QGDFoamCase:
     def set_bc(self, patch, U=("zeroGradient", None), T=("zeroGradient", None), p=("zeroGradient", None)):
         kinds = {"zeroGradient": L.BC_ZEROGRADIENT, "fixedValue": L.BC_FIXEDVALUE, "slip": L.BC_SLIP, "qgdFlux": L.BC_QGDFLUX,
                  "none": L.BC_NONE}
-        vu = np.asarray(U[1] if U[1] is not None else (0.0, 0.0, 0.0), dtype=np.float64)
+        # a fixedValue entry takes the patch's one value ((3,) for U, a float for T and p) or one value per face of the patch on this
+        # device's mesh ((nFaces, 3), (nFaces,)): qgd_case_set_bc_values, after the entry itself
+        lists = {}
+        for field, entry in (("U", U), ("T", T), ("p", p)):
+            if entry[1] is not None and np.ndim(entry[1]) == (2 if field == "U" else 1):
+                if entry[0] != "fixedValue":
+                    raise ValueError(f"set_bc: {field} of patch {patch}: a value list belongs to a fixedValue entry, not to '{entry[0]}'")
+                lists[field] = np.ascontiguousarray(entry[1], dtype=np.float64)
+        one = lambda field, entry: 0.0 if field in lists else float(entry[1] or 0.0)   # noqa: E731
+        vu = np.asarray(U[1] if (U[1] is not None and "U" not in lists) else (0.0, 0.0, 0.0), dtype=np.float64)
         L.check(L.lib.qgd_case_set_bc(self._h, patch, kinds[U[0]], vu.ctypes.data_as(L.c_double_p), kinds[T[0]],
-                                      float(T[1] or 0.0), kinds[p[0]], float(p[1] or 0.0)), "qgd_case_set_bc")
+                                      one("T", T), kinds[p[0]], one("p", p)), "qgd_case_set_bc")
+        for field, values in lists.items():
+            self.set_bc_values(patch, field, values)
+
+    _BC_FIELDS = {"U": 0, "T": 1, "p": 2}
+
+    def set_bc_values(self, patch, field, values):
+        """one value per face of a fixedValue entry (qgd_case_set_bc_values): field "U" (nFaces, 3), "T" / "p" (nFaces,), in the patch's
+        face order on this device's mesh; None drops the list (the entry reads its uniform value again).  Before set_fields."""
+        k = self._BC_FIELDS[field]
+        if values is None:
+            L.check(L.lib.qgd_case_set_bc_values(self._h, int(patch), k, None, 0), "qgd_case_set_bc_values")
+            return
+        a = np.ascontiguousarray(values, dtype=np.float64)
+        if a.ndim != (2 if k == 0 else 1) or (k == 0 and a.shape[1] != 3):
+            raise ValueError(f"set_bc_values: {field} takes an array of shape {'(nFaces, 3)' if k == 0 else '(nFaces,)'}, got {a.shape}")
+        buf = a if a.size else np.zeros(3)
+        L.check(L.lib.qgd_case_set_bc_values(self._h, int(patch), k, buf.ctypes.data_as(L.c_double_p), int(a.shape[0])), "qgd_case_set_bc_values")
+
+    def get_bc_values(self, patch, field):
+        """(what a fixedValue entry prescribes per face of the patch, whether it is a value list) -- qgd_case_get_bc_values"""
+        k = self._BC_FIELDS[field]
+        n = int(self.mesh.array("patchSize")[patch])
+        out = np.zeros((n, 3) if k == 0 else (n,))
+        buf = out if out.size else np.zeros(3)
+        is_list = C.c_int32()
+        L.check(L.lib.qgd_case_get_bc_values(self._h, int(patch), k, buf.ctypes.data_as(L.c_double_p), n, C.byref(is_list)), "qgd_case_get_bc_values")
+        return out, bool(is_list.value)
 
     def set_fields(self, U, T, p):
         U = np.ascontiguousarray(U, dtype=np.float64)
