@@ -681,6 +681,27 @@ int qgd_case_get_bc_values(qgd_case_t c, int32_t patch, int32_t field, double* v
 int qgd_case_set_qgd_coeffs(qgd_case_t c, const double* alphaQGD, const double* alphaQGDb, const double* ScQGD,
                             const double* ScQGDb);
 
+/* The varScModel7 closure of QGDCoeffs [varScModel7_8C_source.html L166-300]: ScQGD of a cell is a shock sensor built from the
+ * pressure jumps across the cell's faces,
+ *     ScQGD = cSc1 |sum_f r_f (p_other - p_self)| / (sum_f p_f / n),   r_f = nonOrthDeltaCoeff_f / deltaCoeff_f,
+ * over the internal faces (p_f = linear interpolate) and the patch faces (p_f = p_b) of the cell, those of empty patches left out;
+ * then max(., minSc) where minSc >= 0, min(., maxSc) where maxSc >= 0, and ScQGD itself on the nConstCells cells of constCells
+ * (the cellSet constScCellSet; labels of this device's mesh).  Patch faces keep ScQGD, clipped the same way.  tauQGD, tauQGDf and
+ * alphauQGD are those of constScPrModel1; muQGD = p ScQGD tauQGD with the pressure of the step's start.  The sensor runs once in
+ * qgd_case_set_fields and once per step, between the flux assembly and the advance, on every path of qgd_case_step /
+ * qgd_case_step_phase / qgd_case_step_sharded, over the owned cells of a shard.
+ * Call before qgd_case_set_fields.  opt == NULL returns the case to its uniform ScQGD (or the array of qgd_case_set_qgd_coeffs).
+ * Refused: together with a ScQGD array of qgd_case_set_qgd_coeffs (alphaQGD arrays are allowed), on a periodic device
+ * (qgd_mesh_unroll_cyclic), a model other than 7, a cell label out of range. */
+typedef struct qgd_var_sc_options {
+    int32_t model;       /* 7 */
+    int32_t nConstCells;
+    double ScQGD, cSc1, minSc, maxSc;   /* minSc, maxSc < 0: no clipping on that side */
+} qgd_var_sc_options;
+int qgd_case_set_var_sc(qgd_case_t c, const qgd_var_sc_options* opt, const int32_t* constCells);
+/* out[0] = max, out[1] = min of ScQGD over the owned cells (the reference's "max/min ScQGD" line), computed when asked. */
+int qgd_case_sc_range(qgd_case_t c, double out[2]);
+
 /* Initial cell fields U (nCells*3), T, p (HOST pointers); evaluates the BCs,
  * thermo.correct() and the derived conserved fields like createFields.H
  * [QGDFoam_2createFields_8H_source.html L3-109]. */
@@ -697,7 +718,8 @@ int qgd_case_update_fluxes(qgd_case_t c);
 int qgd_case_step(qgd_case_t c, int32_t nSteps);
 
 /* Named field copy-out to HOST.  Cell fields: "rho","U","p","e","T","rhoU",
- * "rhoE","c","psi","mu","alphau","tauQGD","muQGD","alphauQGD","hQGD","H".
+ * "rhoE","c","psi","mu","alphau","tauQGD","muQGD","alphauQGD","hQGD","H","ScQGD"
+ * (the uniform value repeated, the array of qgd_case_set_qgd_coeffs, or the last result of the varScModel7 sensor).
  * Face fields: see qgd_case_update_fluxes plus "hQGDf"; with implicitDiffusion true also "phiTauMC" (3 per face)
  * and "phiSigmaDotU" as the last step formed them [QGDFoam_2updateFluxes_8H_source.html L107-111, QGDUEqn_8H_source.html L72-74].
  * Boundary fields: "<cellfield>.boundary".  outDoubles = capacity of out. */
@@ -865,7 +887,8 @@ enum {
     QGD_K_CELL = 3,    /* flux gather + Euler update + thermo + QGD coefficients */
     QGD_K_BC = 4,      /* boundary-condition refresh                            */
     QGD_K_BPOINT = 5,  /* patch points: mean of the surrounding patch-face values */
-    QGD_K_COUNT = 6
+    QGD_K_VARSC = 6,   /* varScModel7: ScQGD from the pressure jumps (qgd_case_set_var_sc) */
+    QGD_K_COUNT = 7
 };
 /* Enable HIP-event timing of every launch of kernel `k` on the case's own
  * stream; totals since the last reset. */

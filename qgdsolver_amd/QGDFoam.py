@@ -101,6 +101,7 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
                                    "in the case's own cell order")
         if "alphaQGD" in fields or "ScQGD" in fields:   # (foamfile.load_case refuses the same case; before any device exists)
             raise ff.FoamFileError(f"{case_dir}: a case with cyclic patches runs with uniform alphaQGD / ScQGD (no alphaQGD or ScQGD field file)")
+        # (QGDCoeffs varScModel7 on such a case is refused by foamfile.read_case_setup, by name)
         mesh = gmesh.unroll_cyclic(gmesh.cyclic_pairs)
         cells = mesh.array("cellGlobal")
         owned = np.arange(mesh.nCells) < n_global
@@ -132,6 +133,13 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             b = np.where(gb >= 0, bndv[np.maximum(gb, 0)], cellv[cells][mesh.array("owner")[mesh.nInternalFaces:]])
             return cellv[cells], b
         case.set_qgd_coeffs(alphaQGD=local(fields.get("alphaQGD")), ScQGD=local(fields.get("ScQGD")))
+    var_sc = opt.get("varSc")
+    if var_sc:
+        # QGDCoeffs varScModel7: the sensor runs on the device, over the owned cells of a shard; the cells of constScCellSet follow the
+        # relabelling and the cut (a shard marks those of them it holds)
+        cs = var_sc["const_cells"]
+        local_cells = np.nonzero(np.isin(cells, cs))[0].astype(np.int32) if cs is not None else None
+        case.set_var_sc(**dict(var_sc, const_cells=local_cells))
     case.set_fields(fields["U"][cells], fields["T"][cells], fields["p"][cells])
     adjust = bool(case.options.adjustTimeStep)
     if world > 1:
@@ -256,13 +264,20 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             if ii["stalled_steps"]:
                 log(f"  NOTE: {ii['stalled_steps']} step(s) so far in which a Chebyshev solve ended at the rounding floor of its residual, above "
                     f"implicitTol {case.options.implicitTol:g} (OpenFOAM would have iterated on to maxIter)")
+        if var_sc:
+            sc_hi, sc_lo = case.sc_range()
+            if world > 1:
+                both = [None] * world
+                dist.all_gather_object(both, (sc_hi, sc_lo))
+                sc_hi, sc_lo = max(b[0] for b in both), min(b[1] for b in both)
+            log(f"max/min ScQGD: {sc_hi:.6g}/{sc_lo:.6g}")     # [varScModel7.C L256-259]
         if not np.isfinite(info["minRho"]) or info["minRho"] <= 0:
             raise FloatingPointError(f"density lost positivity at time {t:g}")
         if write:
             name = time_name(t, precision)
-            data = {f: gather(f) for f in ("U", "T", "p", "rho")}
+            data = {f: gather(f) for f in ("U", "T", "p", "rho") + (("ScQGD",) if var_sc else ())}
             if rank == 0:
-                _write_cell_fields(case_dir, name, data, bcs, gmesh)
+                _write_cell_fields(case_dir, name, data, bcs, gmesh, var_sc)
             written.append(name)
         if total is None and t >= end_time - 1e-12 * max(1.0, abs(end_time)):
             break
@@ -273,10 +288,16 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
     return dev, case, written
 
 
-def _write_cell_fields(case_dir, name, data, bcs, file_mesh):
+def _write_cell_fields(case_dir, name, data, bcs, file_mesh, var_sc=None):
     """Time directory from gathered cell fields.  Patch entries carry the BC type; values of fixedValue patches are
-    the prescribed ones, the others are written without a value (the solver evaluates them at start-up)."""
-    dims = {"U": "[0 1 -1 0 0 0 0]", "T": "[0 0 0 1 0 0 0]", "p": "[1 -1 -2 0 0 0 0]", "rho": "[1 -3 0 0 0 0 0]"}
+    the prescribed ones, the others are written without a value (the solver evaluates them at start-up).  ScQGD (varScModel7) has
+    calculated patches with the dictionary's value, clipped like the field [varScModel7.C L237-244]."""
+    dims = {"U": "[0 1 -1 0 0 0 0]", "T": "[0 0 0 1 0 0 0]", "p": "[1 -1 -2 0 0 0 0]", "rho": "[1 -3 0 0 0 0 0]", "ScQGD": "[0 0 0 0 0 0 0]"}
+    sc_b = None
+    if var_sc:
+        sc_b = var_sc["ScQGD"]
+        sc_b = max(sc_b, var_sc["minSc"]) if var_sc["minSc"] >= 0 else sc_b
+        sc_b = min(sc_b, var_sc["maxSc"]) if var_sc["maxSc"] >= 0 else sc_b
     names = file_mesh.patch_names
     pt = file_mesh.array("patchType")
     for fname, values in data.items():
@@ -285,6 +306,9 @@ def _write_cell_fields(case_dir, name, data, bcs, file_mesh):
             word = ff.PATCH_WORDS.get(int(pt[i]), "patch")
             if word in ff._CONSTRAINT_BCS:
                 patches[pn] = (word, None)
+                continue
+            if fname == "ScQGD":
+                patches[pn] = ("calculated", np.float64(sc_b))
                 continue
             kind, val = bcs[i].get(fname, ("calculated", None)) if fname != "rho" else ("calculated", None)
             if kind == "none":

@@ -48,6 +48,12 @@ class CaseOptions(C.Structure):
     ]
 
 
+class VarScOptions(C.Structure):
+    """qgd_var_sc_options"""
+    _fields_ = [("model", C.c_int32), ("nConstCells", C.c_int32), ("ScQGD", C.c_double), ("cSc1", C.c_double), ("minSc", C.c_double),
+                ("maxSc", C.c_double)]
+
+
 class QhdOptions(C.Structure):
     """qgd_qhd_options"""
     _fields_ = [("stencil", C.c_int32), ("implicitDiffusion", C.c_int32), ("tauModel", C.c_int32), ("pRefCell", C.c_int32),
@@ -170,6 +176,8 @@ SIGNATURES = {
     "qgd_case_get_bc_values": (C.c_int, [handle, C.c_int32, C.c_int32, c_double_p, C.c_int64, c_int32_p]),
     "qgd_case_set_fields": (C.c_int, [handle, c_double_p, c_double_p, c_double_p]),
     "qgd_case_set_qgd_coeffs": (C.c_int, [handle, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "qgd_case_set_var_sc": (C.c_int, [handle, C.POINTER(VarScOptions), c_int32_p]),
+    "qgd_case_sc_range": (C.c_int, [handle, c_double_p]),
     "qgd_case_update_fluxes": (C.c_int, [handle]),
     "qgd_case_step": (C.c_int, [handle, C.c_int32]),
     "qgd_case_get_field": (C.c_int, [handle, C.c_char_p, c_double_p, C.c_int64]),
@@ -235,7 +243,7 @@ DEVICE_NO_FUSED_TABLES, DEVICE_FUSED_ANY_BLOCKS = 1, 2   # flags of qgd_device_c
 BC_ZEROGRADIENT, BC_FIXEDVALUE, BC_SLIP, BC_QGDFLUX, BC_NONE, BC_QHDFLUX = range(6)
 FVSC_REDUCED, FVSC_LEASTSQUARES, FVSC_GAUSSVOLPOINT = range(3)
 FLUX_LINEAR, FLUX_UPWIND = range(2)
-K_POINT, K_FACE, K_BFACE, K_CELL, K_BC, K_BPOINT = range(6)
+K_POINT, K_FACE, K_BFACE, K_CELL, K_BC, K_BPOINT, K_VARSC = range(7)
 
 
 class QgdError(RuntimeError):

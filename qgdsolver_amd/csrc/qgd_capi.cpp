@@ -243,6 +243,13 @@ struct qgd_device_s {
     // with faces (their coupled / rotated patch fields are not served), a symmetryPlane that is not planar (fatal in OpenFOAM too)
     std::string caseRefusal; int caseRefusalCode = 0;
     std::vector<double> hf;  // host copy of hQGDf for the accessor
+    // varScModel7 (VarScView::rf): r_f per face, -1 on faces without fields; the device copy is made when the first case asks for the model
+    std::vector<double> sensorRatio;
+    const double* sensorRatioDev = nullptr;
+    const double* ensureSensorRatio() {
+        if (!sensorRatioDev && !sensorRatio.empty()) sensorRatioDev = arena.upload(sensorRatio);
+        return sensorRatioDev;
+    }
     // halo lists (device) and sizes, one entry per halo slot (neighbouring shard)
     struct HaloSlot {
         int32_t *ghost = nullptr, *send = nullptr, *ghostBF = nullptr, *sendBF = nullptr;
@@ -353,6 +360,11 @@ struct qgd_case_s {
     bool reuseGradU = true;                 // QGD_IMPL_REUSE_GRADU (default 1)
     bool gradUValid = false;                // implicit branch, unsharded: fvc::grad(U) of phase 29 is still that of the records (phase 20 of the next step skips it)
     double* coef[4] = {nullptr, nullptr, nullptr, nullptr};  // device copies of non-uniform alphaQGD / ScQGD (cells, patch faces)
+    // varScModel7 (qgd_case_set_var_sc): the sensor writes coef[2], which CaseView::sc reads; coef[3] holds the clipped dictionary value
+    bool varSc = false;
+    VarScView vsc{};
+    uint8_t* constCellDev = nullptr;
+    double* scPart = nullptr;   // partials of qgd_case_sc_range
     double time = 0;
     int64_t steps = 0;
     // timing
@@ -731,6 +743,19 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
         d->patches = m.patches;
         residentCasePatchCheck(m, d->caseRefusal, d->caseRefusalCode);
         d->hf.assign(s.hf.begin(), s.hf.end());
+        d->sensorRatio.resize((size_t)m.nFaces);
+#pragma omp parallel for schedule(static)
+        for (int64_t f = 0; f < m.nFaces; ++f) {
+            // internal: nonOrthDeltaCoeffs / deltaCoeffs; patch: the patch snGrad coefficient (HostMesh::deltaCoeffs there) times |Cf - C_O|
+            double r = -1.0;
+            if (f < m.nInternalFaces) r = m.nonOrthDeltaCoeffs[f] / m.deltaCoeffs[f];
+            else if (s.fkind[f] != FK_SKIP) {
+                double d2 = 0;
+                for (int k = 0; k < 3; ++k) { const double x = m.Cf[3 * (size_t)f + k] - m.C[3 * (size_t)m.owner[f] + k]; d2 += x * x; }
+                r = m.deltaCoeffs[f] * std::sqrt(d2);
+            }
+            d->sensorRatio[f] = r;
+        }
         const bool range = m.ownedEnd > m.ownedBegin;
         d->ownedBegin = range ? m.ownedBegin : 0;
         d->ownedEnd = range ? m.ownedEnd : m.nCells;
@@ -1774,6 +1799,9 @@ int qgd_case_set_qgd_coeffs(qgd_case_t c, const double* alphaQGD, const double* 
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (c->dev->view.nBF > 0 && ((alphaQGD && !alphaQGDb) || (ScQGD && !ScQGDb)))
         return fail(QGD_ERR_INVALID, "qgd_case_set_qgd_coeffs: a field needs both its cell and its patch values");
+    if (c->varSc && ScQGD)
+        return fail(QGD_ERR_INVALID, "qgd_case_set_qgd_coeffs: the case runs varScModel7 (qgd_case_set_var_sc), which computes ScQGD itself; "
+                                     "pass ScQGD = NULL, or drop the model first");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
     const MeshView& m = c->dev->view;
     auto put = [&](const double* src, size_t n, double*& slot) -> const double* {
@@ -1784,10 +1812,91 @@ int qgd_case_set_qgd_coeffs(qgd_case_t c, const double* alphaQGD, const double* 
     };
     c->view.aQ = put(alphaQGD, (size_t)m.nC, c->coef[0]);
     c->view.aQb = put(alphaQGD ? alphaQGDb : nullptr, (size_t)m.nBF, c->coef[1]);
-    c->view.sc = put(ScQGD, (size_t)m.nC, c->coef[2]);
-    c->view.scb = put(ScQGD ? ScQGDb : nullptr, (size_t)m.nBF, c->coef[3]);
+    if (!c->varSc) {
+        c->view.sc = put(ScQGD, (size_t)m.nC, c->coef[2]);
+        c->view.scb = put(ScQGD ? ScQGDb : nullptr, (size_t)m.nBF, c->coef[3]);
+    }
     c->fieldsSet = false;
     c->gradUValid = false;
+    return QGD_OK;
+    QGD_CATCH
+}
+
+int qgd_case_set_var_sc(qgd_case_t c, const qgd_var_sc_options* opt, const int32_t* constCells) {
+    QGD_TRY
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    qgd_device_s* d = c->dev;
+    const MeshView& m = d->view;
+    if (!opt) {
+        if (c->varSc) { c->varSc = false; c->view.sc = nullptr; c->view.scb = nullptr; c->fieldsSet = false; c->gradUValid = false; }
+        return QGD_OK;
+    }
+    if (opt->model != 7)
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_var_sc: model " + std::to_string(opt->model) + " is not served (varScModel7 only: model = 7)");
+    if (d->periodic())
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_var_sc: varScModel7 is not served on a periodic device (cyclic patches served by ghost copies, "
+                                             "qgd_mesh_unroll_cyclic): such a case runs with uniform coefficients");
+    if (!c->varSc && c->view.sc)
+        return fail(QGD_ERR_INVALID, "qgd_case_set_var_sc: the case carries a ScQGD array (qgd_case_set_qgd_coeffs); varScModel7 computes ScQGD itself -- "
+                                     "drop the array first (alphaQGD arrays may stay)");
+    if (!std::isfinite(opt->ScQGD) || !std::isfinite(opt->cSc1) || !std::isfinite(opt->minSc) || !std::isfinite(opt->maxSc))
+        return fail(QGD_ERR_INVALID, "qgd_case_set_var_sc: ScQGD, cSc1, minSc, maxSc must be finite");
+    if (opt->nConstCells < 0 || (opt->nConstCells > 0 && !constCells))
+        return fail(QGD_ERR_INVALID, "qgd_case_set_var_sc: nConstCells cells need their labels");
+    for (int32_t i = 0; i < opt->nConstCells; ++i)
+        if (constCells[i] < 0 || constCells[i] >= m.nC)
+            return fail(QGD_ERR_INVALID, "qgd_case_set_var_sc: cell label " + std::to_string(constCells[i]) + " of constCells is out of range [0, " +
+                                         std::to_string(m.nC) + ")");
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    HIP_CHECK(hipStreamSynchronize(c->stream()));
+    VarScView v{};
+    v.rf = d->ensureSensorRatio();
+    if (!c->coef[2]) c->coef[2] = c->arena.alloc<double>(std::max<size_t>((size_t)m.nC, 1), false);
+    if (!c->coef[3]) c->coef[3] = c->arena.alloc<double>(std::max<size_t>((size_t)m.nBF, 1), false);
+    if (!c->scPart) c->scPart = c->arena.alloc<double>(2 * (size_t)QGD_FACE_REDUCE_PARTIALS + 2);
+    // the constructor's field: the dictionary value everywhere [L77-84]; patch values keep it, clipped like the field [L237-244]
+    double scb = opt->ScQGD;
+    if (opt->minSc >= 0.0) scb = std::max(scb, opt->minSc);
+    if (opt->maxSc >= 0.0) scb = std::min(scb, opt->maxSc);
+    {
+        const std::vector<double> fillC((size_t)m.nC, opt->ScQGD), fillB((size_t)m.nBF, scb);
+        if (m.nC) HIP_CHECK(hipMemcpy(c->coef[2], fillC.data(), sizeof(double) * fillC.size(), hipMemcpyHostToDevice));
+        if (m.nBF) HIP_CHECK(hipMemcpy(c->coef[3], fillB.data(), sizeof(double) * fillB.size(), hipMemcpyHostToDevice));
+    }
+    v.constCell = nullptr;
+    if (opt->nConstCells > 0) {
+        std::vector<uint8_t> mask((size_t)m.nC, 0);
+        for (int32_t i = 0; i < opt->nConstCells; ++i) mask[(size_t)constCells[i]] = 1;
+        if (!c->constCellDev) c->constCellDev = c->arena.alloc<uint8_t>((size_t)m.nC, false);
+        HIP_CHECK(hipMemcpy(c->constCellDev, mask.data(), mask.size(), hipMemcpyHostToDevice));
+        v.constCell = c->constCellDev;
+    }
+    v.sc = c->coef[2]; v.part = c->scPart;
+    v.ScQGD = opt->ScQGD; v.cSc1 = opt->cSc1; v.minSc = opt->minSc; v.maxSc = opt->maxSc;
+    c->vsc = v;
+    c->view.sc = c->coef[2];
+    c->view.scb = c->coef[3];
+    c->varSc = true;
+    c->fieldsSet = false;
+    c->gradUValid = false;
+    return QGD_OK;
+    QGD_CATCH
+}
+
+int qgd_case_sc_range(qgd_case_t c, double out[2]) {
+    QGD_TRY
+    if (!c || !out) return fail(QGD_ERR_INVALID, "null argument");
+    const qgd_device_s* d = c->dev;
+    if (!c->view.sc || d->ownedEnd <= d->ownedBegin) { out[0] = out[1] = c->gas.ScQGD; return QGD_OK; }
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    if (!c->scPart) c->scPart = c->arena.alloc<double>(2 * (size_t)QGD_FACE_REDUCE_PARTIALS + 2);
+    VarScView v = c->vsc;
+    v.sc = const_cast<double*>(c->view.sc); v.part = c->scPart;
+    (void)hipGetLastError();
+    launchVarScRange(c->stream(), v, d->ownedBegin, d->ownedEnd);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, c->scPart + 2 * (size_t)QGD_FACE_REDUCE_PARTIALS, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream()));
+    HIP_CHECK(hipStreamSynchronize(c->stream()));
     return QGD_OK;
     QGD_CATCH
 }
@@ -1849,6 +1958,7 @@ int qgd_case_set_fields(qgd_case_t c, const double* U, const double* T, const do
         (void)hipGetLastError();
         launchCellInit(L, m, c->view, c->gas, dU, dT, dp);
         launchBoundaryUpdate(L, m, c->view, c->gas, c->bcDev, true, false, 0, nullptr, 0);
+        if (c->varSc) launchVarSc7(L, m, c->view, c->gas, c->vsc, true);   // the thermo object's constructor runs the model once, on the evaluated patch pressures
         launchResetReductions(L, c->view);
         if (c->fused) {   // a shard's ghost records are written by the halo exchange only: both buffers start with the initial ones
             HIP_CHECK(hipMemcpyAsync(c->view.A2, c->view.A, sizeof(RecA) * (size_t)m.nC, hipMemcpyDeviceToDevice, c->stream()));
@@ -1924,6 +2034,7 @@ static void implicitPhase(qgd_case_s* c, int phase) {
     switch (phase) {
         case 20: {
             const bool adjust = c->opt.adjustTimeStep != 0;
+            if (c->varSc) launchVarSc7(launcherOf(c), m, c->view, c->gas, c->vsc, false);   // thermo.correct() of this step sees the pressures the step starts with
             if (adjust) launchDeltaT(launcherOf(c), c->view, c->opt.maxCo, c->opt.maxDeltaT, c->opt.cTau);
             if (adjust) launchImplicitStartWeights(st, c->view, c->impl);   // the start values' Lagrange weights from the deltaT ratios
             c->steps++;
@@ -1988,6 +2099,9 @@ static void stepAdvance(qgd_case_s* c, int part) {
         return;
     }
     if (part != 2) {
+        // varScModel7: the Schmidt numbers thermo.correct() of this step forms, from the pressures the step starts with (every owned cell, ahead
+        // of the boundary layer's advance: the cell update writes p in place)
+        if (c->varSc) launchVarSc7(L, m, c->view, c->gas, c->vsc, false);
         if (adjust) launchDeltaT(L, c->view, c->opt.maxCo, c->opt.maxDeltaT, c->opt.cTau);
         c->steps++;
         if (!adjust) c->time += c->opt.deltaT;
@@ -3386,6 +3500,14 @@ int qgd_case_get_field(qgd_case_t c, const char* name, double* out, int64_t outD
         {"rho", XF_RHO}, {"U", XF_U}, {"p", XF_P}, {"e", XF_E}, {"T", XF_T}, {"rhoU", XF_RHOU}, {"rhoE", XF_RHOE}, {"c", XF_C},
         {"psi", XF_PSI}, {"mu", XF_MU}, {"alphau", XF_ALPHAU}, {"tauQGD", XF_TAUQGD}, {"muQGD", XF_MUQGD},
         {"alphauQGD", XF_ALPHAUQGD}, {"hQGD", XF_HQGD}, {"H", XF_H}, {"gamma", XF_GAMMA}};
+    if (s == "ScQGD") {   // the uniform value repeated, the array of qgd_case_set_qgd_coeffs, or the sensor's last result
+        const int64_t n = bnd ? m.nBF : m.nC;
+        if (n > outDoubles) return fail(QGD_ERR_INVALID, "output too small");
+        const double* src = bnd ? c->view.scb : c->view.sc;
+        if (src && n) HIP_CHECK(hipMemcpy(out, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        else std::fill(out, out + n, g.ScQGD);
+        return QGD_OK;
+    }
     auto cf = cellFields.find(s);
     if (cf == cellFields.end()) return fail(QGD_ERR_UNKNOWN_NAME, "qgd_case_get_field: unknown field " + s);
     const int64_t n = bnd ? m.nBF : m.nC;

@@ -133,6 +133,17 @@ struct CaseView {
     // a patch whose PatchBCDev::valList names the field; nullptr = no patch of the case has a list for that field
     const double* bValU; const double* bValT; const double* bValP;
 };
+// varScModel7 [varScModel7_8C L166-300]: ScQGD of a cell from the pressure jumps across its faces.  sc is the array CaseView::sc reads;
+// rf per face (by label): r_f = nonOrthDeltaCoeff_f / deltaCoeff_f, on a patch face the patch's snGrad coefficient over its deltaCoeff,
+// -1 on faces of empty patches (skipped: no sum, no count).  L0 assumptions, as elsewhere: fvc::snGrad is the `reduced` stencil's
+// (1 / max(n.d, 0.05 |d|)), deltaCoeffs = 1/|d| with d = C_N - C_O (internal) and Cf - C_O (patch)
+struct VarScView {
+    double* sc;                 // nC
+    const double* rf;           // nF
+    const uint8_t* constCell;   // nC: 1 on the cells of constScCellSet (nullptr: no set)
+    double* part;               // 2 * QGD_FACE_REDUCE_PARTIALS + 2: partial and final {max, min} of qgd_case_sc_range
+    double ScQGD, cSc1, minSc, maxSc;
+};
 #if defined(__HIPCC__)
 // the prescribed value of a fixedValue patch face: the face's own entry where the patch carries a list, the patch's one value otherwise
 __device__ __forceinline__ void fixedValueU(const CaseView& c, const PatchBCDev& bc, const int b, double& ux, double& uy, double& uz) {
@@ -195,6 +206,10 @@ void launchHaloPack(const Launcher& L, const CaseView& c, const GasModel& g, con
                     int32_t nFaces, double* buf, bool pack);
 void launchMidHalo(hipStream_t s, const CaseView& c, const int32_t* bfaces, int32_t n, double* buf, bool pack);
 void launchFaceGeoPos(hipStream_t s, const MeshView& m, double4* out);   // fills MeshView::geoPos
+// ---- varScModel7 (qgd_varsc.hip) ------------------------------------------------------------------------------------------
+// ScQGD of every cell but the ghosts from the records' p and the patch pressures bPmid; init: muQGD of the records follows (createFields.H)
+void launchVarSc7(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, const VarScView& v, bool init);
+void launchVarScRange(hipStream_t s, const VarScView& v, int32_t begin, int32_t end);   // {max, min} over cells [begin, end) -> v.part[2 * QGD_FACE_REDUCE_PARTIALS ...]
 
 // ---- accessor: one named cell / patch field out of the records (K == nullptr on patches) ----------------------------
 enum ExtractField : int { XF_RHO = 0, XF_U, XF_P, XF_E, XF_T, XF_RHOU, XF_RHOE, XF_C, XF_PSI, XF_MU, XF_ALPHAU, XF_TAUQGD, XF_MUQGD,

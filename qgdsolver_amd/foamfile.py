@@ -686,8 +686,9 @@ def read_case_setup(case_dir, time="0"):
 
     Returns (mesh, options dict for ``default_options``, {'U','T','p'} internal arrays, per-patch BC triples).
     Entries read: constant/polyMesh; constant/thermophysicalProperties (mixture.specie.molWeight,
-    thermodynamics.Cv|Cp, transport.mu/Pr; QGD{implicitDiffusion, QGDCoeffs, <model>Dict{ScQGD,PrQGD}} as in
-    QGDThermo.C L48-82, QGDCoeffs.C L57-160, constScPrModel1.C L48-90); system/fvSchemes fvsc.default (fvsc.C L47-58);
+    thermodynamics.Cv|Cp, transport.mu/Pr; QGD{implicitDiffusion, QGDCoeffs constScPrModel1 | varScModel7, <model>Dict{ScQGD,PrQGD}} as in
+    QGDThermo.C L48-82, QGDCoeffs.C L57-160, constScPrModel1.C L48-90; varScModel7 also cSc1, minSc, maxSc, constScCellSet
+    (constant/polyMesh/sets/<name>), returned as options["varSc"] [varScModel7.C L77-158]); system/fvSchemes fvsc.default (fvsc.C L47-58);
     system/controlDict deltaT/adjustTimeStep/maxCo/maxDeltaT (setDeltaT-QGDQHD.H); system/fvSolution solvers.{U,e}
     tolerance/maxIter (implicitDiffusion only); <time>/{U,T,p}.
     """
@@ -713,11 +714,35 @@ def read_case_setup(case_dir, time="0"):
     if "consistentEnergy" in qgd:
         opt["consistentEnergy"] = 1 if str(qgd["consistentEnergy"]) in ("true", "on", "yes", "1") else 0
     model = str(qgd["QGDCoeffs"])
-    if model != "constScPrModel1":
-        raise FoamFileError(f"QGDCoeffs '{model}' is not supported (only constScPrModel1)")
+    if model not in ("constScPrModel1", "varScModel7"):
+        raise FoamFileError(f"QGDCoeffs '{model}' is not supported (served: constScPrModel1, varScModel7)")
     md = qgd.get(model + "Dict", qgd)  # QGDCoeffs::New: <type>Dict when present, else the QGD dict [QGDCoeffs.C L81-116]
-    for k in ("ScQGD", "PrQGD"):       # both default to 1 [constScPrModel1.C L58-89]
-        opt[k] = float(md[k]) if k in md else 1.0
+    if model == "varScModel7":
+        # ScQGD and PrQGD are dict.lookup()s [varScModel7.C L77-78]; cSc1 defaults to 1, minSc / maxSc to -1 (off); smoothCoeff, rC,
+        # badQualitySc and maxAspectRatio are read by the reference and never used [L262-265]: accepted, ignored
+        for k in ("ScQGD", "PrQGD"):
+            if k not in md:
+                raise FoamFileError(f"QGD.{model}: entry '{k}' is missing [varScModel7.C L77-78]")
+            opt[k] = float(md[k])
+        if getattr(mesh, "cyclic_pairs", None):
+            raise FoamFileError(f"{case_dir}: a case with cyclic patches runs with uniform alphaQGD / ScQGD: QGDCoeffs varScModel7 is not served there")
+        var_sc = {"model": model, "ScQGD": opt["ScQGD"], "cSc1": float(md.get("cSc1", 1.0)), "minSc": float(md.get("minSc", -1.0)),
+                  "maxSc": float(md.get("maxSc", -1.0)), "const_cells": None}
+        if "constScCellSet" in md:     # cells that keep the dictionary's ScQGD [L143-158, L246-254]
+            set_name = str(md["constScCellSet"]).strip('"')
+            spath = os.path.join(case_dir, "constant", "polyMesh", "sets", set_name)
+            if not _exists(spath):
+                raise FoamFileError(f"QGD.{model}: constScCellSet '{set_name}': {spath} is missing")
+            _, nset, labels = _read_list_file(spath)
+            if labels.size != nset:
+                raise FoamFileError(f"sets/{set_name}: size mismatch")
+            if labels.size and (labels.min() < 0 or labels.max() >= mesh.nCells):
+                raise FoamFileError(f"sets/{set_name}: cell label out of range [0, {mesh.nCells})")
+            var_sc["const_cells"] = labels.astype(np.int32)
+        opt["varSc"] = var_sc          # QGDFoamCase.set_var_sc(**opt["varSc"]); default_options passes it by
+    else:
+        for k in ("ScQGD", "PrQGD"):   # both default to 1 [constScPrModel1.C L58-89]
+            opt[k] = float(md[k]) if k in md else 1.0
     tdir = os.path.join(case_dir, str(time))
     # alphaQGD and ScQGD are READ_IF_PRESENT fields of the time directory [QGDCoeffs.C L119-160, constScPrModel1.C
     # L66-79]: a uniform one becomes the scalar of the options, a non-uniform one travels as (cell values, patch values)
@@ -725,6 +750,8 @@ def read_case_setup(case_dir, time="0"):
     coeff_fields = {}
     for fname in ("alphaQGD", "ScQGD"):
         fpath = os.path.join(tdir, fname)
+        if fname == "ScQGD" and model == "varScModel7":
+            continue                   # the model's constructor overwrites the field it reads [varScModel7.C L77-84]: the file is ignored
         if _exists(fpath):
             vals, bvals = read_field(fpath, mesh)
             patch_vals = _patch_values(mesh, vals[:, 0], bvals, fpath)
@@ -1162,6 +1189,8 @@ def load_case(case_dir, time="0", device_id=0):
         case.set_bc(i, U=bc["U"], T=bc["T"], p=bc["p"])
     if "alphaQGD" in fields or "ScQGD" in fields:
         case.set_qgd_coeffs(alphaQGD=fields.get("alphaQGD"), ScQGD=fields.get("ScQGD"))
+    if opt.get("varSc"):
+        case.set_var_sc(**opt["varSc"])
     case.set_fields(fields["U"], fields["T"], fields["p"])
     return dev, case
 

@@ -34,6 +34,8 @@ def default_options(**kw):
             for term, word in (v or {}).items():
                 o.termStencil[TERM_ORDER.index(term)] = 1 + (STENCIL_IDS[word] if isinstance(word, str) else int(word))
             continue
+        if k == "varSc":     # the varScModel7 entries of foamfile.read_case_setup: they go to QGDFoamCase.set_var_sc
+            continue
         setattr(o, k, v)
     return o
 
@@ -159,6 +161,29 @@ class QGDFoamCase:
         a, ab = ptrs(alphaQGD)
         s, sb = ptrs(ScQGD)
         L.check(L.lib.qgd_case_set_qgd_coeffs(self._h, a, ab, s, sb), "qgd_case_set_qgd_coeffs")
+
+    def set_var_sc(self, model="varScModel7", ScQGD=None, cSc1=1.0, minSc=-1.0, maxSc=-1.0, const_cells=None):
+        """the varScModel7 closure (varScModel7.C L166-300; qgd_case_set_var_sc): ScQGD per cell from the pressure jumps across the
+        cell's faces, cSc1 |sum r_f dp| / mean p_f, clipped to [minSc, maxSc] where those are >= 0, ``ScQGD`` itself on the cells of
+        ``const_cells`` (labels of this device's mesh) and on the patches.  model None: back to the uniform ScQGD.  Before set_fields."""
+        if model is None:
+            L.check(L.lib.qgd_case_set_var_sc(self._h, None, None), "qgd_case_set_var_sc")
+            return
+        if ScQGD is None:
+            raise ValueError("set_var_sc: ScQGD (the dictionary's mandatory entry) is missing")
+        cells = np.ascontiguousarray(const_cells if const_cells is not None else [], dtype=np.int32).reshape(-1)
+        o = L.VarScOptions()
+        # another word travels as model 0, which the library refuses by name
+        o.model = 7 if model in ("varScModel7", 7) else (int(model) if isinstance(model, (int, np.integer)) else 0)
+        o.nConstCells = int(cells.size)
+        o.ScQGD, o.cSc1, o.minSc, o.maxSc = float(ScQGD), float(cSc1), float(minSc), float(maxSc)
+        L.check(L.lib.qgd_case_set_var_sc(self._h, C.byref(o), cells.ctypes.data_as(L.c_int32_p) if cells.size else None), "qgd_case_set_var_sc")
+
+    def sc_range(self):
+        """(max, min) of ScQGD over the owned cells: the reference's ``max/min ScQGD`` line (qgd_case_sc_range)"""
+        a = (C.c_double * 2)()
+        L.check(L.lib.qgd_case_sc_range(self._h, a), "qgd_case_sc_range")
+        return a[0], a[1]
 
     def updateFluxes(self):
         L.check(L.lib.qgd_case_update_fluxes(self._h), "qgd_case_update_fluxes")
