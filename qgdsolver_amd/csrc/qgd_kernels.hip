@@ -926,9 +926,9 @@ void pointInterpRecKernel(const MeshView m, const RecA* __restrict__ A, RecA* __
 
 // QGDRhoEqn / QGDUEqn / QGDEEqn + thermo + QGD coefficients of one cell from the sum of its net face fluxes (shared by the cell kernel and
 // the fused face + cell kernel)
-__device__ __forceinline__ void advanceCell(const CaseView& c, const GasModel& gm, const int ci, const RecA& A, const double rEold,
-                                            const double Vc, const double hq, const double (&sum)[5], RecA& An, RecB& Bn, double& rEnew) {
-    const double dtV = c.dt[0] / Vc;
+// (dtV = deltaT / V of the cell: the fused kernel forms it while it waits for its records, ahead of the update's chain of divisions)
+__device__ __forceinline__ void advanceCellDtV(const CaseView& c, const GasModel& gm, const int ci, const RecA& A, const double rEold,
+                                               const double dtV, const double hq, const double (&sum)[5], RecA& An, RecB& Bn, double& rEnew) {
     // QGDRhoEqn / QGDUEqn / QGDEEqn: explicit Euler on rho, rhoU, rhoE
     const double rho = A.rho - dtV * sum[0];
     // rhoU is not stored: it equals rho*U up to rounding by the re-solve identity below, so its increment is taken
@@ -955,6 +955,10 @@ __device__ __forceinline__ void advanceCell(const CaseView& c, const GasModel& g
     Bn.aOc = aq / cs;
     An.p = rho / psi;                  // [QGDFoam_8C L152-154]
     Bn.H = (rEnew + An.p) / rho;       // H = (rhoE + p)/rho [QGDFoam/updateFields.H L71]
+}
+__device__ __forceinline__ void advanceCell(const CaseView& c, const GasModel& gm, const int ci, const RecA& A, const double rEold,
+                                            const double Vc, const double hq, const double (&sum)[5], RecA& An, RecB& Bn, double& rEnew) {
+    advanceCellDtV(c, gm, ci, A, rEold, c.dt[0] / Vc, hq, sum, An, Bn, rEnew);
 }
 
 // ---------------------------------------------------------------------------
@@ -1045,15 +1049,27 @@ void cellUpdateKernel(const MeshView m, const CaseView c, const GasModel gm, con
 // masked block, where it would put a wait for the load between the loads of a round (no instruction is emitted)
 template <class T> __device__ __forceinline__ void fuPin(T& v) { asm volatile("" : "+v"(v)); }
 
+// 3 l + o as a shift and a three-operand add.  Written as a product the compiler takes the 64-bit multiply-add, whose addend is a register
+// pair with an unused upper half: whatever register that half lands on is waited for, and between the rounds of the fused kernel it lands
+// on a load still in flight.
+__device__ __forceinline__ int fuTimes3Plus(const int l, const int o) {
+    int l2 = l << 1;
+    fuPin(l2);
+    return l2 + l + o;
+}
+
 // ---------------------------------------------------------------------------
 // QGD_FUSED: the explicit step of a BLOCK of cells in one workgroup (qgd_setup.hpp FusedBlocks) -- vertex values, internal faces, cell update.
 // The three kernels of the explicit step (P, F, C above) run at what the memory system delivers (profiles/r05_ab_face_four_waves.txt), and
 // most of the step's bytes are what they hand each other through HBM: 48 B per vertex written by P and read back by F, 40 B per face written
 // by F and read back twice by C.  Here a workgroup (256 threads) takes <= 128 cells that are compact in space -- an 8x4x4 brick on a box --
 // and
-//   (0) reads its lists (no address depends on a loaded value: they are padded to fixed strides, so round 0 needs no count) and, one round
-//       trip later -- every lane loading only what it keeps: the counts have arrived with the lists (see "which lanes load what" in the
-//       body) -- stages in LDS
+//   (0) reads its header (counts and template id) through the scalar path and its lists through the vector path (no address of a list
+//       depends on a loaded value: they are padded to fixed strides, so they need no count); behind the lists, in the same round, it asks
+//       for what needs the header but no label -- the template's face positions and face entries, the vertices' cell positions and weights
+//       (a third of the bytes a block loads): the lists are latency and leave the return path idle.  A counted wait ends the round for the
+//       lists alone; one round trip later -- every lane loading only what it keeps (see "which lanes load what" in the body) -- it stages
+//       in LDS
 //       RecA of its own cells, of the cells across its surface and of the edge / corner cells around its vertices (360 on a box), RecB and
 //       the centres of the first two groups (288), the coordinates of its vertices (225);
 //   (1) thread v forms vertex v: volPointInterpolation's weighted sum over pointCells, in their order (pointInterpRecKernel's arithmetic,
@@ -1101,35 +1117,52 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     const int32_t* __restrict__ tCells = m.fuCells + (size_t)blk * capC;
     const int32_t* __restrict__ tVerts = m.fuVerts + (size_t)blk * capV;
     const int32_t* __restrict__ tFaceLabel = m.fuFaceLabel + (size_t)blk * capF;
-    // (0) everything whose address does not depend on a loaded value: the counts and the template id, the piece labels out of the lists (padded
-    // to their strides with their last entry, so no count is needed to read them), the labels of this thread's two faces, its vertex and its
-    // cell.  Nothing in this round waits for the counts: they arrive with it.
-    // WHICH LANES LOAD WHAT, from round 1 on: a lane loads only what it keeps.  The own-cell data (label and entry count already in round 0,
-    // face entries, rhoE, V, hQGD) under tid < 128 -- waves 2 and 3 branch round it; a record piece under the condition of its LDS store; a
-    // vertex's weights, cell positions and patch-point record under tid < nUv; a face's positions and streams under lf < nFc.  A wavefront
-    // whose whole slot range is empty branches round the instruction (wv0 + k NT is the wavefront's first slot: a scalar compare).  A value
-    // loaded under a mask is used under that mask only; it passes an empty asm first where the compiler would otherwise move integer
-    // arithmetic on it into the masked block, behind a wait for the load (fuPin).
+    // (0) THE HEADER, through the scalar path: blk is wave-uniform, so the block's counts and its template id (fuHdr[blk], fuHdr2[blk]) are
+    // two uniform reads out of the constant address space, asked for before anything else.  They land in SGPRs while the list loads go out:
+    // nothing in front of the last list load waits for them.
+    // (of fuHdr2 only the two words that are used: a register of a scalar load still in flight that nothing reads is handed to the next
+    // scalar value, behind a wait for the load -- in the middle of the list loads)
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x2 __attribute__((ext_vector_type(2)));
+    typedef const i32x4 __attribute__((address_space(4)))* HdrPtr;
+    typedef const i32x2 __attribute__((address_space(4)))* Hdr2Ptr;
+    __builtin_amdgcn_sched_barrier(0);
+    const i32x4 hdr = *(HdrPtr)(uintptr_t)(m.fuHdr + blk);
+    const i32x2 hdr2 = *(Hdr2Ptr)(uintptr_t)(m.fuHdr2 + blk);
+    __builtin_amdgcn_sched_barrier(0);
+    // (0a) THE LISTS: everything whose address depends on no loaded value -- the piece labels out of the lists (padded to their strides with
+    // their last entry, so no count is needed to read them), the labels of this thread's two faces, its vertex and its cell.
+    // WHICH LANES LOAD WHAT, behind the lists: a lane loads only what it keeps.  The own-cell data (label and entry count with the lists,
+    // face entries, rhoE, V, hQGD) under tid < 128; a record piece under the condition of its LDS store; a vertex's weights, cell positions
+    // and patch-point record under tid < nUv; a face's positions and streams under lf < nFc.  In round 1 a wavefront whose whole slot range
+    // is empty branches round the instruction (wv0 + k NT is the wavefront's first slot: a scalar compare).  A value loaded under a mask is
+    // used under that mask only; it passes an empty asm first where the compiler would otherwise move integer arithmetic on it into a
+    // masked block, behind a wait for the load (fuPin).
     const int wv0 = __builtin_amdgcn_readfirstlane(tid & ~63);
     int fl[KF];
 #pragma unroll
     for (int j = 0; j < KF; ++j) fl[j] = tFaceLabel[min(tid + j * NT, capF - 1)];
+    // (the labels as loaded: the piece indices are formed from them behind the wait that ends the round, idC / idB / idV below)
     int idC[KC], idB[KB2], idV[KV];
 #pragma unroll
     for (int k = 0; k < KC; ++k) {
         const int q = tid + k * NT, r = (q * 43691) >> 17;
-        idC[k] = tCells[min(r, capC - 1)] * 3 + (q - 3 * r);
+        idC[k] = tCells[min(r, capC - 1)];
     }
 #pragma unroll
     for (int k = 0; k < KB2; ++k) {
         const int q = tid + k * NT, r = q >> 1;
-        idB[k] = tCells[min(r, capC - 1)] * 2 + (q & 1);
+        idB[k] = tCells[min(r, capC - 1)];
     }
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
         const int q = tid + k * NT, r = (q * 43691) >> 17;
-        idV[k] = tVerts[min(r, capV - 1)] * 3 + (q - 3 * r);
+        idV[k] = tVerts[min(r, capV - 1)];
     }
+    // this thread's vertex (thread v forms vertex v of the block's list; threads beyond the block's vertices repeat its last one)
+    const int vt = min(tid, capV - 1);
+    const int myVert = tVerts[vt];
+    const int nPc = (int)m.fuVCount[(size_t)blk * capV + vt];
     // this thread's own cell (threads 0..127; those beyond the block's cells repeat its last label: the list is padded)
     const bool cellLane = wv0 < 128;
     int ci, nEraw;
@@ -1137,53 +1170,74 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         ci = tCells[min(tid, capC - 1)];
         nEraw = (int)m.fuNEntry[(size_t)blk * 128 + tid];
     }
-    // (the counts: block-uniform, but loaded through the vector path and broadcast -- asked for behind the branch above, or the broadcast,
-    // and with it a wait for them, lands in front of that branch and of the loads behind it)
-    const int4 hdr = m.fuHdr[blk];
-    const int4 hdr2 = m.fuHdr2[blk];
+    __builtin_amdgcn_sched_barrier(0);
+    // (0b) THE FRONT-LOADED GROUP, in the same round behind the lists: what needs the header but no label -- the block's local topology out
+    // of its TEMPLATE (hdr2.y; qgd_setup.hpp FusedBlocks: the interior bricks of a structured region share a few hundred templates, which
+    // stay in L2): the positions of this thread's two faces' cells and vertices in the staged lists, its cell's six face entries, its
+    // vertex's eight cell positions -- and the vertex's eight weights.  The lists are latency: they leave the return path idle, and these
+    // bytes fill it instead of competing with the records one round trip later.  The header is waited for HERE (lgkmcnt), behind the lists.
+    // The group stays in flight across the wait that ends the round, so the number of memory instructions between the last list load and
+    // that wait must be the same on every path: no branch in here.  A lane outside its mask (lf < nFc, tid < 128, tid < nUv) keeps its
+    // instruction and asks a buffer descriptor of exactly its table for an offset beyond it: the hardware's range check returns zero and
+    // fetches nothing.  kFrontLoads instructions per wavefront, whatever the counts.
     const int nTot = hdr2.x;
-    // this thread's vertex (thread v forms vertex v of the block's list; threads beyond the block's vertices repeat its last one)
-    const int vt = min(tid, capV - 1);
-    const int myVert = tVerts[vt];
-    const int nPc = (int)m.fuVCount[(size_t)blk * capV + vt];
-    // The round ends HERE, for everything at once (s_waitcnt vmcnt(0): the loads above went out back to back and return together).  The
-    // memory counter counts in order, and behind a masked block the compiler no longer knows how many loads are outstanding: left to
-    // itself it waits for a label of this round by waiting for masked loads of the next one as well -- a third round trip.
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __builtin_amdgcn_sched_barrier(0);
-    // (1) one round trip later: the records, piece by piece; the faces' streams; the cell's own scalars; the vertex's weights; a patch
-    // point's record -- and the block's local topology out of its TEMPLATE (hdr2.y; qgd_setup.hpp FusedBlocks: the interior bricks of a structured region share a few
-    // hundred templates, which stay in L2): the positions of this thread's two faces' cells and vertices in the staged lists, its cell's face
-    // entries, its vertex's cell positions.  None of it is needed before the records are staged, so the template costs no round trip.
     const int nOwn = hdr.x, nUc = hdr.y, nUv = hdr.z, nFc = hdr.w;
-    const bool vertWave = wv0 < nUv, vertLane = tid < nUv;
+    const bool vertLane = tid < nUv;
     const size_t tpl = (size_t)hdr2.y;
+    constexpr int kFrontLoads = KF + KE + 2 * KP;
+    constexpr int kRsrcWord3 = 0x00020000;          // raw buffer, 32-bit data format
+    constexpr int kBeyond = 0x40000000;             // an offset no table reaches (a descriptor spans one block's or one template's part)
     struct Pos3 { uint32_t c, va, vb; };
-    const Pos3* __restrict__ tFacePos = reinterpret_cast<const Pos3*>(m.fuFacePos) + tpl * capF;
-    const int32_t* __restrict__ ent = m.fuEntry + tpl * m.fuCapE * 128 + (tid & 127);
-    const uint16_t* __restrict__ vPos = m.fuVPos + tpl * capPE * capV + vt;
-    const double* __restrict__ vW = m.fuVW + (size_t)blk * capPE * capV + vt;
+    typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+    // (where an own cell's entries beyond the sixth and a vertex's cells beyond the eighth are read from, far below: kept as three lane
+    // addresses -- with a scalar template id the compiler would otherwise hold three scalar bases to the end, and spill other scalars for them)
+    const int32_t* ent = m.fuEntry + tpl * m.fuCapE * 128 + (tid & 127);
+    const uint16_t* vPos = m.fuVPos + tpl * capPE * capV + vt;
+    const double* vW = m.fuVW + (size_t)blk * capPE * capV + vt;
+    fuPin(ent); fuPin(vPos); fuPin(vW);
     Pos3 fp[KF];
-#pragma unroll
-    for (int j = 0; j < KF; ++j) {
-        if (wv0 + j * NT < nFc) { if (tid + j * NT < nFc) fp[j] = tFacePos[tid + j * NT]; }
-    }
     int e6[KE];
-    if (cellLane) {
-#pragma unroll
-        for (int i = 0; i < KE; ++i) e6[i] = ent[(size_t)min(i, m.fuCapE - 1) * 128];
-    }
     int pcPos[KP];
     double pcW[KP];
-    if (vertWave) {
-        if (vertLane) {
+    {
+        const __amdgpu_buffer_rsrc_t rFacePos = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(m.fuFacePos + tpl * capF * 3), 0, capF * 12, kRsrcWord3);
+        const __amdgpu_buffer_rsrc_t rEntry = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(m.fuEntry + tpl * m.fuCapE * 128), 0, m.fuCapE * 128 * 4, kRsrcWord3);
+        const __amdgpu_buffer_rsrc_t rVPos = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(m.fuVPos + tpl * capPE * capV), 0, capPE * capV * 2, kRsrcWord3);
+        const __amdgpu_buffer_rsrc_t rVW = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(m.fuVW + (size_t)blk * capPE * capV), 0, capPE * capV * 8, kRsrcWord3);
 #pragma unroll
-            for (int i = 0; i < KP; ++i) pcPos[i] = (int)vPos[(size_t)min(i, capPE - 1) * capV];
-#pragma unroll
-            for (int i = 0; i < KP; ++i) pcW[i] = vW[(size_t)min(i, capPE - 1) * capV];
+        for (int j = 0; j < KF; ++j) {
+            const int lf = tid + j * NT;
+            const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(rFacePos, lf < nFc ? lf * 12 : kBeyond, 0, 0);
+            fp[j].c = w[0]; fp[j].va = w[1]; fp[j].vb = w[2];
         }
+#pragma unroll
+        for (int i = 0; i < KE; ++i)
+            e6[i] = (int)__builtin_amdgcn_raw_buffer_load_b32(rEntry, tid < 128 ? (min(i, m.fuCapE - 1) * 128 + tid) * 4 : kBeyond, 0, 0);
+#pragma unroll
+        for (int i = 0; i < KP; ++i)
+            pcPos[i] = (int)__builtin_amdgcn_raw_buffer_load_b16(rVPos, vertLane ? (min(i, capPE - 1) * capV + vt) * 2 : kBeyond, 0, 0);
+#pragma unroll
+        for (int i = 0; i < KP; ++i)
+            pcW[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rVW, vertLane ? (min(i, capPE - 1) * capV + vt) * 8 : kBeyond, 0, 0));
     }
+    // The round ends HERE for the lists, at once (the loads above went out back to back and return in issue order): the memory counter may
+    // stay at the front-loaded group, which nothing needs before the records are staged.  Left to itself the compiler waits label by label.
+    // (The count is safe by construction: the static_assert and a group without a branch.  WHERE the other waits stand is not: the header
+    // wait behind the lists, no wait inside round 1 -- the two-word read of fuHdr2 and fuTimes3Plus answer register-allocation accidents of
+    // one compiler version, and only the disassembly shows them.  Redo the ISA check of DESIGN.md section 5 after every ROCm change; a wait
+    // that comes back costs speed, not correctness.)
+    static_assert(kFrontLoads == 24, "the wait below is written for vmcnt(24)");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0x4F78);   // vmcnt(24): low four bits 8, high two bits 1; expcnt and lgkmcnt left alone
+    __builtin_amdgcn_sched_barrier(0);
+    // (1) one round trip later, what needs a label: the records, piece by piece; the faces' streams; the cell's own scalars; a patch
+    // point's record.  No wait for a front-loaded value stands between the first of these loads and the staging stores.
+#pragma unroll
+    for (int k = 0; k < KC; ++k) { const int q = tid + k * NT, r = (q * 43691) >> 17; idC[k] = fuTimes3Plus(idC[k], q - 3 * r); }
+#pragma unroll
+    for (int k = 0; k < KB2; ++k) idB[k] = idB[k] * 2 + ((tid + k * NT) & 1);
+#pragma unroll
+    for (int k = 0; k < KV; ++k) { const int q = tid + k * NT, r = (q * 43691) >> 17; idV[k] = fuTimes3Plus(idV[k], q - 3 * r); }
     const v2d* __restrict__ gA = reinterpret_cast<const v2d*>(c.A);
     const v2d* __restrict__ gB = reinterpret_cast<const v2d*>(c.B);
     const v2d* __restrict__ gP = reinterpret_cast<const v2d*>(c.P);
@@ -1214,8 +1268,11 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         }
     }
     fuPin(ci);
-    double rEold, Vc, hq;
-    if (cellLane) { rEold = c.rE[ci]; Vc = m.V[ci]; hq = m.hQGD[ci]; }
+    double rEold, Vc, hq, dt0;
+    if (cellLane) {
+        rEold = c.rE[ci]; Vc = m.V[ci]; hq = m.hQGD[ci];
+        if constexpr (!IMPL && !ADJ) dt0 = c.dt[0];
+    }
     v2d dPt[3];
     dPt[0] = dPt[1] = dPt[2] = v2d{0.0, 0.0};
     if (vertLane && nPc == 0) {   // a patch point: the patch-point kernel has put its value into the vertex records
@@ -1248,6 +1305,13 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     for (int k = 0; k < KB2; ++k) { const int q = tid + k * NT; if (q < 2 * nUc) sB[q] = dB[k]; }
 #pragma unroll
     for (int k = 0; k < KV; ++k) { const int q = tid + k * NT; if (q < 3 * nUv) sX[q] = dX[k]; }
+    // deltaT / V of the own cell, the head of the update's dependent chain of divisions: both operands are here, so it is formed in front
+    // of the barrier and not behind the last one (advanceCell's operands and operation: the same bits)
+    double dtV = 0.0;
+    if constexpr (!IMPL && !ADJ) {
+        if (cellLane) dtV = dt0 / Vc;
+        fuPin(dtV);
+    }
     __syncthreads();
     // (every load of the two rounds has arrived: from here on the values loaded under a mask may be computed with)
     fuPin(nEraw);
@@ -1559,7 +1623,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             RecA An;
             RecB Bn;
             double rEnew;
-            advanceCell(c, gm, ci, A, rEold, Vc, hq, sum, An, Bn, rEnew);
+            advanceCellDtV(c, gm, ci, A, rEold, dtV, hq, sum, An, Bn, rEnew);
             c.A2[ci] = An;
             c.B2[ci] = Bn;
             c.rE[ci] = rEnew;
