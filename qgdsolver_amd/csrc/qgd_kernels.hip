@@ -1058,6 +1058,21 @@ __device__ __forceinline__ int fuTimes3Plus(const int l, const int o) {
     return l2 + l + o;
 }
 
+// (max x, min y) over each row of 16 lanes, left in every lane of the row: four exchanges inside the row through the vector unit's lane
+// crossbar -- neighbour, pair, the other quad (mirror of 8), the other half (mirror of 16) -- instead of shuffles through LDS.  Every lane
+// of the wavefront must be active.
+template <int CTRL> __device__ __forceinline__ double fuRowLane(const double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ v2d fuRowMaxMin(v2d r) {
+    r.x = fmax(r.x, fuRowLane<0xB1>(r.x)); r.y = fmin(r.y, fuRowLane<0xB1>(r.y));       // quad_perm [1,0,3,2]
+    r.x = fmax(r.x, fuRowLane<0x4E>(r.x)); r.y = fmin(r.y, fuRowLane<0x4E>(r.y));       // quad_perm [2,3,0,1]
+    r.x = fmax(r.x, fuRowLane<0x141>(r.x)); r.y = fmin(r.y, fuRowLane<0x141>(r.y));     // row_half_mirror
+    r.x = fmax(r.x, fuRowLane<0x140>(r.x)); r.y = fmin(r.y, fuRowLane<0x140>(r.y));     // row_mirror
+    return r;
+}
+
 // ---------------------------------------------------------------------------
 // QGD_FUSED: the explicit step of a BLOCK of cells in one workgroup (qgd_setup.hpp FusedBlocks) -- vertex values, internal faces, cell update.
 // The three kernels of the explicit step (P, F, C above) run at what the memory system delivers (profiles/r05_ab_face_four_waves.txt), and
@@ -1080,6 +1095,9 @@ __device__ __forceinline__ int fuTimes3Plus(const int l, const int o) {
 //   (3) once every face is done with the vertex records and coordinates, the fluxes take their place in LDS, and threads 0..127 advance one
 //       own cell each: the ordered sum of its faces' fluxes in ascending face label = fvc::surfaceIntegrate's order (patch faces from c.flux,
 //       where the patch-face kernel put them), advanceCell, 88 B of new records.
+//   (4) the positivity monitor: the block's slot (max -rho, min e since the last query) was asked for in round 1 and waits in LDS; waves 0
+//       and 1 fold their cells' values row by row in the vector unit, thread 0 folds the rows into the slot value and stores it -- the
+//       kernel's last memory instruction is a store that nothing waits for (THE BLOCK'S END in the body).
 // The block reads the OLD records of its neighbours while other blocks write new ones: the step writes A2 / B2, the host swaps them with A / B.
 // Same arithmetic per vertex, face and cell as P + F + C, same orders: bit-identical states (tests/test_fused_step_gpu.py).  Fixed deltaT,
 // no debug fields (everything else keeps the three kernels); UPW = `Gauss upwind` fluxes; shards run it too (the boundary-layer blocks first,
@@ -1102,8 +1120,11 @@ template <bool SGEO, bool UPW = false, bool IMPL = false, bool ADJ = false>
 // (IMPL with `Gauss upwind` fluxes needs a few registers more than three waves per SIMD leave: that instantiation is compiled for two -- no scratch)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((IMPL && UPW) ? 2 : 3, (IMPL && UPW) ? 2 : 3)))
 void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, const int firstBlock, const ImplView iv,
-                         const PatchBCDev* __restrict__ bcs) {
+                         const PatchBCDev* __restrict__ bcs, const int xcdFull, const int xcdShift) {
     extern __shared__ v2d tileLds[];
+    // the positivity monitor's two doubles (max -rho, min e since the last query: the block's slot of blkCell, read in round 1 and parked
+    // here) and the partial extrema of the eight 16-lane rows of waves 0 and 1, which own the cells (THE BLOCK'S END, below)
+    __shared__ v2d sMon[9];
     __builtin_amdgcn_s_setprio(3);
     constexpr int NT = 256, KC = 5, KCC = 4, KB2 = 3, KV = 3, KF = 2, KE = 6, KP = 8, KG = 12;
     static_assert(9 * kFusedCapCDev <= KG * NT, "caps");
@@ -1111,7 +1132,8 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // vertices; faces per thread; face entries of a cell / cells of a vertex held in registers
     static_assert(3 * kFusedCapTotDev <= KC * NT && 3 * kFusedCapCDev <= KCC * NT && 2 * kFusedCapCDev <= KB2 * NT && 3 * kFusedCapVDev <= KV * NT &&
                   kFusedCapFDev <= KF * NT && kFusedCapVDev <= NT, "caps");
-    const int blk = firstBlock + xcdTile((int)gridDim.x, m.fuXcdRun);
+    // (the launcher has divided for the XCD order: a run that is a power of two costs shifts here, not two divisions in front of the first load)
+    const int blk = firstBlock + xcdTileHost((int)gridDim.x, m.fuXcdRun, xcdFull, xcdShift);
     const int tid = (int)threadIdx.x;
     const int capC = m.fuCapC, capV = m.fuCapV, capF = m.fuCapF, capPE = m.fuCapPE;
     const int32_t* __restrict__ tCells = m.fuCells + (size_t)blk * capC;
@@ -1243,6 +1265,12 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     const v2d* __restrict__ gP = reinterpret_cast<const v2d*>(c.P);
     v2d dA[KC], dB[KB2];
     double dC[KCC], dX[KV];
+    // the block's monitor slot, in front of the records: thread 0 folds the block's extrema into it at the very end, and a load there is
+    // a memory round trip during which the block holds its LDS for nothing.  (Loads return in issue order: it is there with dA[0].)
+    v2d mon = {-1e300, 1e300};
+    if constexpr (!IMPL && !ADJ) {
+        if (wv0 == 0) { if (tid == 0) mon = *reinterpret_cast<const v2d*>(c.blkCell + 2 * (size_t)blk); }
+    }
 #pragma unroll
     for (int k = 0; k < KC; ++k) {
         if (wv0 + k * NT < 3 * nTot) { if (tid + k * NT < 3 * nTot) dA[k] = gA[idC[k]]; }
@@ -1299,6 +1327,9 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     }
 #pragma unroll
     for (int k = 0; k < KC; ++k) { const int q = tid + k * NT; if (q < 3 * nTot) sA[q] = dA[k]; }
+    if constexpr (!IMPL && !ADJ) {
+        if (tid == 0) sMon[0] = mon;   // (behind the stores of dA, which was asked for later: no wait of its own)
+    }
 #pragma unroll
     for (int k = 0; k < KCC; ++k) { const int q = tid + k * NT; if (q < 3 * nUc) sC[q] = dC[k]; }
 #pragma unroll
@@ -1632,7 +1663,23 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         }
     }
     if constexpr (ADJ) blockMaxMin<NT>(cofMax, tauMinAll, c.blkFace + 2 * ((size_t)c.fuBlkFace + blk), false);
-    else blockMaxMin<NT>(-rmin, emin, c.blkCell + 2 * (size_t)blk, true);
+    else {
+        // THE BLOCK'S END: max / min are exact and need no order.  Only waves 0 and 1 carry values; each folds its four rows of 16 lanes
+        // in the vector unit (four lane exchanges inside a row), one lane per row leaves the row's pair in LDS, and thread 0 folds the
+        // eight pairs into the slot value parked in round 1: no load and no wait for memory behind the last barrier, only the store.
+        if (wv0 < 128) {
+            v2d r = {-rmin, emin};
+            r = fuRowMaxMin(r);
+            if ((tid & 15) == 0) sMon[1 + (tid >> 4)] = r;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            v2d r = sMon[0];
+#pragma unroll
+            for (int i = 1; i < 9; ++i) { const v2d q = sMon[i]; r.x = fmax(r.x, q.x); r.y = fmin(r.y, q.y); }
+            *reinterpret_cast<v2d*>(c.blkCell + 2 * (size_t)blk) = r;
+        }
+    }
 }
 
 // Courant-number control with the fused step: the cells advance from the flux sums the blocks left in cellSum, once deltaT is known
@@ -2267,14 +2314,25 @@ void launchBoundaryFaceFlux(const Launcher& L, int stencil, const MeshView& m, c
     QGD_TIMED(L, QGD_K_BFACE, (c.dbg && phiwOnly != 1 ? launchBFaceFluxT<true>(L, stencil, m, c, g, bc, phiwOnly, adjustDt)
                                                    : launchBFaceFluxT<false>(L, stencil, m, c, g, bc, phiwOnly, adjustDt)));
 }
+// what xcdTile divides for, once per launch (xcdTileHost): the blocks inside whole spans of 8 runs, and the run's logarithm where it is a
+// power of two (-1: the kernel divides as before)
+struct FusedXcdOrder { int full, shift; };
+static FusedXcdOrder fusedXcdOrder(int nBlocks, int run) {
+    if (run <= 0 || (run & (run - 1)) != 0) return {0, -1};
+    int shift = 0;
+    while ((1 << shift) < run) ++shift;
+    const int span = run << 3;
+    return {(nBlocks / span) * span, shift};
+}
 void launchFusedFaceCell(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, int firstBlock, int nBlocks) {
     if (nBlocks <= 0) return;
+    const FusedXcdOrder x = fusedXcdOrder(nBlocks, m.fuXcdRun);
     const bool upw = g.upwindU || g.upwindH;   // a `Gauss upwind` entry for div(phiJm,U) or div(phiJm,H)
     const ImplView none{};
-    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr)));
-    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr)));
-    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr)));
-    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr)));
+    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
+    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
+    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
+    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
 }
 // Courant-number control: all blocks up to their flux sums (+ the Courant partials), then -- after deltaTKernel -- the cells
 void launchFusedAdjust(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g) {
@@ -2282,10 +2340,11 @@ void launchFusedAdjust(const Launcher& L, const MeshView& m, const CaseView& c, 
     const bool upw = g.upwindU || g.upwindH;
     const ImplView none{};
     const int n = m.fuBlocks;
-    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr)));
-    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr)));
-    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, false, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr)));
-    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, false, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr)));
+    const FusedXcdOrder x = fusedXcdOrder(n, m.fuXcdRun);
+    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
+    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
+    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, false, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
+    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, false, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
 }
 void launchCellFinish(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, int mode, const int32_t* list, int nList) {
     const int n = (mode == 1) ? nList : m.nC;
@@ -2311,10 +2370,11 @@ bool fusedImplUPrepare(const MeshView& m, const GasModel& g) {
 void launchFusedImplU(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, const ImplView& iv, const PatchBCDev* bc) {
     const bool upw = g.upwindU || g.upwindH;
     const int n = m.fuBlocks;
-    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc)));
-    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc)));
-    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, false, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc)));
-    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, false, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc)));
+    const FusedXcdOrder x = fusedXcdOrder(n, m.fuXcdRun);
+    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
+    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
+    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, false, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
+    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, false, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
 }
 void launchCellUpdate(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, int mode,
                       const int32_t* list, int nList) {

@@ -325,6 +325,16 @@ __device__ __forceinline__ int xcdTile(int nTiles, int run = 0) {
     const int xcd = b & 7, i = b >> 3;
     return ((i / run) * 8 + xcd) * run + (i % run);
 }
+// xcdTile of a launch whose host has done the dividing: full = the tiles inside whole spans of 8 * run (fuXcdFull, per launch) and, where
+// the run is a power of two, shift = its logarithm -- two shifts and a mask, no division in front of the kernel's first load.  shift < 0
+// (another run, or the plain order run <= 0): xcdTile as it stands.
+__device__ __forceinline__ int xcdTileHost(int nTiles, int run, int full, int shift) {
+    if (shift < 0) return xcdTile(nTiles, run);
+    const int b = blockIdx.x;
+    if (b >= full) return b;
+    const int xcd = b & 7, i = b >> 3;
+    return ((((i >> shift) << 3) + xcd) << shift) + (i & ((1 << shift) - 1));
+}
 
 // transform(T, v) = T & v and transform(T, A) = T & A & T^T (L0: transform.H), T row-major
 __device__ __forceinline__ void transformVec(const double* __restrict__ T, const double v[3], double out[3]) {

@@ -12,7 +12,10 @@ ONE step, then the fields are read back as tick counts.
 
 rho: start -> the block's lists are there (round 0) | Ux: -> records loaded and staged in LDS (round 1) | Uy: first barrier + vertex values |
 Uz: second barrier + the faces | p: third barrier, flux planes into LDS, fourth barrier | e: the cell's sums and advanceCell.
-Waves 0 and 1 of a block own its cells, so these are their clocks (cells 0-63 / 64-127 of a block)."""
+Waves 0 and 1 of a block own its cells, so these are their clocks (cells 0-63 / 64-127 of a block).
+rhoE of a block's first cell: THE TAIL, from the end of thread 0's update to its last instruction, the store of the block's monitor slot
+(the reduction of the block's minima, the barrier, the slot value); zero in every other cell.  It is thread 0's clock alone and comes on
+top of the six phases."""
 import json
 import os
 import sys
@@ -52,6 +55,10 @@ def main():
         c = cols[:, i]
         out["phases"][nm] = {"mean_ticks": round(float(c.mean()), 1), "share": round(float(c.mean() / tot.mean()), 4),
                              "p10_p50_p90": [round(float(x), 1) for x in np.percentile(c, [10, 50, 90])]}
+    tail = np.asarray(case.field("rhoE"), dtype=np.float64)
+    tail = tail[tail > 0]   # one per block
+    out["tail (thread 0: reduction, barrier, monitor slot)"] = {"blocks": int(tail.size), "mean_ticks": round(float(tail.mean()), 1),
+                                                               "p10_p50_p90": [round(float(x), 1) for x in np.percentile(tail, [10, 50, 90])]}
     print(json.dumps(out, indent=1))
 
 
