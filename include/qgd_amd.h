@@ -105,7 +105,7 @@ typedef struct qgd_case_s* qgd_case_t;     /* a QGDFoam case on one device      
 
 /* ---- library ---------------------------------------------------------------- */
 /* Bumped whenever an options struct grows or an entry changes its meaning (3: round 3). */
-#define QGD_ABI_VERSION 8
+#define QGD_ABI_VERSION 9
 const char* qgd_version(void);
 /* sizes[0..2] = sizeof(qgd_case_options), sizeof(qgd_qhd_options), sizeof(qgd_poisson_control) as THIS library was built,
  * sizes[3] = its QGD_ABI_VERSION: a host compiled against another header compares before it passes a struct (the structs
@@ -897,6 +897,46 @@ int qgd_case_kernel_time(qgd_case_t c, int k, double* totalMs, int64_t* launches
 int qgd_case_timing_reset(qgd_case_t c);
 /* Bytes resident on the device for this case + its mesh. */
 int qgd_case_device_bytes(qgd_case_t c, int64_t* bytes);
+
+/* ---- run monitors of a QGDFoam case ------------------------------------------ */
+/* A monitor is created once for a case with a specification (probe cells, patches) and sampled by a few launches and one small
+ * copy on the case's stream: volume integrals over the owned cells, extrema with the cells they sit in, the count and first
+ * label of non-finite cells, the probes' values and, per requested patch, the totals of the net face fluxes the cell update
+ * consumes.  Sampling writes nothing to the case and changes none of its launches; the order of every sum depends on the mesh
+ * and the specification only, so two samples of one state are bitwise equal.
+ *
+ * Result block (doubles; qgd_monitor_layout gives the offsets of its QGD_MONITOR_SECTIONS sections):
+ *   0 header (8):    owned cells | flux state (0: no assembly yet, patch fluxes are NaN; 1: all five; 2: implicitDiffusion, where
+ *                    flux[1..4] hold the explicit part only: mass is reported, the other four are NaN) | nProbes | nPatches |
+ *                    non-finite cells (any of rho, p, e, U) | lowest label among them (-1: none) | deltaT | time under adjustTimeStep
+ *   1 integrals (8): V, rho V, rho Ux V, rho Uy V, rho Uz V, rho E V, rho e V, rho |U|^2/2 V summed over the owned cells
+ *   2 extrema (20):  {min, its cell, max, its cell} of rho, p, T = e/Cv, |U|, Mach = |U|/c over the owned cells whose state is
+ *                    finite; ties go to the lowest label; NaN and -1 when there is no such cell
+ *   3 probes (7 each):  rho, Ux, Uy, Uz, p, T, e of the probe's cell (NaN where the label is -1)
+ *   4 patches (9 each): sum |Sf|, the five net fluxes {phiJm, phiJmU + phiP - phiPi (3), phiJmH + phiQ - phiPiU}, sum p_b Sf (3)
+ * Cell labels are those of the unsharded mesh, as doubles.  Ghost cells of a shard and the copies behind cyclic halves are never
+ * counted, nor are patch faces they own or faces without fields.  The patch fluxes are those of the assembly that produced the
+ * state held (the last step's, or qgd_case_update_fluxes'), so that with the integrals of successive samples they close the
+ * discrete balance of mass, momentum and total energy to rounding. */
+typedef struct qgd_monitor_s* qgd_monitor_t;
+#define QGD_MONITOR_SECTIONS 5
+#define QGD_MONITOR_SLOTS 4
+typedef struct qgd_monitor_spec {
+    int32_t nProbes;            /* probeCells: labels of this device's mesh; -1 = not on this rank (a row of NaN) */
+    int32_t nPatches;           /* patches: indices of real patches (a halo, empty, cyclic or wedge patch is refused by name) */
+    const int32_t* probeCells;
+    const int32_t* patches;
+} qgd_monitor_spec;
+/* After qgd_case_set_fields.  The monitor belongs to its case: qgd_case_free frees the monitors still open first (a later
+ * qgd_monitor_free of such a handle does nothing). */
+int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out);
+/* offsets of the sections, doubles in a result block, most workgroups of the cell pass (its lanes stride beyond gridCap * 256 cells) */
+int qgd_monitor_layout(qgd_monitor_t m, int64_t offsets[QGD_MONITOR_SECTIONS], int64_t* nDoubles, int32_t* gridCap);
+/* Stream-ordered on the case's stream, no host wait: the pass, a copy into pinned host memory of slot 0..3, an event. */
+int qgd_monitor_sample(qgd_monitor_t m, int32_t slot);
+/* Waits for that slot's event only.  time / step: those of the case when the slot was sampled. */
+int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, double* time, int64_t* step);
+int qgd_monitor_free(qgd_monitor_t m);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,8 @@ What the reference's ``main`` does per step -- updateFields.H, updateFluxes.H, Q
 setDeltaT-QGDQHD.H, the three explicit equations, thermo.correct(), runTime.write() -- is
 ``QGDFoamCase.step`` plus ``foamfile.write_time`` here.  Read from system/controlDict:
 startFrom/startTime, endTime, deltaT, writeControl (timeStep, or runTime/adjustableRunTime with a
-fixed deltaT), writeInterval, adjustTimeStep/maxCo/maxDeltaT, timePrecision.
+fixed deltaT), writeInterval, adjustTimeStep/maxCo/maxDeltaT, timePrecision, and of ``functions{}`` the types
+probes, fieldMinMax, qgdIntegrals and qgdPatchFluxes (foamfile.read_functions; files under postProcessing/).
 """
 import argparse
 import os
@@ -177,7 +178,40 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         else:
             halo.exchange()
 
+    # functions{} of system/controlDict: probes, fieldMinMax, qgdIntegrals, qgdPatchFluxes through one device monitor (monitor.py), sampled
+    # after the steps at which one of them is due and read two samples late.  On several ranks every rank samples its shard and the
+    # parts are combined on rank 0 (monitor.combine) -- a combination that has not run on more than one GPU yet.
+    functions = None
+    func_specs = ff.read_functions(cd, warn=log)
+    if func_specs:
+        from .monitor import FunctionObjects
+        if world > 1:
+            cg = mesh.array("cellGlobal")
+            where = {int(cg[i]): int(i) for i in np.nonzero(owned)[0]}
+            local_of = lambda g: where.get(g, -1)     # noqa: E731
+
+            def gather_parts(sample):
+                parts = [None] * world
+                dist.all_gather_object(parts, sample)
+                return parts
+        else:
+            local_of, gather_parts = (lambda g: g), None
+        functions = FunctionObjects(case, func_specs, gmesh, case_dir, t0_name, local_of, old_of_new, is_root=rank == 0,
+                                    gather=gather_parts, log=log)
+    steps_taken = [0]
+
     def advance(n):
+        if functions is None:
+            advance_plain(n)
+            return
+        while n > 0:
+            k = min(n, functions.next_due(steps_taken[0]))
+            advance_plain(k)
+            steps_taken[0] += k
+            n -= k
+            functions.after_step(steps_taken[0], t0)
+
+    def advance_plain(n):
         if world == 1:
             case.step(n)
             return
@@ -281,6 +315,8 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             written.append(name)
         if total is None and t >= end_time - 1e-12 * max(1.0, abs(end_time)):
             break
+    if functions is not None:
+        functions.finish()
     log("End")
     if world > 1:
         dist.barrier()

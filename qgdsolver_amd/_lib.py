@@ -54,6 +54,11 @@ class VarScOptions(C.Structure):
                 ("maxSc", C.c_double)]
 
 
+class MonitorSpec(C.Structure):
+    """qgd_monitor_spec"""
+    _fields_ = [("nProbes", C.c_int32), ("nPatches", C.c_int32), ("probeCells", C.POINTER(C.c_int32)), ("patches", C.POINTER(C.c_int32))]
+
+
 class QhdOptions(C.Structure):
     """qgd_qhd_options"""
     _fields_ = [("stencil", C.c_int32), ("implicitDiffusion", C.c_int32), ("tauModel", C.c_int32), ("pRefCell", C.c_int32),
@@ -220,6 +225,11 @@ SIGNATURES = {
     "qgd_case_kernel_time": (C.c_int, [handle, C.c_int, c_double_p, c_int64_p]),
     "qgd_case_timing_reset": (C.c_int, [handle]),
     "qgd_case_device_bytes": (C.c_int, [handle, c_int64_p]),
+    "qgd_monitor_create": (C.c_int, [handle, C.POINTER(MonitorSpec), handle_p]),
+    "qgd_monitor_layout": (C.c_int, [handle, c_int64_p, c_int64_p, c_int32_p]),
+    "qgd_monitor_sample": (C.c_int, [handle, C.c_int32]),
+    "qgd_monitor_read": (C.c_int, [handle, C.c_int32, c_double_p, C.c_int64, c_double_p, c_int64_p]),
+    "qgd_monitor_free": (C.c_int, [handle]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -244,6 +254,7 @@ BC_ZEROGRADIENT, BC_FIXEDVALUE, BC_SLIP, BC_QGDFLUX, BC_NONE, BC_QHDFLUX = range
 FVSC_REDUCED, FVSC_LEASTSQUARES, FVSC_GAUSSVOLPOINT = range(3)
 FLUX_LINEAR, FLUX_UPWIND = range(2)
 K_POINT, K_FACE, K_BFACE, K_CELL, K_BC, K_BPOINT, K_VARSC = range(7)
+MONITOR_SECTIONS, MONITOR_SLOTS = 5, 4
 
 
 class QgdError(RuntimeError):

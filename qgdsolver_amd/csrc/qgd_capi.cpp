@@ -344,6 +344,8 @@ struct qgd_case_s {
     bool hasQgdFlux = false;
     bool phiwRegistered = false;
     bool fieldsSet = false;
+    bool fluxAssembled = false;     // CaseView::flux holds the fluxes of an assembly of this case's fields (what a monitor reports per patch)
+    std::vector<struct qgd_monitor_s*> monitors;   // qgd_monitor_create: freed with the case where still open
     std::vector<PatchBCDev> bc;
     PatchBCDev* bcDev = nullptr;
     // per-face values of fixedValue patches (qgd_case_set_bc_values), field 0 U (3 per boundary face), 1 T, 2 p: the host copy serves
@@ -1676,9 +1678,11 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
     return QGD_OK;
     QGD_CATCH
 }
+static void freeMonitorsOf(qgd_case_s* c);
 int qgd_case_free(qgd_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
+    freeMonitorsOf(c);
     harvestTiming(c);
     for (hipEvent_t e : c->freeEvents) (void)hipEventDestroy(e);
     if (c->implSolver) { (void)hipStreamSynchronize(c->stream()); implicitSolverFree(c->implSolver); }
@@ -1924,6 +1928,7 @@ static void assembleFluxes(qgd_case_s* c, bool adjust, int part = 0, bool intern
         if (mid) bface(1, false);  // + the mid-step pressure itself
     }
     if (part == 1) return;
+    c->fluxAssembled = true;
     if (mid) launchBoundaryPoints(L, m, v, true);
     if (!internalFaces) {}
     else if (c->mixB >= 0) launchFaceFluxMixed(L, c->stencil, c->mixB, c->mixMask, m, v, c->gas, adjust);
@@ -1973,6 +1978,7 @@ int qgd_case_set_fields(qgd_case_t c, const double* U, const double* T, const do
     c->phiwRegistered = true;  // createFaceFluxes.H registers "phiwStar" before the loop starts
     c->ghostsCurrent = false;  // (cyclic pairs served by ghost cells: the copies take their originals' records before the first step)
     c->fieldsSet = true;
+    c->fluxAssembled = false;
     c->gradUValid = false;
     c->impl.have = 0;          // the start values of the implicit solves begin without a history
     c->time = 0; c->steps = 0;
@@ -3660,6 +3666,174 @@ int qgd_case_timing_reset(qgd_case_t c) {
 int qgd_case_device_bytes(qgd_case_t c, int64_t* bytes) {
     if (!c || !bytes) return fail(QGD_ERR_INVALID, "null argument");
     *bytes = c->arena.bytes + c->dev->arena.bytes;
+    return QGD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// run monitors (qgd_monitor.hip)
+// ---------------------------------------------------------------------------
+struct qgd_monitor_s {
+    qgd_case_s* c = nullptr;
+    MonitorView view{};
+    DeviceArena arena;
+    double* result = nullptr;    // device: one result block (the copy into a slot follows the fold in stream order)
+    double* host = nullptr;      // pinned: QGD_MONITOR_SLOTS result blocks
+    int64_t nDoubles = 0;
+    hipEvent_t ev[QGD_MONITOR_SLOTS] = {};
+    bool sampled[QGD_MONITOR_SLOTS] = {};
+    double time[QGD_MONITOR_SLOTS] = {};
+    int64_t step[QGD_MONITOR_SLOTS] = {};
+};
+// the open monitors of this process: a handle whose case was freed first is no longer among them
+static std::vector<qgd_monitor_s*> g_monitors;
+static bool monitorLive(const qgd_monitor_s* m) { return m && std::find(g_monitors.begin(), g_monitors.end(), m) != g_monitors.end(); }
+static void monitorDestroy(qgd_monitor_s* m) {
+    for (hipEvent_t e : m->ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+    if (m->host) (void)hipHostFree(m->host);
+    m->arena.release();
+    g_monitors.erase(std::remove(g_monitors.begin(), g_monitors.end(), m), g_monitors.end());
+    delete m;
+}
+static void freeMonitorsOf(qgd_case_s* c) {
+    if (c->monitors.empty()) return;
+    (void)hipStreamSynchronize(c->stream());
+    for (qgd_monitor_s* m : c->monitors) monitorDestroy(m);
+    c->monitors.clear();
+}
+static const char* patchTypeWord(int t) {
+    switch (t) {
+        case QGD_PATCH_EMPTY: return "empty";
+        case QGD_PATCH_WEDGE: return "wedge";
+        case QGD_PATCH_CYCLIC: return "cyclic";
+        case QGD_PATCH_HALO: return "halo";
+        default: return "real";
+    }
+}
+
+int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
+    QGD_TRY
+    if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_monitor_create: null argument");
+    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_create: call qgd_case_set_fields first (a monitor samples the state the case holds)");
+    if (spec->nProbes < 0 || spec->nPatches < 0 || (spec->nProbes > 0 && !spec->probeCells) || (spec->nPatches > 0 && !spec->patches))
+        return fail(QGD_ERR_INVALID, "qgd_monitor_create: bad specification (negative count or null list)");
+    const qgd_device_s* d = c->dev;
+    const MeshView& m = d->view;
+    for (int32_t i = 0; i < spec->nProbes; ++i)
+        if (spec->probeCells[i] < -1 || spec->probeCells[i] >= m.nC)
+            return fail(QGD_ERR_INVALID, "qgd_monitor_create: probe " + std::to_string(i) + ": cell label " + std::to_string(spec->probeCells[i]) +
+                                             " is out of range [0, " + std::to_string(m.nC) + ") (-1 = not on this rank)");
+    for (int32_t i = 0; i < spec->nPatches; ++i) {
+        const int32_t p = spec->patches[i];
+        if (p < 0 || p >= (int32_t)d->patches.size())
+            return fail(QGD_ERR_INVALID, "qgd_monitor_create: patch index " + std::to_string(p) + " is out of range [0, " + std::to_string(d->patches.size()) + ")");
+        const int t = d->patches[p].type;
+        if (t == QGD_PATCH_HALO || t == QGD_PATCH_EMPTY || t == QGD_PATCH_CYCLIC || t == QGD_PATCH_WEDGE)
+            return fail(QGD_ERR_INVALID, "qgd_monitor_create: patch " + std::to_string(p) + " ('" + d->patches[p].name + "') is a " + patchTypeWord(t) +
+                                             " patch: it carries no boundary fluxes of its own (patch totals are formed on real patches only)");
+    }
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    // the faces of the requested patches that carry fields and belong to an owned cell, patch by patch in label order, cut into chunks
+    // of at most 256 that never span two patches
+    std::vector<uint8_t> fkind((size_t)m.nBF);
+    std::vector<int32_t> own((size_t)m.nBF);
+    if (m.nBF) {
+        HIP_CHECK(hipMemcpy(fkind.data(), m.fkind + m.nIF, (size_t)m.nBF, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(own.data(), m.own + m.nIF, sizeof(int32_t) * (size_t)m.nBF, hipMemcpyDeviceToHost));
+    }
+    std::vector<int32_t> faceList, chunkStart{0}, patchChunk{0};
+    for (int32_t i = 0; i < spec->nPatches; ++i) {
+        const Patch& pt = d->patches[spec->patches[i]];
+        int32_t inChunk = 0;
+        for (int32_t f = pt.start; f < pt.start + pt.size; ++f) {
+            const int32_t b = f - m.nIF;
+            if (b < 0 || b >= m.nBF) throw std::invalid_argument("qgd_monitor_create: patch '" + pt.name + "' has faces outside the boundary range");
+            if (fkind[b] == FK_SKIP || own[b] < d->ownedBegin || own[b] >= d->ownedEnd) continue;
+            if (inChunk == 256) { chunkStart.push_back((int32_t)faceList.size()); inChunk = 0; }
+            faceList.push_back(b);
+            ++inChunk;
+        }
+        if (inChunk > 0) chunkStart.push_back((int32_t)faceList.size());
+        patchChunk.push_back((int32_t)chunkStart.size() - 1);
+    }
+    qgd_monitor_s* mo = new qgd_monitor_s();
+    try {
+        mo->c = c;
+        MonitorView& v = mo->view;
+        DeviceArena& a = mo->arena;
+        v.ownedBegin = d->ownedBegin; v.ownedEnd = d->ownedEnd;
+        v.cellGlobal = a.upload(d->cellGlobal); v.cellGlobalOffset = d->cellGlobalOffset;
+        v.cellPart = a.alloc<double>((size_t)QGD_MONITOR_BLOCKS * QGD_MONITOR_CELL_ROW);
+        v.nProbes = spec->nProbes;
+        v.probeCell = a.upload(std::vector<int32_t>(spec->probeCells, spec->probeCells + spec->nProbes));
+        v.nPatches = spec->nPatches; v.nChunks = (int32_t)chunkStart.size() - 1;
+        v.faceList = a.upload(faceList); v.chunkStart = a.upload(chunkStart); v.patchChunk = a.upload(patchChunk);
+        v.patchPart = a.alloc<double>((size_t)std::max(1, v.nChunks) * QGD_MONITOR_PATCH_ROW);
+        v.off[0] = 0; v.off[1] = 8; v.off[2] = v.off[1] + QGD_MONITOR_SUMS; v.off[3] = v.off[2] + 4 * QGD_MONITOR_EXTREMA;
+        v.off[4] = v.off[3] + (int64_t)QGD_MONITOR_PROBE_ROW * v.nProbes;
+        mo->nDoubles = v.off[4] + (int64_t)QGD_MONITOR_PATCH_ROW * v.nPatches;
+        mo->result = a.alloc<double>((size_t)mo->nDoubles);
+        HIP_CHECK(hipHostMalloc((void**)&mo->host, sizeof(double) * (size_t)mo->nDoubles * QGD_MONITOR_SLOTS, hipHostMallocDefault));
+        for (int k = 0; k < QGD_MONITOR_SLOTS; ++k) HIP_CHECK(hipEventCreateWithFlags(&mo->ev[k], hipEventDisableTiming));
+    } catch (...) {
+        for (hipEvent_t e : mo->ev) if (e) (void)hipEventDestroy(e);
+        if (mo->host) (void)hipHostFree(mo->host);
+        mo->arena.release();
+        delete mo;
+        throw;
+    }
+    g_monitors.push_back(mo);
+    c->monitors.push_back(mo);
+    *out = mo;
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_monitor_layout(qgd_monitor_t m, int64_t offsets[QGD_MONITOR_SECTIONS], int64_t* nDoubles, int32_t* gridCap) {
+    if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_layout: not an open monitor (a monitor is freed with its case)");
+    if (offsets) for (int k = 0; k < QGD_MONITOR_SECTIONS; ++k) offsets[k] = m->view.off[k];
+    if (nDoubles) *nDoubles = m->nDoubles;
+    if (gridCap) *gridCap = QGD_MONITOR_BLOCKS;
+    return QGD_OK;
+}
+int qgd_monitor_sample(qgd_monitor_t m, int32_t slot) {
+    QGD_TRY
+    if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: not an open monitor (a monitor is freed with its case)");
+    if (slot < 0 || slot >= QGD_MONITOR_SLOTS) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: slot must be 0.." + std::to_string(QGD_MONITOR_SLOTS - 1));
+    qgd_case_s* c = m->c;
+    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: the case's boundary conditions or coefficients changed: call qgd_case_set_fields first");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    const int fluxState = !c->fluxAssembled ? 0 : (c->opt.implicitDiffusion ? 2 : 1);
+    hipStream_t st = c->stream();
+    (void)hipGetLastError();
+    launchMonitorSample(st, m->view, c->dev->view, c->view, c->gas, fluxState, m->result);   // (the view as it stands now: the fused step swaps A / B)
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(m->host + (size_t)slot * m->nDoubles, m->result, sizeof(double) * (size_t)m->nDoubles, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipEventRecord(m->ev[slot], st));
+    m->sampled[slot] = true; m->time[slot] = c->time; m->step[slot] = c->steps;
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, double* time, int64_t* step) {
+    QGD_TRY
+    if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_read: not an open monitor (a monitor is freed with its case)");
+    if (slot < 0 || slot >= QGD_MONITOR_SLOTS) return fail(QGD_ERR_INVALID, "qgd_monitor_read: slot must be 0.." + std::to_string(QGD_MONITOR_SLOTS - 1));
+    if (!out || cap < m->nDoubles) return fail(QGD_ERR_INVALID, "qgd_monitor_read: output too small (qgd_monitor_layout gives the doubles of a result block)");
+    if (!m->sampled[slot]) return fail(QGD_ERR_INVALID, "qgd_monitor_read: slot " + std::to_string(slot) + " was never sampled");
+    HIP_CHECK(hipSetDevice(m->c->dev->deviceId));
+    HIP_CHECK(hipEventSynchronize(m->ev[slot]));
+    const double* src = m->host + (size_t)slot * m->nDoubles;
+    std::copy(src, src + m->nDoubles, out);
+    if (time) *time = m->c->opt.adjustTimeStep ? src[7] : m->time[slot];
+    if (step) *step = m->step[slot];
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_monitor_free(qgd_monitor_t m) {
+    if (!monitorLive(m)) return QGD_OK;   // null, or freed with its case
+    qgd_case_s* c = m->c;
+    (void)hipSetDevice(c->dev->deviceId);
+    (void)hipStreamSynchronize(c->stream());
+    c->monitors.erase(std::remove(c->monitors.begin(), c->monitors.end(), m), c->monitors.end());
+    monitorDestroy(m);
     return QGD_OK;
 }
 

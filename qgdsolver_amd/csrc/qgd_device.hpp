@@ -211,6 +211,28 @@ void launchFaceGeoPos(hipStream_t s, const MeshView& m, double4* out);   // fill
 void launchVarSc7(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, const VarScView& v, bool init);
 void launchVarScRange(hipStream_t s, const VarScView& v, int32_t begin, int32_t end);   // {max, min} over cells [begin, end) -> v.part[2 * QGD_FACE_REDUCE_PARTIALS ...]
 
+// ---- run monitors (qgd_monitor.hip; qgd_monitor_* of include/qgd_amd.h) ---------------------------------------------------------
+#define QGD_MONITOR_BLOCKS 1024      // most workgroups of monitorCellKernel (its lanes stride over the owned cells beyond that)
+#define QGD_MONITOR_SUMS 8           // V, rho V, rho U V (3), rho E V, rho e V, rho |U|^2/2 V
+#define QGD_MONITOR_EXTREMA 5        // rho, p, T, |U|, Mach: {min, label, max, label} each
+#define QGD_MONITOR_CELL_ROW (QGD_MONITOR_SUMS + 4 * QGD_MONITOR_EXTREMA + 2)
+#define QGD_MONITOR_PROBE_ROW 7      // rho, Ux, Uy, Uz, p, T, e
+#define QGD_MONITOR_PATCH_ROW 9      // |Sf|, the five net fluxes, p_b Sf (3)
+struct MonitorView {
+    int32_t ownedBegin, ownedEnd;
+    const int32_t* cellGlobal; int64_t cellGlobalOffset;   // labels of the unsharded mesh (nullptr: local label + offset)
+    double* cellPart;                                      // QGD_MONITOR_BLOCKS rows of QGD_MONITOR_CELL_ROW
+    int32_t nProbes; const int32_t* probeCell;             // local labels, -1: not on this device
+    int32_t nPatches, nChunks;
+    const int32_t* faceList;                               // boundary-face indices, sorted by requested patch
+    const int32_t* chunkStart;                             // nChunks + 1 offsets into faceList: <= 256 faces of one patch each
+    const int32_t* patchChunk;                             // nPatches + 1: the chunks of a patch are consecutive
+    double* patchPart;                                     // nChunks rows of QGD_MONITOR_PATCH_ROW
+    int64_t off[5];                                        // sections of the result block: header, integrals, extrema, probes, patches
+};
+// fluxState: 0 no assembly yet (patch fluxes NaN), 1 all five, 2 implicitDiffusion (mass only)
+void launchMonitorSample(hipStream_t s, const MonitorView& mv, const MeshView& m, const CaseView& c, const GasModel& g, int fluxState, double* out);
+
 // ---- accessor: one named cell / patch field out of the records (K == nullptr on patches) ----------------------------
 enum ExtractField : int { XF_RHO = 0, XF_U, XF_P, XF_E, XF_T, XF_RHOU, XF_RHOE, XF_C, XF_PSI, XF_MU, XF_ALPHAU, XF_TAUQGD, XF_MUQGD,
                           XF_ALPHAUQGD, XF_HQGD, XF_H, XF_GAMMA };

@@ -253,6 +253,70 @@ def read_dict(path):
     return parse_foam_text(_read_text(path))
 
 
+# function objects of system/controlDict the QGDFoam application serves (monitor.FunctionObjects): type -> the fields it may name
+FUNCTION_TYPES = {"probes": ("rho", "U", "p", "T", "e"), "fieldMinMax": ("rho", "p", "T", "U", "mag(U)", "Mach"), "qgdIntegrals": (),
+                  "qgdPatchFluxes": ()}
+
+
+def read_functions(control_dict, warn=print):
+    """specifications of the served entries of ``functions{}``: a list of dict(name, type, interval, fields, probeLocations, patches).
+    ``probes`` (fields out of rho U p T e, probeLocations), ``fieldMinMax`` (fields out of rho p T U Mach; U is its magnitude),
+    and the project's own ``qgdIntegrals`` and ``qgdPatchFluxes`` (patches) are served, each every ``writeInterval`` steps
+    (``writeControl timeStep``, the default; default interval 1).  Anything else -- another type, another writeControl, a field a
+    type does not serve -- gets one warning line and is skipped, so that a case with functions the solver does not know still runs."""
+    funcs = control_dict.get("functions", {})
+    out = []
+    if not isinstance(funcs, dict):
+        return out
+    for name, d in funcs.items():
+        if not isinstance(d, dict):
+            continue
+        typ = str(d.get("type", ""))
+        if typ not in FUNCTION_TYPES:
+            warn(f"functions: '{name}' has type '{typ}', which is not served (served: {', '.join(FUNCTION_TYPES)}): skipped")
+            continue
+        if not _truthy(d.get("enabled", "yes")):
+            continue
+        control = str(d.get("writeControl", d.get("outputControl", "timeStep")))
+        if control != "timeStep":
+            warn(f"functions: '{name}': writeControl '{control}' is not served (timeStep is): skipped")
+            continue
+        interval = int(d.get("writeInterval", d.get("outputInterval", 1)))
+        if interval < 1:
+            raise FoamFileError(f"functions: '{name}': writeInterval must be at least 1, got {interval}")
+        spec = dict(name=str(name), type=typ, interval=interval)
+        if FUNCTION_TYPES[typ]:
+            fields = d.get("fields", [])
+            fields = [str(f) for f in (fields if isinstance(fields, (list, tuple)) else [fields])]
+            served = [f for f in fields if f in FUNCTION_TYPES[typ]]
+            for f in fields:
+                if f not in served:
+                    warn(f"functions: '{name}': field '{f}' is not served by type {typ} (served: {', '.join(FUNCTION_TYPES[typ])}): left out")
+            if not served:
+                warn(f"functions: '{name}': no served field: skipped")
+                continue
+            spec["fields"] = served
+        if typ == "probes":
+            locs = d.get("probeLocations")
+            try:
+                locs = np.asarray(locs, dtype=np.float64).reshape(-1, 3)
+            except (TypeError, ValueError):
+                raise FoamFileError(f"functions: '{name}': probeLocations must be a list of points (x y z)") from None
+            if locs.shape[0] == 0:
+                warn(f"functions: '{name}': no probeLocations: skipped")
+                continue
+            spec["probeLocations"] = locs
+        if typ == "qgdPatchFluxes":
+            patches = d.get("patches", [])
+            patches = [str(p) for p in (patches if isinstance(patches, (list, tuple)) else [patches])]
+            if not patches:
+                warn(f"functions: '{name}': no patches: skipped")
+                continue
+            spec["patches"] = patches
+        out.append(spec)
+    return out
+
+
 def _split_header(text):
     """(FoamFile dict, rest of the text) of a list-style file (points, faces, owner, ...)"""
     text = _strip_comments(text)

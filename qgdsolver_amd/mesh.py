@@ -163,6 +163,69 @@ class PolyMesh:
             out.patch_names = list(names) + ["halo"]
         return out
 
+    # ---- point location (host) ---------------------------------------------------
+    def _locator(self):
+        """cell -> faces (CSR, with the sign that turns Sf outwards) and cell -> cells sharing a vertex, built on first use"""
+        loc = getattr(self, "_loc", None)
+        if loc is not None and loc["nCells"] == self.nCells and loc["nFaces"] == self.nFaces:
+            return loc
+        own, nei = self.array("owner").astype(np.int64), self.array("neighbour").astype(np.int64)
+        nif = nei.size
+        cell_of = np.concatenate([own, nei])
+        face_of = np.concatenate([np.arange(own.size), np.arange(nif)])
+        sign_of = np.concatenate([np.ones(own.size), -np.ones(nif)])
+        order = np.argsort(cell_of, kind="stable")
+        start = np.zeros(self.nCells + 1, dtype=np.int64)
+        np.cumsum(np.bincount(cell_of, minlength=self.nCells), out=start[1:])
+        Sf = self.array("Sf").reshape(-1, 3)
+        mag = np.maximum(np.linalg.norm(Sf, axis=1), 1e-300)
+        pts = self.array("points").reshape(-1, 3)
+        # vertex neighbours: the cells of every face that touches one of the cell's vertices
+        fo, fp = self.array("faceOffsets").astype(np.int64), self.array("facePoints").astype(np.int64)
+        face_id = np.repeat(np.arange(own.size), np.diff(fo))
+        pc_p = np.concatenate([fp, fp[face_id < nif]])
+        pc_c = np.concatenate([own[face_id], nei[face_id[face_id < nif]]])
+        pair = np.unique(pc_p * self.nCells + pc_c)
+        pp, cc = pair // self.nCells, pair % self.nCells
+        pstart = np.zeros(self.nPoints + 1, dtype=np.int64)
+        np.cumsum(np.bincount(pp, minlength=self.nPoints), out=pstart[1:])
+        by_cell = np.argsort(cc, kind="stable")
+        cstart = np.zeros(self.nCells + 1, dtype=np.int64)
+        np.cumsum(np.bincount(cc, minlength=self.nCells), out=cstart[1:])
+        self._loc = dict(nCells=self.nCells, nFaces=self.nFaces, start=start, face=face_of[order], sign=sign_of[order], n=Sf / mag[:, None],
+                         Cf=self.array("Cf").reshape(-1, 3), C=self.array("C").reshape(-1, 3), lo=pts.min(axis=0), hi=pts.max(axis=0),
+                         pstart=pstart, pcell=cc, cstart=cstart, cpoint=pp[by_cell])
+        return self._loc
+
+    def find_cells(self, points):
+        """label of the cell that holds each point, -1 outside the mesh.  The nearest cell centre gives a candidate; the point is tested
+        against the face planes (face centre, area vector) of the candidate and of the cells that share a vertex with it, with a
+        tolerance of 1e-10 of the bounding box; where several cells hold the point (it lies on a face, an edge, a vertex) the lowest
+        label is returned.  Host side, for a handful of probe locations: the nearest-centre search is a plain scan."""
+        x = np.atleast_2d(np.asarray(points, dtype=np.float64))
+        if x.shape[1] != 3:
+            raise ValueError(f"find_cells: points must have shape (n, 3), got {x.shape}")
+        k = self._locator()
+        tol = 1e-10 * float(np.linalg.norm(k["hi"] - k["lo"]))
+        out = np.full(x.shape[0], -1, dtype=np.int64)
+
+        def holds(c, pt):
+            sl = slice(k["start"][c], k["start"][c + 1])
+            f = k["face"][sl]
+            return bool(np.all(np.einsum("ij,ij->i", pt - k["Cf"][f], k["n"][f]) * k["sign"][sl] <= tol))
+
+        for i, pt in enumerate(x):
+            if np.any(pt < k["lo"] - tol) or np.any(pt > k["hi"] + tol):
+                continue
+            c0 = int(np.argmin(np.einsum("ij,ij->i", k["C"] - pt, k["C"] - pt)))
+            vp = k["cpoint"][k["cstart"][c0]:k["cstart"][c0 + 1]]
+            ring = np.unique(np.concatenate([k["pcell"][k["pstart"][p]:k["pstart"][p + 1]] for p in vp] + [np.array([c0])]))
+            for c in ring:     # ascending labels: the first hit is the lowest
+                if holds(int(c), pt):
+                    out[i] = c
+                    break
+        return out
+
     def close(self):
         if self._h:
             L.lib.qgd_mesh_free(self._h)

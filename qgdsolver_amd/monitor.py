@@ -1,0 +1,313 @@
+"""Run monitors of a resident QGDFoam case (qgd_monitor_* of include/qgd_amd.h) and the function objects of
+``system/controlDict`` the QGDFoam application serves with them.
+
+A ``Monitor`` is created once (``QGDFoamCase.monitor(probes=..., patches=...)``); ``sample()`` enqueues the pass and a small copy
+on the case's stream and returns at once, ``read()`` waits for that sample only.  Four slots form a ring, so a loop can read a
+sample a step or two after it was taken and never drain the stream.
+"""
+import collections
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib as L
+
+INTEGRALS = ("volume", "mass", "momentum_x", "momentum_y", "momentum_z", "totalEnergy", "internalEnergy", "kineticEnergy")
+EXTREMA_FIELDS = ("rho", "p", "T", "magU", "Mach")
+PROBE_COLUMNS = ("rho", "Ux", "Uy", "Uz", "p", "T", "e")
+PATCH_COLUMNS = ("area", "massFlux", "momentumFlux_x", "momentumFlux_y", "momentumFlux_z", "energyFlux",
+                 "pressureForce_x", "pressureForce_y", "pressureForce_z")
+
+
+class Monitor:
+    def __init__(self, case, probes=None, patches=None):
+        """probes: cell labels of the case's device mesh (-1: not on this rank, its row reads NaN); patches: patch indices"""
+        self.case = case
+        self.probes = np.ascontiguousarray(probes if probes is not None else [], dtype=np.int32).reshape(-1)
+        self.patches = np.ascontiguousarray(patches if patches is not None else [], dtype=np.int32).reshape(-1)
+        spec = L.MonitorSpec()
+        spec.nProbes, spec.nPatches = int(self.probes.size), int(self.patches.size)
+        spec.probeCells = self.probes.ctypes.data_as(L.c_int32_p) if self.probes.size else None
+        spec.patches = self.patches.ctypes.data_as(L.c_int32_p) if self.patches.size else None
+        h = C.c_void_p()
+        L.check(L.lib.qgd_monitor_create(case._h, C.byref(spec), C.byref(h)), "qgd_monitor_create")
+        self._handle = L.NativeHandle(h, L.lib.qgd_monitor_free)
+        off = (C.c_int64 * L.MONITOR_SECTIONS)()
+        n, cap = C.c_int64(), C.c_int32()
+        L.check(L.lib.qgd_monitor_layout(h, off, C.byref(n), C.byref(cap)), "qgd_monitor_layout")
+        self.offsets, self.n_doubles, self.grid_cap = [int(x) for x in off], int(n.value), int(cap.value)
+        self._pending = collections.deque()   # sampled and not yet read, oldest first
+        self._last = -1
+
+    @property
+    def _h(self):
+        return self._handle.value
+
+    def sample(self, slot=None):
+        """enqueue one sample on the case's stream (no host wait); slot None: the next slot of the ring.  Returns the slot."""
+        if slot is None:
+            slot = (self._last + 1) % L.MONITOR_SLOTS
+        L.check(L.lib.qgd_monitor_sample(self._h, int(slot)), "qgd_monitor_sample")
+        if slot in self._pending:          # sampled again before it was read: the older sample is gone
+            self._pending.remove(slot)
+        self._pending.append(slot)
+        self._last = slot
+        return slot
+
+    def read_raw(self, slot=None):
+        """(result block, time, step) of a slot; slot None: the oldest sample not read yet"""
+        if slot is None:
+            if not self._pending:
+                raise ValueError("Monitor.read: no sample is waiting to be read")
+            slot = self._pending[0]
+        out = np.empty(self.n_doubles)
+        t, step = C.c_double(), C.c_int64()
+        L.check(L.lib.qgd_monitor_read(self._h, int(slot), out.ctypes.data_as(L.c_double_p), out.size, C.byref(t), C.byref(step)),
+                "qgd_monitor_read")
+        if slot in self._pending:
+            self._pending.remove(slot)
+        return out, t.value, int(step.value)
+
+    def read(self, slot=None):
+        raw, t, step = self.read_raw(slot)
+        return unpack(raw, self.offsets, t, step)
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._handle.free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def unpack(raw, offsets, time, step):
+    """named arrays of one result block (the layout of include/qgd_amd.h)"""
+    o = offsets
+    hd, integ = raw[o[0]:o[1]], raw[o[1]:o[2]]
+    ex = raw[o[2]:o[3]].reshape(len(EXTREMA_FIELDS), 4)
+    n_probes, n_patches = int(hd[2]), int(hd[3])
+    probes = raw[o[3]:o[4]].reshape(n_probes, len(PROBE_COLUMNS))
+    patches = raw[o[4]:o[4] + n_patches * len(PATCH_COLUMNS)].reshape(n_patches, len(PATCH_COLUMNS))
+    return dict(time=time, step=step, deltaT=float(hd[6]), ownedCells=int(hd[0]), fluxState=int(hd[1]),
+                # fluxState 0: no assembly yet (patch fluxes NaN); 1: all five; 2: implicitDiffusion (mass flux only, the other four NaN)
+                nonFinite=int(hd[4]), firstNonFinite=int(hd[5]),
+                integrals=integ.copy(), volume=float(integ[0]), mass=float(integ[1]), momentum=integ[2:5].copy(),
+                totalEnergy=float(integ[5]), internalEnergy=float(integ[6]), kineticEnergy=float(integ[7]),
+                min=ex[:, 0].copy(), minCell=ex[:, 1].astype(np.int64), max=ex[:, 2].copy(), maxCell=ex[:, 3].astype(np.int64),
+                probes=probes.copy(), patchArea=patches[:, 0].copy(), patchFlux=patches[:, 1:6].copy(),
+                patchPressureForce=patches[:, 6:9].copy(), raw=raw)
+
+
+def combine(parts):
+    """the samples of the ranks of one run as one: sums in rank order, extrema by (value, label) with ties to the lowest label, a probe
+    from the rank that holds its cell (the others carry NaN rows), patch totals summed"""
+    out = dict(parts[0])
+    if len(parts) == 1:
+        return out
+    for key in ("integrals", "momentum", "patchArea", "patchFlux", "patchPressureForce"):
+        acc = np.array(parts[0][key], dtype=np.float64)
+        for p in parts[1:]:
+            acc = acc + p[key]
+        out[key] = acc
+    for key in ("volume", "mass", "totalEnergy", "internalEnergy", "kineticEnergy"):
+        out[key] = float(out["integrals"][INTEGRALS.index(key)])
+    out["ownedCells"] = sum(p["ownedCells"] for p in parts)
+    out["nonFinite"] = sum(p["nonFinite"] for p in parts)
+    bad = [p["firstNonFinite"] for p in parts if p["firstNonFinite"] >= 0]
+    out["firstNonFinite"] = min(bad) if bad else -1
+    for val, cell, sign in (("min", "minCell", 1.0), ("max", "maxCell", -1.0)):
+        v, c = np.array(parts[0][val]), np.array(parts[0][cell])
+        for p in parts[1:]:
+            for k in range(v.size):
+                if p[cell][k] < 0:
+                    continue
+                better = c[k] < 0 or sign * p[val][k] < sign * v[k] or (p[val][k] == v[k] and p[cell][k] < c[k])
+                if better:
+                    v[k], c[k] = p[val][k], p[cell][k]
+        out[val], out[cell] = v, c
+    probes = np.array(parts[0]["probes"])
+    for p in parts[1:]:
+        take = np.isnan(probes).all(axis=1) & ~np.isnan(p["probes"]).all(axis=1)
+        probes[take] = p["probes"][take]
+    out["probes"] = probes
+    out.pop("raw", None)
+    return out
+
+
+# ---- the function objects of system/controlDict (foamfile.read_functions gives the specifications) ----------------------------------------
+def _num(x):
+    return f"{float(x):.17g}"
+
+
+class _Table:
+    """one output file: header once, one row per write"""
+
+    def __init__(self, path, header_lines):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        self.path = path
+        with open(path, "w") as f:
+            f.write("".join(line + "\n" for line in header_lines))
+
+    def row(self, text):
+        with open(self.path, "a") as f:
+            f.write(text + "\n")
+
+
+class ProbesWriter:
+    """OpenFOAM's probes layout: postProcessing/<name>/<startTime>/<field>, one file per field, `# Probe i (x y z)` lines, the probe
+    numbers, `# Time`, then one row per write: the time and one value per probe (vectors in parentheses)"""
+    _COLS = {"rho": (0,), "U": (1, 2, 3), "p": (4,), "T": (5,), "e": (6,)}
+
+    def __init__(self, out_dir, spec, found):
+        self.fields = list(spec["fields"])
+        locs = np.asarray(spec["probeLocations"], dtype=np.float64).reshape(-1, 3)
+        head = [f"# Probe {i} ({_num(x[0])} {_num(x[1])} {_num(x[2])})" + ("" if found[i] else "  # Not Found") for i, x in enumerate(locs)]
+        head.append("# Probe " + " ".join(str(i) for i in range(len(locs))))
+        head.append("# Time")
+        self.tables = {f: _Table(os.path.join(out_dir, f), head) for f in self.fields}
+
+    def write(self, t, s):
+        for f, table in self.tables.items():
+            cols = self._COLS[f]
+            vals = [(_num(r[cols[0]]) if len(cols) == 1 else "(" + " ".join(_num(r[c]) for c in cols) + ")") for r in s["probes"]]
+            table.row(" ".join([_num(t)] + vals))
+
+
+class FieldMinMaxWriter:
+    """fieldMinMax.dat: per write one row -- the time, then per field min, its cell and the cell's centre, max, its cell and centre
+    (U stands for mag(U), as fieldMinMax's default mode has it)"""
+    _INDEX = {"rho": 0, "p": 1, "T": 2, "U": 3, "mag(U)": 3, "Mach": 4}
+
+    def __init__(self, out_dir, spec, centres, file_label):
+        self.fields = list(spec["fields"])
+        self.centres, self.file_label = centres, file_label
+        cols = ["Time"]
+        for f in self.fields:
+            n = "mag(U)" if f == "U" else f
+            for w in ("min", "max"):
+                cols += [f"{w}({n})", f"cell({w})", f"x({w})", f"y({w})", f"z({w})"]
+        self.table = _Table(os.path.join(out_dir, "fieldMinMax.dat"), ["# Field minima and maxima", "# " + "\t".join(cols)])
+
+    def write(self, t, s):
+        row = [_num(t)]
+        for f in self.fields:
+            k = self._INDEX[f]
+            for val, cell in (("min", "minCell"), ("max", "maxCell")):
+                c = int(s[cell][k])
+                x = self.centres[c] if c >= 0 else (np.nan,) * 3
+                row += [_num(s[val][k]), str(int(self.file_label[c]) if c >= 0 else -1)] + [_num(v) for v in x]
+        self.table.row("\t".join(row))
+
+
+class IntegralsWriter:
+    """volIntegrals.dat: the time, the eight volume integrals, the count of non-finite cells and the first of them (-1: none)"""
+
+    def __init__(self, out_dir, spec, file_label):
+        self.file_label = file_label
+        self.table = _Table(os.path.join(out_dir, "volIntegrals.dat"),
+                            ["# Volume integrals over the mesh", "# " + "\t".join(("Time",) + INTEGRALS + ("nonFiniteCells", "firstNonFiniteCell"))])
+
+    def write(self, t, s):
+        first = int(self.file_label[s["firstNonFinite"]]) if s["firstNonFinite"] >= 0 else -1
+        self.table.row("\t".join([_num(t)] + [_num(v) for v in s["integrals"]] + [str(int(s["nonFinite"])), str(first)]))
+
+
+class PatchFluxWriter:
+    """patchFluxes.dat: the time, then per patch its area, the five net fluxes out of the domain (mass, momentum, total energy: what the
+    cell update consumed in the step that produced the state) and sum p_b Sf"""
+
+    def __init__(self, out_dir, spec, rows):
+        self.rows = rows                    # rows of the monitor's patch table, in the order of spec["patches"]
+        cols = ["Time"] + [f"{p}:{c}" for p in spec["patches"] for c in PATCH_COLUMNS]
+        self.table = _Table(os.path.join(out_dir, "patchFluxes.dat"), ["# Patch totals of the net face fluxes", "# " + "\t".join(cols)])
+
+    def write(self, t, s):
+        row = [_num(t)]
+        for r in self.rows:
+            row += [_num(s["patchArea"][r])] + [_num(v) for v in s["patchFlux"][r]] + [_num(v) for v in s["patchPressureForce"][r]]
+        self.table.row("\t".join(row))
+
+
+class FunctionObjects:
+    """the served functions of a run: one Monitor for all of them, sampled after the steps at which a function is due, read two samples
+    late.  ``local_of`` maps a cell label of the file mesh (as relabelled for the device) to this rank's label or -1; ``file_label`` maps
+    it back to the label in the case files; ``gather`` (None on one rank) is all_gather_object."""
+
+    def __init__(self, case, specs, file_mesh, case_dir, start_name, local_of, file_label, is_root=True, gather=None, log=print):
+        self.specs, self.is_root, self.gather = specs, is_root, gather
+        locations = [np.asarray(s["probeLocations"], dtype=np.float64).reshape(-1, 3) for s in specs if s["type"] == "probes"]
+        cells = file_mesh.find_cells(np.concatenate(locations)) if locations else np.zeros(0, dtype=np.int64)
+        names = list(getattr(file_mesh, "patch_names", []))
+        patch_rows, patches = {}, []
+        for s in specs:
+            for p in s.get("patches", []):
+                if p not in names:
+                    raise ValueError(f"functions: '{s['name']}': no patch named '{p}' (patches: {', '.join(names)})")
+                if p not in patch_rows:
+                    patch_rows[p] = len(patches)
+                    patches.append(names.index(p))
+        self.monitor = Monitor(case, probes=[local_of(int(c)) if c >= 0 else -1 for c in cells], patches=patches)
+        self.writers = []
+        centres = file_mesh.array("C").reshape(-1, 3)
+        at = 0
+        for s in specs:
+            out_dir = os.path.join(case_dir, "postProcessing", s["name"], start_name)
+            w = None
+            if s["type"] == "probes":
+                n = len(np.asarray(s["probeLocations"]).reshape(-1, 3))
+                rows = slice(at, at + n)
+                at += n
+                if is_root:
+                    for i, c in enumerate(cells[rows]):
+                        if c < 0:
+                            log(f"functions: '{s['name']}': probe {i} is outside the mesh: its column reads nan")
+                    w = ProbesWriter(out_dir, s, cells[rows] >= 0)
+                    w.rows = rows
+            elif not is_root:
+                pass
+            elif s["type"] == "fieldMinMax":
+                w = FieldMinMaxWriter(out_dir, s, centres, file_label)
+            elif s["type"] == "qgdIntegrals":
+                w = IntegralsWriter(out_dir, s, file_label)
+            elif s["type"] == "qgdPatchFluxes":
+                w = PatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]])
+            self.writers.append(w)
+        self._waiting = collections.deque()   # (due specs) of the samples not read yet
+
+    def next_due(self, step):
+        """steps from `step` to the next one at which some function writes"""
+        return min(s["interval"] - step % s["interval"] for s in self.specs)
+
+    def after_step(self, step, t0):
+        due = [i for i, s in enumerate(self.specs) if step % s["interval"] == 0]
+        if not due:
+            return
+        self.monitor.sample()
+        self._waiting.append((due, t0))
+        while len(self._waiting) > 2:
+            self._flush_one()
+
+    def _flush_one(self):
+        due, t0 = self._waiting.popleft()
+        s = self.monitor.read()
+        if self.gather is not None:
+            s.pop("raw", None)
+            s = combine(self.gather(s))
+        if not self.is_root:
+            return
+        t = t0 + s["time"]
+        for i in due:
+            w = self.writers[i]
+            if isinstance(w, ProbesWriter):
+                w.write(t, dict(s, probes=s["probes"][w.rows]))
+            elif w is not None:
+                w.write(t, s)
+
+    def finish(self):
+        while self._waiting:
+            self._flush_one()
+        self.monitor.close()

@@ -89,6 +89,7 @@ class QGDFoamCase:
         L.check(L.lib.qgd_case_create(dev._h, C.byref(self.options), C.byref(h)), "qgd_case_create")
         self._handle = L.NativeHandle(h, L.lib.qgd_case_free)
         dev.adopt(self._handle)
+        self._monitor_handles = []
         self.thermo = QGDThermo(self)
 
     def set_bc(self, patch, U=("zeroGradient", None), T=("zeroGradient", None), p=("zeroGradient", None)):
@@ -229,6 +230,16 @@ class QGDFoamCase:
                     f"qgd_case_get_field({name})")
         return out
 
+    def monitor(self, probes=None, patches=None):
+        """a run monitor of this case (monitor.Monitor; qgd_monitor_create): volume integrals, extrema with their cells, the first
+        non-finite cell, the values at ``probes`` (cell labels of this device's mesh, -1 = not on this rank; PolyMesh.find_cells
+        locates points) and the totals of the net face fluxes over ``patches`` (indices of real patches), formed on the device by
+        ``sample()`` and fetched by ``read()``.  After set_fields.  The monitor is freed with the case where still open."""
+        from .monitor import Monitor
+        m = Monitor(self, probes=probes, patches=patches)
+        self._monitor_handles = [h for h in self._monitor_handles if h.value] + [m._handle]
+        return m
+
     def info(self):
         a = (C.c_double * 6)()
         L.check(L.lib.qgd_case_info(self._h, a), "qgd_case_info")
@@ -353,6 +364,9 @@ class QGDFoamCase:
 
     def close(self):
         if getattr(self, "_handle", None):
+            for h in getattr(self, "_monitor_handles", ()):   # a monitor keeps a pointer to its case: freed before it (NativeHandle: once)
+                h.free()
+            self._monitor_handles = []
             self._handle.free()
 
     def __del__(self):
