@@ -702,6 +702,40 @@ int qgd_case_set_var_sc(qgd_case_t c, const qgd_var_sc_options* opt, const int32
 /* out[0] = max, out[1] = min of ScQGD over the owned cells (the reference's "max/min ScQGD" line), computed when asked. */
 int qgd_case_sc_range(qgd_case_t c, double out[2]);
 
+/* Species mass fractions carried by the case: the species block of reactingLagrangianQGDFoam [reactingLagrangianQGDFoam_8C_source.html
+ * L92-140].  Every qgd_case_step then advances nSpecies fields Y_i with the flow, in the reference's order: the species fluxes
+ * [reactingLagrangianQGDFoam_2updateFluxes_8H_source.html L103-132], QGDRhoEqn, the species equations [QGDYEqn_8H_source.html L38-92,
+ * explicit branch L67-86], QGDUEqn, QGDEEqn:
+ *     phiJmY_i = phiJm Yf_i - phi tauQGDf (Uf & fvsc::grad(Y_i)),   ddt(rho Y_i) + div(phiJmY_i) - laplacian(muf / Sc_i, Y_i) = 0,
+ *     Y_i.max(0),   Y_inert = max(1 - sum of the others, 0),
+ * with the case's stencil (reduced, leastSquares 2-D, GaussVolPoint 2-D / 3-D) and the uncorrected snGrad in the laplacian.
+ * The composition is PASSIVE: all species share the case's one `mixture` thermo; there is no chemistry (combustion->R), no parcel
+ * source, and Y does not feed back into thermo.  Reacting thermo is out of scope.
+ * The block reads the mass flux of every face, which the fused kernels never write: a case with species runs the three-kernel explicit
+ * step (fixed or adjusted deltaT) -- qgd_case_fused_info reports 0 after this call.
+ * Legal after qgd_case_create and before qgd_case_set_fields (QGD_ERR_INVALID afterwards).  At most QGD_MAX_SPECIES species.
+ * QGD_ERR_NOT_IMPLEMENTED, with the reason named: implicitDiffusion true, a sharded device, a periodic (qgd_mesh_unroll_cyclic)
+ * device, per-term stencils (qgd_case_options::termStencil).  QGD_ERR_INVALID: nSpecies < 2 or > QGD_MAX_SPECIES, inertIndex out of
+ * range, a Schmidt number <= 0 (ScNumbers == NULL: all 1), unknown flags.  Not served: monitors of species.
+ * qgd_case_step_phase is refused on a case with species; qgd_case_step (and qgd_case_step_sharded, which steps an unsharded device the same
+ * way) with a species whose field was never set is QGD_ERR_INVALID.
+ * These five entries were added without a change of QGD_ABI_VERSION (no struct grew, no existing entry changed its meaning): a host that
+ * must run against older builds of the library looks the symbols up (dlsym) instead of comparing the number. */
+#define QGD_MAX_SPECIES 32
+#define QGD_SPECIES_KEEP_FLUXES 1   /* flags: keep phiJmY_i and diffusiveFlux_i of the last step (qgd_case_get_species_field) */
+int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, const double* ScNumbers, int32_t flags);
+/* Boundary condition of one species on one patch: QGD_BC_ZEROGRADIENT (the default of generic patches), QGD_BC_FIXEDVALUE with one
+ * value for the patch, QGD_BC_NONE; constraint patches keep QGD_BC_NONE (their faces carry no species flux, or a zero gradient). */
+int qgd_case_set_species_bc(qgd_case_t c, int32_t species, int32_t patch, int32_t bc, double value);
+/* Cell values of one species (nCells doubles, HOST); its patch values follow from its boundary conditions. */
+int qgd_case_set_species_fields(qgd_case_t c, int32_t species, const double* Y);
+/* "Y" (nCells), "Y.boundary" (nBoundaryFaces); with QGD_SPECIES_KEEP_FLUXES also "phiJmY" and "diffusiveFlux" (nFaces, by face label)
+ * as the last step formed them: the inert species' phiJmY is zero, its diffusiveFlux minus the sum of the others' [QGDYEqn.H L83]. */
+int qgd_case_get_species_field(qgd_case_t c, int32_t species, const char* name, double* out, int64_t outDoubles);
+/* info[0] = nSpecies (0: the case carries none), [1] = inertIndex, [2] = species per register batch of the face and cell kernels,
+ * [3] = 1 with QGD_SPECIES_KEEP_FLUXES */
+int qgd_case_species_info(qgd_case_t c, int64_t info[4]);
+
 /* Initial cell fields U (nCells*3), T, p (HOST pointers); evaluates the BCs,
  * thermo.correct() and the derived conserved fields like createFields.H
  * [QGDFoam_2createFields_8H_source.html L3-109]. */

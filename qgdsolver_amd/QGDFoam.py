@@ -109,7 +109,11 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
     # this driver builds the block tables for a fixed-deltaT case with one GaussVolPoint stencil only: an adjustTimeStep case, which the library
     # can step on the blocks as well (QGD_FUSED_ADJUST, include/qgd_amd.h qgd_case_fused_info), runs the separate kernels here
     # (the blocks serve the explicit branch's one-launch step, shards included, and the implicitDiffusion branch's assembly of the U systems on one rank)
-    eligible = (not (opt.get("adjustTimeStep") or opt.get("termStencils")) and opt["stencil"] == "GaussVolPoint"
+    species = opt.get("species")
+    if species and (world > 1 or getattr(gmesh, "cyclic_pairs", None)):
+        raise ff.FoamFileError(f"{case_dir}: a case with species runs on one rank, on a mesh without cyclic patches")
+    # (a case with species steps with the separate kernels: its species block reads the mass flux of every face)
+    eligible = (not (opt.get("adjustTimeStep") or opt.get("termStencils") or species) and opt["stencil"] == "GaussVolPoint"
                 and not (opt.get("implicitDiffusion") and world > 1))
     dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}}, fused_tables=eligible)
     case = QGDFoamCase(dev, default_options(**opt))
@@ -141,6 +145,9 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         cs = var_sc["const_cells"]
         local_cells = np.nonzero(np.isin(cells, cs))[0].astype(np.int32) if cs is not None else None
         case.set_var_sc(**dict(var_sc, const_cells=local_cells))
+    if species:
+        # the species block of reactingLagrangianQGDFoam, passive: the Y_i advance with the flow on the device (QGDFoamCase.set_species)
+        ff.apply_species(case, species, cells)
     case.set_fields(fields["U"][cells], fields["T"][cells], fields["p"][cells])
     adjust = bool(case.options.adjustTimeStep)
     if world > 1:
@@ -253,6 +260,8 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
     branch = "implicitDiffusion true" if opt.get("implicitDiffusion") else "explicit branch"
     log(f"QGDFoam (qgdsolver_amd, {branch}): {n_global} cells on {world} rank(s), fvsc {opt['stencil']}, "
         f"deltaT {dt:g}, start {t0_name}, cell order {renumber}")
+    if species:
+        log(f"  species {' '.join(species['names'])} (inert {species['inert']}): passive composition, one thermo, no chemistry")
     if opt.get("implicitDiffusion"):
         x = os.environ.get("QGD_IMPL_XEXTRAP", "3")
         if x != "0":
@@ -312,6 +321,12 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             data = {f: gather(f) for f in ("U", "T", "p", "rho") + (("ScQGD",) if var_sc else ())}
             if rank == 0:
                 _write_cell_fields(case_dir, name, data, bcs, gmesh, var_sc)
+            if species:
+                Y = {}
+                for sn in species["names"]:
+                    Y[sn] = np.empty(n_global)
+                    Y[sn][cells] = case.species_field(sn)
+                ff.write_species_fields(case_dir, name, gmesh, species, Y)
             written.append(name)
         if total is None and t >= end_time - 1e-12 * max(1.0, abs(end_time)):
             break

@@ -367,6 +367,14 @@ struct qgd_case_s {
     VarScView vsc{};
     uint8_t* constCellDev = nullptr;
     double* scPart = nullptr;   // partials of qgd_case_sc_range
+    // species mass fractions (qgd_case_set_species; qgd_species.hip): sp.nS == 0: none.  The host tables of the per-species per-patch boundary
+    // conditions go to the device, and the patch values are evaluated from them, before the first use after a change (spDirty)
+    SpeciesView sp{};
+    std::vector<uint8_t> spBcKind, spFieldSet;
+    std::vector<double> spBcVal;
+    uint8_t* spBcKindDev = nullptr;
+    double* spBcValDev = nullptr;
+    bool spDirty = false, spKeep = false, spFluxesValid = false;
     double time = 0;
     int64_t steps = 0;
     // timing
@@ -1905,6 +1913,157 @@ int qgd_case_sc_range(qgd_case_t c, double out[2]) {
     QGD_CATCH
 }
 
+// ---- species mass fractions carried by the case (qgd_species.hip) ---------------------------------------------------------------
+int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, const double* ScNumbers, int32_t flags) {
+    QGD_TRY
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    qgd_device_s* d = c->dev;
+    if (c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_case_set_species: call it before qgd_case_set_fields");
+    if (c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_set_species: the case carries species already");
+    if (c->opt.implicitDiffusion)
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: implicitDiffusion true is not served (the species equations' fvm::laplacian branch, "
+                                             "QGDYEqn.H L47-66, is a stateless operator only: qgd_species_step_implicit); set implicitDiffusion false");
+    if (d->periodic())
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: a periodic device (cyclic patches served by ghost copies, qgd_mesh_unroll_cyclic) is not served: "
+                                             "the copies would need the species' values");
+    if (d->sharded())
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: a sharded device is not served (the halo messages carry no species)");
+    if (c->mixB >= 0)
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: per-term stencils (qgd_case_options::termStencil) are not served: fvsc::grad(Y) has no entry of its own");
+    if (nSpecies < 2) return fail(QGD_ERR_INVALID, "qgd_case_set_species: nSpecies must be at least 2 (one transported species and the inert one)");
+    if (nSpecies > QGD_MAX_SPECIES) return fail(QGD_ERR_INVALID, "qgd_case_set_species: at most " + std::to_string(QGD_MAX_SPECIES) + " species are served");
+    if (inertIndex < 0 || inertIndex >= nSpecies) return fail(QGD_ERR_INVALID, "qgd_case_set_species: inertIndex out of range");
+    if (flags & ~QGD_SPECIES_KEEP_FLUXES) return fail(QGD_ERR_INVALID, "qgd_case_set_species: unknown flags");
+    for (int32_t i = 0; ScNumbers && i < nSpecies; ++i)
+        if (!(ScNumbers[i] > 0) || !std::isfinite(ScNumbers[i]))
+            return fail(QGD_ERR_INVALID, "qgd_case_set_species: the Schmidt number of species " + std::to_string(i) + " must be positive (Sc <= 0)");
+    static_assert(QGD_MAX_SPECIES <= QGD_MAX_SPECIES_DEV, "SpeciesView tables");
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    const MeshView& m = d->view;
+    DeviceArena& a = c->arena;
+    SpeciesView sv{};
+    const size_t nS = (size_t)nSpecies, nP = std::max<size_t>(c->bc.size(), 1);
+    sv.nS = nSpecies; sv.inert = inertIndex; sv.nPatches = (int32_t)nP;
+    for (int32_t i = 0; i < nSpecies; ++i) {
+        sv.Sc[i] = ScNumbers ? ScNumbers[i] : 1.0;
+        if (i != inertIndex) sv.act[sv.nAct++] = i;
+    }
+    sv.Y = a.alloc<double>(nS * std::max<size_t>((size_t)m.nC, 1));
+    sv.Yb = a.alloc<double>(nS * std::max<size_t>((size_t)m.nBF, 1));
+    const size_t nAct = (size_t)sv.nAct;   // the inert species is not transported: no vertex values, no face flux of its own
+    sv.ptY = c->usesPoints ? a.alloc<double>(nAct * std::max<size_t>((size_t)m.nP, 1)) : nullptr;
+    sv.F = a.alloc<double>(nAct * std::max<size_t>((size_t)m.nF, 1));
+    c->spKeep = (flags & QGD_SPECIES_KEEP_FLUXES) != 0;
+    if (c->spKeep) { sv.phiJmY = a.alloc<double>(nS * std::max<size_t>((size_t)m.nF, 1)); sv.dflux = a.alloc<double>(nS * std::max<size_t>((size_t)m.nF, 1)); }
+    c->spBcKindDev = a.alloc<uint8_t>(nS * nP);
+    c->spBcValDev = a.alloc<double>(nS * nP);
+    sv.bcKind = c->spBcKindDev; sv.bcVal = c->spBcValDev;
+    c->spBcKind.assign(nS * nP, (uint8_t)QGD_BC_NONE);
+    c->spBcVal.assign(nS * nP, 0.0);
+    for (size_t i = 0; i < nS; ++i)
+        for (size_t p = 0; p < c->bc.size(); ++p)
+            if (d->patches[p].type == QGD_PATCH_GENERIC) c->spBcKind[i * nP + p] = (uint8_t)QGD_BC_ZEROGRADIENT;
+    c->spFieldSet.assign(nS, 0);
+    c->sp = sv;
+    c->spDirty = true;
+    c->spFluxesValid = false;
+    // the species block reads phiJm of every face, which the fused kernels never write: the three-kernel explicit step
+    c->fused = false;
+    c->fusedAdj = false;
+    c->view.nBlkFace = c->view.fuBlkFace;
+    return QGD_OK;
+    QGD_CATCH
+}
+
+int qgd_case_set_species_bc(qgd_case_t c, int32_t species, int32_t patch, int32_t bc, double value) {
+    QGD_TRY
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    if (!c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_set_species_bc: the case carries no species (qgd_case_set_species)");
+    if (species < 0 || species >= c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_set_species_bc: species out of range");
+    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, "qgd_case_set_species_bc: patch out of range");
+    if (bc != QGD_BC_ZEROGRADIENT && bc != QGD_BC_FIXEDVALUE && bc != QGD_BC_NONE)
+        return fail(QGD_ERR_INVALID, "qgd_case_set_species_bc: a species takes zeroGradient, fixedValue or none");
+    if (bc == QGD_BC_FIXEDVALUE && !std::isfinite(value)) return fail(QGD_ERR_INVALID, "qgd_case_set_species_bc: the value must be finite");
+    if (c->dev->patches[patch].type != QGD_PATCH_GENERIC) bc = QGD_BC_NONE;   // a constraint patch keeps its own field type
+    const size_t e = (size_t)species * c->sp.nPatches + patch;
+    c->spBcKind[e] = (uint8_t)bc;
+    c->spBcVal[e] = bc == QGD_BC_FIXEDVALUE ? value : 0.0;
+    c->spDirty = true;
+    return QGD_OK;
+    QGD_CATCH
+}
+
+int qgd_case_set_species_fields(qgd_case_t c, int32_t species, const double* Y) {
+    QGD_TRY
+    if (!c || !Y) return fail(QGD_ERR_INVALID, "qgd_case_set_species_fields: null argument");
+    if (!c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_set_species_fields: the case carries no species (qgd_case_set_species)");
+    if (species < 0 || species >= c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_set_species_fields: species out of range");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    const MeshView& m = c->dev->view;
+    HIP_CHECK(hipStreamSynchronize(c->stream()));
+    if (m.nC) HIP_CHECK(hipMemcpy(c->sp.Y + (size_t)species * m.nC, Y, sizeof(double) * (size_t)m.nC, hipMemcpyHostToDevice));
+    c->spFieldSet[species] = 1;
+    c->spDirty = true;
+    c->spFluxesValid = false;
+    return QGD_OK;
+    QGD_CATCH
+}
+
+// before the first use after a change: every species has its field, the boundary-condition tables are on the device, the patch values follow them
+static int speciesReady(qgd_case_s* c, const char* who) {
+    for (int32_t i = 0; i < c->sp.nS; ++i)
+        if (!c->spFieldSet[i])
+            return fail(QGD_ERR_INVALID, std::string(who) + ": the field of species " + std::to_string(i) + " was never set (qgd_case_set_species_fields)");
+    if (!c->spDirty) return QGD_OK;
+    HIP_CHECK(hipStreamSynchronize(c->stream()));
+    HIP_CHECK(hipMemcpy(c->spBcKindDev, c->spBcKind.data(), c->spBcKind.size(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(c->spBcValDev, c->spBcVal.data(), sizeof(double) * c->spBcVal.size(), hipMemcpyHostToDevice));
+    (void)hipGetLastError();
+    launchSpeciesPatchValues(c->stream(), c->dev->view, c->sp);
+    HIP_CHECK(hipGetLastError());
+    c->spDirty = false;
+    return QGD_OK;
+}
+
+int qgd_case_get_species_field(qgd_case_t c, int32_t species, const char* name, double* out, int64_t outDoubles) {
+    QGD_TRY
+    if (!c || !name || !out) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: null argument");
+    if (!c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: the case carries no species (qgd_case_set_species)");
+    if (species < 0 || species >= c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: species out of range");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    const MeshView& m = c->dev->view;
+    const std::string s(name);
+    const double* src = nullptr;
+    int64_t n = 0;
+    if (s == "Y" || s == "Y.boundary") {
+        if (!c->spFieldSet[species]) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: the field of species " + std::to_string(species) + " was never set");
+        if (s == "Y") { src = c->sp.Y + (size_t)species * m.nC; n = m.nC; }
+        else {
+            const int rs = speciesReady(c, "qgd_case_get_species_field");
+            if (rs) return rs;
+            src = c->sp.Yb + (size_t)species * m.nBF; n = m.nBF;
+        }
+    } else if (s == "phiJmY" || s == "diffusiveFlux") {
+        if (!c->spKeep) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: " + s + " is kept with QGD_SPECIES_KEEP_FLUXES only");
+        if (!c->spFluxesValid) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: " + s + " is formed by a step; none has run since the fields were set");
+        src = (s == "phiJmY" ? c->sp.phiJmY : c->sp.dflux) + (size_t)species * m.nF; n = m.nF;
+    } else return fail(QGD_ERR_UNKNOWN_NAME, "qgd_case_get_species_field: unknown field " + s);
+    if (n > outDoubles) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: output too small");
+    HIP_CHECK(hipStreamSynchronize(c->stream()));
+    if (n) HIP_CHECK(hipMemcpy(out, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    return QGD_OK;
+    QGD_CATCH
+}
+
+int qgd_case_species_info(qgd_case_t c, int64_t info[4]) {
+    if (!c || !info) return fail(QGD_ERR_INVALID, "null argument");
+    info[0] = c->sp.nS;
+    info[1] = c->sp.nS ? c->sp.inert : -1;
+    info[2] = speciesBatchWidth();
+    info[3] = c->spKeep ? 1 : 0;
+    return QGD_OK;
+}
+
 // one flux-assembly pass (updateFields.H + updateFluxes.H) on the current state; part 0 = all of it, 1 = up to p's mid-step boundary
 // conditions, 2 = the rest.  A shard whose GaussVolPoint stencil meets a qgdFlux wall exchanges the mid-step patch pressure of the
 // boundary layer's patch faces between 1 and 2 (midExchangeNeeded): a ghost cell's patch face forms it from an incomplete stencil, and the
@@ -1979,6 +2138,7 @@ int qgd_case_set_fields(qgd_case_t c, const double* U, const double* T, const do
     c->ghostsCurrent = false;  // (cyclic pairs served by ghost cells: the copies take their originals' records before the first step)
     c->fieldsSet = true;
     c->fluxAssembled = false;
+    c->spFluxesValid = false;  // (the species fluxes kept from a step before this call are no longer "the last step's")
     c->gradUValid = false;
     c->impl.have = 0;          // the start values of the implicit solves begin without a history
     c->time = 0; c->steps = 0;
@@ -2142,6 +2302,9 @@ static void stepAdvance(qgd_case_s* c, int part) {
         return;
     }
     if (part == 0) {
+        // the species block reads the old records, the assembled mass flux and this step's deltaT: ahead of the flow's cell update
+        // [reactingLagrangianQGDFoam_8C L92-140: QGDRhoEqn, QGDYEqn, QGDUEqn, QGDEEqn]
+        if (c->sp.nS) { launchSpeciesAdvance(L.stream, c->stencil, m, c->view, c->gas, c->sp); c->spFluxesValid = true; }
         launchCellUpdate(L, m, c->view, c->gas, 0, nullptr, 0);
         launchBoundaryUpdate(L, m, c->view, c->gas, c->bcDev, false, c->phiwRegistered, 0, nullptr, 0);
     } else if (part == 1) {
@@ -2178,6 +2341,7 @@ int qgd_case_step(qgd_case_t c, int32_t nSteps) {
         HIP_CHECK(hipStreamSynchronize(c->stream()));
         return QGD_OK;
     }
+    if (c->sp.nS) { const int rs = speciesReady(c, "qgd_case_step"); if (rs) return rs; }
     for (int i = 0; i < nSteps; ++i) { stepAssemble(c); stepAdvance(c, 0); }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream()));
@@ -2189,6 +2353,8 @@ int qgd_case_step_phase(qgd_case_t c, int phase) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_case_step_phase: call qgd_case_set_fields first");
+    if (c->sp.nS)
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_step_phase: the case carries species (qgd_case_set_species), which advance inside qgd_case_step only");
     if (c->dev->periodic())
         return fail(QGD_ERR_INVALID, "qgd_case_step_phase: a periodic device (cyclic patches served by ghost copies, qgd_mesh_unroll_cyclic) is stepped with "
                                      "qgd_case_step, which refreshes the copies after every step; a phase would compute on stale copies");
@@ -3345,6 +3511,8 @@ int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, i
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_case_step_sharded: call qgd_case_set_fields first");
+    // (a case with species lives on an unsharded device, which this entry steps like qgd_case_step)
+    if (c->sp.nS) { const int rs = speciesReady(c, "qgd_case_step_sharded"); if (rs) return rs; }
     const bool sharded = !c->dev->halo.empty() && nSlots > 0;
     if (sharded && (!comm || !peers)) return fail(QGD_ERR_INVALID, "qgd_case_step_sharded: null argument");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));

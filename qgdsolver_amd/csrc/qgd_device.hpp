@@ -211,6 +211,28 @@ void launchFaceGeoPos(hipStream_t s, const MeshView& m, double4* out);   // fill
 void launchVarSc7(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, const VarScView& v, bool init);
 void launchVarScRange(hipStream_t s, const VarScView& v, int32_t begin, int32_t end);   // {max, min} over cells [begin, end) -> v.part[2 * QGD_FACE_REDUCE_PARTIALS ...]
 
+// ---- species mass fractions carried by a case (qgd_species.hip; qgd_case_set_species of include/qgd_amd.h) ------------------------
+// Passive composition [reactingLagrangianQGDFoam: updateFluxes.H L103-132, QGDYEqn.H L38-92, explicit branch]: every species shares the
+// case's one thermo; no chemistry, no parcel source, no feedback of Y into thermo.
+#define QGD_MAX_SPECIES_DEV 32
+struct SpeciesView {
+    int32_t nS, inert, nAct, nPatches;
+    int32_t act[QGD_MAX_SPECIES_DEV];   // the species that are transported (all but the inert one), in their own order
+    double Sc[QGD_MAX_SPECIES_DEV];     // ScNumbers
+    double* Y;                          // nS * nC, species-major: Y[i * nC + cell]
+    double* Yb;                         // nS * nBF patch values
+    double* ptY;                        // nAct * nP vertex values of the transported species, plane a = species act[a] (GaussVolPoint only, else nullptr)
+    double* F;                          // nAct * nF, plane a = species act[a]: phiJmY_i - (muf/Sc_i) snGrad(Y_i) |Sf| at the faces' slot-major positions (MeshView::fpos)
+    double* phiJmY; double* dflux;      // nS * nF by face label, QGD_SPECIES_KEEP_FLUXES only (else nullptr)
+    const uint8_t* bcKind;              // nS * nPatches: QGD_BC_NONE / _ZEROGRADIENT / _FIXEDVALUE
+    const double* bcVal;                // nS * nPatches: the value of a fixedValue entry
+};
+// one step of every species on the OLD records and the assembled mass flux (CaseView::flux plane 0), deltaT from CaseView::dt: between
+// launchDeltaT and the flow's cell update; leaves the patch values of the new time level behind
+void launchSpeciesAdvance(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv);
+void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesView& sv);
+int speciesBatchWidth();
+
 // ---- run monitors (qgd_monitor.hip; qgd_monitor_* of include/qgd_amd.h) ---------------------------------------------------------
 #define QGD_MONITOR_BLOCKS 1024      // most workgroups of monitorCellKernel (its lanes stride over the owned cells beyond that)
 #define QGD_MONITOR_SUMS 8           // V, rho V, rho U V (3), rho E V, rho e V, rho |U|^2/2 V

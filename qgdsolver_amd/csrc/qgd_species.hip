@@ -1,0 +1,283 @@
+// qgd_species.hip -- the species block of reactingLagrangianQGDFoam resident in a QGDFoam case (gfx950 / CDNA4, wave64).
+//
+// A case with species (qgd_case_set_species) advances nS mass fractions Y_i with the flow, inside qgd_case_step, in the reference's
+// order [reactingLagrangianQGDFoam_8C L92-140]: updateFluxes.H L103-132, QGDRhoEqn, QGDYEqn.H L38-92, QGDUEqn, QGDEEqn.  The composition
+// is PASSIVE: every species shares the case's one `mixture` thermo; no chemistry (combustion->R), no parcel source, no feedback of Y into
+// thermo.  Explicit branch only (QGDYEqn.H L67-86).
+//
+//   SP  caseSpeciesPointKernel / caseSpeciesBoundaryPointKernel   GaussVolPoint: vertex values of ALL species in one walk over the points
+//   SF  caseSpeciesFaceKernel<ST, W>        internal faces: labels, geometry, phiJm (plane 0 of CaseView::flux) and the two cells' records are
+//                                       loaded once; tauQGDf, Uf, phi, muf are rebuilt from the records in registers (none of the four is
+//                                       materialised); the species follow in register batches of W
+//   SFB caseSpeciesBoundaryFaceKernel<ST, W> the same on patch faces (mirror-point stencil, patch records)
+//   SC  caseSpeciesCellKernel<W>            one lane per cell over the cell -> face table, no atomics: rhoNew from phiJm and the device's deltaT
+//                                       (the value the flow's cell update forms), then Y_i, Yi.max(0), Y_inert = max(1 - sum, 0)
+//   SB  caseSpeciesPatchKernel              patch values for the next step
+//
+// Per species the face kernels form [updateFluxes.H L122-127, QGDYEqn.H L75, L82]
+//     gradYf, phiJmY_i = phiJm Yf_i - phi tauQGDf (Uf & gradYf), lap_i = (muf / Sc_i) snGrad(Y_i.old) |Sf|
+// and write ONE number, phiJmY_i - lap_i, at the face's slot-major position (MeshView::fpos), so the cell kernel reads contiguously.
+// With QGD_SPECIES_KEEP_FLUXES they also write phiJmY_i and diffusiveFlux_i by face label; the inert species' diffusiveFlux, cleared at
+// updateFluxes.H L103-116, is minus the running sum of the others' [QGDYEqn.H L83].
+//
+// The gradients are those of qgd_stencil_dev.hpp (faceGradient: reduced, leastSquares 2-D, GaussVolPoint 2-D / 3-D with the nf*snGrad
+// fallback on faces with more than four vertices and on degenerate faces), one call per species of a batch on the species' own plane:
+// what does not depend on the species -- geometry loads, the GaussVolPoint coefficients -- is common to the calls of a batch.
+#include "qgd_device.hpp"
+
+#include "../../include/qgd_amd.h"
+#include "qgd_stencil_dev.hpp"
+
+namespace qgd {
+
+#define QGD_SPECIES_W 4   // species per register batch (qgd_case_species_info reports it; profiles/kernel_resources.txt lists the instantiations: none spills)
+
+static inline int gridOfS(int64_t n) { return (int)((n + QGD_BLOCK - 1) / QGD_BLOCK); }
+
+// what a face knows before the species come: loaded / rebuilt once
+struct SpeciesFace {
+    double phiJm, phiTau, Uf[3], mufS;   // phiTau = phi tauQGDf; mufS = muf |Sf|
+    double w, dn;
+    int o, n;                            // n: neighbour cell (internal) or boundary face index (patch)
+};
+
+// the species a0 .. a0 + W - 1 of the transported ones on one face (slots past the last species repeat it and store nothing)
+template <int ST, int W, bool INTERNAL>
+__device__ __forceinline__ void speciesBatch(const MeshView& m, const SpeciesView& sv, const SpeciesFace& F, const int f, const size_t pos,
+                                             const int a0, double& inertDf) {
+    const size_t nC = (size_t)m.nC, nP = (size_t)m.nP, nF = (size_t)m.nF, nBF = (size_t)m.nBF;
+    int sp[W], slot[W];   // the species' label, and its place among the transported ones: the planes of F and ptY
+    FaceVals<1> v[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        slot[k] = min(a0 + k, sv.nAct - 1);
+        sp[k] = sv.act[slot[k]];
+        const double* __restrict__ Y = sv.Y + (size_t)sp[k] * nC;
+        v[k].o[0] = Y[F.o];
+        if (INTERNAL) { v[k].n[0] = Y[F.n]; v[k].sn[0] = 0.0; }
+        else { v[k].n[0] = sv.Yb[(size_t)sp[k] * nBF + F.n]; v[k].sn[0] = F.dn * (v[k].n[0] - v[k].o[0]); }   // fvPatchField::snGrad (L0)
+    }
+    double g[W][3];
+#pragma unroll
+    for (int k = 0; k < W; ++k)
+        faceGradient<ST, 1, -1>(m, f, v[k], sv.Y + (size_t)sp[k] * nC, sv.ptY ? sv.ptY + (size_t)slot[k] * nP : nullptr, g[k]);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        const double Yf = INTERNAL ? lerpf(F.w, v[k].o[0], v[k].n[0]) : v[k].n[0];
+        const double dydt = (-F.phiTau) * (F.Uf[0] * g[k][0] + F.Uf[1] * g[k][1] + F.Uf[2] * g[k][2]);   // [updateFluxes.H L124-125]
+        const double pjy = F.phiJm * Yf + dydt;                                                          // [L123, L126]
+        const double sn = INTERNAL ? F.dn * (v[k].n[0] - v[k].o[0]) : v[k].sn[0];
+        const double lap = (F.mufS / sv.Sc[sp[k]]) * sn;                                                 // [QGDYEqn.H L75, L82]
+        if (a0 + k < sv.nAct) {
+            sv.F[(size_t)slot[k] * nF + pos] = pjy - lap;
+            if (sv.phiJmY) {
+                const double df = dydt + lap;
+                sv.phiJmY[(size_t)sp[k] * nF + f] = pjy;
+                sv.dflux[(size_t)sp[k] * nF + f] = df;
+                inertDf -= df;                                                                            // [QGDYEqn.H L83]
+            }
+        }
+    }
+}
+
+template <int ST, int W>
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesFaceKernel(const MeshView m, const CaseView c, const GasModel gm, const SpeciesView sv) {
+    const int f = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (f >= m.nIF) return;
+    const size_t pos = (size_t)m.fpos[f];
+    SpeciesFace F;
+    F.o = m.own[f]; F.n = m.nei[f];
+    F.w = m.w[f]; F.dn = m.dn[f];
+    const double hf = m.hf[f], ms = m.magSf[f];
+    const double S[3] = {m.Sx[f], m.Sy[f], m.Sz[f]};
+    F.phiJm = c.flux[pos];
+    const RecA Ao = c.A[F.o], An = c.A[F.n];
+    const RecB Bo = c.B[F.o], Bn = c.B[F.n];
+    const double Uo[3] = {Ao.ux, Ao.uy, Ao.uz}, Un[3] = {An.ux, An.uy, An.uz};
+    double phi = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        F.Uf[k] = lerpf(F.w, Uo[k], Un[k]);
+        phi += S[k] * lerpf(F.w, Ao.rho * Uo[k], An.rho * Un[k]);   // phi = Sf & lin(rho U)
+    }
+    F.phiTau = phi * (lerpf(F.w, Bo.aOc, Bn.aOc) * hf);             // tauQGDf = lin(alphaQGD / c) hQGDf [constScPrModel1_8C L103]
+    F.mufS = lerpf(F.w, muEffOf(gm, Bo.muQGD), muEffOf(gm, Bn.muQGD)) * ms;
+    double inertDf = 0.0;
+    for (int a0 = 0; a0 < sv.nAct; a0 += W) speciesBatch<ST, W, true>(m, sv, F, f, pos, a0, inertDf);
+    if (sv.phiJmY) {
+        sv.phiJmY[(size_t)sv.inert * m.nF + f] = 0.0;
+        sv.dflux[(size_t)sv.inert * m.nF + f] = inertDf;
+    }
+}
+
+template <int ST, int W>
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesBoundaryFaceKernel(const MeshView m, const CaseView c, const GasModel gm, const SpeciesView sv) {
+    const int b = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (b >= m.nBF) return;
+    const int f = m.nIF + b;
+    const size_t nF = (size_t)m.nF;
+    if (m.fkind[f] == 3) {   // empty patches carry no field
+        for (int a = 0; a < sv.nAct; ++a) sv.F[(size_t)a * nF + f] = 0.0;
+        if (sv.phiJmY)
+            for (int i = 0; i < sv.nS; ++i) { sv.phiJmY[(size_t)i * nF + f] = 0.0; sv.dflux[(size_t)i * nF + f] = 0.0; }
+        return;
+    }
+    SpeciesFace F;
+    F.o = m.own[f]; F.n = b;
+    F.w = 1.0; F.dn = m.dn[f];
+    const double hf = m.hf[f], ms = m.magSf[f];
+    const double S[3] = {m.Sx[f], m.Sy[f], m.Sz[f]};
+    F.phiJm = c.flux[f];
+    const RecA Ab = c.bA[b];
+    const RecB Bb = c.bB[b];
+    const double Ub[3] = {Ab.ux, Ab.uy, Ab.uz}, rhoLag = c.bRhoLag[b];
+    double phi = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { F.Uf[k] = Ub[k]; phi += S[k] * (rhoLag * Ub[k]); }   // rhoU_b [QGDUEqn_8H L88-89]
+    F.phiTau = phi * (Bb.aOc * hf);
+    F.mufS = muEffOf(gm, Bb.muQGD) * ms;
+    double inertDf = 0.0;
+    for (int a0 = 0; a0 < sv.nAct; a0 += W) speciesBatch<ST, W, false>(m, sv, F, f, (size_t)f, a0, inertDf);
+    if (sv.phiJmY) {
+        sv.phiJmY[(size_t)sv.inert * nF + f] = 0.0;
+        sv.dflux[(size_t)sv.inert * nF + f] = inertDf;
+    }
+}
+
+// vertex values of every species: the weights of launchPointInterp (volPointInterpolation's, pointCells order), read once per batch
+template <int W>
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesPointKernel(const MeshView m, const SpeciesView sv) {
+    const int p = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (p >= m.nP) return;
+    const int n = m.pcCount[p];
+    if (n == 0) return;   // patch point: caseSpeciesBoundaryPointKernel
+    const size_t base = (size_t)m.pcSlice[p >> 6] * 64 + (p & 63);
+    const size_t nC = (size_t)m.nC, nP = (size_t)m.nP;
+    for (int a0 = 0; a0 < sv.nAct; a0 += W) {
+        int sp[W];
+        double acc[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) { sp[k] = sv.act[min(a0 + k, sv.nAct - 1)]; acc[k] = 0.0; }
+        for (int i = 0; i < n; ++i) {
+            const double w = m.pcW[base + (size_t)i * 64];
+            const size_t cell = (size_t)m.pcCell[base + (size_t)i * 64];
+#pragma unroll
+            for (int k = 0; k < W; ++k) acc[k] += w * sv.Y[(size_t)sp[k] * nC + cell];
+        }
+#pragma unroll
+        for (int k = 0; k < W; ++k) if (a0 + k < sv.nAct) sv.ptY[(size_t)(a0 + k) * nP + p] = acc[k];
+    }
+}
+// patch points: the weights of launchBoundaryPoints (scalars: no point constraints apply)
+template <int W>
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesBoundaryPointKernel(const MeshView m, const SpeciesView sv) {
+    const int i = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (i >= m.nBP) return;
+    const int p = m.bpPoint[i];
+    const int e0 = m.bpOff[i], e1 = m.bpOff[i + 1];
+    const size_t nBF = (size_t)m.nBF, nP = (size_t)m.nP;
+    for (int a0 = 0; a0 < sv.nAct; a0 += W) {
+        int sp[W];
+        double acc[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) { sp[k] = sv.act[min(a0 + k, sv.nAct - 1)]; acc[k] = 0.0; }
+        for (int e = e0; e < e1; ++e) {
+            const double w = m.bpW[e];
+            const size_t bf = (size_t)m.bpFace[e];
+#pragma unroll
+            for (int k = 0; k < W; ++k) acc[k] += w * sv.Yb[(size_t)sp[k] * nBF + bf];
+        }
+#pragma unroll
+        for (int k = 0; k < W; ++k) if (a0 + k < sv.nAct) sv.ptY[(size_t)(a0 + k) * nP + p] = acc[k];
+    }
+}
+
+// QGDYEqn.H L67-91 of one cell: fvm::ddt(rho, Yi) + fvc::div(phiJmYi - lap_i) == 0 (Euler), the divergence gathered in ascending face
+// label like fvc::surfaceIntegrate; rho.oldTime() is the record's density (the flow's cell update runs after this kernel), rho the value
+// that update forms from the same mass fluxes and the same deltaT [QGDRhoEqn_8H L40-47]
+template <int W>
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesCellKernel(const MeshView m, const CaseView c, const SpeciesView sv) {
+    const int ci = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (ci >= m.nC) return;
+    const int n = m.cfCount[ci];
+    const size_t base = (size_t)m.cfSlice[ci >> 6] * 64 + (ci & 63);
+    const size_t nC = (size_t)m.nC, nF = (size_t)m.nF;
+    double sum0 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int it = m.cfPos[base + (size_t)i * 64];
+        const double x = c.flux[(size_t)(it >= 0 ? it : ~it)];
+        sum0 = it >= 0 ? sum0 + x : sum0 - x;
+    }
+    const double V = m.V[ci], dt = c.dt[0];
+    const double rhoOld = c.A[ci].rho;
+    const double dtV = dt / V;
+    const double rhoNew = rhoOld - dtV * sum0;
+    const double rDeltaT = 1.0 / dt;
+    const double den = rDeltaT * rhoNew * V;
+    double Yt = 0.0;                                                   // volScalarField Yt(0.0*Y[0]) [L38]
+    for (int a0 = 0; a0 < sv.nAct; a0 += W) {
+        int sp[W];
+        double s[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) { sp[k] = sv.act[min(a0 + k, sv.nAct - 1)]; s[k] = 0.0; }
+        for (int i = 0; i < n; ++i) {
+            const int it = m.cfPos[base + (size_t)i * 64];
+            const size_t pos = (size_t)(it >= 0 ? it : ~it);
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                const double x = sv.F[(size_t)min(a0 + k, sv.nAct - 1) * nF + pos];
+                s[k] = it >= 0 ? s[k] + x : s[k] - x;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            if (a0 + k < sv.nAct) {
+                double* __restrict__ y = sv.Y + (size_t)sp[k] * nC + ci;
+                const double yn = fmax((rDeltaT * rhoOld * (*y) * V - s[k]) / den, 0.0);   // solve(...) [L69-80]; Yi.max(0.0) [L86]
+                *y = yn;
+                Yt += yn;                                                                  // [L87]
+            }
+        }
+    }
+    sv.Y[(size_t)sv.inert * nC + ci] = fmax(1.0 - Yt, 0.0);                                // [L90-91]
+}
+
+// patch values of every species: fixedValue keeps its value, zeroGradient (and the constraint patches' `none`) takes the owner's
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesPatchKernel(const MeshView m, const SpeciesView sv) {
+    const int b = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (b >= m.nBF) return;
+    const int o = m.own[m.nIF + b], patch = m.bPatch[b];
+    for (int i = 0; i < sv.nS; ++i) {
+        const size_t e = (size_t)i * sv.nPatches + patch;
+        sv.Yb[(size_t)i * m.nBF + b] = sv.bcKind[e] == QGD_BC_FIXEDVALUE ? sv.bcVal[e] : sv.Y[(size_t)i * m.nC + o];
+    }
+}
+
+void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesView& sv) {
+    if (m.nBF) caseSpeciesPatchKernel<<<gridOfS(m.nBF), QGD_BLOCK, 0, s>>>(m, sv);
+}
+
+template <int ST>
+static void launchSpeciesAdvanceT(hipStream_t s, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv) {
+    constexpr int W = QGD_SPECIES_W;
+    if (ST == ST_GVP3 || ST == ST_GVP2) {
+        caseSpeciesPointKernel<W><<<gridOfS(m.nP), QGD_BLOCK, 0, s>>>(m, sv);
+        if (m.nBP) caseSpeciesBoundaryPointKernel<W><<<gridOfS(m.nBP), QGD_BLOCK, 0, s>>>(m, sv);
+    }
+    if (m.nIF) caseSpeciesFaceKernel<ST, W><<<gridOfS(m.nIF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
+    if (m.nBF) caseSpeciesBoundaryFaceKernel<ST, W><<<gridOfS(m.nBF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
+    caseSpeciesCellKernel<W><<<gridOfS(m.nC), QGD_BLOCK, 0, s>>>(m, c, sv);
+    launchSpeciesPatchValues(s, m, sv);
+}
+void launchSpeciesAdvance(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv) {
+    if (m.nC == 0 || sv.nS == 0) return;
+    switch (stencil) {
+        case ST_REDUCED: launchSpeciesAdvanceT<ST_REDUCED>(s, m, c, g, sv); break;
+        case ST_LSQ: launchSpeciesAdvanceT<ST_LSQ>(s, m, c, g, sv); break;
+        case ST_GVP3: launchSpeciesAdvanceT<ST_GVP3>(s, m, c, g, sv); break;
+        default: launchSpeciesAdvanceT<ST_GVP2>(s, m, c, g, sv); break;
+    }
+}
+int speciesBatchWidth() { return QGD_SPECIES_W; }
+
+}  // namespace qgd

@@ -764,7 +764,8 @@ def read_case_setup(case_dir, time="0"):
     for key, want in (("equationOfState", "perfectGas"), ("transport", "const")):
         if isinstance(tt, dict) and key in tt and str(tt[key]) != want:
             raise FoamFileError(f"thermoType.{key} '{tt[key]}' is not supported (only {want})")
-    mix = tp["mixture"]
+    species_names = [str(w) for w in tp["species"]] if "species" in tp else None
+    mix = _species_mixture(tp, species_names) if species_names else tp["mixture"]
     R = RR / float(mix["specie"]["molWeight"])
     th = mix["thermodynamics"]
     opt["R"] = R
@@ -774,6 +775,9 @@ def read_case_setup(case_dir, time="0"):
     qgd = tp["QGD"]
     # QGDThermo::read(): implicitDiffusion defaults to true when absent [QGDThermo.C L70-82]
     opt["implicitDiffusion"] = 1 if str(qgd.get("implicitDiffusion", "true")) in ("true", "on", "yes", "1") else 0
+    if species_names and opt["implicitDiffusion"]:
+        raise FoamFileError(f"{case_dir}: a case with species runs the explicit branch only: set implicitDiffusion false in the QGD dictionary "
+                            "(absent, the entry defaults to true [QGDThermo.C L70-82])")
     # not a reference entry: selects the physically consistent explicit energy update (qgd_case_options::consistentEnergy)
     if "consistentEnergy" in qgd:
         opt["consistentEnergy"] = 1 if str(qgd["consistentEnergy"]) in ("true", "on", "yes", "1") else 0
@@ -873,7 +877,95 @@ def read_case_setup(case_dir, time="0"):
                     "p": _bc(bP[name], False, ptw[i], f"p.{name}", lists=True)})
     fields = {"U": U, "T": T[:, 0], "p": p[:, 0]}
     fields.update(coeff_fields)
+    if species_names:
+        opt["species"] = _read_species(case_dir, tdir, tp, species_names, mesh, ptw)   # QGDFoamCase.set_species; default_options passes it by
     return mesh, opt, fields, bcs
+
+
+def _species_mixture(tp, names):
+    """the one thermo of a case with a `species` list: `mixture{}` where there is one, else the species' own dictionaries, which must all be
+    equal -- the composition is passive (no feedback of Y into thermo)"""
+    if "mixture" in tp:
+        return tp["mixture"]
+    dicts = []
+    for n in names:
+        if not isinstance(tp.get(n), dict):
+            raise FoamFileError(f"thermophysicalProperties: neither a mixture dictionary nor one for species '{n}'")
+        dicts.append(tp[n])
+    for n, d in zip(names[1:], dicts[1:]):
+        if d != dicts[0]:
+            raise FoamFileError(f"thermophysicalProperties: species '{names[0]}' and '{n}': species with different thermophysical properties are "
+                                "not served: the composition is passive")
+    return dicts[0]
+
+
+def _read_species(case_dir, tdir, tp, names, mesh, ptw):
+    """the species entries of a reactingLagrangianQGDFoam case: {'names', 'inert', 'ScNumbers' (per species), 'fields' {name: cell values},
+    'bcs' {name: per patch (kind, value)}}.  inertSpecie is required and must be a species [createFields.H L31-39]; ScNumbers ((name Sc) ...)
+    is optional, names that are no species are ignored, the default is 1 [readScNumbers.H L1-19]; the field of species X is <time>/X, else
+    <time>/Ydefault (OpenFOAM's rule); boundary conditions: the patch's own constraint type, zeroGradient, uniform fixedValue."""
+    if len(set(names)) != len(names):
+        raise FoamFileError(f"thermophysicalProperties: the species list repeats a name: {names}")
+    if "inertSpecie" not in tp:
+        raise FoamFileError("thermophysicalProperties: a case with species needs inertSpecie [createFields.H L31-39]")
+    inert = str(tp["inertSpecie"])
+    if inert not in names:
+        raise FoamFileError(f"thermophysicalProperties: inertSpecie '{inert}' is not in the species list {names} [createFields.H L31-39]")
+    if getattr(mesh, "cyclic_pairs", None):
+        raise FoamFileError(f"{case_dir}: species on a mesh with cyclic patches are not served")
+    sc = {n: 1.0 for n in names}
+    for pair in tp.get("ScNumbers", []) or []:
+        if not (isinstance(pair, (list, tuple)) and len(pair) == 2):
+            raise FoamFileError(f"thermophysicalProperties: ScNumbers takes (name Sc) pairs, got '{pair}' [readScNumbers.H L1-19]")
+        if str(pair[0]) in sc:
+            sc[str(pair[0])] = float(pair[1])
+    fields, bcs = {}, {}
+    for n in names:
+        path = os.path.join(tdir, n)
+        if not _exists(path):
+            path = os.path.join(tdir, "Ydefault")
+            if not _exists(path):
+                raise FoamFileError(f"{tdir}: neither '{n}' nor 'Ydefault'")
+        Y, bY = read_field(path, mesh)
+        if Y.shape[1] != 1:
+            raise FoamFileError(f"{path}: a species is a volScalarField")
+        entries = []
+        for i, pn in enumerate(mesh.patch_names):
+            kind, val = _bc(bY[pn], False, ptw[i], f"{os.path.basename(path)}.{pn}")
+            if kind not in ("none", "zeroGradient", "fixedValue"):
+                raise FoamFileError(f"{path}: patch '{pn}': boundary condition '{kind}' of a species is not supported (zeroGradient, uniform fixedValue)")
+            entries.append((kind, val))
+        fields[n], bcs[n] = Y[:, 0].copy(), entries
+    return {"names": names, "inert": inert, "ScNumbers": [sc[n] for n in names], "fields": fields, "bcs": bcs}
+
+
+def species_entries_text(species):
+    """the thermophysicalProperties entries of opt["species"]: what _read_species takes back"""
+    pairs = " ".join(f"({n} {_fmt(float(s))})" for n, s in zip(species["names"], species["ScNumbers"]))
+    return f"species ({' '.join(species['names'])});\ninertSpecie {species['inert']};\nScNumbers ({pairs});\n"
+
+
+def apply_species(case, species, cells=None):
+    """opt["species"] of read_case_setup onto a QGDFoamCase (before set_fields); cells: the case files' labels of the device mesh's cells"""
+    case.set_species(species["names"], species["inert"], ScNumbers=species["ScNumbers"])
+    for n in species["names"]:
+        for patch, entry in enumerate(species["bcs"][n]):
+            case.set_species_bc(n, patch, entry)
+        Y = species["fields"][n]
+        case.set_species_field(n, Y if cells is None else Y[cells])
+
+
+def write_species_fields(case_dir, time_name, mesh, species, values):
+    """the Y_i files of a time directory: values {name: cell values}; patch entries carry each species' own boundary condition"""
+    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
+    pt = mesh.array("patchType")
+    for n in species["names"]:
+        patches = {}
+        for i, pn in enumerate(names):
+            word = PATCH_WORDS.get(int(pt[i]), "patch")
+            kind, val = species["bcs"][n][i]
+            patches[pn] = (word, None) if word in _CONSTRAINT_BCS else (("fixedValue", np.float64(val)) if kind == "fixedValue" else ("zeroGradient", None))
+        write_field(os.path.join(case_dir, str(time_name), n), mesh, n, values[n], patches)
 
 
 def _truthy(v):
@@ -1255,12 +1347,14 @@ def load_case(case_dir, time="0", device_id=0):
         case.set_qgd_coeffs(alphaQGD=fields.get("alphaQGD"), ScQGD=fields.get("ScQGD"))
     if opt.get("varSc"):
         case.set_var_sc(**opt["varSc"])
+    if opt.get("species"):
+        apply_species(case, opt["species"])
     case.set_fields(fields["U"], fields["T"], fields["p"])
     return dev, case
 
 
-def write_time(case, case_dir, time_name, bcs=None):
-    """Write U, T, p, rho of a QGDFoamCase into <case_dir>/<time_name>/ (what runTime.write() leaves for QGDFoam's
+def write_time(case, case_dir, time_name, bcs=None, species=None):
+    """Write U, T, p, rho of a QGDFoamCase -- and, with ``species`` (opt["species"] of read_case_setup), every Y_i -- into <case_dir>/<time_name>/ (what runTime.write() leaves for QGDFoam's
     AUTO_WRITE fields); patch entries carry the patch values as ``value`` -- a fixedValue entry what the case prescribes there
     (``uniform`` for one value per patch, ``nonuniform List<...>`` for a value list: what the reader takes back), zeroGradient / slip /
     qgdFlux entries none (the case evaluates them at start-up; the reader refuses a value list there)."""
@@ -1294,3 +1388,5 @@ def write_time(case, case_dir, time_name, bcs=None):
             else:
                 patches[pn] = (kind, bvals[b0:b0 + int(pz[i])])
         write_field(os.path.join(case_dir, str(time_name), fname), mesh, fname, internal, patches, dims[fname])
+    if species:
+        write_species_fields(case_dir, time_name, mesh, species, {n: case.species_field(n) for n in species["names"]})

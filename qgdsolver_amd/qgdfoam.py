@@ -36,6 +36,8 @@ def default_options(**kw):
             continue
         if k == "varSc":     # the varScModel7 entries of foamfile.read_case_setup: they go to QGDFoamCase.set_var_sc
             continue
+        if k == "species":   # the species entries of foamfile.read_case_setup: they go to QGDFoamCase.set_species
+            continue
         setattr(o, k, v)
     return o
 
@@ -185,6 +187,63 @@ class QGDFoamCase:
         a = (C.c_double * 2)()
         L.check(L.lib.qgd_case_sc_range(self._h, a), "qgd_case_sc_range")
         return a[0], a[1]
+
+    # ---- species mass fractions advanced with the flow (qgd_case_set_species; passive composition: one thermo, no chemistry) ----
+    def set_species(self, names, inert, ScNumbers=None, keep_fluxes=False):
+        """the case carries the mass fractions ``names`` (reactingLagrangianQGDFoam's species block: updateFluxes.H L103-132, QGDYEqn.H
+        L38-92, explicit branch); ``inert`` (a name or an index) is the species that takes 1 - sum of the others; ScNumbers a dict
+        {name: Sc} or a sequence (default 1); keep_fluxes keeps phiJmY / diffusiveFlux of the last step for species_field.  After
+        creation, before set_fields.  The case then steps with the separate kernels (fused_info)."""
+        names = [str(n) for n in names]
+        if len(set(names)) != len(names):
+            raise ValueError(f"set_species: species names repeat: {names}")
+        k = names.index(inert) if isinstance(inert, str) else int(inert)
+        if isinstance(ScNumbers, dict):
+            sc = np.array([float(ScNumbers.get(n, 1.0)) for n in names])
+        else:
+            sc = np.ones(len(names)) if ScNumbers is None else np.ascontiguousarray(ScNumbers, dtype=np.float64).reshape(-1)
+        if sc.size != len(names):
+            raise ValueError(f"set_species: {len(names)} species, {sc.size} Schmidt numbers")
+        buf = sc if sc.size else np.ones(1)
+        L.check(L.lib.qgd_case_set_species(self._h, len(names), k, buf.ctypes.data_as(L.c_double_p), L.SPECIES_KEEP_FLUXES if keep_fluxes else 0),
+                "qgd_case_set_species")
+        self.species = names
+
+    def _species_index(self, s):
+        if not isinstance(s, str):
+            return int(s)
+        names = getattr(self, "species", None)
+        if names is None:
+            raise ValueError("the case carries no species (set_species)")
+        return names.index(s)
+
+    def set_species_bc(self, species, patch, entry=("zeroGradient", None)):
+        """boundary condition of one species on one patch: ("zeroGradient", None), ("fixedValue", value) or ("none", None)"""
+        kinds = {"zeroGradient": L.BC_ZEROGRADIENT, "fixedValue": L.BC_FIXEDVALUE, "none": L.BC_NONE}
+        if entry[0] not in kinds:
+            raise ValueError(f"set_species_bc: a species takes zeroGradient, fixedValue or none, not '{entry[0]}'")
+        L.check(L.lib.qgd_case_set_species_bc(self._h, self._species_index(species), int(patch), kinds[entry[0]], float(entry[1] or 0.0)),
+                "qgd_case_set_species_bc")
+
+    def set_species_field(self, species, Y):
+        Y = np.ascontiguousarray(Y, dtype=np.float64).reshape(-1)
+        if Y.size != self.mesh.nCells:
+            raise ValueError(f"set_species_field: {Y.size} values for {self.mesh.nCells} cells")
+        buf = Y if Y.size else np.zeros(1)
+        L.check(L.lib.qgd_case_set_species_fields(self._h, self._species_index(species), buf.ctypes.data_as(L.c_double_p)), "qgd_case_set_species_fields")
+
+    def species_field(self, species, what="Y"):
+        """"Y" (cells), "Y.boundary" (patch faces); with keep_fluxes also "phiJmY" and "diffusiveFlux" of the last step (faces, by label)"""
+        n = {"Y": self.mesh.nCells, "Y.boundary": self.mesh.nBoundaryFaces}.get(what, self.mesh.nFaces)
+        out = np.zeros(max(n, 1))
+        L.check(L.lib.qgd_case_get_species_field(self._h, self._species_index(species), what.encode(), out.ctypes.data_as(L.c_double_p), n),
+                f"qgd_case_get_species_field({what})")
+        return out[:n]
+
+    def species_info(self):
+        a = (C.c_int64 * 4)()
+        L.check(L.lib.qgd_case_species_info(self._h, a), "qgd_case_species_info")
+        return dict(nSpecies=int(a[0]), inertIndex=int(a[1]), batchWidth=int(a[2]), keepFluxes=bool(a[3]), names=list(getattr(self, "species", []) or []))
 
     def updateFluxes(self):
         L.check(L.lib.qgd_case_update_fluxes(self._h), "qgd_case_update_fluxes")
