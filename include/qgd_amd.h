@@ -704,25 +704,36 @@ int qgd_case_sc_range(qgd_case_t c, double out[2]);
 
 /* Species mass fractions carried by the case: the species block of reactingLagrangianQGDFoam [reactingLagrangianQGDFoam_8C_source.html
  * L92-140].  Every qgd_case_step then advances nSpecies fields Y_i with the flow, in the reference's order: the species fluxes
- * [reactingLagrangianQGDFoam_2updateFluxes_8H_source.html L103-132], QGDRhoEqn, the species equations [QGDYEqn_8H_source.html L38-92,
- * explicit branch L67-86], QGDUEqn, QGDEEqn:
+ * [reactingLagrangianQGDFoam_2updateFluxes_8H_source.html L103-132], QGDRhoEqn, the species equations [QGDYEqn_8H_source.html L38-92:
+ * the branch of the case's implicitDiffusion, L47-66 (the reference's default) or L67-86], QGDUEqn, QGDEEqn:
  *     phiJmY_i = phiJm Yf_i - phi tauQGDf (Uf & fvsc::grad(Y_i)),   ddt(rho Y_i) + div(phiJmY_i) - laplacian(muf / Sc_i, Y_i) = 0,
  *     Y_i.max(0),   Y_inert = max(1 - sum of the others, 0),
  * with the case's stencil (reduced, leastSquares 2-D, GaussVolPoint 2-D / 3-D) and the uncorrected snGrad in the laplacian.
  * The composition is PASSIVE: all species share the case's one `mixture` thermo; there is no chemistry (combustion->R), no parcel
  * source, and Y does not feed back into thermo.  Reacting thermo is out of scope.
  * The block reads the mass flux of every face, which the fused kernels never write: a case with species runs the three-kernel explicit
- * step (fixed or adjusted deltaT) -- qgd_case_fused_info reports 0 after this call.
+ * step (fixed or adjusted deltaT), or, with implicitDiffusion, the separate kernels of the implicit branch (the block-fused assembly of
+ * the U systems keeps the internal faces' mass flux in its blocks) -- qgd_case_fused_info reports 0 after this call.
+ * implicitDiffusion true, asked for with the flag QGD_SPECIES_IMPLICIT [QGDYEqn.H L47-66]: fvm::ddt(rho, Y_i) + fvc::div(phiJmY_i) - fvm::laplacian(muf / Sc_i, Y_i), solved inside the
+ * implicit advance, after deltaT and before the U systems, on the old records.  All species share the face coefficient muf |Sf| delta_f
+ * and differ by 1 / Sc_i: a register batch of species ([2] of qgd_case_species_info) is ONE solve of the case's implicit solver
+ * (Chebyshev, or conjugate gradients with QGD_IMPL_SOLVER=pcg) with that many right-hand sides.  fixedValue patches of a species enter
+ * its diagonal and source; diffusiveFlux_i += YEqn.flux() of the new Y_i, with the listing's sign (opposite to the explicit branch's).
+ * The solves start from the old Y_i: the time-extrapolated start values of the flow's solves (QGD_IMPL_XEXTRAP) are not extended to them.
  * Legal after qgd_case_create and before qgd_case_set_fields (QGD_ERR_INVALID afterwards).  At most QGD_MAX_SPECIES species.
- * QGD_ERR_NOT_IMPLEMENTED, with the reason named: implicitDiffusion true, a sharded device, a periodic (qgd_mesh_unroll_cyclic)
- * device, per-term stencils (qgd_case_options::termStencil).  QGD_ERR_INVALID: nSpecies < 2 or > QGD_MAX_SPECIES, inertIndex out of
+ * QGD_ERR_NOT_IMPLEMENTED, with the reason named: implicitDiffusion true without the flag QGD_SPECIES_IMPLICIT, a sharded device,
+ * a periodic (qgd_mesh_unroll_cyclic) device, per-term stencils (qgd_case_options::termStencil).  QGD_ERR_INVALID: nSpecies < 2 or > QGD_MAX_SPECIES, inertIndex out of
  * range, a Schmidt number <= 0 (ScNumbers == NULL: all 1), unknown flags.  Not served: monitors of species.
  * qgd_case_step_phase is refused on a case with species; qgd_case_step (and qgd_case_step_sharded, which steps an unsharded device the same
  * way) with a species whose field was never set is QGD_ERR_INVALID.
- * These five entries were added without a change of QGD_ABI_VERSION (no struct grew, no existing entry changed its meaning): a host that
+ * These entries (the five of the explicit block, then qgd_case_set_species_solver and qgd_case_species_implicit_info) were added without a change of QGD_ABI_VERSION (no struct grew, no existing entry changed its meaning): a host that
  * must run against older builds of the library looks the symbols up (dlsym) instead of comparing the number. */
 #define QGD_MAX_SPECIES 32
 #define QGD_SPECIES_KEEP_FLUXES 1   /* flags: keep phiJmY_i and diffusiveFlux_i of the last step (qgd_case_get_species_field) */
+#define QGD_SPECIES_IMPLICIT 2      /* flags: the caller accepts the implicitDiffusion branch of the species equations (a case created with
+                                     * implicitDiffusion = 1).  Without it such a case is answered with QGD_ERR_NOT_IMPLEMENTED as before this
+                                     * branch was served: a host that runs the stateless qgd_species_step_implicit loop on that answer keeps
+                                     * working unchanged, and nobody gets linear solves inside the step without asking.  Ignored on the explicit branch. */
 int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, const double* ScNumbers, int32_t flags);
 /* Boundary condition of one species on one patch: QGD_BC_ZEROGRADIENT (the default of generic patches), QGD_BC_FIXEDVALUE with one
  * value for the patch, QGD_BC_NONE; constraint patches keep QGD_BC_NONE (their faces carry no species flux, or a zero gradient). */
@@ -735,6 +746,16 @@ int qgd_case_get_species_field(qgd_case_t c, int32_t species, const char* name, 
 /* info[0] = nSpecies (0: the case carries none), [1] = inertIndex, [2] = species per register batch of the face and cell kernels,
  * [3] = 1 with QGD_SPECIES_KEEP_FLUXES */
 int qgd_case_species_info(qgd_case_t c, int64_t info[4]);
+/* Controls of the species' solves on the implicitDiffusion branch (fvSolution.solvers.<species>): tolerance > 0, maxIter >= 1, for all
+ * species.  Without this call they are the case's implicitTol / implicitMaxIter.  QGD_ERR_INVALID on a case without species or on the
+ * explicit branch. */
+int qgd_case_set_species_solver(qgd_case_t c, double tolerance, int32_t maxIter);
+/* Statistics of the species' solves, 3 + 3 nSpecies doubles (infoDoubles: what info holds): info[0] = steps in which a species' solve
+ * stopped above its tolerance (iteration limit or breakdown), [1] = steps in which one ended at the rounding floor of its residual above
+ * the tolerance -- the meanings of [12] and [14] of qgd_case_implicit_info --, [2] = nSpecies; then per species i, by its index:
+ * [3 + 3 i] = iterations, [4 + 3 i] = initial and [5 + 3 i] = final normalised residual of the last step (the inert species: zeros).
+ * Counted since qgd_case_set_fields.  Waits for the case's stream. */
+int qgd_case_species_implicit_info(qgd_case_t c, double* info, int64_t infoDoubles);
 
 /* Initial cell fields U (nCells*3), T, p (HOST pointers); evaluates the BCs,
  * thermo.correct() and the derived conserved fields like createFields.H

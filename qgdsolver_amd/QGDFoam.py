@@ -112,7 +112,7 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
     species = opt.get("species")
     if species and (world > 1 or getattr(gmesh, "cyclic_pairs", None)):
         raise ff.FoamFileError(f"{case_dir}: a case with species runs on one rank, on a mesh without cyclic patches")
-    # (a case with species steps with the separate kernels: its species block reads the mass flux of every face)
+    # (a case with species steps with the separate kernels, on either branch: its species block reads the mass flux of every face)
     eligible = (not (opt.get("adjustTimeStep") or opt.get("termStencils") or species) and opt["stencil"] == "GaussVolPoint"
                 and not (opt.get("implicitDiffusion") and world > 1))
     dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}}, fused_tables=eligible)
@@ -262,6 +262,9 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         f"deltaT {dt:g}, start {t0_name}, cell order {renumber}")
     if species:
         log(f"  species {' '.join(species['names'])} (inert {species['inert']}): passive composition, one thermo, no chemistry")
+        if opt.get("implicitDiffusion"):
+            log(f"  species solves: tolerance {species['tolerance']:g}, maxIter {species['maxIter']}, {case.species_info()['batchWidth']} species per solve; "
+                "they start from the old Y_i, as OpenFOAM's do")
     if opt.get("implicitDiffusion"):
         x = os.environ.get("QGD_IMPL_XEXTRAP", "3")
         if x != "0":
@@ -307,6 +310,15 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             if ii["stalled_steps"]:
                 log(f"  NOTE: {ii['stalled_steps']} step(s) so far in which a Chebyshev solve ended at the rounding floor of its residual, above "
                     f"implicitTol {case.options.implicitTol:g} (OpenFOAM would have iterated on to maxIter)")
+        if species and opt.get("implicitDiffusion"):
+            si = case.species_implicit_info()
+            log("  " + "  ".join(f"{k}: {v['initial']:.3g} -> {v['final']:.3g} in {v['iterations']}" for k, v in si["species"].items()))
+            if si["unconvergedSteps"]:
+                log(f"  WARNING: {si['unconvergedSteps']} step(s) so far in which a species solve stopped above its tolerance "
+                    f"(tolerance {species['tolerance']:g}, maxIter {species['maxIter']})")
+            if si["stalledSteps"]:
+                log(f"  NOTE: {si['stalledSteps']} step(s) so far in which a species solve ended at the rounding floor of its residual, above "
+                    f"its tolerance {species['tolerance']:g}")
         if var_sc:
             sc_hi, sc_lo = case.sc_range()
             if world > 1:

@@ -188,6 +188,8 @@ SIGNATURES = {
     "qgd_case_set_species_fields": (C.c_int, [handle, C.c_int32, c_double_p]),
     "qgd_case_get_species_field": (C.c_int, [handle, C.c_int32, C.c_char_p, c_double_p, C.c_int64]),
     "qgd_case_species_info": (C.c_int, [handle, c_int64_p]),
+    "qgd_case_set_species_solver": (C.c_int, [handle, C.c_double, C.c_int32]),
+    "qgd_case_species_implicit_info": (C.c_int, [handle, c_double_p, C.c_int64]),
     "qgd_case_update_fluxes": (C.c_int, [handle]),
     "qgd_case_step": (C.c_int, [handle, C.c_int32]),
     "qgd_case_get_field": (C.c_int, [handle, C.c_char_p, c_double_p, C.c_int64]),
@@ -260,7 +262,7 @@ FVSC_REDUCED, FVSC_LEASTSQUARES, FVSC_GAUSSVOLPOINT = range(3)
 FLUX_LINEAR, FLUX_UPWIND = range(2)
 K_POINT, K_FACE, K_BFACE, K_CELL, K_BC, K_BPOINT, K_VARSC = range(7)
 MONITOR_SECTIONS, MONITOR_SLOTS = 5, 4
-MAX_SPECIES, SPECIES_KEEP_FLUXES = 32, 1
+MAX_SPECIES, SPECIES_KEEP_FLUXES, SPECIES_IMPLICIT = 32, 1, 2
 
 
 class QgdError(RuntimeError):

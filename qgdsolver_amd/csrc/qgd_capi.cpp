@@ -375,6 +375,13 @@ struct qgd_case_s {
     uint8_t* spBcKindDev = nullptr;
     double* spBcValDev = nullptr;
     bool spDirty = false, spKeep = false, spFluxesValid = false;
+    // the implicitDiffusion branch of the species [QGDYEqn.H L47-66]: rows and solutions, the statistics of the batches' solves, the controls
+    // of qgd_case_set_species_solver (< 0: the case's implicitTol / implicitMaxIter)
+    SpeciesImplView spImpl{};
+    double* spStats = nullptr;
+    int spBatches = 0;
+    double spTol = -1.0;
+    int32_t spMaxIter = -1;
     double time = 0;
     int64_t steps = 0;
     // timing
@@ -1920,9 +1927,10 @@ int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, con
     qgd_device_s* d = c->dev;
     if (c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_case_set_species: call it before qgd_case_set_fields");
     if (c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_set_species: the case carries species already");
-    if (c->opt.implicitDiffusion)
-        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: implicitDiffusion true is not served (the species equations' fvm::laplacian branch, "
-                                             "QGDYEqn.H L47-66, is a stateless operator only: qgd_species_step_implicit); set implicitDiffusion false");
+    if (c->opt.implicitDiffusion && !(flags & QGD_SPECIES_IMPLICIT))
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: implicitDiffusion true is not served without the flag QGD_SPECIES_IMPLICIT (the species equations' "
+                                             "fvm::laplacian branch, QGDYEqn.H L47-66, solves one linear system per batch of species inside the step: a caller asks for it by "
+                                             "name); pass the flag, or set implicitDiffusion false");
     if (d->periodic())
         return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: a periodic device (cyclic patches served by ghost copies, qgd_mesh_unroll_cyclic) is not served: "
                                              "the copies would need the species' values");
@@ -1933,7 +1941,7 @@ int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, con
     if (nSpecies < 2) return fail(QGD_ERR_INVALID, "qgd_case_set_species: nSpecies must be at least 2 (one transported species and the inert one)");
     if (nSpecies > QGD_MAX_SPECIES) return fail(QGD_ERR_INVALID, "qgd_case_set_species: at most " + std::to_string(QGD_MAX_SPECIES) + " species are served");
     if (inertIndex < 0 || inertIndex >= nSpecies) return fail(QGD_ERR_INVALID, "qgd_case_set_species: inertIndex out of range");
-    if (flags & ~QGD_SPECIES_KEEP_FLUXES) return fail(QGD_ERR_INVALID, "qgd_case_set_species: unknown flags");
+    if (flags & ~(QGD_SPECIES_KEEP_FLUXES | QGD_SPECIES_IMPLICIT)) return fail(QGD_ERR_INVALID, "qgd_case_set_species: unknown flags");
     for (int32_t i = 0; ScNumbers && i < nSpecies; ++i)
         if (!(ScNumbers[i] > 0) || !std::isfinite(ScNumbers[i]))
             return fail(QGD_ERR_INVALID, "qgd_case_set_species: the Schmidt number of species " + std::to_string(i) + " must be positive (Sc <= 0)");
@@ -1964,12 +1972,25 @@ int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, con
         for (size_t p = 0; p < c->bc.size(); ++p)
             if (d->patches[p].type == QGD_PATCH_GENERIC) c->spBcKind[i * nP + p] = (uint8_t)QGD_BC_ZEROGRADIENT;
     c->spFieldSet.assign(nS, 0);
+    if (c->opt.implicitDiffusion) {   // [QGDYEqn.H L47-66]: one solve per register batch
+        const size_t cells = std::max<size_t>((size_t)m.nC, 1);
+        c->spImpl.aF = a.alloc<double>(std::max<size_t>((size_t)m.nF, 1));
+        c->spImpl.diag = a.alloc<double>(4 * cells);
+        c->spImpl.rhs = a.alloc<double>(4 * cells);
+        c->spImpl.x = a.alloc<double>((nAct + 3) * cells);
+        c->spBatches = (sv.nAct + speciesBatchWidth() - 1) / speciesBatchWidth();
+        const size_t nStat = (size_t)implicitStatsDoubles(c->spBatches);
+        c->spStats = a.alloc<double>(nStat);
+        HIP_CHECK(hipMemset(c->spStats, 0, sizeof(double) * nStat));
+    }
     c->sp = sv;
     c->spDirty = true;
     c->spFluxesValid = false;
-    // the species block reads phiJm of every face, which the fused kernels never write: the three-kernel explicit step
+    // the species block reads phiJm of every face, which the fused kernels never write: the three-kernel explicit step, or the separate
+    // kernels of the implicit branch (the block-fused assembly of the U systems keeps the internal faces' mass flux in its blocks)
     c->fused = false;
     c->fusedAdj = false;
+    c->fusedImpl = false;
     c->view.nBlkFace = c->view.fuBlkFace;
     return QGD_OK;
     QGD_CATCH
@@ -2051,6 +2072,35 @@ int qgd_case_get_species_field(qgd_case_t c, int32_t species, const char* name, 
     if (n > outDoubles) return fail(QGD_ERR_INVALID, "qgd_case_get_species_field: output too small");
     HIP_CHECK(hipStreamSynchronize(c->stream()));
     if (n) HIP_CHECK(hipMemcpy(out, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    return QGD_OK;
+    QGD_CATCH
+}
+
+int qgd_case_set_species_solver(qgd_case_t c, double tolerance, int32_t maxIter) {
+    if (!c) return fail(QGD_ERR_INVALID, "null case");
+    if (!c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_case_set_species_solver: the case carries no species (qgd_case_set_species)");
+    if (!c->opt.implicitDiffusion) return fail(QGD_ERR_INVALID, "qgd_case_set_species_solver: the explicit branch of the species equations solves nothing (implicitDiffusion false)");
+    if (!(tolerance > 0) || !std::isfinite(tolerance) || maxIter < 1)
+        return fail(QGD_ERR_INVALID, "qgd_case_set_species_solver: tolerance must be positive, maxIter >= 1");
+    c->spTol = tolerance;
+    c->spMaxIter = maxIter;
+    return QGD_OK;
+}
+int qgd_case_species_implicit_info(qgd_case_t c, double* info, int64_t infoDoubles) {
+    QGD_TRY
+    if (!c || !info) return fail(QGD_ERR_INVALID, "null argument");
+    if (!c->sp.nS || !c->spStats || !c->implSolver)
+        return fail(QGD_ERR_INVALID, "qgd_case_species_implicit_info: a case with species on the implicitDiffusion branch (qgd_case_set_species)");
+    const int64_t need = 3 + 3 * (int64_t)c->sp.nS;
+    if (infoDoubles < need) return fail(QGD_ERR_INVALID, "qgd_case_species_implicit_info: output too small (3 + 3 nSpecies doubles)");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    implicitSolverSetStream(c->implSolver, c->stream());
+    for (int64_t k = 0; k < need; ++k) info[k] = 0.0;
+    std::vector<double> act(3 * (size_t)c->sp.nAct);
+    implicitStatsRead(c->implSolver, c->spStats, c->spBatches, speciesBatchWidth(), c->sp.nAct, act.data(), &info[0], &info[1]);
+    info[2] = c->sp.nS;
+    for (int a = 0; a < c->sp.nAct; ++a)
+        for (int j = 0; j < 3; ++j) info[3 + 3 * c->sp.act[a] + j] = act[3 * (size_t)a + j];
     return QGD_OK;
     QGD_CATCH
 }
@@ -2142,6 +2192,7 @@ int qgd_case_set_fields(qgd_case_t c, const double* U, const double* T, const do
     c->gradUValid = false;
     c->impl.have = 0;          // the start values of the implicit solves begin without a history
     c->time = 0; c->steps = 0;
+    if (c->spStats) HIP_CHECK(hipMemsetAsync(c->spStats, 0, sizeof(double) * (size_t)implicitStatsDoubles(c->spBatches), c->stream()));
     if (c->implSolver) { implicitSolverSetStream(c->implSolver, c->stream()); implicitStatsReset(c->implSolver); HIP_CHECK(hipStreamSynchronize(c->stream())); }
     return QGD_OK;
     QGD_CATCH
@@ -2242,6 +2293,16 @@ static void implicitAdvanceWith(qgd_case_s* c, const SolveHooks* hooks, const st
     ImplicitSolver* S = c->implSolver;
     implicitPhase(c, 20);
     if (haloImpl) haloImpl(1);
+    if (c->sp.nS) {
+        // the species block [reactingLagrangianQGDFoam_8C L92-140: the species fluxes, QGDRhoEqn, QGDYEqn L47-66, then QGDUEqn, QGDEEqn]: the
+        // records still hold the state before the step (phase 28 writes rho and U), deltaT is this step's (phase 20), plane 0 of the flux
+        // is the assembled mass flux of every face (a case with species takes the separate assembly kernels)
+        (void)hipGetLastError();
+        launchSpeciesAdvanceImplicit(c->stream(), c->stencil, c->dev->view, c->view, c->gas, c->sp, c->spImpl, S,
+                                     c->spTol > 0 ? c->spTol : c->opt.implicitTol, c->spMaxIter > 0 ? c->spMaxIter : c->opt.implicitMaxIter, c->spStats);
+        HIP_CHECK(hipGetLastError());
+        c->spFluxesValid = true;
+    }
     implicitPhase(c, 21);
     implicitSolveRun(S, hooks);     // message kind 4, phase 0, ... through the hooks
     implicitPhase(c, 28);

@@ -212,7 +212,7 @@ void launchVarSc7(const Launcher& L, const MeshView& m, const CaseView& c, const
 void launchVarScRange(hipStream_t s, const VarScView& v, int32_t begin, int32_t end);   // {max, min} over cells [begin, end) -> v.part[2 * QGD_FACE_REDUCE_PARTIALS ...]
 
 // ---- species mass fractions carried by a case (qgd_species.hip; qgd_case_set_species of include/qgd_amd.h) ------------------------
-// Passive composition [reactingLagrangianQGDFoam: updateFluxes.H L103-132, QGDYEqn.H L38-92, explicit branch]: every species shares the
+// Passive composition [reactingLagrangianQGDFoam: updateFluxes.H L103-132, QGDYEqn.H L38-92, either branch]: every species shares the
 // case's one thermo; no chemistry, no parcel source, no feedback of Y into thermo.
 #define QGD_MAX_SPECIES_DEV 32
 struct SpeciesView {
@@ -231,6 +231,18 @@ struct SpeciesView {
 // launchDeltaT and the flow's cell update; leaves the patch values of the new time level behind
 void launchSpeciesAdvance(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv);
 void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesView& sv);
+void launchSpeciesPoints(hipStream_t s, const MeshView& m, const SpeciesView& sv);   // vertex values of the transported species (GaussVolPoint)
+// the implicitDiffusion branch [QGDYEqn.H L47-66]: SpeciesView::F then holds phiJmY_i alone; one solve per register batch (qgd_species_implicit.hip)
+struct SpeciesImplView {
+    double* aF;                         // nF: a_f = muf |Sf| delta_f at the faces' slot-major positions, 0 on empty faces (common to all species)
+    double* diag; double* rhs;          // 4 * nC each: the rows of the batch in flight, component-major
+    double* x;                          // (nAct + 3) * nC: the solutions, plane a = species act[a]; a batch's solve works on its planes in place
+};
+struct ImplicitSolver;
+// between the deltaT of the implicit advance and the assembly of the U systems (the records still hold the old state); statistics of the
+// solves into `stats` (implicitStatsDoubles(batches) doubles, slot = batch)
+void launchSpeciesAdvanceImplicit(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv,
+                                  const SpeciesImplView& iv, ImplicitSolver* S, double tol, int maxIter, double* stats);
 int speciesBatchWidth();
 
 // ---- run monitors (qgd_monitor.hip; qgd_monitor_* of include/qgd_amd.h) ---------------------------------------------------------
@@ -352,6 +364,13 @@ void launchSolverHalo(hipStream_t s, ImplicitSolver* S, const int32_t* cells, in
 void implicitSolveEnd(ImplicitSolver* S, int which);             // which = 0: the U solve, 1: the e solve
 double implicitApplyMs(ImplicitSolver* S, const ImplView& iv, int reps, int* rows);   // measurement: average ms of the U system's matrix product
 void implicitStepMark(ImplicitSolver* S, bool begin);
+// the same bookkeeping for solves that are neither U's nor e's (the species' batches), in a block of the caller's: implicitStatsDoubles(slots)
+// doubles, zeroed by the caller; slot = which control block the finished solve leaves behind
+int64_t implicitStatsDoubles(int slots);
+void implicitSolveEndInto(ImplicitSolver* S, double* stats, int slot);
+void implicitStatsMarkOn(ImplicitSolver* S, double* stats, bool begin);
+// waits for the stream: right-hand side k of slot b is entry b * width + k of the n asked for -> {iterations, initial, final} each
+void implicitStatsRead(ImplicitSolver* S, const double* stats, int slots, int width, int n, double* out3, double* unconvergedSteps, double* stalledSteps);
 void implicitStatsReset(ImplicitSolver* S);
 void implicitSolverInfo(ImplicitSolver* S, int iters[4], double res0[4], double res[4], double* unconvergedSteps, double* stalledSteps);
 int implicitHaloWidth(const ImplicitSolver* S, int kind);   // doubles per cell of message kind 1 (grad U), 2 (U), 3 (search direction), 4 (initial guess)

@@ -1095,6 +1095,25 @@ void implicitSolveEnd(ImplicitSolver* S, int which) {
     iStatKernel<<<1, 1, 0, S->stream>>>(S->ctl, S->stats, S->NR, 1, S->tol);
     ICHECK(hipMemcpyAsync(S->stats + ISTAT_COUNT + (size_t)which * I_COUNT, S->ctl, sizeof(double) * I_COUNT, hipMemcpyDeviceToDevice, S->stream));
 }
+int64_t implicitStatsDoubles(int slots) { return ISTAT_COUNT + (int64_t)slots * I_COUNT; }
+void implicitSolveEndInto(ImplicitSolver* S, double* stats, int slot) {
+    if (S->cheb) iChebHomeKernel<<<S->v.nBlocks, QGD_BLOCK, 0, S->stream>>>(S->v);
+    iStatKernel<<<1, 1, 0, S->stream>>>(S->ctl, stats, S->NR, 1, S->tol);
+    ICHECK(hipMemcpyAsync(stats + ISTAT_COUNT + (size_t)slot * I_COUNT, S->ctl, sizeof(double) * I_COUNT, hipMemcpyDeviceToDevice, S->stream));
+}
+void implicitStatsMarkOn(ImplicitSolver* S, double* stats, bool begin) { iStatKernel<<<1, 1, 0, S->stream>>>(S->ctl, stats, 0, begin ? 0 : 2, 0.0); }
+void implicitStatsRead(ImplicitSolver* S, const double* stats, int slots, int width, int n, double* out3, double* unconvergedSteps, double* stalledSteps) {
+    std::vector<double> h((size_t)implicitStatsDoubles(slots));
+    ICHECK(hipMemcpyAsync(h.data(), stats, sizeof(double) * h.size(), hipMemcpyDeviceToHost, S->stream));
+    ICHECK(hipStreamSynchronize(S->stream));
+    *unconvergedSteps = h[0]; *stalledSteps = h[2];
+    for (int i = 0; i < n; ++i) {
+        const double* u = h.data() + ISTAT_COUNT + (size_t)(i / width) * I_COUNT;
+        const int k = i % width;
+        const bool on = u[ICTL(I_DONE, k)] != 3.0;
+        out3[3 * i] = on ? u[ICTL(I_ITER, k)] : 0.0; out3[3 * i + 1] = on ? u[ICTL(I_RES0, k)] : 0.0; out3[3 * i + 2] = on ? u[ICTL(I_RES, k)] : 0.0;
+    }
+}
 void implicitStepMark(ImplicitSolver* S, bool begin) { iStatKernel<<<1, 1, 0, S->stream>>>(S->ctl, S->stats, 0, begin ? 0 : 2, 0.0); }
 void implicitStatsReset(ImplicitSolver* S) { ICHECK(hipMemsetAsync(S->stats, 0, sizeof(double) * (ISTAT_COUNT + 2 * I_COUNT), S->stream)); }
 // waits for the stream: iterations / initial / final residual of Ux, Uy, Uz, e in the last step, steps with an unconverged solve

@@ -3,7 +3,8 @@
 // A case with species (qgd_case_set_species) advances nS mass fractions Y_i with the flow, inside qgd_case_step, in the reference's
 // order [reactingLagrangianQGDFoam_8C L92-140]: updateFluxes.H L103-132, QGDRhoEqn, QGDYEqn.H L38-92, QGDUEqn, QGDEEqn.  The composition
 // is PASSIVE: every species shares the case's one `mixture` thermo; no chemistry (combustion->R), no parcel source, no feedback of Y into
-// thermo.  Explicit branch only (QGDYEqn.H L67-86).
+// thermo.  This file: the explicit branch (QGDYEqn.H L67-86) and what both branches share; the implicitDiffusion branch (L47-66, the
+// reference's default) is qgd_species_implicit.hip: the same vertex and face walks, then one linear solve per register batch.
 //
 //   SP  caseSpeciesPointKernel / caseSpeciesBoundaryPointKernel   GaussVolPoint: vertex values of ALL species in one walk over the points
 //   SF  caseSpeciesFaceKernel<ST, W>        internal faces: labels, geometry, phiJm (plane 0 of CaseView::flux) and the two cells' records are
@@ -26,59 +27,10 @@
 #include "qgd_device.hpp"
 
 #include "../../include/qgd_amd.h"
+#include "qgd_species_dev.hpp"
 #include "qgd_stencil_dev.hpp"
 
 namespace qgd {
-
-#define QGD_SPECIES_W 4   // species per register batch (qgd_case_species_info reports it; profiles/kernel_resources.txt lists the instantiations: none spills)
-
-static inline int gridOfS(int64_t n) { return (int)((n + QGD_BLOCK - 1) / QGD_BLOCK); }
-
-// what a face knows before the species come: loaded / rebuilt once
-struct SpeciesFace {
-    double phiJm, phiTau, Uf[3], mufS;   // phiTau = phi tauQGDf; mufS = muf |Sf|
-    double w, dn;
-    int o, n;                            // n: neighbour cell (internal) or boundary face index (patch)
-};
-
-// the species a0 .. a0 + W - 1 of the transported ones on one face (slots past the last species repeat it and store nothing)
-template <int ST, int W, bool INTERNAL>
-__device__ __forceinline__ void speciesBatch(const MeshView& m, const SpeciesView& sv, const SpeciesFace& F, const int f, const size_t pos,
-                                             const int a0, double& inertDf) {
-    const size_t nC = (size_t)m.nC, nP = (size_t)m.nP, nF = (size_t)m.nF, nBF = (size_t)m.nBF;
-    int sp[W], slot[W];   // the species' label, and its place among the transported ones: the planes of F and ptY
-    FaceVals<1> v[W];
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        slot[k] = min(a0 + k, sv.nAct - 1);
-        sp[k] = sv.act[slot[k]];
-        const double* __restrict__ Y = sv.Y + (size_t)sp[k] * nC;
-        v[k].o[0] = Y[F.o];
-        if (INTERNAL) { v[k].n[0] = Y[F.n]; v[k].sn[0] = 0.0; }
-        else { v[k].n[0] = sv.Yb[(size_t)sp[k] * nBF + F.n]; v[k].sn[0] = F.dn * (v[k].n[0] - v[k].o[0]); }   // fvPatchField::snGrad (L0)
-    }
-    double g[W][3];
-#pragma unroll
-    for (int k = 0; k < W; ++k)
-        faceGradient<ST, 1, -1>(m, f, v[k], sv.Y + (size_t)sp[k] * nC, sv.ptY ? sv.ptY + (size_t)slot[k] * nP : nullptr, g[k]);
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        const double Yf = INTERNAL ? lerpf(F.w, v[k].o[0], v[k].n[0]) : v[k].n[0];
-        const double dydt = (-F.phiTau) * (F.Uf[0] * g[k][0] + F.Uf[1] * g[k][1] + F.Uf[2] * g[k][2]);   // [updateFluxes.H L124-125]
-        const double pjy = F.phiJm * Yf + dydt;                                                          // [L123, L126]
-        const double sn = INTERNAL ? F.dn * (v[k].n[0] - v[k].o[0]) : v[k].sn[0];
-        const double lap = (F.mufS / sv.Sc[sp[k]]) * sn;                                                 // [QGDYEqn.H L75, L82]
-        if (a0 + k < sv.nAct) {
-            sv.F[(size_t)slot[k] * nF + pos] = pjy - lap;
-            if (sv.phiJmY) {
-                const double df = dydt + lap;
-                sv.phiJmY[(size_t)sp[k] * nF + f] = pjy;
-                sv.dflux[(size_t)sp[k] * nF + f] = df;
-                inertDf -= df;                                                                            // [QGDYEqn.H L83]
-            }
-        }
-    }
-}
 
 template <int ST, int W>
 __global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesFaceKernel(const MeshView m, const CaseView c, const GasModel gm, const SpeciesView sv) {
@@ -103,7 +55,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesFaceKernel(const MeshVie
     F.phiTau = phi * (lerpf(F.w, Bo.aOc, Bn.aOc) * hf);             // tauQGDf = lin(alphaQGD / c) hQGDf [constScPrModel1_8C L103]
     F.mufS = lerpf(F.w, muEffOf(gm, Bo.muQGD), muEffOf(gm, Bn.muQGD)) * ms;
     double inertDf = 0.0;
-    for (int a0 = 0; a0 < sv.nAct; a0 += W) speciesBatch<ST, W, true>(m, sv, F, f, pos, a0, inertDf);
+    for (int a0 = 0; a0 < sv.nAct; a0 += W) speciesBatch<ST, W, true, false>(m, sv, F, f, pos, a0, inertDf);
     if (sv.phiJmY) {
         sv.phiJmY[(size_t)sv.inert * m.nF + f] = 0.0;
         sv.dflux[(size_t)sv.inert * m.nF + f] = inertDf;
@@ -137,7 +89,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesBoundaryFaceKernel(const
     F.phiTau = phi * (Bb.aOc * hf);
     F.mufS = muEffOf(gm, Bb.muQGD) * ms;
     double inertDf = 0.0;
-    for (int a0 = 0; a0 < sv.nAct; a0 += W) speciesBatch<ST, W, false>(m, sv, F, f, (size_t)f, a0, inertDf);
+    for (int a0 = 0; a0 < sv.nAct; a0 += W) speciesBatch<ST, W, false, false>(m, sv, F, f, (size_t)f, a0, inertDf);
     if (sv.phiJmY) {
         sv.phiJmY[(size_t)sv.inert * nF + f] = 0.0;
         sv.dflux[(size_t)sv.inert * nF + f] = inertDf;
@@ -257,13 +209,17 @@ void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesVie
     if (m.nBF) caseSpeciesPatchKernel<<<gridOfS(m.nBF), QGD_BLOCK, 0, s>>>(m, sv);
 }
 
+// vertex values of the transported species (GaussVolPoint): the implicit branch's walk (qgd_species_implicit.hip) starts with them too
+void launchSpeciesPoints(hipStream_t s, const MeshView& m, const SpeciesView& sv) {
+    constexpr int W = QGD_SPECIES_W;
+    caseSpeciesPointKernel<W><<<gridOfS(m.nP), QGD_BLOCK, 0, s>>>(m, sv);
+    if (m.nBP) caseSpeciesBoundaryPointKernel<W><<<gridOfS(m.nBP), QGD_BLOCK, 0, s>>>(m, sv);
+}
+
 template <int ST>
 static void launchSpeciesAdvanceT(hipStream_t s, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv) {
     constexpr int W = QGD_SPECIES_W;
-    if (ST == ST_GVP3 || ST == ST_GVP2) {
-        caseSpeciesPointKernel<W><<<gridOfS(m.nP), QGD_BLOCK, 0, s>>>(m, sv);
-        if (m.nBP) caseSpeciesBoundaryPointKernel<W><<<gridOfS(m.nBP), QGD_BLOCK, 0, s>>>(m, sv);
-    }
+    if (ST == ST_GVP3 || ST == ST_GVP2) launchSpeciesPoints(s, m, sv);
     if (m.nIF) caseSpeciesFaceKernel<ST, W><<<gridOfS(m.nIF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
     if (m.nBF) caseSpeciesBoundaryFaceKernel<ST, W><<<gridOfS(m.nBF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
     caseSpeciesCellKernel<W><<<gridOfS(m.nC), QGD_BLOCK, 0, s>>>(m, c, sv);

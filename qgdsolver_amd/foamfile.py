@@ -707,7 +707,7 @@ def read_face_schemes(fs, flux_terms, grad_terms, what="system/fvSchemes"):
     return words, flux
 
 
-def _check_fv_schemes(fs, mesh, need_laplacian, need_grad, what="system/fvSchemes"):
+def _check_fv_schemes(fs, mesh, need_laplacian, need_grad, what="system/fvSchemes", otherwise=""):
     """ddtSchemes / laplacianSchemes / gradSchemes as far as the path's fvm:: / fvc:: operators read them (L0): Euler; the uncorrected
     Gauss linear laplacian (a corrected one is the same operator on an orthogonal mesh and is accepted there); Gauss linear gradients"""
     ddt = fs.get("ddtSchemes", {})
@@ -721,7 +721,7 @@ def _check_fv_schemes(fs, mesh, need_laplacian, need_grad, what="system/fvScheme
             ok = w[:2] == ["Gauss", "linear"] and len(w) == 3 and w[2] in ("uncorrected", "orthogonal", "corrected")
             if ok and w[2] == "corrected" and not _orthogonal(mesh):
                 raise FoamFileError(f"{what}: laplacianSchemes.{key} 'Gauss linear corrected' on a non-orthogonal mesh: the explicit "
-                                    f"non-orthogonal correction is not part of the path (accepted: Gauss linear uncorrected)")
+                                    f"non-orthogonal correction is not part of the path (accepted: Gauss linear uncorrected{otherwise})")
             if not ok:
                 raise FoamFileError(f"{what}: laplacianSchemes.{key} '{' '.join(w)}' is not supported (accepted: Gauss linear uncorrected)")
     if need_grad:
@@ -775,9 +775,6 @@ def read_case_setup(case_dir, time="0"):
     qgd = tp["QGD"]
     # QGDThermo::read(): implicitDiffusion defaults to true when absent [QGDThermo.C L70-82]
     opt["implicitDiffusion"] = 1 if str(qgd.get("implicitDiffusion", "true")) in ("true", "on", "yes", "1") else 0
-    if species_names and opt["implicitDiffusion"]:
-        raise FoamFileError(f"{case_dir}: a case with species runs the explicit branch only: set implicitDiffusion false in the QGD dictionary "
-                            "(absent, the entry defaults to true [QGDThermo.C L70-82])")
     # not a reference entry: selects the physically consistent explicit energy update (qgd_case_options::consistentEnergy)
     if "consistentEnergy" in qgd:
         opt["consistentEnergy"] = 1 if str(qgd["consistentEnergy"]) in ("true", "on", "yes", "1") else 0
@@ -842,7 +839,10 @@ def read_case_setup(case_dir, time="0"):
         opt["termStencils"] = per_term
     opt["fluxSchemeU"] = 1 if flux["div(phiJm,U)"] == "upwind" else 0
     opt["fluxSchemeH"] = 1 if flux["div(phiJm,H)"] == "upwind" else 0
-    _check_fv_schemes(fs, mesh, need_laplacian=bool(opt["implicitDiffusion"]), need_grad=bool(opt["implicitDiffusion"]), what=fs_path)
+    # (only the implicit branch reads a laplacian scheme: a case whose QGD dictionary has no implicitDiffusion entry runs it, QGDThermo.C L70-82)
+    _check_fv_schemes(fs, mesh, need_laplacian=bool(opt["implicitDiffusion"]), need_grad=bool(opt["implicitDiffusion"]), what=fs_path,
+                      otherwise="; or the explicit branch, which reads no laplacian scheme: implicitDiffusion false in the QGD dictionary, where the "
+                                "entry defaults to true when absent")
     cd = read_dict(os.path.join(case_dir, "system", "controlDict"))
     opt["deltaT"] = float(cd["deltaT"])
     opt["adjustTimeStep"] = 1 if str(cd.get("adjustTimeStep", "no")) in ("yes", "on", "true", "1") else 0
@@ -879,7 +879,34 @@ def read_case_setup(case_dir, time="0"):
     fields.update(coeff_fields)
     if species_names:
         opt["species"] = _read_species(case_dir, tdir, tp, species_names, mesh, ptw)   # QGDFoamCase.set_species; default_options passes it by
+        if opt["implicitDiffusion"]:
+            # YEqn.solve() [QGDYEqn.H L62] looks up solvers.<species name>: the tightest tolerance and the largest maxIter of the transported
+            # species serve them all (QGDFoamCase.set_species_solver has one pair)
+            solvers = read_dict(fsol_path).get("solvers", {}) if _exists(fsol_path) else {}
+            sp = opt["species"]
+            pairs = [_solver_controls(solvers, n) for n in sp["names"] if n != sp["inert"]]
+            sp["tolerance"], sp["maxIter"] = min(t for t, _ in pairs), max(i for _, i in pairs)
     return mesh, opt, fields, bcs
+
+
+def _solver_controls(solvers, name):
+    """(tolerance, maxIter) of fvSolution.solvers for field `name`: the entry of that name, else the last key that matches it whole as a
+    regular expression (OpenFOAM's dictionary lookup; read_dict hands quoted keys over without their quotes, and a plain word matches
+    itself only); absent, or an entry without them: OpenFOAM's defaults 1e-6 and 1000"""
+    entry = None
+    if isinstance(solvers, dict):
+        if isinstance(solvers.get(name), dict):
+            entry = solvers[name]
+        else:
+            for key, e in solvers.items():
+                try:
+                    hit = isinstance(e, dict) and re.fullmatch(str(key), name) is not None
+                except re.error:
+                    hit = False
+                if hit:
+                    entry = e
+    entry = entry or {}
+    return float(entry.get("tolerance", 1e-6)), int(float(entry.get("maxIter", 1000)))
 
 
 def _species_mixture(tp, names):
@@ -947,7 +974,10 @@ def species_entries_text(species):
 
 def apply_species(case, species, cells=None):
     """opt["species"] of read_case_setup onto a QGDFoamCase (before set_fields); cells: the case files' labels of the device mesh's cells"""
-    case.set_species(species["names"], species["inert"], ScNumbers=species["ScNumbers"])
+    # (a case read with implicitDiffusion true carries the species' solver controls: it asks for the implicit branch by name)
+    case.set_species(species["names"], species["inert"], ScNumbers=species["ScNumbers"], **({"implicit": True} if species.get("tolerance") is not None else {}))
+    if species.get("tolerance") is not None:     # the implicitDiffusion branch: fvSolution.solvers.<species>
+        case.set_species_solver(species["tolerance"], species["maxIter"])
     for n in species["names"]:
         for patch, entry in enumerate(species["bcs"][n]):
             case.set_species_bc(n, patch, entry)

@@ -189,10 +189,12 @@ class QGDFoamCase:
         return a[0], a[1]
 
     # ---- species mass fractions advanced with the flow (qgd_case_set_species; passive composition: one thermo, no chemistry) ----
-    def set_species(self, names, inert, ScNumbers=None, keep_fluxes=False):
+    def set_species(self, names, inert, ScNumbers=None, keep_fluxes=False, implicit=False):
         """the case carries the mass fractions ``names`` (reactingLagrangianQGDFoam's species block: updateFluxes.H L103-132, QGDYEqn.H
-        L38-92, explicit branch); ``inert`` (a name or an index) is the species that takes 1 - sum of the others; ScNumbers a dict
-        {name: Sc} or a sequence (default 1); keep_fluxes keeps phiJmY / diffusiveFlux of the last step for species_field.  After
+        L38-92, the branch of the case's implicitDiffusion); ``inert`` (a name or an index) is the species that takes 1 - sum of the others; ScNumbers a dict
+        {name: Sc} or a sequence (default 1); keep_fluxes keeps phiJmY / diffusiveFlux of the last step for species_field; implicit accepts
+        the implicitDiffusion branch (QGD_SPECIES_IMPLICIT: one linear solve per batch of species inside the step; without it a case created
+        with implicitDiffusion=1 refuses species, as it always did).  After
         creation, before set_fields.  The case then steps with the separate kernels (fused_info)."""
         names = [str(n) for n in names]
         if len(set(names)) != len(names):
@@ -205,7 +207,8 @@ class QGDFoamCase:
         if sc.size != len(names):
             raise ValueError(f"set_species: {len(names)} species, {sc.size} Schmidt numbers")
         buf = sc if sc.size else np.ones(1)
-        L.check(L.lib.qgd_case_set_species(self._h, len(names), k, buf.ctypes.data_as(L.c_double_p), L.SPECIES_KEEP_FLUXES if keep_fluxes else 0),
+        L.check(L.lib.qgd_case_set_species(self._h, len(names), k, buf.ctypes.data_as(L.c_double_p),
+                                           (L.SPECIES_KEEP_FLUXES if keep_fluxes else 0) | (L.SPECIES_IMPLICIT if implicit else 0)),
                 "qgd_case_set_species")
         self.species = names
 
@@ -244,6 +247,23 @@ class QGDFoamCase:
         a = (C.c_int64 * 4)()
         L.check(L.lib.qgd_case_species_info(self._h, a), "qgd_case_species_info")
         return dict(nSpecies=int(a[0]), inertIndex=int(a[1]), batchWidth=int(a[2]), keepFluxes=bool(a[3]), names=list(getattr(self, "species", []) or []))
+
+    def set_species_solver(self, tolerance, maxIter):
+        """controls of the species' solves on the implicitDiffusion branch (fvSolution.solvers.<species>; default: the case's implicitTol /
+        implicitMaxIter)"""
+        L.check(L.lib.qgd_case_set_species_solver(self._h, float(tolerance), int(maxIter)), "qgd_case_set_species_solver")
+
+    def species_implicit_info(self):
+        """the species' solves of the last step: {unconvergedSteps, stalledSteps, species: {name: {iterations, initial, final}}} (transported
+        species only; the counts have the meaning implicit_info gives them)"""
+        names = list(getattr(self, "species", []) or [])
+        n = 3 + 3 * len(names)
+        a = np.zeros(n)
+        L.check(L.lib.qgd_case_species_implicit_info(self._h, a.ctypes.data_as(L.c_double_p), n), "qgd_case_species_implicit_info")
+        inert = self.species_info()["inertIndex"]
+        return dict(unconvergedSteps=int(a[0]), stalledSteps=int(a[1]),
+                    species={s: dict(iterations=int(a[3 + 3 * i]), initial=float(a[4 + 3 * i]), final=float(a[5 + 3 * i]))
+                             for i, s in enumerate(names) if i != inert})
 
     def updateFluxes(self):
         L.check(L.lib.qgd_case_update_fluxes(self._h), "qgd_case_update_fluxes")
