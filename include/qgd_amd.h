@@ -721,11 +721,21 @@ int qgd_case_sc_range(qgd_case_t c, double out[2]);
  * its diagonal and source; diffusiveFlux_i += YEqn.flux() of the new Y_i, with the listing's sign (opposite to the explicit branch's).
  * The solves start from the old Y_i: the time-extrapolated start values of the flow's solves (QGD_IMPL_XEXTRAP) are not extended to them.
  * Legal after qgd_case_create and before qgd_case_set_fields (QGD_ERR_INVALID afterwards).  At most QGD_MAX_SPECIES species.
- * QGD_ERR_NOT_IMPLEMENTED, with the reason named: implicitDiffusion true without the flag QGD_SPECIES_IMPLICIT, a sharded device,
- * a periodic (qgd_mesh_unroll_cyclic) device, per-term stencils (qgd_case_options::termStencil).  QGD_ERR_INVALID: nSpecies < 2 or > QGD_MAX_SPECIES, inertIndex out of
- * range, a Schmidt number <= 0 (ScNumbers == NULL: all 1), unknown flags.  Not served: monitors of species.
- * qgd_case_step_phase is refused on a case with species; qgd_case_step (and qgd_case_step_sharded, which steps an unsharded device the same
- * way) with a species whose field was never set is QGD_ERR_INVALID.
+ * QGD_ERR_NOT_IMPLEMENTED, with the reason named: implicitDiffusion true without the flag QGD_SPECIES_IMPLICIT; a sharded device or
+ * a periodic (qgd_mesh_unroll_cyclic) device without the flag QGD_SPECIES_HALO, or with it and implicitDiffusion true (the batched species
+ * solves are not distributed); per-term stencils (qgd_case_options::termStencil).  QGD_ERR_INVALID: nSpecies < 2 or > QGD_MAX_SPECIES, inertIndex out of
+ * range, a Schmidt number <= 0 (ScNumbers == NULL: all 1), unknown flags.  Not served: monitors of species, the fused blocks, reacting thermo.
+ * Cell-range shards and cyclic patches, asked for with the flag QGD_SPECIES_HALO, explicit branch: ghost cells then carry their originals'
+ * composition.  The state message (kind 0: qgd_case_halo_count / _pack / _unpack, qgd_case_halo_exchange, qgd_case_step_sharded in both
+ * orders, the self-exchange of a periodic device) grows from 8 to 8 + nSpecies doubles per cell: its front -- 8 per cell, 12 per patch
+ * face -- is laid out as without species, the species follow as nSpecies planes of one double per cell of the slot's list (species-major,
+ * the inert species included).  Patch values do not travel: the unpack re-evaluates those of the slot's ghost patch faces from each
+ * species' boundary condition.  The species' cell and patch kernels then follow the cell roles of the flow's (ghosts are written by the
+ * unpack alone; the boundary layer of a shard can go first, phases 10 / 11).
+ * qgd_case_step_phase is refused on a case with species, except phases 0, 1, 2, 5, 6, 10, 11 of a case with QGD_SPECIES_HALO on a sharded
+ * device; qgd_case_step (and qgd_case_step_sharded, and phases 0 / 5) with a species whose field was never set is QGD_ERR_INVALID.
+ * QGD_SPECIES_HALO was added without a change of QGD_ABI_VERSION (it stays 9: no struct grew, no entry was added or changed its meaning;
+ * a library without the flag answers it with QGD_ERR_INVALID "unknown flags").
  * These entries (the five of the explicit block, then qgd_case_set_species_solver and qgd_case_species_implicit_info) were added without a change of QGD_ABI_VERSION (no struct grew, no existing entry changed its meaning): a host that
  * must run against older builds of the library looks the symbols up (dlsym) instead of comparing the number. */
 #define QGD_MAX_SPECIES 32
@@ -734,6 +744,9 @@ int qgd_case_sc_range(qgd_case_t c, double out[2]);
                                      * implicitDiffusion = 1).  Without it such a case is answered with QGD_ERR_NOT_IMPLEMENTED as before this
                                      * branch was served: a host that runs the stateless qgd_species_step_implicit loop on that answer keeps
                                      * working unchanged, and nobody gets linear solves inside the step without asking.  Ignored on the explicit branch. */
+#define QGD_SPECIES_HALO 4          /* flags: the caller accepts species on a sharded or periodic device: the state message carries the
+                                     * composition (8 + nSpecies doubles per cell; size the buffers by qgd_case_halo_count).  Without it such a
+                                     * device is answered with QGD_ERR_NOT_IMPLEMENTED as before.  On an ordinary device it changes nothing. */
 int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, const double* ScNumbers, int32_t flags);
 /* Boundary condition of one species on one patch: QGD_BC_ZEROGRADIENT (the default of generic patches), QGD_BC_FIXEDVALUE with one
  * value for the patch, QGD_BC_NONE; constraint patches keep QGD_BC_NONE (their faces carry no species flux, or a zero gradient). */

@@ -94,6 +94,13 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         owned = (mesh.array("cellGlobal") >= lo) & (mesh.array("cellGlobal") < hi)
     else:
         mesh, cells, owned = gmesh, old_of_new, np.ones(n_global, dtype=bool)
+    species = opt.get("species")
+    species_halo = bool(species) and (world > 1 or bool(getattr(gmesh, "cyclic_pairs", None)))
+    if species_halo and opt.get("implicitDiffusion"):
+        # (named ahead of the flow's own refusal of cyclic patches with implicitDiffusion below)
+        raise ff.FoamFileError(f"{case_dir}: species with implicitDiffusion true run on one rank, on a mesh without cyclic patches (the batched species "
+                               f"solves are not distributed): this case has {world} rank(s)"
+                               + (" and cyclic patches" if getattr(gmesh, "cyclic_pairs", None) else "") + "; use QGD { implicitDiffusion false; }")
     if getattr(gmesh, "cyclic_pairs", None):
         # translational cyclic pairs: the halves are glued, translated copies of the cells behind either half are refreshed by the library
         # after every step (PolyMesh.unroll_cyclic, DESIGN 6 "cyclic patches"); real cells keep their labels, the copies follow them
@@ -109,9 +116,6 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
     # this driver builds the block tables for a fixed-deltaT case with one GaussVolPoint stencil only: an adjustTimeStep case, which the library
     # can step on the blocks as well (QGD_FUSED_ADJUST, include/qgd_amd.h qgd_case_fused_info), runs the separate kernels here
     # (the blocks serve the explicit branch's one-launch step, shards included, and the implicitDiffusion branch's assembly of the U systems on one rank)
-    species = opt.get("species")
-    if species and (world > 1 or getattr(gmesh, "cyclic_pairs", None)):
-        raise ff.FoamFileError(f"{case_dir}: a case with species runs on one rank, on a mesh without cyclic patches")
     # (a case with species steps with the separate kernels, on either branch: its species block reads the mass flux of every face)
     eligible = (not (opt.get("adjustTimeStep") or opt.get("termStencils") or species) and opt["stencil"] == "GaussVolPoint"
                 and not (opt.get("implicitDiffusion") and world > 1))
@@ -147,7 +151,8 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         case.set_var_sc(**dict(var_sc, const_cells=local_cells))
     if species:
         # the species block of reactingLagrangianQGDFoam, passive: the Y_i advance with the flow on the device (QGDFoamCase.set_species)
-        ff.apply_species(case, species, cells)
+        # (shards and cyclic patches: ghost cells carry their originals' composition, which travels in the state message)
+        ff.apply_species(case, species, cells, **({"halo": True} if species_halo else {}))
     case.set_fields(fields["U"][cells], fields["T"][cells], fields["p"][cells])
     adjust = bool(case.options.adjustTimeStep)
     if world > 1:
@@ -229,9 +234,9 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
                 halo.step(allreduce_max if adjust else None)
         case.sync()
 
-    def gather(name):
-        """owned cells of every rank -> the field in the case's own cell order (rank 0; None elsewhere)"""
-        local = case.field(name)
+    def gather(name, local=None):
+        """owned cells of every rank -> the field in the case's own cell order (rank 0; None elsewhere); local: this rank's values (default: the flow field `name`)"""
+        local = case.field(name) if local is None else local
         if world == 1:
             out = np.empty((n_global,) + local.shape[1:])
             out[cells[owned]] = local[owned]     # (a mesh with cyclic patches carries copies of its cells behind the real ones)
@@ -334,11 +339,10 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             if rank == 0:
                 _write_cell_fields(case_dir, name, data, bcs, gmesh, var_sc)
             if species:
-                Y = {}
-                for sn in species["names"]:
-                    Y[sn] = np.empty(n_global)
-                    Y[sn][cells] = case.species_field(sn)
-                ff.write_species_fields(case_dir, name, gmesh, species, Y)
+                # (gathered from the owned cells like the flow fields: the real cells only of a mesh with cyclic patches)
+                Y = {sn: gather(sn, case.species_field(sn)) for sn in species["names"]}
+                if rank == 0:
+                    ff.write_species_fields(case_dir, name, gmesh, species, Y)
             written.append(name)
         if total is None and t >= end_time - 1e-12 * max(1.0, abs(end_time)):
             break

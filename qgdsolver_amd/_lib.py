@@ -262,7 +262,7 @@ FVSC_REDUCED, FVSC_LEASTSQUARES, FVSC_GAUSSVOLPOINT = range(3)
 FLUX_LINEAR, FLUX_UPWIND = range(2)
 K_POINT, K_FACE, K_BFACE, K_CELL, K_BC, K_BPOINT, K_VARSC = range(7)
 MONITOR_SECTIONS, MONITOR_SLOTS = 5, 4
-MAX_SPECIES, SPECIES_KEEP_FLUXES, SPECIES_IMPLICIT = 32, 1, 2
+MAX_SPECIES, SPECIES_KEEP_FLUXES, SPECIES_IMPLICIT, SPECIES_HALO = 32, 1, 2, 4
 
 
 class QgdError(RuntimeError):

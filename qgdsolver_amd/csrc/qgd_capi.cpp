@@ -375,6 +375,7 @@ struct qgd_case_s {
     uint8_t* spBcKindDev = nullptr;
     double* spBcValDev = nullptr;
     bool spDirty = false, spKeep = false, spFluxesValid = false;
+    bool spHalo = false;        // QGD_SPECIES_HALO: the state message (kind 0) carries the composition behind the flow's records
     // the implicitDiffusion branch of the species [QGDYEqn.H L47-66]: rows and solutions, the statistics of the batches' solves, the controls
     // of qgd_case_set_species_solver (< 0: the case's implicitTol / implicitMaxIter)
     SpeciesImplView spImpl{};
@@ -1931,17 +1932,21 @@ int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, con
         return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: implicitDiffusion true is not served without the flag QGD_SPECIES_IMPLICIT (the species equations' "
                                              "fvm::laplacian branch, QGDYEqn.H L47-66, solves one linear system per batch of species inside the step: a caller asks for it by "
                                              "name); pass the flag, or set implicitDiffusion false");
-    if (d->periodic())
+    const bool halo = (flags & QGD_SPECIES_HALO) != 0;   // the state message carries the composition (asked for by name)
+    if (d->periodic() && !halo)
         return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: a periodic device (cyclic patches served by ghost copies, qgd_mesh_unroll_cyclic) is not served: "
                                              "the copies would need the species' values");
-    if (d->sharded())
+    if (d->sharded() && !halo)
         return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: a sharded device is not served (the halo messages carry no species)");
+    if (d->sharded() && c->opt.implicitDiffusion)   // (a periodic device is sharded() too)
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: implicitDiffusion true with species on a sharded or periodic device is not served: the batched "
+                                             "species solves are not distributed (no messages, no reductions across ghosts); use the explicit branch");
     if (c->mixB >= 0)
         return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_set_species: per-term stencils (qgd_case_options::termStencil) are not served: fvsc::grad(Y) has no entry of its own");
     if (nSpecies < 2) return fail(QGD_ERR_INVALID, "qgd_case_set_species: nSpecies must be at least 2 (one transported species and the inert one)");
     if (nSpecies > QGD_MAX_SPECIES) return fail(QGD_ERR_INVALID, "qgd_case_set_species: at most " + std::to_string(QGD_MAX_SPECIES) + " species are served");
     if (inertIndex < 0 || inertIndex >= nSpecies) return fail(QGD_ERR_INVALID, "qgd_case_set_species: inertIndex out of range");
-    if (flags & ~(QGD_SPECIES_KEEP_FLUXES | QGD_SPECIES_IMPLICIT)) return fail(QGD_ERR_INVALID, "qgd_case_set_species: unknown flags");
+    if (flags & ~(QGD_SPECIES_KEEP_FLUXES | QGD_SPECIES_IMPLICIT | QGD_SPECIES_HALO)) return fail(QGD_ERR_INVALID, "qgd_case_set_species: unknown flags");
     for (int32_t i = 0; ScNumbers && i < nSpecies; ++i)
         if (!(ScNumbers[i] > 0) || !std::isfinite(ScNumbers[i]))
             return fail(QGD_ERR_INVALID, "qgd_case_set_species: the Schmidt number of species " + std::to_string(i) + " must be positive (Sc <= 0)");
@@ -1986,6 +1991,8 @@ int qgd_case_set_species(qgd_case_t c, int32_t nSpecies, int32_t inertIndex, con
     c->sp = sv;
     c->spDirty = true;
     c->spFluxesValid = false;
+    c->spHalo = halo;
+    if (halo) { c->haloBuf.send.clear(); c->haloBuf.recv.clear(); }   // (the case's own message buffers are sized for the wider state message on their next use)
     // the species block reads phiJm of every face, which the fused kernels never write: the three-kernel explicit step, or the separate
     // kernels of the implicit branch (the block-fused assembly of the U systems keeps the internal faces' mass flux in its blocks)
     c->fused = false;
@@ -2010,6 +2017,7 @@ int qgd_case_set_species_bc(qgd_case_t c, int32_t species, int32_t patch, int32_
     c->spBcKind[e] = (uint8_t)bc;
     c->spBcVal[e] = bc == QGD_BC_FIXEDVALUE ? value : 0.0;
     c->spDirty = true;
+    c->ghostsCurrent = false;   // (a periodic device: the copies' patch values follow the new rule with the next refresh)
     return QGD_OK;
     QGD_CATCH
 }
@@ -2026,6 +2034,7 @@ int qgd_case_set_species_fields(qgd_case_t c, int32_t species, const double* Y) 
     c->spFieldSet[species] = 1;
     c->spDirty = true;
     c->spFluxesValid = false;
+    c->ghostsCurrent = false;   // (a periodic device: the copies take their originals' composition before the first step)
     return QGD_OK;
     QGD_CATCH
 }
@@ -2040,7 +2049,7 @@ static int speciesReady(qgd_case_s* c, const char* who) {
     HIP_CHECK(hipMemcpy(c->spBcKindDev, c->spBcKind.data(), c->spBcKind.size(), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(c->spBcValDev, c->spBcVal.data(), sizeof(double) * c->spBcVal.size(), hipMemcpyHostToDevice));
     (void)hipGetLastError();
-    launchSpeciesPatchValues(c->stream(), c->dev->view, c->sp);
+    launchSpeciesPatchValues(c->stream(), c->dev->view, c->sp, -1);   // every face, those of ghost cells too, from the values the caller set
     HIP_CHECK(hipGetLastError());
     c->spDirty = false;
     return QGD_OK;
@@ -2210,6 +2219,7 @@ int qgd_case_update_fluxes(qgd_case_t c) {
     if (c->dev->periodic()) {
         // cyclic pairs served by ghost cells: the copies belong to the library, whatever the caller put into them with set_fields -- they take
         // their originals' records before anything is computed from them (and the mid-step message where qgd_case_step has one)
+        if (c->sp.nS && !c->ghostsCurrent) { const int rs = speciesReady(c, "qgd_case_update_fluxes"); if (rs) return rs; }   // (the refresh moves the composition too)
         if (!c->ghostsCurrent) { selfHaloExchange(c, false); c->ghostsCurrent = true; }
         if (midExchangeNeeded(c)) { assembleFluxes(c, false, 1); selfHaloExchange(c, true); assembleFluxes(c, false, 2); }
         else assembleFluxes(c, false);
@@ -2369,9 +2379,21 @@ static void stepAdvance(qgd_case_s* c, int part) {
         launchCellUpdate(L, m, c->view, c->gas, 0, nullptr, 0);
         launchBoundaryUpdate(L, m, c->view, c->gas, c->bcDev, false, c->phiwRegistered, 0, nullptr, 0);
     } else if (part == 1) {
+        // The species on a shard, boundary layer first.  Part 1 runs the vertex values and BOTH face kernels over ALL faces -- they read the
+        // old records and the old Y of both sides, which nothing has touched yet -- then the species' cell and patch kernels on the layer,
+        // ahead of the flow's, which overwrites the layer's records.  Part 2 can then run beside the unpack of the state message on the
+        // halo stream: it reads SpeciesView::F and CaseView::flux (complete since part 1 / the assembly, written by neither), and the
+        // records, Y and patch faces of ordinary owned cells only, and writes Y and Y.boundary of those alone; the unpack writes the
+        // records, Y and patch values of GHOST cells alone, the pack reads those of the layer alone.  No kernel of part 2 reads or writes
+        // what the concurrent exchange writes or reads.
+        if (c->sp.nS) {
+            launchSpeciesAdvance(L.stream, c->stencil, m, c->view, c->gas, c->sp, 1, d->sendAll, d->nSendAll, d->sendBFAll, d->nSendBFAll);
+            c->spFluxesValid = true;
+        }
         launchCellUpdate(L, m, c->view, c->gas, 1, d->sendAll, d->nSendAll);
         launchBoundaryUpdate(L, m, c->view, c->gas, c->bcDev, false, c->phiwRegistered, 1, d->sendBFAll, d->nSendBFAll);
     } else {
+        if (c->sp.nS) launchSpeciesAdvance(L.stream, c->stencil, m, c->view, c->gas, c->sp, 2);
         launchCellUpdate(L, m, c->view, c->gas, 2, nullptr, 0);
         launchBoundaryUpdate(L, m, c->view, c->gas, c->bcDev, false, c->phiwRegistered, 2, nullptr, 0);
     }
@@ -2390,6 +2412,8 @@ int qgd_case_step(qgd_case_t c, int32_t nSteps) {
         if (c->opt.implicitDiffusion)
             return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_step: the implicitDiffusion branch on a mesh with cyclic patches (qgd_mesh_unroll_cyclic) is not served: "
                                                  "its solves would need the coupled rows; use the explicit branch");
+        // (the species' boundary-condition tables reach the device first: the refresh re-evaluates the copies' patch values from them)
+        if (c->sp.nS) { const int rs = speciesReady(c, "qgd_case_step"); if (rs) return rs; }
         if (!c->ghostsCurrent) { selfHaloExchange(c, false); c->ghostsCurrent = true; }
         for (int i = 0; i < nSteps; ++i) {
             if (midExchangeNeeded(c)) { stepAssemble(c, 1); selfHaloExchange(c, true); stepAssemble(c, 2); }
@@ -2414,7 +2438,10 @@ int qgd_case_step_phase(qgd_case_t c, int phase) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_case_step_phase: call qgd_case_set_fields first");
-    if (c->sp.nS)
+    // (a case with species and QGD_SPECIES_HALO on a cell-range shard advances through the phases like any other; a periodic device is sharded() too)
+    const bool speciesPhases = c->sp.nS && c->spHalo && c->dev->sharded() && !c->dev->periodic() && !c->opt.implicitDiffusion &&
+                               (phase == 0 || phase == 1 || phase == 2 || phase == 5 || phase == 6 || phase == 10 || phase == 11);
+    if (c->sp.nS && !speciesPhases)
         return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_step_phase: the case carries species (qgd_case_set_species), which advance inside qgd_case_step only");
     if (c->dev->periodic())
         return fail(QGD_ERR_INVALID, "qgd_case_step_phase: a periodic device (cyclic patches served by ghost copies, qgd_mesh_unroll_cyclic) is stepped with "
@@ -2432,6 +2459,7 @@ int qgd_case_step_phase(qgd_case_t c, int phase) {
     if (c->opt.implicitDiffusion && phase == 1 && c->dev->sharded())
         return fail(QGD_ERR_INVALID, "qgd_case_step_phase: on a shard the implicitDiffusion branch advances through phases 20..35 with the "
                                      "exchanges between them");
+    if (c->sp.nS && (phase == 0 || phase == 5)) { const int rs = speciesReady(c, "qgd_case_step_phase"); if (rs) return rs; }   // where a step begins
     if (phase == 0) stepAssemble(c);
     else if (phase == 5) stepAssemble(c, 1);
     else if (phase == 6) stepAssemble(c, 2);
@@ -2497,6 +2525,7 @@ int qgd_device_release(qgd_device_t d, void* devicePtr) {
 
 // ---- the halo messages of the QGD case -------------------------------------------------------------------------------------
 // kind 0: the state message, QGD_HALO_CELL_DOUBLES_HOST doubles per cell (RecA, RecB), 12 per boundary face (RecA, RecB, p gradient, lagged rho);
+//         a case with species and QGD_SPECIES_HALO appends nS planes of one double per cell (qgd_species.hip caseSpeciesHaloKernel);
 // kinds 1..4: the implicitDiffusion branch's own (1 grad U, 2 U, 3 search direction, 4 guess: implicitHaloWidth doubles per cell);
 // kind 5: the message between step phases 5 and 6 (see assembleFluxes), 2 doubles per patch face of the slot's boundary-layer cells
 static int caseHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pack, hipStream_t stream) {
@@ -2512,6 +2541,10 @@ static int caseHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pac
         Launcher L = launcherOf(c);
         L.pre = nullptr; L.post = nullptr; L.stream = stream;
         launchHaloPack(L, c->view, c->gas, cells, nCells, faces, nFaces, buf, pack);
+        // the species tail behind the flow's part, which keeps its layout; on the same stream: the patch values follow the cells' Y
+        if (c->spHalo)
+            launchSpeciesHalo(stream, d->view, c->sp, cells, nCells, faces, nFaces,
+                              buf + (size_t)QGD_HALO_CELL_DOUBLES_HOST * (size_t)nCells + 12 * (size_t)nFaces, pack);
     } else if (kind == 5) launchMidHalo(stream, c->view, faces, nFaces, buf, pack);
     else launchImplicitHalo(stream, d->view, c->view, c->impl, c->implSolver, kind, cells, nCells, buf, pack);
     HIP_CHECK(hipGetLastError());
@@ -2520,7 +2553,7 @@ static int caseHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pac
 // forCount: kinds 3 and 4 with room for the widest solve (what a caller sizes its buffers by); what is SENT has the width of the solve in flight
 static HaloMessage haloMessage(qgd_case_s* c, int kind, bool forCount = false) {
     HaloMessage m;
-    if (kind == 0) { m.perCell = QGD_HALO_CELL_DOUBLES_HOST; m.perFace = 12; }
+    if (kind == 0) { m.perCell = QGD_HALO_CELL_DOUBLES_HOST + (c->spHalo ? c->sp.nS : 0); m.perFace = 12; }
     else if (kind == 5) m.perFace = 2;
     else m.perCell = (forCount && kind >= 3) ? 3 : implicitHaloWidth(c->implSolver, kind);
     m.move = [c, kind](int slot, double* buf, bool pack, hipStream_t stream) { return caseHaloMove(c, slot, kind, buf, pack, stream); };
@@ -2529,6 +2562,7 @@ static HaloMessage haloMessage(qgd_case_s* c, int kind, bool forCount = false) {
 static HaloBuffers& haloBuffers(qgd_case_s* c) {
     c->haloBuf.arena = &c->arena;
     c->haloBuf.widest.perCell = c->implSolver ? 9 : QGD_HALO_CELL_DOUBLES_HOST;   // grad U: 9 per cell; state: 8 per cell and ...
+    if (c->spHalo) c->haloBuf.widest.perCell = std::max(c->haloBuf.widest.perCell, QGD_HALO_CELL_DOUBLES_HOST + (int)c->sp.nS);   // (+ the species' planes)
     c->haloBuf.widest.perFace = 12;                                               // ... 12 per face
     return c->haloBuf;
 }
@@ -3572,7 +3606,8 @@ int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, i
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_case_step_sharded: call qgd_case_set_fields first");
-    // (a case with species lives on an unsharded device, which this entry steps like qgd_case_step)
+    // (a case with species: on an unsharded device, which this entry steps like qgd_case_step, or with QGD_SPECIES_HALO on a shard, where the
+    // state message carries the composition and stepAdvance's parts the species block -- nothing else differs)
     if (c->sp.nS) { const int rs = speciesReady(c, "qgd_case_step_sharded"); if (rs) return rs; }
     const bool sharded = !c->dev->halo.empty() && nSlots > 0;
     if (sharded && (!comm || !peers)) return fail(QGD_ERR_INVALID, "qgd_case_step_sharded: null argument");

@@ -229,8 +229,16 @@ struct SpeciesView {
 };
 // one step of every species on the OLD records and the assembled mass flux (CaseView::flux plane 0), deltaT from CaseView::dt: between
 // launchDeltaT and the flow's cell update; leaves the patch values of the new time level behind
-void launchSpeciesAdvance(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv);
-void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesView& sv);
+// part / list / blist: the cell roles of launchCellUpdate and launchBoundaryUpdate (0 everything but ghosts; 1 the vertex and face walks over
+// ALL faces, then the cells of `list` and the patch faces of `blist`; 2 the remaining owned cells and their patch faces)
+void launchSpeciesAdvance(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv, int part = 0,
+                          const int32_t* list = nullptr, int nList = 0, const int32_t* blist = nullptr, int nBList = 0);
+// mode as above by the role of the face's owner; mode < 0: every face (the first evaluation, from the caller's fields)
+void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesView& sv, int mode = 0, const int32_t* list = nullptr, int nList = 0);
+// the species tail of the state message (QGD_SPECIES_HALO): nS planes of nCells doubles at `tail`, species-major; the unpack re-evaluates the
+// patch values of `bfaces` (the slot's ghost patch faces) from the patch rule
+void launchSpeciesHalo(hipStream_t s, const MeshView& m, const SpeciesView& sv, const int32_t* cells, int32_t nCells, const int32_t* bfaces,
+                       int32_t nFaces, double* tail, bool pack);
 void launchSpeciesPoints(hipStream_t s, const MeshView& m, const SpeciesView& sv);   // vertex values of the transported species (GaussVolPoint)
 // the implicitDiffusion branch [QGDYEqn.H L47-66]: SpeciesView::F then holds phiJmY_i alone; one solve per register batch (qgd_species_implicit.hip)
 struct SpeciesImplView {

@@ -14,6 +14,11 @@
 //   SC  caseSpeciesCellKernel<W>            one lane per cell over the cell -> face table, no atomics: rhoNew from phiJm and the device's deltaT
 //                                       (the value the flow's cell update forms), then Y_i, Yi.max(0), Y_inert = max(1 - sum, 0)
 //   SB  caseSpeciesPatchKernel              patch values for the next step
+//   SH  caseSpeciesHaloKernel               the species tail of the state message (QGD_SPECIES_HALO): nS planes behind the flow's records
+//
+// SC and SB take the cell roles of cellUpdateKernel (mode / list): ghost cells and the patch faces of ghost cells are written by the unpack
+// of the state message alone, a shard's boundary layer can go first.  SP, SF and SFB always walk everything: they read, and write only
+// what SC reads.
 //
 // Per species the face kernels form [updateFluxes.H L122-127, QGDYEqn.H L75, L82]
 //     gradYf, phiJmY_i = phiJm Yf_i - phi tauQGDf (Uf & gradYf), lap_i = (muf / Sc_i) snGrad(Y_i.old) |Sf|
@@ -147,10 +152,20 @@ __global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesBoundaryPointKernel(cons
 // QGDYEqn.H L67-91 of one cell: fvm::ddt(rho, Yi) + fvc::div(phiJmYi - lap_i) == 0 (Euler), the divergence gathered in ascending face
 // label like fvc::surfaceIntegrate; rho.oldTime() is the record's density (the flow's cell update runs after this kernel), rho the value
 // that update forms from the same mass fluxes and the same deltaT [QGDRhoEqn_8H L40-47]
+// mode 0: every cell but the ghosts; mode 1: the cells of `list` (a shard's boundary layer); mode 2: ordinary owned cells only -- the
+// convention of cellUpdateKernel.  Without cell roles (MeshView::ghost null) mode 0 is every cell.
 template <int W>
-__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesCellKernel(const MeshView m, const CaseView c, const SpeciesView sv) {
-    const int ci = blockIdx.x * QGD_BLOCK + threadIdx.x;
-    if (ci >= m.nC) return;
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesCellKernel(const MeshView m, const CaseView c, const SpeciesView sv, const int mode,
+                                                                  const int32_t* __restrict__ list, const int nList) {
+    const int idx = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    int ci;
+    if (mode == 1) { if (idx >= nList) return; ci = list[idx]; }
+    else {
+        if (idx >= m.nC) return;
+        const int role = m.ghost ? m.ghost[idx] : 0;
+        if (role == 1 || (mode == 2 && role == 2)) return;
+        ci = idx;
+    }
     const int n = m.cfCount[ci];
     const size_t base = (size_t)m.cfSlice[ci >> 6] * 64 + (ci & 63);
     const size_t nC = (size_t)m.nC, nF = (size_t)m.nF;
@@ -194,19 +209,47 @@ __global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesCellKernel(const MeshVie
     sv.Y[(size_t)sv.inert * nC + ci] = fmax(1.0 - Yt, 0.0);                                // [L90-91]
 }
 
-// patch values of every species: fixedValue keeps its value, zeroGradient (and the constraint patches' `none`) takes the owner's
-__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesPatchKernel(const MeshView m, const SpeciesView sv) {
-    const int b = blockIdx.x * QGD_BLOCK + threadIdx.x;
-    if (b >= m.nBF) return;
+// patch values of every species: fixedValue keeps its value, zeroGradient (and the constraint patches' `none`) takes the owner's.
+// Modes as in caseSpeciesCellKernel, by the role of the face's owner cell (mode 1: the patch faces of `list`, which the unpack of the state
+// message uses for the patch faces of a slot's ghost cells too); mode < 0 evaluates every face (the first evaluation, from the caller's fields)
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesPatchKernel(const MeshView m, const SpeciesView sv, const int mode,
+                                                                   const int32_t* __restrict__ list, const int nList) {
+    const int idx = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    int b;
+    if (mode == 1) { if (idx >= nList) return; b = list[idx]; }
+    else { if (idx >= m.nBF) return; b = idx; }
     const int o = m.own[m.nIF + b], patch = m.bPatch[b];
+    if (mode != 1 && mode >= 0 && m.ghost) {
+        const int role = m.ghost[o];
+        if (role == 1 || (mode == 2 && role == 2)) return;
+    }
     for (int i = 0; i < sv.nS; ++i) {
         const size_t e = (size_t)i * sv.nPatches + patch;
         sv.Yb[(size_t)i * m.nBF + b] = sv.bcKind[e] == QGD_BC_FIXEDVALUE ? sv.bcVal[e] : sv.Y[(size_t)i * m.nC + o];
     }
 }
 
-void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesView& sv) {
-    if (m.nBF) caseSpeciesPatchKernel<<<gridOfS(m.nBF), QGD_BLOCK, 0, s>>>(m, sv);
+// The species tail of the state message: nS planes of n doubles behind the flow's records, species-major, so that a wavefront's stores on
+// pack and loads on unpack are contiguous; one lane per entry of the slot's cell list (send cells on pack, ghost cells on unpack), all nS
+// species -- the inert one too: a ghost cell holds its original's whole composition.  Patch values do not travel: the unpack re-evaluates
+// those of the slot's ghost patch faces from the patch rule (caseSpeciesPatchKernel on that list), as the state message does c and alpha/c.
+__global__ __launch_bounds__(QGD_BLOCK) void caseSpeciesHaloKernel(const SpeciesView sv, const int nC, const int32_t* __restrict__ cells, const int n,
+                                                                  double* __restrict__ tail, const int pack) {
+    const int i = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const size_t ci = (size_t)cells[i];
+    if (pack) for (int s = 0; s < sv.nS; ++s) tail[(size_t)s * n + i] = sv.Y[(size_t)s * nC + ci];
+    else for (int s = 0; s < sv.nS; ++s) sv.Y[(size_t)s * nC + ci] = tail[(size_t)s * n + i];
+}
+
+void launchSpeciesPatchValues(hipStream_t s, const MeshView& m, const SpeciesView& sv, int mode, const int32_t* list, int nList) {
+    const int n = (mode == 1) ? nList : m.nBF;
+    if (n) caseSpeciesPatchKernel<<<gridOfS(n), QGD_BLOCK, 0, s>>>(m, sv, mode, list, nList);
+}
+void launchSpeciesHalo(hipStream_t s, const MeshView& m, const SpeciesView& sv, const int32_t* cells, int32_t nCells, const int32_t* bfaces,
+                       int32_t nFaces, double* tail, bool pack) {
+    if (nCells) caseSpeciesHaloKernel<<<gridOfS(nCells), QGD_BLOCK, 0, s>>>(sv, m.nC, cells, nCells, tail, pack ? 1 : 0);
+    if (!pack) launchSpeciesPatchValues(s, m, sv, 1, bfaces, nFaces);   // behind the cells on the same stream: the faces' owners are among them
 }
 
 // vertex values of the transported species (GaussVolPoint): the implicit branch's walk (qgd_species_implicit.hip) starts with them too
@@ -216,22 +259,29 @@ void launchSpeciesPoints(hipStream_t s, const MeshView& m, const SpeciesView& sv
     if (m.nBP) caseSpeciesBoundaryPointKernel<W><<<gridOfS(m.nBP), QGD_BLOCK, 0, s>>>(m, sv);
 }
 
+// part 0: everything; part 1: the walks over ALL faces, then the cells of `list` and the patch faces of `blist` (a shard's boundary layer);
+// part 2: the remaining owned cells and their patch faces, from the face values part 1 left
 template <int ST>
-static void launchSpeciesAdvanceT(hipStream_t s, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv) {
+static void launchSpeciesAdvanceT(hipStream_t s, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv, int part,
+                                  const int32_t* list, int nList, const int32_t* blist, int nBList) {
     constexpr int W = QGD_SPECIES_W;
-    if (ST == ST_GVP3 || ST == ST_GVP2) launchSpeciesPoints(s, m, sv);
-    if (m.nIF) caseSpeciesFaceKernel<ST, W><<<gridOfS(m.nIF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
-    if (m.nBF) caseSpeciesBoundaryFaceKernel<ST, W><<<gridOfS(m.nBF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
-    caseSpeciesCellKernel<W><<<gridOfS(m.nC), QGD_BLOCK, 0, s>>>(m, c, sv);
-    launchSpeciesPatchValues(s, m, sv);
+    if (part != 2) {
+        if (ST == ST_GVP3 || ST == ST_GVP2) launchSpeciesPoints(s, m, sv);
+        if (m.nIF) caseSpeciesFaceKernel<ST, W><<<gridOfS(m.nIF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
+        if (m.nBF) caseSpeciesBoundaryFaceKernel<ST, W><<<gridOfS(m.nBF), QGD_BLOCK, 0, s>>>(m, c, g, sv);
+    }
+    const int n = (part == 1) ? nList : m.nC;
+    if (n) caseSpeciesCellKernel<W><<<gridOfS(n), QGD_BLOCK, 0, s>>>(m, c, sv, part, list, nList);
+    launchSpeciesPatchValues(s, m, sv, part, blist, nBList);
 }
-void launchSpeciesAdvance(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv) {
+void launchSpeciesAdvance(hipStream_t s, int stencil, const MeshView& m, const CaseView& c, const GasModel& g, const SpeciesView& sv, int part,
+                          const int32_t* list, int nList, const int32_t* blist, int nBList) {
     if (m.nC == 0 || sv.nS == 0) return;
     switch (stencil) {
-        case ST_REDUCED: launchSpeciesAdvanceT<ST_REDUCED>(s, m, c, g, sv); break;
-        case ST_LSQ: launchSpeciesAdvanceT<ST_LSQ>(s, m, c, g, sv); break;
-        case ST_GVP3: launchSpeciesAdvanceT<ST_GVP3>(s, m, c, g, sv); break;
-        default: launchSpeciesAdvanceT<ST_GVP2>(s, m, c, g, sv); break;
+        case ST_REDUCED: launchSpeciesAdvanceT<ST_REDUCED>(s, m, c, g, sv, part, list, nList, blist, nBList); break;
+        case ST_LSQ: launchSpeciesAdvanceT<ST_LSQ>(s, m, c, g, sv, part, list, nList, blist, nBList); break;
+        case ST_GVP3: launchSpeciesAdvanceT<ST_GVP3>(s, m, c, g, sv, part, list, nList, blist, nBList); break;
+        default: launchSpeciesAdvanceT<ST_GVP2>(s, m, c, g, sv, part, list, nList, blist, nBList); break;
     }
 }
 int speciesBatchWidth() { return QGD_SPECIES_W; }

@@ -938,8 +938,6 @@ def _read_species(case_dir, tdir, tp, names, mesh, ptw):
     inert = str(tp["inertSpecie"])
     if inert not in names:
         raise FoamFileError(f"thermophysicalProperties: inertSpecie '{inert}' is not in the species list {names} [createFields.H L31-39]")
-    if getattr(mesh, "cyclic_pairs", None):
-        raise FoamFileError(f"{case_dir}: species on a mesh with cyclic patches are not served")
     sc = {n: 1.0 for n in names}
     for pair in tp.get("ScNumbers", []) or []:
         if not (isinstance(pair, (list, tuple)) and len(pair) == 2):
@@ -972,10 +970,12 @@ def species_entries_text(species):
     return f"species ({' '.join(species['names'])});\ninertSpecie {species['inert']};\nScNumbers ({pairs});\n"
 
 
-def apply_species(case, species, cells=None):
-    """opt["species"] of read_case_setup onto a QGDFoamCase (before set_fields); cells: the case files' labels of the device mesh's cells"""
+def apply_species(case, species, cells=None, halo=False):
+    """opt["species"] of read_case_setup onto a QGDFoamCase (before set_fields); cells: the case files' labels of the device mesh's cells;
+    halo: the device is a shard or serves cyclic patches by ghost copies (QGDFoamCase.set_species halo=True)"""
     # (a case read with implicitDiffusion true carries the species' solver controls: it asks for the implicit branch by name)
-    case.set_species(species["names"], species["inert"], ScNumbers=species["ScNumbers"], **({"implicit": True} if species.get("tolerance") is not None else {}))
+    case.set_species(species["names"], species["inert"], ScNumbers=species["ScNumbers"], **({"implicit": True} if species.get("tolerance") is not None else {}),
+                     **({"halo": True} if halo else {}))
     if species.get("tolerance") is not None:     # the implicitDiffusion branch: fvSolution.solvers.<species>
         case.set_species_solver(species["tolerance"], species["maxIter"])
     for n in species["names"]:
@@ -1378,7 +1378,9 @@ def load_case(case_dir, time="0", device_id=0):
     if opt.get("varSc"):
         case.set_var_sc(**opt["varSc"])
     if opt.get("species"):
-        apply_species(case, opt["species"])
+        # (cyclic patches: the copies behind either half carry their originals' composition, which the library refreshes with their records)
+        cyclic = hasattr(mesh, "file_mesh")
+        apply_species(case, opt["species"], *((mesh.array("cellGlobal"), True) if cyclic else ()))
     case.set_fields(fields["U"], fields["T"], fields["p"])
     return dev, case
 

@@ -189,12 +189,13 @@ class QGDFoamCase:
         return a[0], a[1]
 
     # ---- species mass fractions advanced with the flow (qgd_case_set_species; passive composition: one thermo, no chemistry) ----
-    def set_species(self, names, inert, ScNumbers=None, keep_fluxes=False, implicit=False):
+    def set_species(self, names, inert, ScNumbers=None, keep_fluxes=False, implicit=False, halo=False):
         """the case carries the mass fractions ``names`` (reactingLagrangianQGDFoam's species block: updateFluxes.H L103-132, QGDYEqn.H
         L38-92, the branch of the case's implicitDiffusion); ``inert`` (a name or an index) is the species that takes 1 - sum of the others; ScNumbers a dict
         {name: Sc} or a sequence (default 1); keep_fluxes keeps phiJmY / diffusiveFlux of the last step for species_field; implicit accepts
         the implicitDiffusion branch (QGD_SPECIES_IMPLICIT: one linear solve per batch of species inside the step; without it a case created
-        with implicitDiffusion=1 refuses species, as it always did).  After
+        with implicitDiffusion=1 refuses species, as it always did); halo accepts a sharded or periodic device (QGD_SPECIES_HALO: the state
+        message then carries the composition, 8 + nSpecies doubles per cell -- halo_count says so; explicit branch only).  After
         creation, before set_fields.  The case then steps with the separate kernels (fused_info)."""
         names = [str(n) for n in names]
         if len(set(names)) != len(names):
@@ -208,7 +209,7 @@ class QGDFoamCase:
             raise ValueError(f"set_species: {len(names)} species, {sc.size} Schmidt numbers")
         buf = sc if sc.size else np.ones(1)
         L.check(L.lib.qgd_case_set_species(self._h, len(names), k, buf.ctypes.data_as(L.c_double_p),
-                                           (L.SPECIES_KEEP_FLUXES if keep_fluxes else 0) | (L.SPECIES_IMPLICIT if implicit else 0)),
+                                           (L.SPECIES_KEEP_FLUXES if keep_fluxes else 0) | (L.SPECIES_IMPLICIT if implicit else 0) | (L.SPECIES_HALO if halo else 0)),
                 "qgd_case_set_species")
         self.species = names
 
