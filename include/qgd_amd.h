@@ -724,7 +724,8 @@ int qgd_case_sc_range(qgd_case_t c, double out[2]);
  * QGD_ERR_NOT_IMPLEMENTED, with the reason named: implicitDiffusion true without the flag QGD_SPECIES_IMPLICIT; a sharded device or
  * a periodic (qgd_mesh_unroll_cyclic) device without the flag QGD_SPECIES_HALO, or with it and implicitDiffusion true (the batched species
  * solves are not distributed); per-term stencils (qgd_case_options::termStencil).  QGD_ERR_INVALID: nSpecies < 2 or > QGD_MAX_SPECIES, inertIndex out of
- * range, a Schmidt number <= 0 (ScNumbers == NULL: all 1), unknown flags.  Not served: monitors of species, the fused blocks, reacting thermo.
+ * range, a Schmidt number <= 0 (ScNumbers == NULL: all 1), unknown flags.  Not served: the fused blocks, reacting thermo.  Run monitors report the species through
+ * qgd_monitor_enable_species (masses, extrema, probes, patch fluxes; below, with the monitors).
  * Cell-range shards and cyclic patches, asked for with the flag QGD_SPECIES_HALO, explicit branch: ghost cells then carry their originals'
  * composition.  The state message (kind 0: qgd_case_halo_count / _pack / _unpack, qgd_case_halo_exchange, qgd_case_step_sharded in both
  * orders, the self-exchange of a periodic device) grows from 8 to 8 + nSpecies doubles per cell: its front -- 8 per cell, 12 per patch
@@ -1005,6 +1006,40 @@ int qgd_monitor_sample(qgd_monitor_t m, int32_t slot);
 /* Waits for that slot's event only.  time / step: those of the case when the slot was sampled. */
 int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, double* time, int64_t* step);
 int qgd_monitor_free(qgd_monitor_t m);
+
+/* The species block of a monitor, for a case that carries species (qgd_case_set_species): the same quantities per species, all nSpecies
+ * in the case's species order, the inert one included.  qgd_monitor_enable_species is called once, after qgd_monitor_create and before the
+ * monitor's first sample; from then on every qgd_monitor_sample forms the species block too (three more launches whatever nSpecies is; the
+ * block travels in the same copy, into the slot's pinned memory behind the flow block, under the same event).  Until it is called a
+ * monitor launches and copies exactly what it did before these entries existed, on a case with species too.  The block follows the
+ * flow block's rules: nothing is written to the case, no sum depends on anything but the mesh, the specification and nSpecies (two
+ * samples of one state are bitwise equal), ghost cells of a shard, the copies behind cyclic halves and patch faces they own are never
+ * counted, labels are those of the unsharded mesh.
+ *
+ * Species block (doubles; qgd_monitor_species_layout gives the offsets of its QGD_MONITOR_SECTIONS sections), S = nSpecies:
+ *   0 header (8):      S | inert index | species flux state (0: no species assembly since qgd_case_set_fields, the patch fluxes are NaN;
+ *                      1: explicit branch; 2: implicitDiffusion branch) | owned cells with a non-finite Y_i | lowest label among them
+ *                      (-1: none) | max |sum_i Y_i - 1| over the owned cells whose Y_i are all finite (NaN: no such cell) | nProbes | nPatches
+ *   1 integrals (S):   sum rho Y_i V over the owned cells, rho from the records
+ *   2 extrema (4 S):   {min, its cell, max, its cell} of Y_i over the owned cells whose Y_i is finite; ties go to the lowest label; NaN
+ *                      and -1 when there is no such cell
+ *   3 probes (S each):  Y_i of the probe's cell (NaN where the label is -1)
+ *   4 patches (S each): the total over the patch's faces of the net flux of species i out of the domain, as the species' cell update of
+ *                      the last step consumed it.  Explicit branch: phiJmY_i - (muf / Sc_i) snGrad(Y_i) |Sf|.  implicitDiffusion: phiJmY_i
+ *                      plus YEqn.flux() on the face, -(a_b / Sc_i)(Y_b - Y_P) with a_b = muf |Sf| delta_f and the new Y_i of the owner, on
+ *                      the faces of the species' fixedValue patches (zero elsewhere).  The inert species: phiJm minus the transported
+ *                      species' fluxes, what Y_inert = 1 - sum implies.  With the integrals of successive samples they close the
+ *                      discrete balance of every species to rounding (explicit branch) or to the residuals of the solves (implicit
+ *                      branch) while no clip (Y_i.max(0), the inert max(1 - sum, 0)) is active.  The inert row takes phiJm from the
+ *                      assembly the flow block reports: after a qgd_case_update_fluxes that followed the step it is that of the new state.
+ * QGD_ERR_INVALID, with the reason named: qgd_monitor_enable_species on a case without species or after the monitor's first sample (a
+ * second call on an enabled monitor does nothing); qgd_monitor_species_layout / _read before it; a slot out of range or never sampled;
+ * cap below the block's doubles.  These three entries were added without a change of QGD_ABI_VERSION (it stays 9: no struct grew, no
+ * existing entry changed its meaning); a host that must run against older builds looks the symbols up. */
+int qgd_monitor_enable_species(qgd_monitor_t m);
+int qgd_monitor_species_layout(qgd_monitor_t m, int64_t offsets[QGD_MONITOR_SECTIONS], int64_t* nDoubles);
+/* Waits for the slot's event only (the one qgd_monitor_read waits for). */
+int qgd_monitor_species_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap);
 
 #ifdef __cplusplus
 }

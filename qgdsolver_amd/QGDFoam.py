@@ -6,7 +6,8 @@ setDeltaT-QGDQHD.H, the three explicit equations, thermo.correct(), runTime.writ
 ``QGDFoamCase.step`` plus ``foamfile.write_time`` here.  Read from system/controlDict:
 startFrom/startTime, endTime, deltaT, writeControl (timeStep, or runTime/adjustableRunTime with a
 fixed deltaT), writeInterval, adjustTimeStep/maxCo/maxDeltaT, timePrecision, and of ``functions{}`` the types
-probes, fieldMinMax, qgdIntegrals and qgdPatchFluxes (foamfile.read_functions; files under postProcessing/).
+probes, fieldMinMax, qgdIntegrals and qgdPatchFluxes, with species names among the fields and qgdSpeciesIntegrals and
+qgdSpeciesPatchFluxes in a case with species (foamfile.read_functions; files under postProcessing/).
 """
 import argparse
 import os
@@ -190,11 +191,12 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         else:
             halo.exchange()
 
-    # functions{} of system/controlDict: probes, fieldMinMax, qgdIntegrals, qgdPatchFluxes through one device monitor (monitor.py), sampled
+    # functions{} of system/controlDict: probes, fieldMinMax, qgdIntegrals, qgdPatchFluxes -- and, in a case with species, species names in
+    # the fields of the first two, qgdSpeciesIntegrals and qgdSpeciesPatchFluxes -- through one device monitor (monitor.py), sampled
     # after the steps at which one of them is due and read two samples late.  On several ranks every rank samples its shard and the
     # parts are combined on rank 0 (monitor.combine) -- a combination that has not run on more than one GPU yet.
     functions = None
-    func_specs = ff.read_functions(cd, warn=log)
+    func_specs = ff.read_functions(cd, warn=log, species=species["names"] if species else None)
     if func_specs:
         from .monitor import FunctionObjects
         if world > 1:
@@ -209,7 +211,7 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
         else:
             local_of, gather_parts = (lambda g: g), None
         functions = FunctionObjects(case, func_specs, gmesh, case_dir, t0_name, local_of, old_of_new, is_root=rank == 0,
-                                    gather=gather_parts, log=log)
+                                    gather=gather_parts, log=log, species=species["names"] if species else None)
     steps_taken = [0]
 
     def advance(n):

@@ -237,6 +237,9 @@ SIGNATURES = {
     "qgd_monitor_sample": (C.c_int, [handle, C.c_int32]),
     "qgd_monitor_read": (C.c_int, [handle, C.c_int32, c_double_p, C.c_int64, c_double_p, c_int64_p]),
     "qgd_monitor_free": (C.c_int, [handle]),
+    "qgd_monitor_enable_species": (C.c_int, [handle]),
+    "qgd_monitor_species_layout": (C.c_int, [handle, c_int64_p, c_int64_p]),
+    "qgd_monitor_species_read": (C.c_int, [handle, C.c_int32, c_double_p, C.c_int64]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

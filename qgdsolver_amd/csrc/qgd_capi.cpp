@@ -3941,8 +3941,11 @@ struct qgd_monitor_s {
     MonitorView view{};
     DeviceArena arena;
     double* result = nullptr;    // device: one result block (the copy into a slot follows the fold in stream order)
-    double* host = nullptr;      // pinned: QGD_MONITOR_SLOTS result blocks
+    double* host = nullptr;      // pinned: QGD_MONITOR_SLOTS slots of nDoubles + spDoubles: the flow block, the species block behind it
     int64_t nDoubles = 0;
+    // the species block (qgd_monitor_enable_species; qgd_monitor_species.hip): spDoubles == 0 until it is enabled
+    SpeciesMonitorView spView{};
+    int64_t spDoubles = 0;
     hipEvent_t ev[QGD_MONITOR_SLOTS] = {};
     bool sampled[QGD_MONITOR_SLOTS] = {};
     double time[QGD_MONITOR_SLOTS] = {};
@@ -4070,7 +4073,13 @@ int qgd_monitor_sample(qgd_monitor_t m, int32_t slot) {
     (void)hipGetLastError();
     launchMonitorSample(st, m->view, c->dev->view, c->view, c->gas, fluxState, m->result);   // (the view as it stands now: the fused step swaps A / B)
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(m->host + (size_t)slot * m->nDoubles, m->result, sizeof(double) * (size_t)m->nDoubles, hipMemcpyDeviceToHost, st));
+    const size_t slotDoubles = (size_t)(m->nDoubles + m->spDoubles);
+    if (m->spDoubles) {   // the species block: three more launches, behind the flow block in the same device buffer, so one copy takes both
+        const int spState = !c->spFluxesValid ? 0 : (c->opt.implicitDiffusion ? 2 : 1);
+        launchMonitorSpeciesSample(st, m->view, m->spView, c->dev->view, c->view, c->sp, c->spImpl.aF, spState, m->result + m->nDoubles);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipMemcpyAsync(m->host + (size_t)slot * slotDoubles, m->result, sizeof(double) * slotDoubles, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipEventRecord(m->ev[slot], st));
     m->sampled[slot] = true; m->time[slot] = c->time; m->step[slot] = c->steps;
     return QGD_OK;
@@ -4084,10 +4093,64 @@ int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, do
     if (!m->sampled[slot]) return fail(QGD_ERR_INVALID, "qgd_monitor_read: slot " + std::to_string(slot) + " was never sampled");
     HIP_CHECK(hipSetDevice(m->c->dev->deviceId));
     HIP_CHECK(hipEventSynchronize(m->ev[slot]));
-    const double* src = m->host + (size_t)slot * m->nDoubles;
+    const double* src = m->host + (size_t)slot * (size_t)(m->nDoubles + m->spDoubles);
     std::copy(src, src + m->nDoubles, out);
     if (time) *time = m->c->opt.adjustTimeStep ? src[7] : m->time[slot];
     if (step) *step = m->step[slot];
+    return QGD_OK;
+    QGD_CATCH
+}
+// the species block of a monitor: sampled by the same qgd_monitor_sample, behind the flow block of the slot
+int qgd_monitor_enable_species(qgd_monitor_t m) {
+    QGD_TRY
+    if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: not an open monitor (a monitor is freed with its case)");
+    qgd_case_s* c = m->c;
+    if (!c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: the case carries no species (qgd_case_set_species)");
+    if (m->spDoubles) return QGD_OK;
+    for (bool s : m->sampled)
+        if (s) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: call it before the monitor's first qgd_monitor_sample (the slots grow by the species block)");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    const MonitorView& v = m->view;
+    SpeciesMonitorView sm{};
+    const int64_t nS = c->sp.nS, nOwned = (int64_t)v.ownedEnd - v.ownedBegin, tile = 256 * QGD_MONITOR_SPECIES_CELLS;
+    sm.nRows = (int32_t)std::min<int64_t>((nOwned + tile - 1) / tile, QGD_MONITOR_BLOCKS);   // workgroups of the cell pass: they stride over the tiles beyond that
+    sm.off[0] = 0; sm.off[1] = QGD_MONITOR_SPECIES_HEADER; sm.off[2] = sm.off[1] + nS; sm.off[3] = sm.off[2] + 4 * nS;
+    sm.off[4] = sm.off[3] + nS * v.nProbes;
+    const int64_t spDoubles = sm.off[4] + nS * v.nPatches;
+    sm.cellPart = m->arena.alloc<double>((size_t)std::max(1, sm.nRows) * (size_t)(5 * nS + 3));
+    sm.patchPart = m->arena.alloc<double>((size_t)std::max(1, v.nChunks) * (size_t)nS);
+    double* result = m->arena.alloc<double>((size_t)(m->nDoubles + spDoubles));   // both blocks, the flow block first (its own buffer stays behind unused)
+    double* host = nullptr;
+    HIP_CHECK(hipHostMalloc((void**)&host, sizeof(double) * (size_t)(m->nDoubles + spDoubles) * QGD_MONITOR_SLOTS, hipHostMallocDefault));
+    HIP_CHECK(hipStreamSynchronize(c->stream()));
+    if (m->host) (void)hipHostFree(m->host);
+    m->host = host;
+    m->result = result;
+    m->spView = sm;
+    m->spDoubles = spDoubles;
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_monitor_species_layout(qgd_monitor_t m, int64_t offsets[QGD_MONITOR_SECTIONS], int64_t* nDoubles) {
+    if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_species_layout: not an open monitor (a monitor is freed with its case)");
+    if (!m->spDoubles) return fail(QGD_ERR_INVALID, "qgd_monitor_species_layout: the species block is not enabled (qgd_monitor_enable_species)");
+    if (offsets) for (int k = 0; k < QGD_MONITOR_SECTIONS; ++k) offsets[k] = m->spView.off[k];
+    if (nDoubles) *nDoubles = m->spDoubles;
+    return QGD_OK;
+}
+int qgd_monitor_species_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap) {
+    QGD_TRY
+    if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_species_read: not an open monitor (a monitor is freed with its case)");
+    if (!m->spDoubles) return fail(QGD_ERR_INVALID, "qgd_monitor_species_read: the species block is not enabled (qgd_monitor_enable_species)");
+    if (slot < 0 || slot >= QGD_MONITOR_SLOTS) return fail(QGD_ERR_INVALID, "qgd_monitor_species_read: slot must be 0.." + std::to_string(QGD_MONITOR_SLOTS - 1));
+    if (!out || cap < m->spDoubles)
+        return fail(QGD_ERR_INVALID, "qgd_monitor_species_read: output too small (qgd_monitor_species_layout gives the doubles of a species block: " +
+                                         std::to_string(m->spDoubles) + ")");
+    if (!m->sampled[slot]) return fail(QGD_ERR_INVALID, "qgd_monitor_species_read: slot " + std::to_string(slot) + " was never sampled");
+    HIP_CHECK(hipSetDevice(m->c->dev->deviceId));
+    HIP_CHECK(hipEventSynchronize(m->ev[slot]));
+    const double* src = m->host + (size_t)slot * (size_t)(m->nDoubles + m->spDoubles) + m->nDoubles;
+    std::copy(src, src + m->spDoubles, out);
     return QGD_OK;
     QGD_CATCH
 }

@@ -274,6 +274,22 @@ struct MonitorView {
 };
 // fluxState: 0 no assembly yet (patch fluxes NaN), 1 all five, 2 implicitDiffusion (mass only)
 void launchMonitorSample(hipStream_t s, const MonitorView& mv, const MeshView& m, const CaseView& c, const GasModel& g, int fluxState, double* out);
+// the species block of a monitor (qgd_monitor_species.hip; qgd_monitor_enable_species): three more launches per sample whatever nS is, on the
+// monitor's owned range, probe cells, face list and chunk table.  The cell pass cuts the owned range into tiles of 256 * QGD_MONITOR_SPECIES_CELLS
+// consecutive cells (each lane QGD_MONITOR_SPECIES_CELLS of them, 256 apart), at most QGD_MONITOR_BLOCKS workgroups stride over the tiles, and a tile's
+// species planes go by once in register batches of QGD_SPECIES_W.
+#define QGD_MONITOR_SPECIES_CELLS 4
+#define QGD_MONITOR_SPECIES_HEADER 8
+struct SpeciesMonitorView {
+    int32_t nRows;                                         // workgroups of the cell pass: min(tiles, QGD_MONITOR_BLOCKS)
+    double* cellPart;                                      // nRows rows of 5 nS + 3: nS sums | nS x {min, label, max, label} | non-finite cells, lowest label, max |sum Y - 1|
+    double* patchPart;                                     // MonitorView::nChunks rows of nS
+    int64_t off[5];                                        // sections of the species block: header, integrals, extrema, probes, patches
+};
+// fluxState: 0 no species assembly since set_fields (patch fluxes NaN), 1 explicit branch (SpeciesView::F is what the cell update consumed),
+// 2 implicit branch (F holds phiJmY_i alone: the boundary part of YEqn.flux() is added from aF = SpeciesImplView::aF, else nullptr)
+void launchMonitorSpeciesSample(hipStream_t s, const MonitorView& mv, const SpeciesMonitorView& sm, const MeshView& m, const CaseView& c,
+                                const SpeciesView& sv, const double* aF, int fluxState, double* out);
 
 // ---- accessor: one named cell / patch field out of the records (K == nullptr on patches) ----------------------------
 enum ExtractField : int { XF_RHO = 0, XF_U, XF_P, XF_E, XF_T, XF_RHOU, XF_RHOE, XF_C, XF_PSI, XF_MU, XF_ALPHAU, XF_TAUQGD, XF_MUQGD,

@@ -254,16 +254,23 @@ def read_dict(path):
 
 
 # function objects of system/controlDict the QGDFoam application serves (monitor.FunctionObjects): type -> the fields it may name
+# (probes and fieldMinMax also take the names of the case's species; qgdSpeciesIntegrals and qgdSpeciesPatchFluxes need a case with species)
 FUNCTION_TYPES = {"probes": ("rho", "U", "p", "T", "e"), "fieldMinMax": ("rho", "p", "T", "U", "mag(U)", "Mach"), "qgdIntegrals": (),
-                  "qgdPatchFluxes": ()}
+                  "qgdPatchFluxes": (), "qgdSpeciesIntegrals": (), "qgdSpeciesPatchFluxes": ()}
+SPECIES_FUNCTION_TYPES = ("qgdSpeciesIntegrals", "qgdSpeciesPatchFluxes")
 
 
-def read_functions(control_dict, warn=print):
+def read_functions(control_dict, warn=print, species=None):
     """specifications of the served entries of ``functions{}``: a list of dict(name, type, interval, fields, probeLocations, patches).
     ``probes`` (fields out of rho U p T e, probeLocations), ``fieldMinMax`` (fields out of rho p T U Mach; U is its magnitude),
     and the project's own ``qgdIntegrals`` and ``qgdPatchFluxes`` (patches) are served, each every ``writeInterval`` steps
     (``writeControl timeStep``, the default; default interval 1).  Anything else -- another type, another writeControl, a field a
-    type does not serve -- gets one warning line and is skipped, so that a case with functions the solver does not know still runs."""
+    type does not serve -- gets one warning line and is skipped, so that a case with functions the solver does not know still runs.
+    ``species``: the names of the case's species (None or empty: it carries none).  ``probes`` and ``fieldMinMax`` then take species names
+    in ``fields`` next to the flow fields, and ``qgdSpeciesIntegrals`` and ``qgdSpeciesPatchFluxes`` (patches) are served; in a case
+    without species those two types are an error that names the function (a species name among ``fields`` is then just a field that is
+    not served: warned about by name and left out, as any unknown field is)."""
+    species = [str(n) for n in (species or [])]
     funcs = control_dict.get("functions", {})
     out = []
     if not isinstance(funcs, dict):
@@ -284,14 +291,17 @@ def read_functions(control_dict, warn=print):
         interval = int(d.get("writeInterval", d.get("outputInterval", 1)))
         if interval < 1:
             raise FoamFileError(f"functions: '{name}': writeInterval must be at least 1, got {interval}")
+        if typ in SPECIES_FUNCTION_TYPES and not species:
+            raise FoamFileError(f"functions: '{name}': type {typ} needs a case with species (thermophysicalProperties lists none)")
         spec = dict(name=str(name), type=typ, interval=interval)
         if FUNCTION_TYPES[typ]:
             fields = d.get("fields", [])
             fields = [str(f) for f in (fields if isinstance(fields, (list, tuple)) else [fields])]
-            served = [f for f in fields if f in FUNCTION_TYPES[typ]]
+            can = FUNCTION_TYPES[typ] + tuple(n for n in species if n not in FUNCTION_TYPES[typ])
+            served = [f for f in fields if f in can]
             for f in fields:
                 if f not in served:
-                    warn(f"functions: '{name}': field '{f}' is not served by type {typ} (served: {', '.join(FUNCTION_TYPES[typ])}): left out")
+                    warn(f"functions: '{name}': field '{f}' is not served by type {typ} (served: {', '.join(can)}): left out")
             if not served:
                 warn(f"functions: '{name}': no served field: skipped")
                 continue
@@ -306,7 +316,7 @@ def read_functions(control_dict, warn=print):
                 warn(f"functions: '{name}': no probeLocations: skipped")
                 continue
             spec["probeLocations"] = locs
-        if typ == "qgdPatchFluxes":
+        if typ in ("qgdPatchFluxes", "qgdSpeciesPatchFluxes"):
             patches = d.get("patches", [])
             patches = [str(p) for p in (patches if isinstance(patches, (list, tuple)) else [patches])]
             if not patches:

@@ -4,6 +4,11 @@
 A ``Monitor`` is created once (``QGDFoamCase.monitor(probes=..., patches=...)``); ``sample()`` enqueues the pass and a small copy
 on the case's stream and returns at once, ``read()`` waits for that sample only.  Four slots form a ring, so a loop can read a
 sample a step or two after it was taken and never drain the stream.
+
+With ``species=True`` on a case that carries species every sample holds the species block as well (qgd_monitor_enable_species):
+``read()`` then also gives, per species in the case's order and with the inert one included, ``speciesMass`` [nS], ``speciesMin`` /
+``speciesMinCell`` / ``speciesMax`` / ``speciesMaxCell`` [nS], ``speciesProbes`` [nProbes, nS], ``speciesPatchFlux`` [nPatches, nS], and
+the scalars ``speciesFluxState``, ``speciesSumDefect``, ``speciesNonFinite``, ``speciesFirstNonFinite``.
 """
 import collections
 import ctypes as C
@@ -21,8 +26,9 @@ PATCH_COLUMNS = ("area", "massFlux", "momentumFlux_x", "momentumFlux_y", "moment
 
 
 class Monitor:
-    def __init__(self, case, probes=None, patches=None):
-        """probes: cell labels of the case's device mesh (-1: not on this rank, its row reads NaN); patches: patch indices"""
+    def __init__(self, case, probes=None, patches=None, species=False):
+        """probes: cell labels of the case's device mesh (-1: not on this rank, its row reads NaN); patches: patch indices; species: the
+        samples carry the species block too (a case with set_species)"""
         self.case = case
         self.probes = np.ascontiguousarray(probes if probes is not None else [], dtype=np.int32).reshape(-1)
         self.patches = np.ascontiguousarray(patches if patches is not None else [], dtype=np.int32).reshape(-1)
@@ -39,6 +45,15 @@ class Monitor:
         self.offsets, self.n_doubles, self.grid_cap = [int(x) for x in off], int(n.value), int(cap.value)
         self._pending = collections.deque()   # sampled and not yet read, oldest first
         self._last = -1
+        self.species, self.species_offsets, self.species_doubles = bool(species), None, 0
+        if self.species:
+            try:
+                L.check(L.lib.qgd_monitor_enable_species(h), "qgd_monitor_enable_species")
+                L.check(L.lib.qgd_monitor_species_layout(h, off, C.byref(n)), "qgd_monitor_species_layout")
+            except Exception:
+                self._handle.free()
+                raise
+            self.species_offsets, self.species_doubles = [int(x) for x in off], int(n.value)
 
     @property
     def _h(self):
@@ -69,9 +84,20 @@ class Monitor:
             self._pending.remove(slot)
         return out, t.value, int(step.value)
 
+    def read_species_raw(self, slot):
+        """the species block of a slot (the sample qgd_monitor_read of that slot gives)"""
+        out = np.empty(max(self.species_doubles, 1))[:self.species_doubles]
+        L.check(L.lib.qgd_monitor_species_read(self._h, int(slot), out.ctypes.data_as(L.c_double_p), out.size), "qgd_monitor_species_read")
+        return out
+
     def read(self, slot=None):
+        if slot is None and self._pending:
+            slot = self._pending[0]
         raw, t, step = self.read_raw(slot)
-        return unpack(raw, self.offsets, t, step)
+        s = unpack(raw, self.offsets, t, step)
+        if self.species:
+            s.update(unpack_species(self.read_species_raw(slot), self.species_offsets))
+        return s
 
     def close(self):
         if getattr(self, "_handle", None):
@@ -102,24 +128,57 @@ def unpack(raw, offsets, time, step):
                 patchPressureForce=patches[:, 6:9].copy(), raw=raw)
 
 
+def unpack_species(raw, offsets):
+    """named arrays of one species block (the layout of include/qgd_amd.h, qgd_monitor_enable_species); all species, the inert one included"""
+    o = offsets
+    hd = raw[o[0]:o[1]]
+    n_s, n_probes, n_patches = int(hd[0]), int(hd[6]), int(hd[7])
+    ex = raw[o[2]:o[3]].reshape(n_s, 4)
+    # speciesFluxState 0: no species assembly since set_fields (speciesPatchFlux NaN); 1: explicit branch; 2: implicitDiffusion
+    return dict(nSpecies=n_s, speciesInert=int(hd[1]), speciesFluxState=int(hd[2]), speciesNonFinite=int(hd[3]), speciesFirstNonFinite=int(hd[4]),
+                speciesSumDefect=float(hd[5]), speciesMass=raw[o[1]:o[2]].copy(),
+                speciesMin=ex[:, 0].copy(), speciesMinCell=ex[:, 1].astype(np.int64), speciesMax=ex[:, 2].copy(), speciesMaxCell=ex[:, 3].astype(np.int64),
+                speciesProbes=raw[o[3]:o[4]].reshape(n_probes, n_s).copy(),
+                speciesPatchFlux=raw[o[4]:o[4] + n_patches * n_s].reshape(n_patches, n_s).copy(), speciesRaw=raw)
+
+
+_FLOW_KEYS = dict(sums=("integrals", "momentum", "patchArea", "patchFlux", "patchPressureForce"), count="nonFinite", first="firstNonFinite",
+                  extrema=(("min", "minCell", 1.0), ("max", "maxCell", -1.0)), probes="probes")
+_SPECIES_KEYS = dict(sums=("speciesMass", "speciesPatchFlux"), count="speciesNonFinite", first="speciesFirstNonFinite",
+                     extrema=(("speciesMin", "speciesMinCell", 1.0), ("speciesMax", "speciesMaxCell", -1.0)), probes="speciesProbes")
+
+
 def combine(parts):
     """the samples of the ranks of one run as one: sums in rank order, extrema by (value, label) with ties to the lowest label, a probe
-    from the rank that holds its cell (the others carry NaN rows), patch totals summed"""
+    from the rank that holds its cell (the others carry NaN rows), patch totals summed.  The species block of the parts (Monitor with
+    species=True) is merged the same way; speciesSumDefect is the largest of the ranks'.  (Nothing here has run on more than one GPU: the
+    parts of the tests are shards on one device.)"""
     out = dict(parts[0])
     if len(parts) == 1:
         return out
-    for key in ("integrals", "momentum", "patchArea", "patchFlux", "patchPressureForce"):
+    _combine_block(out, parts, _FLOW_KEYS)
+    for key in ("volume", "mass", "totalEnergy", "internalEnergy", "kineticEnergy"):
+        out[key] = float(out["integrals"][INTEGRALS.index(key)])
+    out["ownedCells"] = sum(p["ownedCells"] for p in parts)
+    if "speciesMass" in parts[0]:
+        _combine_block(out, parts, _SPECIES_KEYS)
+        defects = [p["speciesSumDefect"] for p in parts if not np.isnan(p["speciesSumDefect"])]
+        out["speciesSumDefect"] = max(defects) if defects else float("nan")
+        out.pop("speciesRaw", None)
+    out.pop("raw", None)
+    return out
+
+
+def _combine_block(out, parts, keys):
+    for key in keys["sums"]:
         acc = np.array(parts[0][key], dtype=np.float64)
         for p in parts[1:]:
             acc = acc + p[key]
         out[key] = acc
-    for key in ("volume", "mass", "totalEnergy", "internalEnergy", "kineticEnergy"):
-        out[key] = float(out["integrals"][INTEGRALS.index(key)])
-    out["ownedCells"] = sum(p["ownedCells"] for p in parts)
-    out["nonFinite"] = sum(p["nonFinite"] for p in parts)
-    bad = [p["firstNonFinite"] for p in parts if p["firstNonFinite"] >= 0]
-    out["firstNonFinite"] = min(bad) if bad else -1
-    for val, cell, sign in (("min", "minCell", 1.0), ("max", "maxCell", -1.0)):
+    out[keys["count"]] = sum(p[keys["count"]] for p in parts)
+    bad = [p[keys["first"]] for p in parts if p[keys["first"]] >= 0]
+    out[keys["first"]] = min(bad) if bad else -1
+    for val, cell, sign in keys["extrema"]:
         v, c = np.array(parts[0][val]), np.array(parts[0][cell])
         for p in parts[1:]:
             for k in range(v.size):
@@ -129,13 +188,11 @@ def combine(parts):
                 if better:
                     v[k], c[k] = p[val][k], p[cell][k]
         out[val], out[cell] = v, c
-    probes = np.array(parts[0]["probes"])
+    probes = np.array(parts[0][keys["probes"]])
     for p in parts[1:]:
-        take = np.isnan(probes).all(axis=1) & ~np.isnan(p["probes"]).all(axis=1)
-        probes[take] = p["probes"][take]
-    out["probes"] = probes
-    out.pop("raw", None)
-    return out
+        take = np.isnan(probes).all(axis=1) & ~np.isnan(p[keys["probes"]]).all(axis=1)
+        probes[take] = p[keys["probes"]][take]
+    out[keys["probes"]] = probes
 
 
 # ---- the function objects of system/controlDict (foamfile.read_functions gives the specifications) ----------------------------------------
@@ -162,8 +219,9 @@ class ProbesWriter:
     numbers, `# Time`, then one row per write: the time and one value per probe (vectors in parentheses)"""
     _COLS = {"rho": (0,), "U": (1, 2, 3), "p": (4,), "T": (5,), "e": (6,)}
 
-    def __init__(self, out_dir, spec, found):
+    def __init__(self, out_dir, spec, found, species=()):
         self.fields = list(spec["fields"])
+        self.species = list(species)          # the case's species names: a field among them is a column of speciesProbes
         locs = np.asarray(spec["probeLocations"], dtype=np.float64).reshape(-1, 3)
         head = [f"# Probe {i} ({_num(x[0])} {_num(x[1])} {_num(x[2])})" + ("" if found[i] else "  # Not Found") for i, x in enumerate(locs)]
         head.append("# Probe " + " ".join(str(i) for i in range(len(locs))))
@@ -172,6 +230,10 @@ class ProbesWriter:
 
     def write(self, t, s):
         for f, table in self.tables.items():
+            if f not in self._COLS:
+                k = self.species.index(f)
+                table.row(" ".join([_num(t)] + [_num(r[k]) for r in s["speciesProbes"]]))
+                continue
             cols = self._COLS[f]
             vals = [(_num(r[cols[0]]) if len(cols) == 1 else "(" + " ".join(_num(r[c]) for c in cols) + ")") for r in s["probes"]]
             table.row(" ".join([_num(t)] + vals))
@@ -182,8 +244,9 @@ class FieldMinMaxWriter:
     (U stands for mag(U), as fieldMinMax's default mode has it)"""
     _INDEX = {"rho": 0, "p": 1, "T": 2, "U": 3, "mag(U)": 3, "Mach": 4}
 
-    def __init__(self, out_dir, spec, centres, file_label):
+    def __init__(self, out_dir, spec, centres, file_label, species=()):
         self.fields = list(spec["fields"])
+        self.species = list(species)          # the case's species names: a field among them reads speciesMin / speciesMax
         self.centres, self.file_label = centres, file_label
         cols = ["Time"]
         for f in self.fields:
@@ -195,8 +258,11 @@ class FieldMinMaxWriter:
     def write(self, t, s):
         row = [_num(t)]
         for f in self.fields:
-            k = self._INDEX[f]
-            for val, cell in (("min", "minCell"), ("max", "maxCell")):
+            if f in self._INDEX:
+                k, keys = self._INDEX[f], (("min", "minCell"), ("max", "maxCell"))
+            else:
+                k, keys = self.species.index(f), (("speciesMin", "speciesMinCell"), ("speciesMax", "speciesMaxCell"))
+            for val, cell in keys:
                 c = int(s[cell][k])
                 x = self.centres[c] if c >= 0 else (np.nan,) * 3
                 row += [_num(s[val][k]), str(int(self.file_label[c]) if c >= 0 else -1)] + [_num(v) for v in x]
@@ -232,13 +298,55 @@ class PatchFluxWriter:
         self.table.row("\t".join(row))
 
 
+class SpeciesIntegralsWriter:
+    """speciesIntegrals.dat: the time, sum rho Y_i V per species (the inert one included), max |sum_i Y_i - 1|, the count of cells with a
+    non-finite Y_i and the first of them (-1: none)"""
+
+    def __init__(self, out_dir, spec, file_label, species):
+        self.file_label = file_label
+        cols = ["Time"] + [f"mass({n})" for n in species] + ["sumDefect", "nonFiniteCells", "firstNonFiniteCell"]
+        self.table = _Table(os.path.join(out_dir, "speciesIntegrals.dat"), ["# Species masses over the mesh", "# " + "\t".join(cols)])
+
+    def write(self, t, s):
+        first = int(self.file_label[s["speciesFirstNonFinite"]]) if s["speciesFirstNonFinite"] >= 0 else -1
+        self.table.row("\t".join([_num(t)] + [_num(v) for v in s["speciesMass"]] + [_num(s["speciesSumDefect"]), str(int(s["speciesNonFinite"])), str(first)]))
+
+
+class SpeciesPatchFluxWriter:
+    """speciesPatchFluxes.dat: the time, then per patch the net flux of every species out of the domain (what the species' cell update
+    consumed in the step that produced the state; the inert species: the mass flux minus the others')"""
+
+    def __init__(self, out_dir, spec, rows, species):
+        self.rows = rows                    # rows of the monitor's patch table, in the order of spec["patches"]
+        cols = ["Time"] + [f"{p}:{n}" for p in spec["patches"] for n in species]
+        self.table = _Table(os.path.join(out_dir, "speciesPatchFluxes.dat"), ["# Patch totals of the net species fluxes", "# " + "\t".join(cols)])
+
+    def write(self, t, s):
+        row = [_num(t)]
+        for r in self.rows:
+            row += [_num(v) for v in s["speciesPatchFlux"][r]]
+        self.table.row("\t".join(row))
+
+
+SPECIES_TYPES = ("qgdSpeciesIntegrals", "qgdSpeciesPatchFluxes")
+
+
 class FunctionObjects:
     """the served functions of a run: one Monitor for all of them, sampled after the steps at which a function is due, read two samples
     late.  ``local_of`` maps a cell label of the file mesh (as relabelled for the device) to this rank's label or -1; ``file_label`` maps
-    it back to the label in the case files; ``gather`` (None on one rank) is all_gather_object."""
+    it back to the label in the case files; ``gather`` (None on one rank) is all_gather_object.  ``species``: the case's species names;
+    a function that names one of them, or one of SPECIES_TYPES, makes the monitor carry the species block."""
 
-    def __init__(self, case, specs, file_mesh, case_dir, start_name, local_of, file_label, is_root=True, gather=None, log=print):
+    def __init__(self, case, specs, file_mesh, case_dir, start_name, local_of, file_label, is_root=True, gather=None, log=print, species=None):
         self.specs, self.is_root, self.gather = specs, is_root, gather
+        species = list(species or [])
+        flow_fields = set(ProbesWriter._COLS) | set(FieldMinMaxWriter._INDEX)
+        wanted = [(s["name"], f) for s in specs for f in s.get("fields", []) if f not in flow_fields] + [(s["name"], s["type"]) for s in specs if s["type"] in SPECIES_TYPES]
+        for name, what in wanted:
+            if what not in species and what not in SPECIES_TYPES:
+                raise ValueError(f"functions: '{name}': field '{what}' is neither a flow field nor a species of this case (species: {', '.join(species) or 'none'})")
+            if not species:
+                raise ValueError(f"functions: '{name}': type {what} needs a case with species; this case carries none")
         locations = [np.asarray(s["probeLocations"], dtype=np.float64).reshape(-1, 3) for s in specs if s["type"] == "probes"]
         cells = file_mesh.find_cells(np.concatenate(locations)) if locations else np.zeros(0, dtype=np.int64)
         names = list(getattr(file_mesh, "patch_names", []))
@@ -250,7 +358,7 @@ class FunctionObjects:
                 if p not in patch_rows:
                     patch_rows[p] = len(patches)
                     patches.append(names.index(p))
-        self.monitor = Monitor(case, probes=[local_of(int(c)) if c >= 0 else -1 for c in cells], patches=patches)
+        self.monitor = Monitor(case, probes=[local_of(int(c)) if c >= 0 else -1 for c in cells], patches=patches, species=bool(wanted))
         self.writers = []
         centres = file_mesh.array("C").reshape(-1, 3)
         at = 0
@@ -265,16 +373,20 @@ class FunctionObjects:
                     for i, c in enumerate(cells[rows]):
                         if c < 0:
                             log(f"functions: '{s['name']}': probe {i} is outside the mesh: its column reads nan")
-                    w = ProbesWriter(out_dir, s, cells[rows] >= 0)
+                    w = ProbesWriter(out_dir, s, cells[rows] >= 0, species)
                     w.rows = rows
             elif not is_root:
                 pass
             elif s["type"] == "fieldMinMax":
-                w = FieldMinMaxWriter(out_dir, s, centres, file_label)
+                w = FieldMinMaxWriter(out_dir, s, centres, file_label, species)
             elif s["type"] == "qgdIntegrals":
                 w = IntegralsWriter(out_dir, s, file_label)
             elif s["type"] == "qgdPatchFluxes":
                 w = PatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]])
+            elif s["type"] == "qgdSpeciesIntegrals":
+                w = SpeciesIntegralsWriter(out_dir, s, file_label, species)
+            elif s["type"] == "qgdSpeciesPatchFluxes":
+                w = SpeciesPatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]], species)
             self.writers.append(w)
         self._waiting = collections.deque()   # (due specs) of the samples not read yet
 
@@ -296,6 +408,7 @@ class FunctionObjects:
         s = self.monitor.read()
         if self.gather is not None:
             s.pop("raw", None)
+            s.pop("speciesRaw", None)
             s = combine(self.gather(s))
         if not self.is_root:
             return
@@ -303,7 +416,7 @@ class FunctionObjects:
         for i in due:
             w = self.writers[i]
             if isinstance(w, ProbesWriter):
-                w.write(t, dict(s, probes=s["probes"][w.rows]))
+                w.write(t, dict(s, probes=s["probes"][w.rows], **({"speciesProbes": s["speciesProbes"][w.rows]} if "speciesProbes" in s else {})))
             elif w is not None:
                 w.write(t, s)
 

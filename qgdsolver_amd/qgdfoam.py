@@ -310,13 +310,15 @@ class QGDFoamCase:
                     f"qgd_case_get_field({name})")
         return out
 
-    def monitor(self, probes=None, patches=None):
+    def monitor(self, probes=None, patches=None, species=False):
         """a run monitor of this case (monitor.Monitor; qgd_monitor_create): volume integrals, extrema with their cells, the first
         non-finite cell, the values at ``probes`` (cell labels of this device's mesh, -1 = not on this rank; PolyMesh.find_cells
         locates points) and the totals of the net face fluxes over ``patches`` (indices of real patches), formed on the device by
-        ``sample()`` and fetched by ``read()``.  After set_fields.  The monitor is freed with the case where still open."""
+        ``sample()`` and fetched by ``read()``.  After set_fields.  The monitor is freed with the case where still open.
+        species=True (a case with set_species): every sample also carries, per species, the inert one included, sum rho Y_i V, the
+        extrema of Y_i with their cells, Y_i at the probes and the net species flux through each patch (qgd_monitor_enable_species)."""
         from .monitor import Monitor
-        m = Monitor(self, probes=probes, patches=patches)
+        m = Monitor(self, probes=probes, patches=patches, species=species)
         self._monitor_handles = [h for h in self._monitor_handles if h.value] + [m._handle]
         return m
 
