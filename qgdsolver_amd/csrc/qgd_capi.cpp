@@ -184,7 +184,49 @@ struct Workspace {
     }
 };
 
-static int envChoice(const char* name, int dflt, const int* allowed, int nAllowed, int lo, int hi);
+// Who owns which slot of Workspace::dev.  The WORK slots WS_CELL, WS_BND, WS_PT, WS_OUT and WS_H belong to the code that launches on device
+// pointers (the *_dev entries, and the host entries that launch themselves: fvsc, interpolate, flux_upwind): records, vertex values and
+// outputs in SoA.  A host-pointer entry that runs device-pointer code stages its arguments in slots from WS_STAGE upwards, through a Stager,
+// and fetches multi-component results through WS_XPOSE (fetchFaceSoA); no device-pointer code names either, so the two cannot alias.
+// WS_A and WS_B are extra arrays of host entries that launch themselves: qgd_flux_upwind (the flux), qgd_scalar_case_get_field (its debug
+// block), and qgd_qhd_case_set_fields / qgd_scalar_case_set_fields, which stage the caller's fields in WS_CELL, WS_A and WS_B before their own
+// kernels copy them into the case -- they call no device-pointer code, so the work slot they borrow is free.
+enum WsSlot { WS_CELL = 0, WS_BND, WS_PT, WS_OUT, WS_H, WS_XPOSE, WS_A, WS_B, WS_STAGE };
+// hands out the staging slots of one host-pointer call in order, and uploads
+struct Stager {
+    Workspace& ws;
+    hipStream_t stream;
+    size_t next = WS_STAGE;
+    double* scratch(size_t n) { return ws.get<double>(next++, n); }
+    double* up(const double* src, size_t n) {
+        double* dst = scratch(n);
+        if (src && n) ws.h2d(dst, src, sizeof(double) * n, stream);
+        return dst;
+    }
+};
+
+// Tuning knobs of the measurement scripts (QGD_*): a value outside the supported set is an error, not a silent change of
+// code path.  allowed == nullptr: any integer in [lo, hi].
+static int envChoice(const char* name, int dflt, const int* allowed, int nAllowed, int lo = 0, int hi = 0) {
+    const char* e = std::getenv(name);
+    if (!e || !*e) return dflt;
+    char* end = nullptr;
+    const long v = std::strtol(e, &end, 10);
+    bool ok = end && *end == '\0';
+    if (ok && allowed) { ok = false; for (int i = 0; i < nAllowed; ++i) ok = ok || allowed[i] == v; }
+    else if (ok) ok = v >= lo && v <= hi;
+    if (!ok) throw std::invalid_argument(std::string(name) + "=" + e + " is not a supported value");
+    return (int)v;
+}
+static int envOnOff(const char* name, int dflt) {   // the two-valued knobs
+    static const int kOnOff[] = {0, 1};
+    return envChoice(name, dflt, kOnOff, 2);
+}
+static double nowMs() {
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return 1e3 * (double)t.tv_sec + 1e-6 * (double)t.tv_nsec;
+}
 
 // ---- constraint patches in the resident cases -----------------------------------------------------------------------------------------
 // OpenFOAM gives a field on a constraint patch the patch's own field type whatever the field file says (L0: fvPatchField<Type>::New,
@@ -280,8 +322,7 @@ struct qgd_device_s {
     ImplicitSolver* opSolver = nullptr;   // the linear solver of the stateless implicit operators (qgd_species_step_implicit), made on first use
     // MeshView::geoPos, built the first time a case that takes fvc::grad(U) per cell is created on this device (QGD_GEOPOS=0: never)
     void ensureFaceGeoPos() {
-        static const int kOnOff[] = {0, 1};
-        if (view.geoPos || view.nF == 0 || !envChoice("QGD_GEOPOS", 1, kOnOff, 2, 0, 0)) return;
+        if (view.geoPos || view.nF == 0 || !envOnOff("QGD_GEOPOS", 1)) return;
         double4* g = arena.alloc<double4>((size_t)view.nF, false);
         (void)hipGetLastError();   // a stale error of an earlier, refused call must not be taken for this launch's
         launchFaceGeoPos(stream, view, g);
@@ -455,22 +496,6 @@ static Launcher launcherOf(qgd_case_s* c) {
 // The OpenMP runtime hipcc links spin-waits between parallel regions by default;
 // on oversubscribed hosts that makes the (short) setup loops slower than serial.
 __attribute__((constructor)) static void qgdInitOpenMP() { setenv("KMP_BLOCKTIME", "0", 0); }
-
-static bool hasWedgeAndPrism(const HostMesh& m);
-
-// Tuning knobs of the measurement scripts (QGD_*): a value outside the supported set is an error, not a silent change of
-// code path.  allowed == nullptr: any integer in [lo, hi].
-static int envChoice(const char* name, int dflt, const int* allowed, int nAllowed, int lo = 0, int hi = 0) {
-    const char* e = std::getenv(name);
-    if (!e || !*e) return dflt;
-    char* end = nullptr;
-    const long v = std::strtol(e, &end, 10);
-    bool ok = end && *end == '\0';
-    if (ok && allowed) { ok = false; for (int i = 0; i < nAllowed; ++i) ok = ok || allowed[i] == v; }
-    else if (ok) ok = v >= lo && v <= hi;
-    if (!ok) throw std::invalid_argument(std::string(name) + "=" + e + " is not a supported value");
-    return (int)v;
-}
 
 // ---------------------------------------------------------------------------
 extern "C" {
@@ -721,14 +746,21 @@ int qgd_mesh_halo_slots(qgd_mesh_t mh, int32_t* nSlots) {
 }
 
 // ---- device ----------------------------------------------------------------------
-static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device_t* out);
-static double nowMs();
-int qgd_device_create(qgd_mesh_t mh, int deviceId, qgd_device_t* out) { return deviceCreate(mh, deviceId, -1, out); }
-int qgd_device_create_with(qgd_mesh_t mh, int deviceId, int32_t flags, qgd_device_t* out) {
-    if (flags & ~(QGD_DEVICE_NO_FUSED_TABLES | QGD_DEVICE_FUSED_ANY_BLOCKS)) return fail(QGD_ERR_INVALID, "qgd_device_create_with: unknown flag");
-    if ((flags & QGD_DEVICE_NO_FUSED_TABLES) && (flags & QGD_DEVICE_FUSED_ANY_BLOCKS))
-        return fail(QGD_ERR_INVALID, "qgd_device_create_with: QGD_DEVICE_NO_FUSED_TABLES and QGD_DEVICE_FUSED_ANY_BLOCKS exclude each other");
-    return deviceCreate(mh, deviceId, (flags & QGD_DEVICE_NO_FUSED_TABLES) ? 0 : ((flags & QGD_DEVICE_FUSED_ANY_BLOCKS) ? 2 : -1), out);
+// prismMatcher + findIndices("wedge") of fvscOpName [fvsc_8C L65-82]: a wedge patch and at least one prism cell
+// (five faces: two triangles and three quadrilaterals, six vertices)
+static bool hasWedgeAndPrism(const HostMesh& m) {
+    bool wedge = false;
+    for (const Patch& p : m.patches) wedge = wedge || (p.type == QGD_PATCH_WEDGE && p.size > 0);
+    if (!wedge) return false;
+    std::vector<uint8_t> nTri((size_t)m.nCells, 0), nQuad((size_t)m.nCells, 0), nOther((size_t)m.nCells, 0);
+    auto count = [&](int32_t c, int n) { if (n == 3) nTri[c]++; else if (n == 4) nQuad[c]++; else nOther[c]++; };
+    for (int32_t f = 0; f < m.nFaces; ++f) {
+        count(m.owner[f], m.faceSize(f));
+        if (f < m.nInternalFaces) count(m.neighbour[f], m.faceSize(f));
+    }
+    for (int32_t c = 0; c < m.nCells; ++c)
+        if (nTri[c] == 2 && nQuad[c] == 3 && nOther[c] == 0) return true;
+    return false;
 }
 // fusedChoice: -1 = QGD_FUSED of the environment (default 1), 0 = no block tables, 2 = blocks of any size
 static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device_t* out) {
@@ -797,8 +829,7 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
         for (int64_t f = 0; f < s.nIF; ++f) if (s.fkind[f] == FK_OTHER) { v.hasOther = 1; break; }
         // Sf of a quadrilateral = (p3-p1) x (p4-p2) / 2 exactly (the triangle fan about any centre sums to it), and the
         // kernel holds those differences already: 24 B per face less to stream.  Not when the caller supplied its own Sf.
-        static const int kOnOff[] = {0, 1};
-        v.sGeo = (envChoice("QGD_SGEO", 1, kOnOff, 2) != 0 && !m.userGeometry && v.fblock == 128) ? 1 : 0;
+        v.sGeo = (envOnOff("QGD_SGEO", 1) != 0 && !m.userGeometry && v.fblock == 128) ? 1 : 0;
         // upload + free each table in turn so the host peak stays at one table
         auto up = [&](auto& vec) { auto* p = a.upload(vec); std::decay_t<decltype(vec)>().swap(vec); return p; };
         {
@@ -813,9 +844,9 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
             if (t.fb != 0 && lds <= 65536 && 4 * (int64_t)t.spill.size() <= nTiles) {
                 v.tileLds = (int32_t)lds;
                 v.tileMaxC = t.maxCells; v.tileMaxV = t.maxVerts;
-                v.qhdTiles = envChoice("QGD_QHD_TILES", 1, kOnOff, 2);
-                v.implTiles = envChoice("QGD_IMPL_TILES", 1, kOnOff, 2);
-                if (v.fblock == 128 && envChoice("QGD_FTILE_FIXED", 1, kOnOff, 2) != 0 &&
+                v.qhdTiles = envOnOff("QGD_QHD_TILES", 1);
+                v.implTiles = envOnOff("QGD_IMPL_TILES", 1);
+                if (v.fblock == 128 && envOnOff("QGD_FTILE_FIXED", 1) != 0 &&
                     (int64_t)nTiles * std::max(t.maxCells, t.maxVerts) < (int64_t)INT32_MAX) {
                     // the lists once more at a fixed stride (built and uploaded one after the other: the host peak stays at one table)
                     std::vector<uint8_t> flag((size_t)nTiles, 0);
@@ -947,6 +978,13 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
     return QGD_OK;
     QGD_CATCH
 }
+int qgd_device_create(qgd_mesh_t mh, int deviceId, qgd_device_t* out) { return deviceCreate(mh, deviceId, -1, out); }
+int qgd_device_create_with(qgd_mesh_t mh, int deviceId, int32_t flags, qgd_device_t* out) {
+    if (flags & ~(QGD_DEVICE_NO_FUSED_TABLES | QGD_DEVICE_FUSED_ANY_BLOCKS)) return fail(QGD_ERR_INVALID, "qgd_device_create_with: unknown flag");
+    if ((flags & QGD_DEVICE_NO_FUSED_TABLES) && (flags & QGD_DEVICE_FUSED_ANY_BLOCKS))
+        return fail(QGD_ERR_INVALID, "qgd_device_create_with: QGD_DEVICE_NO_FUSED_TABLES and QGD_DEVICE_FUSED_ANY_BLOCKS exclude each other");
+    return deviceCreate(mh, deviceId, (flags & QGD_DEVICE_NO_FUSED_TABLES) ? 0 : ((flags & QGD_DEVICE_FUSED_ANY_BLOCKS) ? 2 : -1), out);
+}
 int qgd_device_free(qgd_device_t d) {
     if (!d) return QGD_OK;
     // a case keeps a pointer to its device and runs on its stream: freed after the device it would read freed memory
@@ -962,22 +1000,6 @@ int qgd_device_free(qgd_device_t d) {
     return QGD_OK;
 }
 
-// prismMatcher + findIndices("wedge") of fvscOpName [fvsc_8C L65-82]: a wedge patch and at least one prism cell
-// (five faces: two triangles and three quadrilaterals, six vertices)
-static bool hasWedgeAndPrism(const HostMesh& m) {
-    bool wedge = false;
-    for (const Patch& p : m.patches) wedge = wedge || (p.type == QGD_PATCH_WEDGE && p.size > 0);
-    if (!wedge) return false;
-    std::vector<uint8_t> nTri((size_t)m.nCells, 0), nQuad((size_t)m.nCells, 0), nOther((size_t)m.nCells, 0);
-    auto count = [&](int32_t c, int n) { if (n == 3) nTri[c]++; else if (n == 4) nQuad[c]++; else nOther[c]++; };
-    for (int32_t f = 0; f < m.nFaces; ++f) {
-        count(m.owner[f], m.faceSize(f));
-        if (f < m.nInternalFaces) count(m.neighbour[f], m.faceSize(f));
-    }
-    for (int32_t c = 0; c < m.nCells; ++c)
-        if (nTri[c] == 2 && nQuad[c] == 3 && nOther[c] == 0) return true;
-    return false;
-}
 static const char* kWedgePrismMessage =
     "GaussVolPoint scheme does not support solving axisymmetric cases with wedge BC and prism cells. Try to set leastSquares scheme.";
 
@@ -991,11 +1013,6 @@ static int stencilWordToId(int nGeomD, const std::string& w, int* id) {
     else return fail(QGD_ERR_UNKNOWN_NAME, "Unknown Model type " + w + "; valid: GaussVolPoint leastSquares leastSquaresOpt reduced");
     return QGD_OK;
 }
-static int deviceStencilRaw(int nGeomD, int id, int* st);
-static int deviceStencil(const qgd_device_s* d, int id, int* st) {
-    if (d->wedgePrism && id == QGD_FVSC_GAUSSVOLPOINT) return fail(QGD_ERR_SCHEME, kWedgePrismMessage);
-    return deviceStencilRaw(d->nGeomD, id, st);
-}
 static int deviceStencilRaw(int nGeomD, int id, int* st) {
     if (id == QGD_FVSC_REDUCED) *st = ST_REDUCED;
     else if (id == QGD_FVSC_LEASTSQUARES) {
@@ -1005,17 +1022,30 @@ static int deviceStencilRaw(int nGeomD, int id, int* st) {
     else return fail(QGD_ERR_UNKNOWN_NAME, "bad stencil id");
     return QGD_OK;
 }
+static int deviceStencil(const qgd_device_s* d, int id, int* st) {
+    if (d->wedgePrism && id == QGD_FVSC_GAUSSVOLPOINT) return fail(QGD_ERR_SCHEME, kWedgePrismMessage);
+    return deviceStencilRaw(d->nGeomD, id, st);
+}
 int qgd_stencil_lookup(qgd_device_t d, const char* word, int* stencilId) {
     if (!d || !word || !stencilId) return fail(QGD_ERR_INVALID, "null argument");
     if (d->wedgePrism && std::string(word) == "GaussVolPoint") return fail(QGD_ERR_SCHEME, kWedgePrismMessage);
     return stencilWordToId(d->nGeomD, word, stencilId);
 }
 
-enum WsSlot { WS_CELL = 0, WS_BND, WS_PT, WS_OUT, WS_A, WS_B, WS_C, WS_D, WS_E, WS_F, WS_G, WS_H };
-static double nowMs() {
-    timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return 1e3 * (double)t.tv_sec + 1e-6 * (double)t.tv_nsec;
+// whether `name` ends in ".boundary", which is stripped
+static bool boundaryName(std::string& name) {
+    const std::string suffix = ".boundary";
+    if (name.size() <= suffix.size() || name.compare(name.size() - suffix.size(), suffix.size(), suffix) != 0) return false;
+    name.resize(name.size() - suffix.size());
+    return true;
+}
+// `count` faces of `nc` components, SoA with stride `count` on the device, to `nc` per face at the caller: one transposition (WS_XPOSE), one copy
+static void fetchFaceSoA(qgd_device_s* d, hipStream_t stream, const double* src, int64_t count, int nc, double* out) {
+    if (nc == 1) { d->ws.d2h(out, src, sizeof(double) * (size_t)count, stream); return; }
+    double* tmp = d->ws.get<double>(WS_XPOSE, (size_t)count * nc);
+    launchSoaToAos(stream, count, nc, src, tmp);
+    HIP_CHECK(hipGetLastError());
+    d->ws.d2h(out, tmp, sizeof(double) * (size_t)count * nc, stream);
 }
 static int fvscOp(qgd_device_t d, int stencilId, int op, int NC, const double* cell, const double* bnd, double* out) {
     QGD_TRY
@@ -1150,21 +1180,24 @@ int qgd_device_copy(qgd_device_t d, void* dst, const void* src, int64_t bytes, i
     return QGD_OK;
     QGD_CATCH
 }
-// qgd_qhd_fluxes on device pointers; outputs in the documented face-major layout
-int qgd_qhd_fluxes_dev(qgd_device_t d, int stencilId, const qgd_qhd_inputs* in, qgd_qhd_outputs* out) {
-    QGD_TRY
-    if (!d || !in || !out) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes_dev: null argument");
+// ---- QHDFoam face fluxes -------------------------------------------------------------
+// what both entries refuse (`who`: the entry the caller called); the same questions of host and of device pointers
+static int qhdFluxesCheck(qgd_device_t d, const std::string& who, int stencilId, const qgd_qhd_inputs* in, const qgd_qhd_outputs* out, int* st) {
+    if (!d || !in || !out) return fail(QGD_ERR_INVALID, who + ": null argument");
     const MeshView& v = d->view;
     if (!in->U || !in->T || !in->rho || !in->tauQGDf || (v.nBF > 0 && (!in->Ub || !in->Tb || !in->rhob)))
-        return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes_dev: U, T, rho (cell + patch values) and tauQGDf are required");
+        return fail(QGD_ERR_INVALID, who + ": U, T, rho (cell + patch values) and tauQGDf are required");
     const bool haveP = in->p != nullptr;
-    if (haveP && v.nBF > 0 && !in->pb) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes_dev: p given without its patch values");
-    if ((out->gradPf || out->Wf || out->phiUf) && !haveP) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes_dev: gradPf/Wf/phiUf need p");
-    if ((out->phiUf || out->phiTf) && !in->phi) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes_dev: phiUf/phiTf need phi");
-    int st = 0;
-    int rc = deviceStencil(d, stencilId, &st);
-    if (rc) return rc;
+    if (haveP && v.nBF > 0 && !in->pb) return fail(QGD_ERR_INVALID, who + ": p given without its patch values");
+    if ((out->gradPf || out->Wf || out->phiUf) && !haveP) return fail(QGD_ERR_INVALID, who + ": gradPf/Wf/phiUf need p");
+    if ((out->phiUf || out->phiTf) && !in->phi) return fail(QGD_ERR_INVALID, who + ": phiUf/phiTf need phi");
+    return deviceStencil(d, stencilId, st);
+}
+// every output from inputs on the device, as the SoA block of launchQhdFluxes (QHD_COUNT slots of nF doubles in WS_OUT)
+static const double* qhdFluxesFill(qgd_device_t d, int st, const qgd_qhd_inputs* in) {
     HIP_CHECK(hipSetDevice(d->deviceId));
+    const MeshView& v = d->view;
+    const bool haveP = in->p != nullptr;
     const size_t nC = (size_t)v.nC, nB = (size_t)v.nBF, nF = (size_t)v.nF, nP = (size_t)v.nP;
     Workspace& ws = d->ws;
     hipStream_t s_ = d->stream;
@@ -1178,27 +1211,68 @@ int qgd_qhd_fluxes_dev(qgd_device_t d, int stencilId, const qgd_qhd_inputs* in, 
     HIP_CHECK(hipMemsetAsync(dPt, 0, sizeof(double) * std::max<size_t>(5 * nP, 1), s_));
     HIP_CHECK(hipMemsetAsync(dOut, 0, sizeof(double) * (size_t)QHD_COUNT * nF, s_));
     launchQhdFluxes(s_, st, v, dCell, dBnd, dPt, in->rho, in->rhob, in->tauQGDf, in->phi, in->beta, in->g[0], in->g[1], in->g[2], dOut);
-    auto fetch = [&](double* dst, int first, int nc) { if (dst) launchSoaToAos(s_, (int64_t)nF, nc, dOut + (size_t)first * nF, dst); };
-    fetch(out->gradUf, QHD_GRADU, 9); fetch(out->gradTf, QHD_GRADT, 3); fetch(out->phiu, QHD_PHIU, 1);
-    fetch(out->phiwo, QHD_PHIWO, 1); fetch(out->taubyrhof, QHD_TAUBYRHO, 1); fetch(out->gradPf, QHD_GRADP, 3);
-    fetch(out->Wf, QHD_WF, 3); fetch(out->phiUf, QHD_PHIUF, 3); fetch(out->phiTf, QHD_PHITF, 1);
-    fetch(out->phiTauTReg, QHD_PHITAUT, 1);
+    HIP_CHECK(hipGetLastError());
+    return dOut;
+}
+// every output of the block: its pointer in qgd_qhd_outputs, first slot, components
+static const struct { double* qgd_qhd_outputs::*dst; int first, nc; } kQhdOutputs[] = {
+    {&qgd_qhd_outputs::gradUf, QHD_GRADU, 9}, {&qgd_qhd_outputs::gradTf, QHD_GRADT, 3}, {&qgd_qhd_outputs::phiu, QHD_PHIU, 1},
+    {&qgd_qhd_outputs::phiwo, QHD_PHIWO, 1}, {&qgd_qhd_outputs::taubyrhof, QHD_TAUBYRHO, 1}, {&qgd_qhd_outputs::gradPf, QHD_GRADP, 3},
+    {&qgd_qhd_outputs::Wf, QHD_WF, 3}, {&qgd_qhd_outputs::phiUf, QHD_PHIUF, 3}, {&qgd_qhd_outputs::phiTf, QHD_PHITF, 1},
+    {&qgd_qhd_outputs::phiTauTReg, QHD_PHITAUT, 1}};
+// qgd_qhd_fluxes on device pointers; outputs in the documented face-major layout
+int qgd_qhd_fluxes_dev(qgd_device_t d, int stencilId, const qgd_qhd_inputs* in, qgd_qhd_outputs* out) {
+    QGD_TRY
+    int st = 0;
+    const int rc = qhdFluxesCheck(d, "qgd_qhd_fluxes_dev", stencilId, in, out, &st);
+    if (rc) return rc;
+    const double* dOut = qhdFluxesFill(d, st, in);
+    const size_t nF = (size_t)d->view.nF;
+    for (const auto& o : kQhdOutputs)
+        if (out->*o.dst) launchSoaToAos(d->stream, (int64_t)nF, o.nc, dOut + (size_t)o.first * nF, out->*o.dst);
     HIP_CHECK(hipGetLastError());
     return QGD_OK;
     QGD_CATCH
 }
-int qgd_species_flux_dev(qgd_device_t d, int stencilId, const double* Y, const double* Yb, const double* U, const double* Ub,
-                         const double* phiJm, const double* phi, const double* tauQGDf, double* phiJmY, double* diffusiveFlux,
-                         double* gradYf) {
+// the same on host pointers: the caller's arrays are staged as they are (the records are packed on the device), and each requested output
+// comes back through the one transposition slot -- never all ten face-major outputs on the device at once
+int qgd_qhd_fluxes(qgd_device_t d, int stencilId, const qgd_qhd_inputs* in, qgd_qhd_outputs* out) {
     QGD_TRY
-    if (!d || !Y || !U || !phiJm || !phi || !tauQGDf || !phiJmY || !diffusiveFlux)
-        return fail(QGD_ERR_INVALID, "qgd_species_flux_dev: null argument");
-    const MeshView& v = d->view;
-    if (v.nBF > 0 && (!Yb || !Ub)) return fail(QGD_ERR_INVALID, "qgd_species_flux_dev: patch values of Y and U are required");
     int st = 0;
-    int rc = deviceStencil(d, stencilId, &st);
+    const int rc = qhdFluxesCheck(d, "qgd_qhd_fluxes", stencilId, in, out, &st);
     if (rc) return rc;
     HIP_CHECK(hipSetDevice(d->deviceId));
+    const size_t nC = (size_t)d->view.nC, nB = (size_t)d->view.nBF, nF = (size_t)d->view.nF;
+    Stager stage{d->ws, d->stream};
+    qgd_qhd_inputs din = *in;
+    din.U = stage.up(in->U, 3 * nC); din.Ub = stage.up(in->Ub, 3 * nB);
+    din.T = stage.up(in->T, nC); din.Tb = stage.up(in->Tb, nB);
+    if (in->p) { din.p = stage.up(in->p, nC); din.pb = stage.up(in->pb, nB); }
+    din.rho = stage.up(in->rho, nC); din.rhob = stage.up(in->rhob, nB);
+    din.tauQGDf = stage.up(in->tauQGDf, nF);
+    if (in->phi) din.phi = stage.up(in->phi, nF);
+    const double* dOut = qhdFluxesFill(d, st, &din);
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    for (const auto& o : kQhdOutputs)
+        if (out->*o.dst) fetchFaceSoA(d, d->stream, dOut + (size_t)o.first * nF, (int64_t)nF, o.nc, out->*o.dst);
+    return QGD_OK;
+    QGD_CATCH
+}
+
+// ---- species flux and step -------------------------------------------------------------
+// As for the QHD fluxes: what both entries refuse (`who`: the entry called), asked of host or of device pointers before any device work; then
+// the launches on device pointers.
+static int speciesFluxCheck(qgd_device_t d, const std::string& who, int stencilId, const double* Y, const double* Yb, const double* U, const double* Ub,
+                            const double* phiJm, const double* phi, const double* tauQGDf, const double* phiJmY, const double* diffusiveFlux, int* st) {
+    if (!d || !Y || !U || !phiJm || !phi || !tauQGDf || !phiJmY || !diffusiveFlux)
+        return fail(QGD_ERR_INVALID, who + ": null argument");
+    if (d->view.nBF > 0 && (!Yb || !Ub)) return fail(QGD_ERR_INVALID, who + ": patch values of Y and U are required");
+    return deviceStencil(d, stencilId, st);
+}
+static void speciesFluxRun(qgd_device_t d, int st, const double* Y, const double* Yb, const double* U, const double* Ub, const double* phiJm,
+                           const double* phi, const double* tauQGDf, double* phiJmY, double* diffusiveFlux, double* gradYf) {
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    const MeshView& v = d->view;
     const size_t nF = (size_t)v.nF, nP = (size_t)v.nP;
     hipStream_t s_ = d->stream;
     double* dPt = d->ws.get<double>(WS_PT, nP);
@@ -1211,55 +1285,82 @@ int qgd_species_flux_dev(qgd_device_t d, int stencilId, const double* Y, const d
     HIP_CHECK(hipMemcpyAsync(diffusiveFlux, dOut + nF, sizeof(double) * nF, hipMemcpyDeviceToDevice, s_));
     if (gradYf) launchSoaToAos(s_, (int64_t)nF, 3, dOut + 2 * nF, gradYf);
     HIP_CHECK(hipGetLastError());
+}
+int qgd_species_flux_dev(qgd_device_t d, int stencilId, const double* Y, const double* Yb, const double* U, const double* Ub,
+                         const double* phiJm, const double* phi, const double* tauQGDf, double* phiJmY, double* diffusiveFlux,
+                         double* gradYf) {
+    QGD_TRY
+    int st = 0;
+    const int rc = speciesFluxCheck(d, "qgd_species_flux_dev", stencilId, Y, Yb, U, Ub, phiJm, phi, tauQGDf, phiJmY, diffusiveFlux, &st);
+    if (rc) return rc;
+    speciesFluxRun(d, st, Y, Yb, U, Ub, phiJm, phi, tauQGDf, phiJmY, diffusiveFlux, gradYf);
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_species_flux(qgd_device_t d, int stencilId, const double* Y, const double* Yb, const double* U, const double* Ub,
+                     const double* phiJm, const double* phi, const double* tauQGDf, double* phiJmY, double* diffusiveFlux,
+                     double* gradYf) {
+    QGD_TRY
+    int st = 0;
+    const int rc = speciesFluxCheck(d, "qgd_species_flux", stencilId, Y, Yb, U, Ub, phiJm, phi, tauQGDf, phiJmY, diffusiveFlux, &st);
+    if (rc) return rc;
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    const size_t nC = (size_t)d->view.nC, nB = (size_t)d->view.nBF, nF = (size_t)d->view.nF;
+    Stager stage{d->ws, d->stream};
+    double *dY = stage.up(Y, nC), *dYb = stage.up(Yb, nB), *dU = stage.up(U, 3 * nC), *dUb = stage.up(Ub, 3 * nB);
+    double *dJm = stage.up(phiJm, nF), *dPhi = stage.up(phi, nF), *dTau = stage.up(tauQGDf, nF);
+    double *dJmY = stage.scratch(nF), *dDf = stage.scratch(nF), *dGrad = gradYf ? stage.scratch(3 * nF) : nullptr;
+    speciesFluxRun(d, st, dY, dYb, dU, dUb, dJm, dPhi, dTau, dJmY, dDf, dGrad);
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    d->ws.d2h(phiJmY, dJmY, sizeof(double) * nF, d->stream);
+    d->ws.d2h(diffusiveFlux, dDf, sizeof(double) * nF, d->stream);
+    if (gradYf) d->ws.d2h(gradYf, dGrad, sizeof(double) * 3 * nF, d->stream);
     return QGD_OK;
     QGD_CATCH
 }
 
+static int speciesStepCheck(qgd_device_t d, const std::string& who, const double* Y, const double* Yb, const double* rhoOld, const double* rho,
+                            const double* phiJmY, const double* muf, double Sc, double deltaT, const double* diffusiveFlux, const double* Ynew) {
+    if (!d || !Y || !rhoOld || !rho || !phiJmY || !muf || !diffusiveFlux || !Ynew) return fail(QGD_ERR_INVALID, who + ": null argument");
+    if (!(Sc > 0) || !(deltaT > 0)) return fail(QGD_ERR_INVALID, who + ": Sc and deltaT must be positive");
+    if (d->view.nBF > 0 && !Yb) return fail(QGD_ERR_INVALID, who + ": patch values of Y are required");
+    return QGD_OK;
+}
+static void speciesStepRun(qgd_device_t d, const double* Y, const double* Yb, const double* rhoOld, const double* rho, const double* phiJmY,
+                           const double* muf, double Sc, double deltaT, const double* Su, double* diffusiveFlux, double* Ynew) {
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    double* net = d->ws.get<double>(WS_OUT, (size_t)d->view.nF);
+    (void)hipGetLastError();
+    launchSpeciesStep(d->stream, d->view, Y, Yb, rhoOld, rho, phiJmY, muf, Sc, deltaT, Su, diffusiveFlux, net, Ynew);
+    HIP_CHECK(hipGetLastError());
+}
 int qgd_species_step_dev(qgd_device_t d, const double* Y, const double* Yb, const double* rhoOld, const double* rho, const double* phiJmY,
                          const double* muf, double Sc, double deltaT, const double* Su, double* diffusiveFlux, double* Ynew) {
     QGD_TRY
-    if (!d || !Y || !rhoOld || !rho || !phiJmY || !muf || !diffusiveFlux || !Ynew) return fail(QGD_ERR_INVALID, "qgd_species_step_dev: null argument");
-    if (!(Sc > 0) || !(deltaT > 0)) return fail(QGD_ERR_INVALID, "qgd_species_step_dev: Sc and deltaT must be positive");
-    const MeshView& v = d->view;
-    if (v.nBF > 0 && !Yb) return fail(QGD_ERR_INVALID, "qgd_species_step_dev: patch values of Y are required");
-    HIP_CHECK(hipSetDevice(d->deviceId));
-    double* net = d->ws.get<double>(WS_OUT, (size_t)v.nF);
-    (void)hipGetLastError();
-    launchSpeciesStep(d->stream, v, Y, Yb, rhoOld, rho, phiJmY, muf, Sc, deltaT, Su, diffusiveFlux, net, Ynew);
-    HIP_CHECK(hipGetLastError());
+    const int rc = speciesStepCheck(d, "qgd_species_step_dev", Y, Yb, rhoOld, rho, phiJmY, muf, Sc, deltaT, diffusiveFlux, Ynew);
+    if (rc) return rc;
+    speciesStepRun(d, Y, Yb, rhoOld, rho, phiJmY, muf, Sc, deltaT, Su, diffusiveFlux, Ynew);
     return QGD_OK;
     QGD_CATCH
 }
 int qgd_species_step(qgd_device_t d, const double* Y, const double* Yb, const double* rhoOld, const double* rho, const double* phiJmY,
                      const double* muf, double Sc, double deltaT, const double* Su, double* diffusiveFlux, double* Ynew) {
     QGD_TRY
-    if (!d || !Y || !rhoOld || !rho || !phiJmY || !muf || !diffusiveFlux || !Ynew) return fail(QGD_ERR_INVALID, "qgd_species_step: null argument");
-    if (!(Sc > 0) || !(deltaT > 0)) return fail(QGD_ERR_INVALID, "qgd_species_step: Sc and deltaT must be positive");
-    const MeshView& v = d->view;
-    if (v.nBF > 0 && !Yb) return fail(QGD_ERR_INVALID, "qgd_species_step: patch values of Y are required");
+    const int rc = speciesStepCheck(d, "qgd_species_step", Y, Yb, rhoOld, rho, phiJmY, muf, Sc, deltaT, diffusiveFlux, Ynew);
+    if (rc) return rc;
     HIP_CHECK(hipSetDevice(d->deviceId));
-    const size_t nC = (size_t)v.nC, nB = (size_t)v.nBF, nF = (size_t)v.nF;
-    Workspace& ws = d->ws;
-    hipStream_t st_ = d->stream;
-    int nextSlot = WS_CELL;
-    auto upD = [&](const double* src, size_t n) {
-        double* dst = ws.get<double>((size_t)nextSlot++, n);
-        if (src && n) ws.h2d(dst, src, sizeof(double) * n, st_);
-        return dst;
-    };
-    double *dY = upD(Y, nC), *dYb = upD(Yb, nB), *dRo = upD(rhoOld, nC), *dR = upD(rho, nC), *dJ = upD(phiJmY, nF), *dMu = upD(muf, nF);
-    double* dSu = Su ? upD(Su, nC) : nullptr;
-    double *dDf = upD(diffusiveFlux, nF), *dNet = upD(nullptr, nF), *dNew = upD(nullptr, nC);
-    (void)hipGetLastError();
-    launchSpeciesStep(st_, v, dY, dYb, dRo, dR, dJ, dMu, Sc, deltaT, dSu, dDf, dNet, dNew);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(st_));
-    ws.d2h(diffusiveFlux, dDf, sizeof(double) * nF, st_);
-    ws.d2h(Ynew, dNew, sizeof(double) * nC, st_);
+    const size_t nC = (size_t)d->view.nC, nB = (size_t)d->view.nBF, nF = (size_t)d->view.nF;
+    Stager stage{d->ws, d->stream};
+    double *dY = stage.up(Y, nC), *dYb = stage.up(Yb, nB), *dRo = stage.up(rhoOld, nC), *dR = stage.up(rho, nC);
+    double *dJ = stage.up(phiJmY, nF), *dMu = stage.up(muf, nF), *dSu = Su ? stage.up(Su, nC) : nullptr;
+    double *dDf = stage.up(diffusiveFlux, nF), *dNew = stage.scratch(nC);
+    speciesStepRun(d, dY, dYb, dRo, dR, dJ, dMu, Sc, deltaT, dSu, dDf, dNew);
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    d->ws.d2h(diffusiveFlux, dDf, sizeof(double) * nF, d->stream);
+    d->ws.d2h(Ynew, dNew, sizeof(double) * nC, d->stream);
     return QGD_OK;
     QGD_CATCH
 }
-
 // the implicitDiffusion branch of the species equation [QGDYEqn_8H L47-66] on device pointers; info (host) = {iterations, initial, final residual}
 int qgd_species_step_implicit_dev(qgd_device_t d, const double* Y, const double* Yb, const uint8_t* fixedValueFace, const double* rhoOld,
                                   const double* rho, const double* phiJmY, const double* muf, double Sc, double deltaT, const double* Su, double tolerance,
@@ -1277,7 +1378,7 @@ int qgd_species_step_implicit_dev(qgd_device_t d, const double* Y, const double*
             return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_species_step_implicit: patch '" + pt.name + "' is cyclic: the implicit laplacian across coupled patches is not served");
     HIP_CHECK(hipSetDevice(d->deviceId));
     if (!d->opSolver) d->opSolver = implicitSolverCreate(d->stream, v, d->ownedBegin, d->ownedEnd);
-    double* work = d->ws.get<double>(WS_H, 3 * (size_t)v.nC + (size_t)v.nF);   // the last slot: the host-pointer entry fills the first ten
+    double* work = d->ws.get<double>(WS_H, 3 * (size_t)v.nC + (size_t)v.nF);
     (void)hipGetLastError();
     launchSpeciesStepImplicit(d->opSolver, v, Y, Yb, fixedValueFace, rhoOld, rho, phiJmY, muf, Sc, deltaT, Su, tolerance, maxIter, work, diffusiveFlux, Ynew, info);
     HIP_CHECK(hipGetLastError());
@@ -1296,18 +1397,13 @@ int qgd_species_step_implicit(qgd_device_t d, const double* Y, const double* Yb,
     const size_t nC = (size_t)v.nC, nB = (size_t)v.nBF, nF = (size_t)v.nF;
     Workspace& ws = d->ws;
     hipStream_t st_ = d->stream;
-    int nextSlot = WS_CELL;
-    auto upD = [&](const double* src, size_t n) {
-        double* dst = ws.get<double>((size_t)nextSlot++, n);
-        if (src && n) ws.h2d(dst, src, sizeof(double) * n, st_);
-        return dst;
-    };
-    double *dY = upD(Y, nC), *dYb = upD(Yb, nB), *dRo = upD(rhoOld, nC), *dR = upD(rho, nC), *dJ = upD(phiJmY, nF), *dMu = upD(muf, nF);
-    double* dSu = Su ? upD(Su, nC) : nullptr;
-    double *dDf = upD(diffusiveFlux, nF), *dNew = upD(nullptr, nC);
+    Stager stage{ws, st_};
+    double *dY = stage.up(Y, nC), *dYb = stage.up(Yb, nB), *dRo = stage.up(rhoOld, nC), *dR = stage.up(rho, nC), *dJ = stage.up(phiJmY, nF), *dMu = stage.up(muf, nF);
+    double* dSu = Su ? stage.up(Su, nC) : nullptr;
+    double *dDf = stage.up(diffusiveFlux, nF), *dNew = stage.scratch(nC);
     uint8_t* dFix = nullptr;
     if (fixedValueFace && nB) {
-        dFix = reinterpret_cast<uint8_t*>(ws.get<double>((size_t)nextSlot++, (nB + 7) / 8));
+        dFix = reinterpret_cast<uint8_t*>(stage.scratch((nB + 7) / 8));
         ws.h2d(dFix, fixedValueFace, nB, st_);
     }
     const int rc = qgd_species_step_implicit_dev(d, dY, dYb, dFix, dRo, dR, dJ, dMu, Sc, deltaT, dSu, tolerance, maxIter, dDf, dNew, info);
@@ -1382,116 +1478,6 @@ int qgd_device_get(qgd_device_t d, const char* name, double* out, int64_t outDou
         if (v.nBF > outDoubles) return fail(QGD_ERR_INVALID, "output too small");
         if (v.nBF) HIP_CHECK(hipMemcpy(out, v.hQGDb, sizeof(double) * (size_t)v.nBF, hipMemcpyDeviceToHost));
     } else return fail(QGD_ERR_UNKNOWN_NAME, "qgd_device_get: unknown name " + s);
-    return QGD_OK;
-    QGD_CATCH
-}
-
-// ---- QHDFoam face fluxes -------------------------------------------------------------
-int qgd_qhd_fluxes(qgd_device_t d, int stencilId, const qgd_qhd_inputs* in, qgd_qhd_outputs* out) {
-    QGD_TRY
-    if (!d || !in || !out) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes: null argument");
-    const MeshView& v = d->view;
-    if (!in->U || !in->T || !in->rho || !in->tauQGDf || (v.nBF > 0 && (!in->Ub || !in->Tb || !in->rhob)))
-        return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes: U, T, rho (cell + patch values) and tauQGDf are required");
-    const bool haveP = in->p != nullptr;
-    if (haveP && v.nBF > 0 && !in->pb) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes: p given without its patch values");
-    if ((out->gradPf || out->Wf || out->phiUf) && !haveP) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes: gradPf/Wf/phiUf need p");
-    if ((out->phiUf || out->phiTf) && !in->phi) return fail(QGD_ERR_INVALID, "qgd_qhd_fluxes: phiUf/phiTf need phi");
-    int st = 0;
-    int rc = deviceStencil(d, stencilId, &st);
-    if (rc) return rc;
-    HIP_CHECK(hipSetDevice(d->deviceId));
-    const size_t nC = (size_t)v.nC, nB = (size_t)v.nBF, nF = (size_t)v.nF, nP = (size_t)v.nP;
-    // host-side packing of the 5-component records {Ux,Uy,Uz,T,p}
-    std::vector<double> cell5(5 * nC), bnd5(5 * std::max<size_t>(nB, 1), 0.0);
-    for (size_t c = 0; c < nC; ++c) {
-        for (int k = 0; k < 3; ++k) cell5[5 * c + k] = in->U[3 * c + k];
-        cell5[5 * c + 3] = in->T[c];
-        cell5[5 * c + 4] = haveP ? in->p[c] : 0.0;
-    }
-    for (size_t b = 0; b < nB; ++b) {
-        for (int k = 0; k < 3; ++k) bnd5[5 * b + k] = in->Ub[3 * b + k];
-        bnd5[5 * b + 3] = in->Tb[b];
-        bnd5[5 * b + 4] = haveP ? in->pb[b] : 0.0;
-    }
-    Workspace& ws = d->ws;
-    hipStream_t st_ = d->stream;
-    auto up = [&](int slot, const double* src, size_t n) {
-        double* dst = ws.get<double>((size_t)slot, n);
-        if (src && n) ws.h2d(dst, src, sizeof(double) * n, st_);
-        return dst;
-    };
-    double* dCell = up(WS_CELL, cell5.data(), cell5.size());
-    double* dBnd = up(WS_BND, bnd5.data(), bnd5.size());
-    double* dPt = ws.get<double>(WS_PT, 5 * nP);
-    HIP_CHECK(hipMemsetAsync(dPt, 0, sizeof(double) * std::max<size_t>(5 * nP, 1), st_));
-    double* dRho = up(WS_A, in->rho, nC);
-    double* dRhob = up(WS_B, in->rhob, nB);
-    double* dTau = up(WS_C, in->tauQGDf, nF);
-    double* dPhi = in->phi ? up(WS_D, in->phi, nF) : nullptr;
-    double* dOut = ws.get<double>(WS_OUT, (size_t)QHD_COUNT * nF);
-    HIP_CHECK(hipMemsetAsync(dOut, 0, sizeof(double) * (size_t)QHD_COUNT * nF, st_));
-    (void)hipGetLastError();
-    launchQhdFluxes(st_, st, v, dCell, dBnd, dPt, dRho, dRhob, dTau, dPhi, in->beta, in->g[0], in->g[1], in->g[2], dOut);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(st_));
-    std::vector<double> slot(nF);
-    auto fetch = [&](double* dst, int first, int nc) {
-        if (!dst) return;
-        if (nc == 1) { ws.d2h(dst, dOut + (size_t)first * nF, sizeof(double) * nF, st_); return; }
-        for (int k = 0; k < nc; ++k) {
-            ws.d2h(slot.data(), dOut + (size_t)(first + k) * nF, sizeof(double) * nF, st_);
-#pragma omp parallel for schedule(static)
-            for (int64_t f = 0; f < (int64_t)nF; ++f) dst[(size_t)f * nc + k] = slot[(size_t)f];
-        }
-    };
-    fetch(out->gradUf, QHD_GRADU, 9); fetch(out->gradTf, QHD_GRADT, 3); fetch(out->phiu, QHD_PHIU, 1);
-    fetch(out->phiwo, QHD_PHIWO, 1); fetch(out->taubyrhof, QHD_TAUBYRHO, 1); fetch(out->gradPf, QHD_GRADP, 3);
-    fetch(out->Wf, QHD_WF, 3); fetch(out->phiUf, QHD_PHIUF, 3); fetch(out->phiTf, QHD_PHITF, 1);
-    fetch(out->phiTauTReg, QHD_PHITAUT, 1);
-    return QGD_OK;
-    QGD_CATCH
-}
-
-int qgd_species_flux(qgd_device_t d, int stencilId, const double* Y, const double* Yb, const double* U, const double* Ub,
-                     const double* phiJm, const double* phi, const double* tauQGDf, double* phiJmY, double* diffusiveFlux,
-                     double* gradYf) {
-    QGD_TRY
-    if (!d || !Y || !U || !phiJm || !phi || !tauQGDf || !phiJmY || !diffusiveFlux)
-        return fail(QGD_ERR_INVALID, "qgd_species_flux: null argument");
-    const MeshView& v = d->view;
-    if (v.nBF > 0 && (!Yb || !Ub)) return fail(QGD_ERR_INVALID, "qgd_species_flux: patch values of Y and U are required");
-    int st = 0;
-    int rc = deviceStencil(d, stencilId, &st);
-    if (rc) return rc;
-    HIP_CHECK(hipSetDevice(d->deviceId));
-    const size_t nC = (size_t)v.nC, nB = (size_t)v.nBF, nF = (size_t)v.nF, nP = (size_t)v.nP;
-    Workspace& ws = d->ws;
-    hipStream_t st_ = d->stream;
-    int nextSlot = WS_CELL;
-    auto upD = [&](const double* src, size_t n) {
-        double* dst = ws.get<double>((size_t)nextSlot++, n);
-        if (src && n) ws.h2d(dst, src, sizeof(double) * n, st_);
-        return dst;
-    };
-    double *dY = upD(Y, nC), *dYb = upD(Yb, nB), *dU = upD(U, 3 * nC), *dUb = upD(Ub, 3 * nB);
-    double *dJm = upD(phiJm, nF), *dPhi = upD(phi, nF), *dTau = upD(tauQGDf, nF);
-    double* dPt = upD(nullptr, nP);
-    HIP_CHECK(hipMemsetAsync(dPt, 0, sizeof(double) * std::max<size_t>(nP, 1), st_));
-    double* dOut = upD(nullptr, 5 * nF);
-    (void)hipGetLastError();
-    launchSpeciesFlux(st_, st, v, dY, dYb, dPt, dU, dUb, dJm, dPhi, dTau, dOut);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(st_));
-    ws.d2h(phiJmY, dOut, sizeof(double) * nF, st_);
-    ws.d2h(diffusiveFlux, dOut + nF, sizeof(double) * nF, st_);
-    if (gradYf) {
-        std::vector<double> slot(nF);
-        for (int k = 0; k < 3; ++k) {
-            ws.d2h(slot.data(), dOut + (size_t)(2 + k) * nF, sizeof(double) * nF, st_);
-            for (size_t f = 0; f < nF; ++f) gradYf[3 * f + k] = slot[f];
-        }
-    }
     return QGD_OK;
     QGD_CATCH
 }
@@ -1633,16 +1619,13 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
         c->fused = v.fuBlocks > 0 && c->stencil == ST_GVP3 && c->mixB < 0 && !opt->implicitDiffusion && !opt->adjustTimeStep;
         if (c->fused) { cv.A2 = a.alloc<RecA>(v.nC); cv.B2 = a.alloc<RecB>(v.nC); }
         {   // the same blocks under Courant-number control: two launches (blocks up to their sums, then the cells) instead of three kernels
-            static const int kOnOff[] = {0, 1};
             c->fusedAdj = v.fuBlocks > 0 && c->stencil == ST_GVP3 && c->mixB < 0 && !opt->implicitDiffusion && opt->adjustTimeStep &&
-                          envChoice("QGD_FUSED_ADJUST", 1, kOnOff, 2) != 0;
+                          envOnOff("QGD_FUSED_ADJUST", 1) != 0;
             if (c->fusedAdj) cv.cellSum = a.alloc<double>(5 * (size_t)v.nC);
         }
-        {   // the reference's default branch on the same blocks (unsharded, fixed deltaT, one 3-D GaussVolPoint stencil)
-            static const int kOnOff[] = {0, 1};
-            c->fusedImpl = v.fuBlocks > 0 && v.fuLdsImpl > 0 && c->stencil == ST_GVP3 && c->mixB < 0 && opt->implicitDiffusion && !opt->adjustTimeStep &&
-                           !d->sharded() && envChoice("QGD_IMPL_FUSED", 1, kOnOff, 2) != 0 && fusedImplUPrepare(v, c->gas);
-        }
+        // the reference's default branch on the same blocks (unsharded, fixed deltaT, one 3-D GaussVolPoint stencil)
+        c->fusedImpl = v.fuBlocks > 0 && v.fuLdsImpl > 0 && c->stencil == ST_GVP3 && c->mixB < 0 && opt->implicitDiffusion && !opt->adjustTimeStep &&
+                       !d->sharded() && envOnOff("QGD_IMPL_FUSED", 1) != 0 && fusedImplUPrepare(v, c->gas);
         cv.bA = a.alloc<RecA>(v.nBF); cv.bB = a.alloc<RecB>(v.nBF);
         cv.bG = a.alloc<double>(v.nBF); cv.bPhiw = a.alloc<double>(v.nBF); cv.bPmid = a.alloc<double>(v.nBF);
         cv.bRhoLag = a.alloc<double>(v.nBF);
@@ -1670,7 +1653,7 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
             iv.xU = a.alloc<double>(3 * nC); iv.diagU = a.alloc<double>(3 * nC); iv.rhsU = a.alloc<double>(3 * nC);
             iv.xE = a.alloc<double>(nC); iv.diagE = a.alloc<double>(nC); iv.rhsE = a.alloc<double>(nC);
             c->implSolver = implicitSolverCreate(d->stream, v, d->ownedBegin, d->ownedEnd);
-            { static const int kOnOff[] = {0, 1}; c->reuseGradU = envChoice("QGD_IMPL_REUSE_GRADU", 1, kOnOff, 2) != 0; }
+            c->reuseGradU = envOnOff("QGD_IMPL_REUSE_GRADU", 1) != 0;
             {   // start values of the two solves (qgd_implicit.hip "start values"): 0 = OpenFOAM's (the predictor), 1..3 = + the extrapolated correction
                 static const int kOrders[] = {0, 1, 2, 3, 4};
                 c->implXOrder = envChoice("QGD_IMPL_XEXTRAP", 3, kOrders, 5);
@@ -1694,7 +1677,38 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
     return QGD_OK;
     QGD_CATCH
 }
-static void freeMonitorsOf(qgd_case_s* c);
+// the handle of a run monitor (its entries: "run monitors" below); here because a case frees the monitors still open on it
+struct qgd_monitor_s {
+    qgd_case_s* c = nullptr;
+    MonitorView view{};
+    DeviceArena arena;
+    double* result = nullptr;    // device: one result block (the copy into a slot follows the fold in stream order)
+    double* host = nullptr;      // pinned: QGD_MONITOR_SLOTS slots of nDoubles + spDoubles: the flow block, the species block behind it
+    int64_t nDoubles = 0;
+    // the species block (qgd_monitor_enable_species; qgd_monitor_species.hip): spDoubles == 0 until it is enabled
+    SpeciesMonitorView spView{};
+    int64_t spDoubles = 0;
+    hipEvent_t ev[QGD_MONITOR_SLOTS] = {};
+    bool sampled[QGD_MONITOR_SLOTS] = {};
+    double time[QGD_MONITOR_SLOTS] = {};
+    int64_t step[QGD_MONITOR_SLOTS] = {};
+};
+// the open monitors of this process: a handle whose case was freed first is no longer among them
+static std::vector<qgd_monitor_s*> g_monitors;
+static bool monitorLive(const qgd_monitor_s* m) { return m && std::find(g_monitors.begin(), g_monitors.end(), m) != g_monitors.end(); }
+static void monitorDestroy(qgd_monitor_s* m) {
+    for (hipEvent_t e : m->ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+    if (m->host) (void)hipHostFree(m->host);
+    m->arena.release();
+    g_monitors.erase(std::remove(g_monitors.begin(), g_monitors.end(), m), g_monitors.end());
+    delete m;
+}
+static void freeMonitorsOf(qgd_case_s* c) {
+    if (c->monitors.empty()) return;
+    (void)hipStreamSynchronize(c->stream());
+    for (qgd_monitor_s* m : c->monitors) monitorDestroy(m);
+    c->monitors.clear();
+}
 int qgd_case_free(qgd_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
@@ -2157,7 +2171,170 @@ static void assembleFluxes(qgd_case_s* c, bool adjust, int part = 0, bool intern
     if (c->fusedAdj && !internalFaces && !c->view.dbg) launchFusedAdjust(L, m, v, c->gas);
 }
 static bool midExchangeNeeded(const qgd_case_s* c) { return c->dev->sharded() && c->pRefresh && c->hasQgdFlux; }
-static void selfHaloExchange(qgd_case_s* c, bool mid);
+// ---- the halo messages of the QGD case -------------------------------------------------------------------------------------
+// kind 0: the state message, QGD_HALO_CELL_DOUBLES_HOST doubles per cell (RecA, RecB), 12 per boundary face (RecA, RecB, p gradient, lagged rho);
+//         a case with species and QGD_SPECIES_HALO appends nS planes of one double per cell (qgd_species.hip caseSpeciesHaloKernel);
+// kinds 1..4: the implicitDiffusion branch's own (1 grad U, 2 U, 3 search direction, 4 guess: implicitHaloWidth doubles per cell);
+// kind 5: the message between step phases 5 and 6 (see assembleFluxes), 2 doubles per patch face of the slot's boundary-layer cells
+static int caseHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pack, hipStream_t stream) {
+    qgd_device_s* d = c->dev;
+    if (slot >= (int)d->halo.size()) return QGD_OK;  // an unsharded mesh has no slots: nothing to exchange
+    const qgd_device_s::HaloSlot& h = d->halo[slot];
+    const int32_t *cells = pack ? h.send : h.ghost, *faces = pack ? h.sendBF : h.ghostBF;
+    const int32_t nCells = pack ? h.nSend : h.nGhost, nFaces = pack ? h.nSendBF : h.nGhostBF;
+    if ((kind == 5 ? nFaces : nCells) == 0) return QGD_OK;
+    if (!buf) return fail(QGD_ERR_INVALID, "null buffer");
+    (void)hipGetLastError();   // a stale error of an earlier, refused call must not be taken for this launch's
+    if (kind == 0) {
+        Launcher L = launcherOf(c);
+        L.pre = nullptr; L.post = nullptr; L.stream = stream;
+        launchHaloPack(L, c->view, c->gas, cells, nCells, faces, nFaces, buf, pack);
+        // the species tail behind the flow's part, which keeps its layout; on the same stream: the patch values follow the cells' Y
+        if (c->spHalo)
+            launchSpeciesHalo(stream, d->view, c->sp, cells, nCells, faces, nFaces,
+                              buf + (size_t)QGD_HALO_CELL_DOUBLES_HOST * (size_t)nCells + 12 * (size_t)nFaces, pack);
+    } else if (kind == 5) launchMidHalo(stream, c->view, faces, nFaces, buf, pack);
+    else launchImplicitHalo(stream, d->view, c->view, c->impl, c->implSolver, kind, cells, nCells, buf, pack);
+    HIP_CHECK(hipGetLastError());
+    return QGD_OK;
+}
+// forCount: kinds 3 and 4 with room for the widest solve (what a caller sizes its buffers by); what is SENT has the width of the solve in flight
+static HaloMessage haloMessage(qgd_case_s* c, int kind, bool forCount = false) {
+    HaloMessage m;
+    if (kind == 0) { m.perCell = QGD_HALO_CELL_DOUBLES_HOST + (c->spHalo ? c->sp.nS : 0); m.perFace = 12; }
+    else if (kind == 5) m.perFace = 2;
+    else m.perCell = (forCount && kind >= 3) ? 3 : implicitHaloWidth(c->implSolver, kind);
+    m.move = [c, kind](int slot, double* buf, bool pack, hipStream_t stream) { return caseHaloMove(c, slot, kind, buf, pack, stream); };
+    return m;
+}
+static HaloBuffers& haloBuffers(qgd_case_s* c) {
+    c->haloBuf.arena = &c->arena;
+    c->haloBuf.widest.perCell = c->implSolver ? 9 : QGD_HALO_CELL_DOUBLES_HOST;   // grad U: 9 per cell; state: 8 per cell and ...
+    if (c->spHalo) c->haloBuf.widest.perCell = std::max(c->haloBuf.widest.perCell, QGD_HALO_CELL_DOUBLES_HOST + (int)c->sp.nS);   // (+ the species' planes)
+    c->haloBuf.widest.perFace = 12;                                               // ... 12 per face
+    return c->haloBuf;
+}
+// ---- native halo transport: RCCL send/recv inside the library -----------------------------------------------------------
+// Replaces, for a C++/MPI host, what the reference does per gradient call with PstreamBuffers
+// [extendedFaceStencilScalarGrad_8C L145-233] and with processor-patch evaluation [GaussVolPointStencil_8C L73]:
+// ONE grouped send/recv pair per neighbouring rank per step, device buffers, stream-ordered, no host synchronisation.
+extern "C++" {
+namespace {
+struct Rccl {
+    void* lib = nullptr;
+    decltype(&ncclGetUniqueId) getUniqueId = nullptr;
+    decltype(&ncclCommInitRank) commInitRank = nullptr;
+    decltype(&ncclCommDestroy) commDestroy = nullptr;
+    decltype(&ncclSend) send = nullptr;
+    decltype(&ncclRecv) recv = nullptr;
+    decltype(&ncclAllReduce) allReduce = nullptr;
+    decltype(&ncclGroupStart) groupStart = nullptr;
+    decltype(&ncclGroupEnd) groupEnd = nullptr;
+    decltype(&ncclGetErrorString) errorString = nullptr;
+    decltype(&ncclCommCount) commCount = nullptr;
+    decltype(&ncclCommUserRank) commUserRank = nullptr;
+    decltype(&ncclCommCuDevice) commCuDevice = nullptr;
+    std::string why;
+};
+Rccl& rcclRef() {
+    static Rccl r;
+    static bool tried = false;
+    if (tried) return r;
+    tried = true;
+    // an RCCL already in the process (e.g. the one torch.distributed brought) is reused; otherwise the ROCm one is loaded
+    const char* env = std::getenv("QGD_RCCL_LIB");
+    const char* names[] = {env, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
+    for (const char* n : names) {
+        if (!n) continue;
+        r.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD);
+        if (r.lib) break;
+    }
+    for (const char* n : names) {
+        if (r.lib) break;
+        if (!n) continue;
+        r.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL);
+    }
+    if (!r.lib) { r.why = "RCCL not found (librccl.so; set QGD_RCCL_LIB)"; return r; }
+    auto sym = [&](const char* name) { void* p = dlsym(r.lib, name); if (!p && r.why.empty()) r.why = std::string("RCCL symbol missing: ") + name; return p; };
+    r.getUniqueId = (decltype(r.getUniqueId))sym("ncclGetUniqueId");
+    r.commInitRank = (decltype(r.commInitRank))sym("ncclCommInitRank");
+    r.commDestroy = (decltype(r.commDestroy))sym("ncclCommDestroy");
+    r.send = (decltype(r.send))sym("ncclSend");
+    r.recv = (decltype(r.recv))sym("ncclRecv");
+    r.allReduce = (decltype(r.allReduce))sym("ncclAllReduce");
+    r.groupStart = (decltype(r.groupStart))sym("ncclGroupStart");
+    r.groupEnd = (decltype(r.groupEnd))sym("ncclGroupEnd");
+    r.errorString = (decltype(r.errorString))sym("ncclGetErrorString");
+    r.commCount = (decltype(r.commCount))sym("ncclCommCount");
+    r.commUserRank = (decltype(r.commUserRank))sym("ncclCommUserRank");
+    r.commCuDevice = (decltype(r.commCuDevice))sym("ncclCommCuDevice");
+    return r;
+}
+}  // namespace
+}  // extern "C++"
+struct qgd_comm_s {
+    ncclComm_t comm = nullptr;
+    int rank = 0, nRanks = 1, deviceId = 0;
+};
+#define RCCL_CHECK(expr)                                                                                          \
+    do {                                                                                                          \
+        ncclResult_t _r = (expr);                                                                                 \
+        if (_r != ncclSuccess)                                                                                    \
+            throw HipError(std::string(#expr) + ": " + (rcclRef().errorString ? rcclRef().errorString(_r) : "RCCL error")); \
+    } while (0)
+// RCCL matches the messages of one peer in issue order, and both sides issue in their own slot order: two slots towards
+// the same rank (two ranks on a periodic cut, two disjoint interfaces with one neighbour) would land in each other's
+// ghost lists.  Refused; a rank exchanging with itself (the one-GPU test of this path) is the one ordered exception.
+// Called by every exchange AND at the top of the sharded step entries, before the first message of a step is issued
+// (the mid-assembly message and the messages inside the implicit solves come before the state message).
+static void checkHaloPeers(const qgd_comm_s* comm, const int32_t* peers, int n) {
+    for (int a = 0; a < n; ++a)
+        for (int b = a + 1; b < n; ++b)
+            if (peers[a] >= 0 && peers[a] == peers[b] && peers[a] != comm->rank)
+                throw std::invalid_argument("halo exchange: rank " + std::to_string(peers[a]) + " is the peer of two halo slots; "
+                                            "one slot per neighbouring rank (qgd_mesh_shard builds them that way)");
+    for (int s = 0; s < n; ++s)
+        if (peers[s] >= comm->nRanks) throw std::invalid_argument("halo exchange: peer rank out of range");
+}
+// THE halo exchange of both case types and every message kind, on `stream`: every slot with a neighbour packs its message into the case's
+// send buffer, the messages travel, every such slot unpacks what arrived.  comm != nullptr: a grouped ncclSend / ncclRecv pair per slot
+// towards peers[slot] (< 0: no neighbour).  comm == nullptr: the cyclic pairs of a periodic device, where slot s takes what its partner
+// slot haloSelf[s] of the same case packed (peers is not read).
+static void exchangeOn(qgd_device_s* d, qgd_comm_s* comm, const int32_t* peers, int nSlots, hipStream_t stream, const HaloMessage& msg,
+                       HaloBuffers& bufs) {
+    const int n = std::min<int>(nSlots, (int)d->halo.size());
+    if (comm) checkHaloPeers(comm, peers, n);
+    bufs.ensure(d);
+    auto move = [&](int s, double* buf, bool pack) {
+        if ((!comm || peers[s] >= 0) && msg.move(s, buf, pack, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
+    };
+    for (int s = 0; s < n; ++s) move(s, bufs.send[s], true);
+    if (comm) {
+        RCCL_CHECK(rcclRef().groupStart());
+        try {
+            for (int s = 0; s < n; ++s) {
+                if (peers[s] < 0) continue;
+                const size_t ns = msg.sendCount(d->halo[s]), nr = msg.recvCount(d->halo[s]);
+                if (ns) RCCL_CHECK(rcclRef().send(bufs.send[s], ns, ncclFloat64, peers[s], comm->comm, stream));
+                if (nr) RCCL_CHECK(rcclRef().recv(bufs.recv[s], nr, ncclFloat64, peers[s], comm->comm, stream));
+            }
+        } catch (...) {
+            (void)rcclRef().groupEnd();   // never leave the group open behind a failed call: the next collective would join it
+            throw;
+        }
+        RCCL_CHECK(rcclRef().groupEnd());
+    } else {
+        for (int s = 0; s < n; ++s)
+            if (d->halo[(size_t)d->haloSelf[s]].nSend != d->halo[s].nGhost || d->halo[(size_t)d->haloSelf[s]].nSendBF != d->halo[s].nGhostBF)
+                throw std::runtime_error("cyclic self-exchange: a slot's ghosts do not match its partner's message");
+    }
+    for (int s = 0; s < n; ++s) move(s, comm ? bufs.recv[s] : bufs.send[(size_t)d->haloSelf[s]], false);
+}
+static void exchangeOn(qgd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots, hipStream_t stream, int kind) {
+    exchangeOn(c->dev, comm, peers, nSlots, stream, haloMessage(c, kind), haloBuffers(c));
+}
+// cyclic pairs served by ghost cells: what a rank does with its neighbours, with itself (mid = the message in the middle of the assembly)
+static void selfHaloExchange(qgd_case_s* c, bool mid) { exchangeOn(c, nullptr, nullptr, (int)c->dev->halo.size(), c->stream(), mid ? 5 : 0); }
 
 int qgd_case_set_fields(qgd_case_t c, const double* U, const double* T, const double* p) {
     QGD_TRY
@@ -2523,49 +2700,6 @@ int qgd_device_release(qgd_device_t d, void* devicePtr) {
     QGD_CATCH
 }
 
-// ---- the halo messages of the QGD case -------------------------------------------------------------------------------------
-// kind 0: the state message, QGD_HALO_CELL_DOUBLES_HOST doubles per cell (RecA, RecB), 12 per boundary face (RecA, RecB, p gradient, lagged rho);
-//         a case with species and QGD_SPECIES_HALO appends nS planes of one double per cell (qgd_species.hip caseSpeciesHaloKernel);
-// kinds 1..4: the implicitDiffusion branch's own (1 grad U, 2 U, 3 search direction, 4 guess: implicitHaloWidth doubles per cell);
-// kind 5: the message between step phases 5 and 6 (see assembleFluxes), 2 doubles per patch face of the slot's boundary-layer cells
-static int caseHaloMove(qgd_case_s* c, int slot, int kind, double* buf, bool pack, hipStream_t stream) {
-    qgd_device_s* d = c->dev;
-    if (slot >= (int)d->halo.size()) return QGD_OK;  // an unsharded mesh has no slots: nothing to exchange
-    const qgd_device_s::HaloSlot& h = d->halo[slot];
-    const int32_t *cells = pack ? h.send : h.ghost, *faces = pack ? h.sendBF : h.ghostBF;
-    const int32_t nCells = pack ? h.nSend : h.nGhost, nFaces = pack ? h.nSendBF : h.nGhostBF;
-    if ((kind == 5 ? nFaces : nCells) == 0) return QGD_OK;
-    if (!buf) return fail(QGD_ERR_INVALID, "null buffer");
-    (void)hipGetLastError();   // a stale error of an earlier, refused call must not be taken for this launch's
-    if (kind == 0) {
-        Launcher L = launcherOf(c);
-        L.pre = nullptr; L.post = nullptr; L.stream = stream;
-        launchHaloPack(L, c->view, c->gas, cells, nCells, faces, nFaces, buf, pack);
-        // the species tail behind the flow's part, which keeps its layout; on the same stream: the patch values follow the cells' Y
-        if (c->spHalo)
-            launchSpeciesHalo(stream, d->view, c->sp, cells, nCells, faces, nFaces,
-                              buf + (size_t)QGD_HALO_CELL_DOUBLES_HOST * (size_t)nCells + 12 * (size_t)nFaces, pack);
-    } else if (kind == 5) launchMidHalo(stream, c->view, faces, nFaces, buf, pack);
-    else launchImplicitHalo(stream, d->view, c->view, c->impl, c->implSolver, kind, cells, nCells, buf, pack);
-    HIP_CHECK(hipGetLastError());
-    return QGD_OK;
-}
-// forCount: kinds 3 and 4 with room for the widest solve (what a caller sizes its buffers by); what is SENT has the width of the solve in flight
-static HaloMessage haloMessage(qgd_case_s* c, int kind, bool forCount = false) {
-    HaloMessage m;
-    if (kind == 0) { m.perCell = QGD_HALO_CELL_DOUBLES_HOST + (c->spHalo ? c->sp.nS : 0); m.perFace = 12; }
-    else if (kind == 5) m.perFace = 2;
-    else m.perCell = (forCount && kind >= 3) ? 3 : implicitHaloWidth(c->implSolver, kind);
-    m.move = [c, kind](int slot, double* buf, bool pack, hipStream_t stream) { return caseHaloMove(c, slot, kind, buf, pack, stream); };
-    return m;
-}
-static HaloBuffers& haloBuffers(qgd_case_s* c) {
-    c->haloBuf.arena = &c->arena;
-    c->haloBuf.widest.perCell = c->implSolver ? 9 : QGD_HALO_CELL_DOUBLES_HOST;   // grad U: 9 per cell; state: 8 per cell and ...
-    if (c->spHalo) c->haloBuf.widest.perCell = std::max(c->haloBuf.widest.perCell, QGD_HALO_CELL_DOUBLES_HOST + (int)c->sp.nS);   // (+ the species' planes)
-    c->haloBuf.widest.perFace = 12;                                               // ... 12 per face
-    return c->haloBuf;
-}
 static int caseHaloCount(qgd_case_s* c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
     *sendCount = *recvCount = 0;
     if (slot >= (int)c->dev->halo.size()) return QGD_OK;
@@ -2704,9 +2838,8 @@ int qgd_qhd_case_create(qgd_device_t d, const qgd_qhd_options* opt, qgd_qhd_case
         q.implicit = opt->implicitDiffusion ? 1 : 0;
         q.upwindU = opt->fluxSchemeU == QGD_FLUX_UPWIND ? 1 : 0;
         q.upwindT = opt->fluxSchemeT == QGD_FLUX_UPWIND ? 1 : 0;
-        static const int kFusedOnOff[] = {0, 1};
         // (off by default: measured at 8 M cells the one launch takes what the three kernels take -- profiles/r06_ab_qhd_fused_advance.txt)
-        if (envChoice("QGD_QHD_FUSED", 0, kFusedOnOff, 2) != 0 && qhdFusedAdvanceEligible(st, v, q, nullptr, nullptr)) c->c4b = a.alloc<double>(4 * nC);
+        if (envOnOff("QGD_QHD_FUSED", 0) != 0 && qhdFusedAdvanceEligible(st, v, q, nullptr, nullptr)) c->c4b = a.alloc<double>(4 * nC);
         if (q.implicit) {
             q.aG = a.alloc<double>(nF); q.diag4 = a.alloc<double>(4 * nC); q.rhs4 = a.alloc<double>(4 * nC); q.x4 = a.alloc<double>(4 * nC);
             c->implSolver = implicitSolverCreate(d->stream, v, d->ownedBegin, d->ownedEnd);
@@ -3136,9 +3269,7 @@ int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int6
     HIP_CHECK(hipStreamSynchronize(d->stream));
     const MeshView& m = d->view;
     std::string s(name);
-    const std::string suffix = ".boundary";
-    bool bnd = false;
-    if (s.size() > suffix.size() && s.compare(s.size() - suffix.size(), suffix.size(), suffix) == 0) { bnd = true; s = s.substr(0, s.size() - suffix.size()); }
+    const bool bnd = boundaryName(s);
     const int64_t n = bnd ? m.nBF : m.nC;
     const QhdView& q = c->view;
     const double* direct = nullptr;
@@ -3379,11 +3510,7 @@ int qgd_scalar_case_get_field(qgd_scalar_case_t c, const char* name, double* out
     } else return fail(QGD_ERR_INVALID, "qgd_scalar_case_get_field: unknown field " + s);
     if (count * nc > outDoubles) return fail(QGD_ERR_INVALID, "output too small");
     if (count == 0) return QGD_OK;
-    if (nc == 1) { d->ws.d2h(out, src, sizeof(double) * (size_t)count, d->stream); return QGD_OK; }
-    double* tmp = d->ws.get<double>(WS_OUT, (size_t)count * nc);
-    launchSoaToAos(d->stream, count, nc, src, tmp);
-    HIP_CHECK(hipGetLastError());
-    d->ws.d2h(out, tmp, sizeof(double) * (size_t)count * nc, d->stream);
+    fetchFaceSoA(d, d->stream, src, count, nc, out);
     return QGD_OK;
     QGD_CATCH
 }
@@ -3412,75 +3539,6 @@ int qgd_scalar_case_sync(qgd_scalar_case_t c) {
     return QGD_OK;
     QGD_CATCH
 }
-
-// ---- native halo transport: RCCL send/recv inside the library -----------------------------------------------------------
-// Replaces, for a C++/MPI host, what the reference does per gradient call with PstreamBuffers
-// [extendedFaceStencilScalarGrad_8C L145-233] and with processor-patch evaluation [GaussVolPointStencil_8C L73]:
-// ONE grouped send/recv pair per neighbouring rank per step, device buffers, stream-ordered, no host synchronisation.
-extern "C++" {
-namespace {
-struct Rccl {
-    void* lib = nullptr;
-    decltype(&ncclGetUniqueId) getUniqueId = nullptr;
-    decltype(&ncclCommInitRank) commInitRank = nullptr;
-    decltype(&ncclCommDestroy) commDestroy = nullptr;
-    decltype(&ncclSend) send = nullptr;
-    decltype(&ncclRecv) recv = nullptr;
-    decltype(&ncclAllReduce) allReduce = nullptr;
-    decltype(&ncclGroupStart) groupStart = nullptr;
-    decltype(&ncclGroupEnd) groupEnd = nullptr;
-    decltype(&ncclGetErrorString) errorString = nullptr;
-    decltype(&ncclCommCount) commCount = nullptr;
-    decltype(&ncclCommUserRank) commUserRank = nullptr;
-    decltype(&ncclCommCuDevice) commCuDevice = nullptr;
-    std::string why;
-};
-Rccl& rcclRef() {
-    static Rccl r;
-    static bool tried = false;
-    if (tried) return r;
-    tried = true;
-    // an RCCL already in the process (e.g. the one torch.distributed brought) is reused; otherwise the ROCm one is loaded
-    const char* env = std::getenv("QGD_RCCL_LIB");
-    const char* names[] = {env, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
-    for (const char* n : names) {
-        if (!n) continue;
-        r.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD);
-        if (r.lib) break;
-    }
-    for (const char* n : names) {
-        if (r.lib) break;
-        if (!n) continue;
-        r.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL);
-    }
-    if (!r.lib) { r.why = "RCCL not found (librccl.so; set QGD_RCCL_LIB)"; return r; }
-    auto sym = [&](const char* name) { void* p = dlsym(r.lib, name); if (!p && r.why.empty()) r.why = std::string("RCCL symbol missing: ") + name; return p; };
-    r.getUniqueId = (decltype(r.getUniqueId))sym("ncclGetUniqueId");
-    r.commInitRank = (decltype(r.commInitRank))sym("ncclCommInitRank");
-    r.commDestroy = (decltype(r.commDestroy))sym("ncclCommDestroy");
-    r.send = (decltype(r.send))sym("ncclSend");
-    r.recv = (decltype(r.recv))sym("ncclRecv");
-    r.allReduce = (decltype(r.allReduce))sym("ncclAllReduce");
-    r.groupStart = (decltype(r.groupStart))sym("ncclGroupStart");
-    r.groupEnd = (decltype(r.groupEnd))sym("ncclGroupEnd");
-    r.errorString = (decltype(r.errorString))sym("ncclGetErrorString");
-    r.commCount = (decltype(r.commCount))sym("ncclCommCount");
-    r.commUserRank = (decltype(r.commUserRank))sym("ncclCommUserRank");
-    r.commCuDevice = (decltype(r.commCuDevice))sym("ncclCommCuDevice");
-    return r;
-}
-}  // namespace
-}  // extern "C++"
-struct qgd_comm_s {
-    ncclComm_t comm = nullptr;
-    int rank = 0, nRanks = 1, deviceId = 0;
-};
-#define RCCL_CHECK(expr)                                                                                          \
-    do {                                                                                                          \
-        ncclResult_t _r = (expr);                                                                                 \
-        if (_r != ncclSuccess)                                                                                    \
-            throw HipError(std::string(#expr) + ": " + (rcclRef().errorString ? rcclRef().errorString(_r) : "RCCL error")); \
-    } while (0)
 
 int qgd_comm_unique_id(void* id128) {
     QGD_TRY
@@ -3530,59 +3588,6 @@ int qgd_comm_info(qgd_comm_t c, int32_t info[3]) {
     QGD_CATCH
 }
 
-// RCCL matches the messages of one peer in issue order, and both sides issue in their own slot order: two slots towards
-// the same rank (two ranks on a periodic cut, two disjoint interfaces with one neighbour) would land in each other's
-// ghost lists.  Refused; a rank exchanging with itself (the one-GPU test of this path) is the one ordered exception.
-// Called by every exchange AND at the top of the sharded step entries, before the first message of a step is issued
-// (the mid-assembly message and the messages inside the implicit solves come before the state message).
-static void checkHaloPeers(const qgd_comm_s* comm, const int32_t* peers, int n) {
-    for (int a = 0; a < n; ++a)
-        for (int b = a + 1; b < n; ++b)
-            if (peers[a] >= 0 && peers[a] == peers[b] && peers[a] != comm->rank)
-                throw std::invalid_argument("halo exchange: rank " + std::to_string(peers[a]) + " is the peer of two halo slots; "
-                                            "one slot per neighbouring rank (qgd_mesh_shard builds them that way)");
-    for (int s = 0; s < n; ++s)
-        if (peers[s] >= comm->nRanks) throw std::invalid_argument("halo exchange: peer rank out of range");
-}
-// THE halo exchange of both case types and every message kind, on `stream`: every slot with a neighbour packs its message into the case's
-// send buffer, the messages travel, every such slot unpacks what arrived.  comm != nullptr: a grouped ncclSend / ncclRecv pair per slot
-// towards peers[slot] (< 0: no neighbour).  comm == nullptr: the cyclic pairs of a periodic device, where slot s takes what its partner
-// slot haloSelf[s] of the same case packed (peers is not read).
-static void exchangeOn(qgd_device_s* d, qgd_comm_s* comm, const int32_t* peers, int nSlots, hipStream_t stream, const HaloMessage& msg,
-                       HaloBuffers& bufs) {
-    const int n = std::min<int>(nSlots, (int)d->halo.size());
-    if (comm) checkHaloPeers(comm, peers, n);
-    bufs.ensure(d);
-    auto move = [&](int s, double* buf, bool pack) {
-        if ((!comm || peers[s] >= 0) && msg.move(s, buf, pack, stream) != QGD_OK) throw std::invalid_argument(g_lastError);
-    };
-    for (int s = 0; s < n; ++s) move(s, bufs.send[s], true);
-    if (comm) {
-        RCCL_CHECK(rcclRef().groupStart());
-        try {
-            for (int s = 0; s < n; ++s) {
-                if (peers[s] < 0) continue;
-                const size_t ns = msg.sendCount(d->halo[s]), nr = msg.recvCount(d->halo[s]);
-                if (ns) RCCL_CHECK(rcclRef().send(bufs.send[s], ns, ncclFloat64, peers[s], comm->comm, stream));
-                if (nr) RCCL_CHECK(rcclRef().recv(bufs.recv[s], nr, ncclFloat64, peers[s], comm->comm, stream));
-            }
-        } catch (...) {
-            (void)rcclRef().groupEnd();   // never leave the group open behind a failed call: the next collective would join it
-            throw;
-        }
-        RCCL_CHECK(rcclRef().groupEnd());
-    } else {
-        for (int s = 0; s < n; ++s)
-            if (d->halo[(size_t)d->haloSelf[s]].nSend != d->halo[s].nGhost || d->halo[(size_t)d->haloSelf[s]].nSendBF != d->halo[s].nGhostBF)
-                throw std::runtime_error("cyclic self-exchange: a slot's ghosts do not match its partner's message");
-    }
-    for (int s = 0; s < n; ++s) move(s, comm ? bufs.recv[s] : bufs.send[(size_t)d->haloSelf[s]], false);
-}
-static void exchangeOn(qgd_case_s* c, qgd_comm_s* comm, const int32_t* peers, int nSlots, hipStream_t stream, int kind) {
-    exchangeOn(c->dev, comm, peers, nSlots, stream, haloMessage(c, kind), haloBuffers(c));
-}
-// cyclic pairs served by ghost cells: what a rank does with its neighbours, with itself (mid = the message in the middle of the assembly)
-static void selfHaloExchange(qgd_case_s* c, bool mid) { exchangeOn(c, nullptr, nullptr, (int)c->dev->halo.size(), c->stream(), mid ? 5 : 0); }
 int qgd_case_halo_exchange(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, int nSlots) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
@@ -3719,12 +3724,7 @@ int qgd_case_get_field(qgd_case_t c, const char* name, double* out, int64_t outD
     const MeshView& m = c->dev->view;
     const GasModel& g = c->gas;
     std::string s(name);
-    bool bnd = false;
-    const std::string suffix = ".boundary";
-    if (s.size() > suffix.size() && s.compare(s.size() - suffix.size(), suffix.size(), suffix) == 0) {
-        bnd = true;
-        s = s.substr(0, s.size() - suffix.size());
-    }
+    const bool bnd = boundaryName(s);
     // face fields from the debug buffer
     static const std::map<std::string, std::pair<int, int>> faceSlots = {
         {"phiJm", {DBG_PHIJM, 1}}, {"phiJmU", {DBG_PHIJMU, 3}}, {"phiP", {DBG_PHIP, 3}}, {"phiPi", {DBG_PHIPI, 3}},
@@ -3758,11 +3758,7 @@ int qgd_case_get_field(qgd_case_t c, const char* name, double* out, int64_t outD
         if (!c->dbgBuf) return fail(QGD_ERR_INVALID, "face fields are materialised by qgd_case_update_fluxes; call it first");
         const int slot = fs->second.first, nc = fs->second.second;
         if ((int64_t)m.nF * nc > outDoubles) return fail(QGD_ERR_INVALID, "output too small");
-        std::vector<double> tmp((size_t)m.nF);
-        for (int k = 0; k < nc; ++k) {
-            HIP_CHECK(hipMemcpy(tmp.data(), c->dbgBuf + (size_t)(slot + k) * m.nF, sizeof(double) * (size_t)m.nF, hipMemcpyDeviceToHost));
-            for (int64_t f = 0; f < m.nF; ++f) out[f * nc + k] = tmp[f];
-        }
+        fetchFaceSoA(c->dev, c->stream(), c->dbgBuf + (size_t)slot * m.nF, m.nF, nc, out);
         return QGD_OK;
     }
     // cell / boundary fields: extracted from the records on the device, one dense copy back
@@ -3936,37 +3932,6 @@ int qgd_case_device_bytes(qgd_case_t c, int64_t* bytes) {
 // ---------------------------------------------------------------------------
 // run monitors (qgd_monitor.hip)
 // ---------------------------------------------------------------------------
-struct qgd_monitor_s {
-    qgd_case_s* c = nullptr;
-    MonitorView view{};
-    DeviceArena arena;
-    double* result = nullptr;    // device: one result block (the copy into a slot follows the fold in stream order)
-    double* host = nullptr;      // pinned: QGD_MONITOR_SLOTS slots of nDoubles + spDoubles: the flow block, the species block behind it
-    int64_t nDoubles = 0;
-    // the species block (qgd_monitor_enable_species; qgd_monitor_species.hip): spDoubles == 0 until it is enabled
-    SpeciesMonitorView spView{};
-    int64_t spDoubles = 0;
-    hipEvent_t ev[QGD_MONITOR_SLOTS] = {};
-    bool sampled[QGD_MONITOR_SLOTS] = {};
-    double time[QGD_MONITOR_SLOTS] = {};
-    int64_t step[QGD_MONITOR_SLOTS] = {};
-};
-// the open monitors of this process: a handle whose case was freed first is no longer among them
-static std::vector<qgd_monitor_s*> g_monitors;
-static bool monitorLive(const qgd_monitor_s* m) { return m && std::find(g_monitors.begin(), g_monitors.end(), m) != g_monitors.end(); }
-static void monitorDestroy(qgd_monitor_s* m) {
-    for (hipEvent_t e : m->ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
-    if (m->host) (void)hipHostFree(m->host);
-    m->arena.release();
-    g_monitors.erase(std::remove(g_monitors.begin(), g_monitors.end(), m), g_monitors.end());
-    delete m;
-}
-static void freeMonitorsOf(qgd_case_s* c) {
-    if (c->monitors.empty()) return;
-    (void)hipStreamSynchronize(c->stream());
-    for (qgd_monitor_s* m : c->monitors) monitorDestroy(m);
-    c->monitors.clear();
-}
 static const char* patchTypeWord(int t) {
     switch (t) {
         case QGD_PATCH_EMPTY: return "empty";

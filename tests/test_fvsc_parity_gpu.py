@@ -181,4 +181,41 @@ def test_device_pointer_qhd_and_species_blocks_match_the_host_entries():
     dev.sync()
     for k, w in dict(phiJmY=1, diffusiveFlux=1, gradYf=3).items():
         assert np.array_equal(dev.to_host(o[k], (nf, w) if w > 1 else (nf,)), want[k]), k
+    # qgd_species_step_dev against the host entry, with the explicit source and without
+    from qgdsolver_amd.qgdfoam import speciesStep
+    rhoOld, rhoNew = 1.0 + 0.1 * rng.random(nc), 1.0 + 0.1 * rng.random(nc)
+    muf, Su = 1e-3 * (1.0 + rng.random(nf)), 1e-2 * rng.standard_normal(nc)
+    for su in (Su, None):
+        dfHost = want["diffusiveFlux"].copy()
+        ynHost = speciesStep(dev, Y, rhoOld, rhoNew, want["phiJmY"], muf, 0.7, 1e-3, dfHost, Su=su)
+        s = {k: dev.to_device(v) for k, v in dict(ro=rhoOld, rn=rhoNew, jmY=want["phiJmY"], mu=muf, df=want["diffusiveFlux"]).items()}
+        s["su"] = dev.to_device(su) if su is not None else None
+        yn = dev.alloc(8 * nc)
+        L.check(L.lib.qgd_species_step_dev(dev._h, vp(d["Y"]), vp(d["Yb"]), vp(s["ro"]), vp(s["rn"]), vp(s["jmY"]), vp(s["mu"]), 0.7, 1e-3,
+                                           vp(s["su"]), vp(s["df"]), vp(yn)), "qgd_species_step_dev")
+        dev.sync()
+        assert not np.array_equal(dfHost, want["diffusiveFlux"]) and np.all(np.isfinite(ynHost))
+        assert np.array_equal(dev.to_host(s["df"], (nf,)), dfHost), ("diffusiveFlux", su is not None)
+        assert np.array_equal(dev.to_host(yn, (nc,)), ynHost), ("Ynew", su is not None)
+    dev.close()
+
+    # one Device's workspace through a sequence of host-pointer entries: a staging slot that aliased a work slot, or a p column left in a
+    # reused slot, would change a repeated call
+    def fluxes(dv, withP):
+        return qhdfoam.updateFluxes(dv, "GaussVolPoint", U, T, rho, tau, 3e-3, (0.0, -9.81, 0.0), p=p if withP else None, phi=phi if withP else None)
+
+    def same_bytes(a, b):
+        return sorted(a) == sorted(b) and all(a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes() for k in a)
+
+    fresh = q.Device(mesh)
+    without_p_first = fluxes(fresh, False)
+    fresh.close()
+    dev = q.Device(mesh)
+    first = fluxes(dev, True)
+    assert sorted(first) == sorted(widths) and same_bytes(first, ref)
+    assert np.array_equal(speciesFlux(dev, "GaussVolPoint", Y, U, phiJm, phi, tau)["gradYf"], want["gradYf"])
+    fvsc.grad(dev, q.volField("U", U[0], U[1]))
+    speciesStep(dev, Y, rhoOld, rhoNew, want["phiJmY"], muf, 0.7, 1e-3, want["diffusiveFlux"].copy())
+    assert same_bytes(fluxes(dev, True), first)
+    assert same_bytes(fluxes(dev, False), without_p_first)
     dev.close()
