@@ -15,10 +15,17 @@
 //   * thin meshes, whose blocks are small, have more blocks than 64-face tiles of internal faces -- the premise of
 //     tests/test_courant_small_blocks_gpu.py: under Courant-number control a block needs a partial slot that is neither a face tile's
 //     nor the patch kernel's.
+// With arguments the program checks meshes it is handed instead of its own: "file capPE minBlocks shardOf" per mesh -- a primitives file written
+// by tests/unstructured.py (tetrahedra, prisms, prisms + hexahedra: vertices of 24 / 12 cells, cells of 4 / 5 faces), the vertex stride
+// wanted (the longest point -> cells row), the least number of blocks, and, when shardOf > 0, "Morton-renumber, cut into shardOf cell
+// ranges, check the middle one".
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <set>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "qgd_mesh.hpp"
@@ -189,7 +196,70 @@ static void checkSmallBlocks(const char* tag, HostMesh& m, bool inletOverwritten
           inletEnd, 256 * (B.nBlocks - faceBlocks));
 }
 
-int main() {
+static HostMesh readPrimitives(const char* path) {
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error(std::string("cannot read ") + path);
+    HostMesh m;
+    int32_t nPatches = 0, nFacePoints = 0;
+    in >> m.nPoints >> m.nFaces >> m.nInternalFaces >> m.nCells >> nPatches >> nFacePoints;
+    auto read = [&](auto& v, size_t n) { v.resize(n); for (auto& x : v) in >> x; };
+    read(m.points, 3 * (size_t)m.nPoints);
+    read(m.faceOffsets, (size_t)m.nFaces + 1);
+    read(m.facePoints, (size_t)nFacePoints);
+    read(m.owner, (size_t)m.nFaces);
+    read(m.neighbour, (size_t)m.nInternalFaces);
+    std::vector<int32_t> start, size, type;
+    read(start, (size_t)nPatches); read(size, (size_t)nPatches); read(type, (size_t)nPatches);
+    if (!in) throw std::runtime_error(std::string("short file ") + path);
+    for (int i = 0; i < nPatches; ++i) {
+        Patch p;
+        p.name = "patch" + std::to_string(i);
+        p.type = type[i]; p.start = start[i]; p.size = size[i];
+        m.patches.push_back(p);
+    }
+    const std::string err = m.check();
+    if (!err.empty()) throw std::runtime_error(std::string(path) + ": " + err);
+    m.computeGeometry();
+    return m;
+}
+
+static int checkFiles(int argc, char** argv) {
+    for (int a = 1; a + 3 < argc; a += 4) {
+        const int wantPE = std::atoi(argv[a + 1]), minBlocks = std::atoi(argv[a + 2]), shardOf = std::atoi(argv[a + 3]);
+        HostMesh m = readPrimitives(argv[a]);
+        std::string tag = argv[a];
+        if (shardOf > 0) {
+            const std::vector<int32_t> order = mortonOrder(m);
+            renumberCells(m, order.data(), nullptr);
+            std::vector<int32_t> cellStart;
+            for (int r = 0; r <= shardOf; ++r) cellStart.push_back((int32_t)((int64_t)m.nCells * r / shardOf));
+            m = extractShard(m, shardOf, cellStart.data(), shardOf / 2);
+            tag += " (Morton order, shard " + std::to_string(shardOf / 2) + " of " + std::to_string(shardOf) + ")";
+            int32_t ghosts = 0;
+            for (uint8_t g : m.cellIsGhost) ghosts += g ? 1 : 0;
+            std::printf("%s: %d ghost cells for %d owned\n", tag.c_str(), ghosts, m.nCells - ghosts);
+            CHECK(ghosts > 0 && ghosts < m.nCells, "%s: %d ghosts of %d cells", tag.c_str(), ghosts, m.nCells);
+        }
+        const FusedBlocks B = checkMesh(tag.c_str(), m);
+        CHECK(B.capPE == wantPE, "%s: capPE %d, %d wanted", tag.c_str(), B.capPE, wantPE);
+        CHECK(B.nBlocks >= minBlocks, "%s: %d blocks, at least %d wanted", tag.c_str(), B.nBlocks, minBlocks);
+        CHECK(B.templateMismatches == 0, "%s: %d template mismatches", tag.c_str(), B.templateMismatches);
+        int32_t minE = 1 << 30, maxE = 0;
+        for (int32_t b = 0; b < B.nBlocks; ++b)
+            for (int32_t j = 0; j < B.hdr[4 * b]; ++j) {
+                const int nE = B.nEntry[(size_t)b * kFusedCells + j];
+                minE = std::min(minE, (int32_t)nE); maxE = std::max(maxE, (int32_t)nE);
+            }
+        std::printf("    face entries per own cell: %d .. %d (stride %d)\n", minE, maxE, B.capE);
+        CHECK(minE >= 4 && minE <= 5 && maxE <= 6, "%s: face entries per cell %d .. %d", tag.c_str(), minE, maxE);
+    }
+    if (fails) { std::printf("%d checks failed\n", fails); return 1; }
+    std::printf("ok\n");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) return checkFiles(argc, argv);
     const double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
     const int32_t pt[6] = {0, 0, 0, 0, 0, 0};
     { HostMesh m = makeBox(16, 8, 8, 0, 8, lo, hi, pt); checkMesh("box 16x8x8 (bricks)", m, 0.0, -1, 8); }

@@ -83,14 +83,31 @@ GPU_CASES = [("box654_jitter", "GaussVolPoint", mixed_bcs), ("box654_tri", "Gaus
              ("plane2d_jitter", "leastSquares", None)]
 
 
+# tetrahedra and prisms (tests/unstructured.py): vertices of 24 / 12 cells -- the vertex walk of the IMPL instantiation beyond its eight register
+# slots -- and matrix rows of four and five off-diagonal entries under the Chebyshev iteration's eight-at-a-time row walk
+UNSTRUCTURED_CASES = [("tet433", "GaussVolPoint", mixed_bcs), ("prism543", "GaussVolPoint", mixed_bcs), ("tet866", "GaussVolPoint", mixed_bcs)]
+DELTA_T = {"tet433": 2e-4, "prism543": 2e-4, "tet866": 2e-4}
+
+
 def _implicit_arms(kind, stencil):
     """3-D GaussVolPoint cases run twice: through the block-fused assembly of the U systems (fusedFaceCellKernel<..., IMPL>: vertex values, QGD
     fluxes, tauMC and the rows of the three systems in one launch) and through the separate kernels; everything else the second way only"""
-    return ["fused", "kernels"] if (stencil == "GaussVolPoint" and kind.startswith("box")) else ["kernels"]
+    mesh = make_mesh(kind)
+    three_d = mesh.nGeometricD == 3
+    mesh.close()
+    return ["fused", "kernels"] if (stencil == "GaussVolPoint" and three_d) else ["kernels"]
+
+
+IMPLICIT_ARMS = [c + (a,) for c in GPU_CASES + UNSTRUCTURED_CASES for a in _implicit_arms(c[0], c[1])]
+
+
+def test_the_implicit_matrix_covers_the_block_fused_assembly():
+    assert [c[0] for c in IMPLICIT_ARMS if c[3] == "fused"] == ["box654_jitter", "box654_tri", "tet433", "prism543", "tet866"]
+    assert sum(1 for c in IMPLICIT_ARMS if c[3] == "kernels") == len(GPU_CASES) + len(UNSTRUCTURED_CASES)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,stencil,bc_fn,arm", [c + (a,) for c in GPU_CASES for a in _implicit_arms(c[0], c[1])])
+@pytest.mark.parametrize("kind,stencil,bc_fn,arm", IMPLICIT_ARMS)
 def test_device_implicit_branch_matches_oracle(kind, stencil, bc_fn, arm):
     mesh = make_mesh(kind)
     C = mesh.array("C").reshape(-1, 3)
@@ -101,7 +118,7 @@ def test_device_implicit_branch_matches_oracle(kind, stencil, bc_fn, arm):
         fields = cases.box_initial_fields(C)
         if mesh.nGeometricD == 2:
             fields[0][:, 2] = 0.0
-    opt = dict(stencil=stencil, deltaT=5e-4, mu=2e-2, implicitDiffusion=1, implicitTol=1e-14, implicitMaxIter=2000)
+    opt = dict(stencil=stencil, deltaT=DELTA_T.get(kind, 5e-4), mu=2e-2, implicitDiffusion=1, implicitTol=1e-14, implicitMaxIter=2000)
 
     def empty_patches(case):
         for ip, t in enumerate(mesh.array("patchType")):
@@ -117,10 +134,16 @@ def test_device_implicit_branch_matches_oracle(kind, stencil, bc_fn, arm):
     setup(gc)
     gc.set_fields(*fields)
     gc.step(12)
+    worst = {}
     for f in ref:
         err = np.abs(gc.field(f) - ref[f]).max() / np.abs(ref[f]).max()
+        worst[f] = float(err)
         assert err <= 1e-10, (kind, stencil, f, err)
     assert gc.info()["minRho"] > 0
+    ii = gc.implicit_info()
+    assert ii["unconverged_steps"] == 0, ii
+    print(f"implicitDiffusion {kind} {stencil} {arm}: worst {max(worst.values()):.3e}; iterations of the last step "
+          f"{ {n: s['iterations'] for n, s in ii['solves'].items()} }")
     # and it is not the explicit branch in disguise
     ex = run_oracle(mesh, setup, fields, 12, **dict(opt, implicitDiffusion=0))
     assert np.abs(ex["U"] - ref["U"]).max() > 1e-6 * np.abs(ref["U"]).max()

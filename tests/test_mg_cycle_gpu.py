@@ -41,6 +41,7 @@ from qgdsolver_amd.synthetic import c5_mesh
 
 import mg_ref
 from test_qhd_case import cavity_bcs, initial, options
+from util import make_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -54,6 +55,7 @@ MESHES = {
     "chain": lambda: q.PolyMesh.box(1024, 1, 1, hi=(1.0, 0.001, 0.001), patch_types=[G, G, E, E, E, E]),   # rows of width <= 2
     "polyhedra": lambda: c5_mesh(16, 8 ** 3, poly=True),
     "plain": lambda: q.PolyMesh.box(20, 14, 9),                                                      # 2520 -> 630 -> 157
+    "tetrahedra": lambda: make_mesh("tet866"),                                                       # 1728 rows of <= 4 entries: 1728 -> 313 -> 22
 }
 # tag: (mesh, knobs, all-Neumann pressure without a reference cell)
 ROWS = {
@@ -78,6 +80,9 @@ ROWS = {
     "double plain": ("plain", {"QGD_MG_SA": "0", "QGD_MG_F32": "0"}, False),
     "double singular deep": ("hex", dict(DEEP, QGD_MG_F32="0"), True),
     "double singular polyhedra": ("polyhedra", {"QGD_MG_F32": "0"}, True),
+    # a graph no box of hexahedra has: four neighbours per cell at most, aggregates grown over 24 cells per vertex (tests/unstructured.py)
+    "tetrahedra": ("tetrahedra", DEEP, False),
+    "double tetrahedra": ("tetrahedra", dict(DEEP, QGD_MG_F32="0"), False),
 }
 FEW_LEVELS = {"singular": 1, "singular ragged": 1, "singular wide": 2, "singular polyhedra": 2, "double singular polyhedra": 2}
 SWEEP_LOOP = {"singular ragged": "ell", "singular polyhedra": "csr", "double singular polyhedra": "csr"}     # else mgCoarseKernel

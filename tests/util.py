@@ -5,6 +5,7 @@ import qgdsolver_amd as q
 from qgdsolver_amd import _lib as L
 
 from oracle import OracleCase, OracleMesh
+import unstructured
 
 
 def rel_err(a, b):
@@ -38,6 +39,10 @@ def make_mesh(kind):
         return q.PolyMesh.forward_step(30, 10, 6, 2, lx=3.0, ly=1.0, lz=0.1)
     if kind == "box_sym":  # symmetryPlane on yMin: constraint patch for leastSquares / GaussVolPoint rules
         return q.PolyMesh.box(6, 5, 1, hi=(1.0, 1.0, 0.1), patch_types=[G, G, L.PATCH_SYMMETRYPLANE, G, E, E])
+    if kind in unstructured.KINDS:  # tetrahedra / prisms / prisms + hexahedra: point valence 24 / 12 / 12, cells of 4 / 5 / 5 + 6 faces
+        a = unstructured.primitives(kind)
+        return q.PolyMesh.from_arrays(a["points"], a["faceOffsets"], a["facePoints"], a["owner"], a["neighbour"], a["nCells"], a["patchStart"],
+                                      a["patchSize"], a["patchType"])
     raise KeyError(kind)
 
 
