@@ -471,6 +471,31 @@ int qgd_qhd_case_fused_info(qgd_qhd_case_t c, int64_t info[4]);
  * {nu, nu, nu, Hi} and are solved as four right-hand sides of one matrix walk. */
 int qgd_qhd_case_implicit_info(qgd_qhd_case_t c, double info[16]);
 
+/* ---- SRFQHDFoam: the QHD case in a single rotating frame ----------------------------------------------------------------------
+ * SRFQHDFoam.C L93-147 is QHDFoam's loop with two differences: the body force carries the Coriolis term,
+ * BdFrc = beta*T*g - 2 (omega ^ Urel) [SRFQHDFoam/updateFields.H L73-74], and QHDTEqn.H is not included -- T stays as read.  The
+ * velocity of the case is the RELATIVE one (the file Urel, createFields.H L22-33).  There is NO centrifugal term, as in the listing:
+ * p is the reduced pressure (it carries the centrifugal potential).  gradWf (updateFields.H L45) is not formed: nothing reads it.
+ *
+ * qgd_qhd_case_set_srf: after qgd_qhd_case_create and before the first qgd_qhd_case_set_fields (later: QGD_ERR_INVALID).  omega in
+ * rad/s.  flags = 0 is SRFQHDFoam's own loop: T, T.boundary are never written by a step, the implicitDiffusion branch solves three
+ * systems (qgd_qhd_case_implicit_info reports 0 iterations for T).  QGD_SRF_SOLVE_T keeps QHDTEqn.H beside the Coriolis force: an
+ * EXTENSION, not the reference's solver.  omega = (0,0,0) with QGD_SRF_SOLVE_T is the plain QHDFoam case, bit for bit.
+ * A rotating or frozen-T case runs the separate kernels whatever QGD_QHD_FUSED says (qgd_qhd_case_fused_info bit 0 reads 0).
+ * Refused: a sharded device (QGD_ERR_NOT_IMPLEMENTED); non-finite omega, a 1-D mesh, a mesh with one empty direction and omega not
+ * parallel to it -- OpenFOAM does not solve the component along an empty direction, the force would be dropped (QGD_ERR_INVALID). */
+#define QGD_SRF_SOLVE_T 1
+int qgd_qhd_case_set_srf(qgd_qhd_case_t c, const double omega[3], int32_t flags);
+/* info[0..2] = omega, [3] = 1 rotating (omega != 0), [4] = 1 T frozen, [5..7] = 0 */
+int qgd_qhd_case_srf_info(qgd_qhd_case_t c, double info[8]);
+/* One velocity per face of a fixedValue patch (3 per face, in the patch's face order) -- what a stationary wall is in the rotating
+ * frame, SRFVelocity with `relative no`: Urel_b = inletValue - omega ^ (Cf - origin).  The contract of qgd_case_set_bc_values: the
+ * patch's U entry must be fixedValue and nFaces the patch's size (else QGD_ERR_INVALID), U = NULL or a later qgd_qhd_case_set_bc of
+ * the patch returns it to its one value, qgd_qhd_case_set_fields follows.  Independent of qgd_qhd_case_set_srf.
+ * These three entries were added without a change of QGD_ABI_VERSION (it stays 9: no struct grew, no existing entry changed its
+ * meaning). */
+int qgd_qhd_case_set_bc_values(qgd_qhd_case_t c, int32_t patch, const double* U, int64_t nFaces);
+
 /* ---- the QHD case on a cell-range shard (qgd_mesh_box slabs, qgd_mesh_shard) ------------------------------------------------
  * What the reference does through processor patches inside fvm::laplacian / PCG / fvc::grad under MPI
  * [QHDpEqn_8H_source.html L35-47, QHDUEqn_8H_source.html L36-84] becomes, per step, with ONE rank per shard:

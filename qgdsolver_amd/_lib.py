@@ -138,6 +138,9 @@ SIGNATURES = {
     "qgd_qhd_case_info": (C.c_int, [handle, c_double_p]),
     "qgd_qhd_case_fused_info": (C.c_int, [handle, C.POINTER(C.c_int64)]),
     "qgd_qhd_case_implicit_info": (C.c_int, [handle, c_double_p]),
+    "qgd_qhd_case_set_srf": (C.c_int, [handle, c_double_p, C.c_int32]),
+    "qgd_qhd_case_srf_info": (C.c_int, [handle, c_double_p]),
+    "qgd_qhd_case_set_bc_values": (C.c_int, [handle, C.c_int32, c_double_p, C.c_int64]),
     "qgd_qhd_case_implicit_control": (C.c_int, [handle, c_double_p, C.c_int]),
     "qgd_qhd_case_implicit_control_ptr": (C.c_int, [handle, handle_p]),
     "qgd_qhd_case_implicit_solve_status": (C.c_int, [handle, c_double_p]),
@@ -261,6 +264,7 @@ ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_SCHEME, ERR_UNKNOWN_NAME, ERR_NOT_IMPLE
 PATCH_GENERIC, PATCH_EMPTY, PATCH_SYMMETRYPLANE, PATCH_SYMMETRY, PATCH_WEDGE, PATCH_CYCLIC, PATCH_HALO = range(7)
 DEVICE_NO_FUSED_TABLES, DEVICE_FUSED_ANY_BLOCKS = 1, 2   # flags of qgd_device_create_with
 BC_ZEROGRADIENT, BC_FIXEDVALUE, BC_SLIP, BC_QGDFLUX, BC_NONE, BC_QHDFLUX = range(6)
+SRF_SOLVE_T = 1   # QGD_SRF_SOLVE_T (qgd_qhd_case_set_srf)
 FVSC_REDUCED, FVSC_LEASTSQUARES, FVSC_GAUSSVOLPOINT = range(3)
 FLUX_LINEAR, FLUX_UPWIND = range(2)
 K_POINT, K_FACE, K_BFACE, K_CELL, K_BC, K_BPOINT, K_VARSC = range(7)

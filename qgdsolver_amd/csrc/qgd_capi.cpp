@@ -2790,6 +2790,7 @@ struct qgd_qhd_case_s {
     HaloBuffers haloBuf;                   // native transport (qgd_qhd_case_halo_exchange, qgd_qhd_case_step_sharded)
     double time = 0, lastIter = 0, lastRes0 = 0, lastRes = 0, lastSolveMs = 0;
     int64_t steps = 0;
+    double* bValUDev = nullptr;            // qgd_qhd_case_set_bc_values: 3 per boundary face (view.bValU while some patch's valList names U)
 };
 
 int qgd_qhd_options_default(qgd_qhd_options* o) {
@@ -2881,6 +2882,12 @@ int qgd_qhd_case_free(qgd_qhd_case_t c) {
     delete c;
     return QGD_OK;
 }
+// QhdView::bValU follows the patches' flags: without a list the kernels read nothing (nullptr) and keep their list-free instantiations
+static void qhdBcValuePointer(qgd_qhd_case_s* c) {
+    int32_t any = 0;
+    for (const PatchBCDev& b : c->bc) any |= b.valList;
+    c->view.bValU = (any & QGD_BC_LIST_U) ? c->bValUDev : nullptr;
+}
 int qgd_qhd_case_set_bc(qgd_qhd_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT, int32_t bcP,
                         double valueP) {
     QGD_TRY
@@ -2895,9 +2902,75 @@ int qgd_qhd_case_set_bc(qgd_qhd_case_t c, int32_t patch, int32_t bcU, const doub
     constraintKinds(b.ptype, bcU, bcT, bcP);   // a constraint patch keeps its own field type whatever the caller asks for
     b.bcU = bcU; b.bcT = bcT; b.bcP = bcP; b.vT = valueT; b.vP = valueP;
     if (valueU) for (int k = 0; k < 3; ++k) b.vU[k] = valueU[k];
+    b.valList = 0;   // the patch is uniform again (qgd_qhd_case_set_bc_values comes after this call)
+    qhdBcValuePointer(c);
     c->fieldsSet = false;
     return QGD_OK;
     QGD_CATCH
+}
+// one velocity per face of a fixedValue patch: the contract of qgd_case_set_bc_values
+int qgd_qhd_case_set_bc_values(qgd_qhd_case_t c, int32_t patch, const double* U, int64_t nFaces) {
+    QGD_TRY
+    const std::string w = "qgd_qhd_case_set_bc_values";
+    if (!c) return fail(QGD_ERR_INVALID, w + ": null case");
+    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, w + ": patch out of range");
+    const Patch& pt = c->dev->patches[patch];
+    if (pt.type != QGD_PATCH_GENERIC)
+        return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a halo, cyclic or constraint patch: its faces carry no fixedValue entry");
+    if (c->bc[patch].bcU != QGD_BC_FIXEDVALUE)
+        return fail(QGD_ERR_INVALID, w + ": the U entry of patch '" + pt.name + "' is not fixedValue (per-face values belong to fixedValue entries only)");
+    if (!U) { c->bc[patch].valList &= ~QGD_BC_LIST_U; qhdBcValuePointer(c); c->fieldsSet = false; return QGD_OK; }
+    if (nFaces != (int64_t)pt.size)
+        return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' has " + std::to_string(pt.size) + " faces on this device's mesh, nFaces = " + std::to_string(nFaces));
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    const MeshView& m = c->dev->view;
+    const size_t nB = (size_t)m.nBF, first = (size_t)(pt.start - m.nIF);
+    if (first + (size_t)pt.size > nB) return fail(QGD_ERR_INVALID, w + ": the patch's faces lie outside the device's boundary faces");
+    for (int64_t i = 0; i < 3 * nFaces; ++i)
+        if (!std::isfinite(U[i])) return fail(QGD_ERR_INVALID, w + ": non-finite value");
+    if (!c->bValUDev) c->bValUDev = c->arena.alloc<double>(3 * std::max<size_t>(nB, 1));   // (zero-filled)
+    if (pt.size > 0) {
+        HIP_CHECK(hipStreamSynchronize(c->dev->stream));   // (no kernel of an earlier step still reads the old values)
+        HIP_CHECK(hipMemcpy(c->bValUDev + 3 * first, U, sizeof(double) * 3 * (size_t)pt.size, hipMemcpyHostToDevice));
+    }
+    c->bc[patch].valList |= QGD_BC_LIST_U;
+    qhdBcValuePointer(c);
+    c->fieldsSet = false;   // like qgd_qhd_case_set_bc: the patch values are evaluated again by qgd_qhd_case_set_fields
+    return QGD_OK;
+    QGD_CATCH
+}
+// SRFQHDFoam: the rotating frame's angular velocity and whether the T equation stays in the loop
+int qgd_qhd_case_set_srf(qgd_qhd_case_t c, const double omega[3], int32_t flags) {
+    QGD_TRY
+    if (!c || !omega) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_srf: null argument");
+    if (c->solver) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_srf: call it after qgd_qhd_case_create and before qgd_qhd_case_set_fields");
+    if (flags & ~QGD_SRF_SOLVE_T) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_srf: unknown flag bits");
+    const qgd_device_s* d = c->dev;
+    if (d->sharded())
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_qhd_case_set_srf: a sharded device is not served (the rotating-frame case runs on one device's whole mesh)");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(omega[k])) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_srf: non-finite omega");
+    const MeshView& v = d->view;
+    if (v.nGeomD < 2) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_srf: a 1-D mesh has no plane for the Coriolis force to act in");
+    if (v.nGeomD == 2)
+        for (int k = 0; k < 3; ++k)
+            if (!v.emptyDir[k] && omega[k] != 0.0)
+                return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_srf: on a mesh with an empty direction omega must be parallel to it (the force's component along "
+                                             "the empty direction is not solved for and would be dropped)");
+    QhdView& q = c->view;
+    for (int k = 0; k < 3; ++k) q.omega[k] = omega[k];
+    q.rotating = (omega[0] != 0.0 || omega[1] != 0.0 || omega[2] != 0.0) ? 1 : 0;
+    q.frozenT = (flags & QGD_SRF_SOLVE_T) ? 0 : 1;
+    if (q.implicit) c->implMask = (c->implMask & 7) | (q.frozenT ? 0 : 8);   // frozen T: its system is not solved
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_qhd_case_srf_info(qgd_qhd_case_t c, double info[8]) {
+    if (!c || !info) return fail(QGD_ERR_INVALID, "qgd_qhd_case_srf_info: null argument");
+    for (int k = 0; k < 8; ++k) info[k] = 0.0;
+    for (int k = 0; k < 3; ++k) info[k] = c->view.omega[k];
+    info[3] = c->view.rotating; info[4] = c->view.frozenT;
+    return QGD_OK;
 }
 int qgd_qhd_case_set_fields(qgd_qhd_case_t c, const double* U, const double* T, const double* p) {
     QGD_TRY
@@ -2983,8 +3056,9 @@ static void qhdPhase(qgd_qhd_case_s* c, int phase) {
                     q.xHave = std::min(q.xHave + 1, q.xOrder);
                 }
                 const double gamma[4] = {c->view.nu, c->view.nu, c->view.nu, c->view.Hi};
-                implicitSolveSetup(c->implSolver, 4, c->implMask, c->view.aG, c->view.diag4, c->view.rhs4, c->view.x4, c->opt.implicitTol,
-                                   c->opt.implicitMaxIter, gamma);
+                // (frozen T, SRFQHDFoam: the three U systems alone -- the first three planes of the component-major vectors)
+                implicitSolveSetup(c->implSolver, c->view.frozenT ? 3 : 4, c->implMask, c->view.aG, c->view.diag4, c->view.rhs4, c->view.x4,
+                                   c->opt.implicitTol, c->opt.implicitMaxIter, gamma);
             }
             break;
         case 10: case 11: case 12: case 13: case 14: case 15:

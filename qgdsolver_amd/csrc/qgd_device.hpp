@@ -426,6 +426,14 @@ struct QhdView {
     double* xd[4]; int xHave, xOrder;
     int32_t tauModel;                          // 0 constTau, 1 HbyUQHD, 2 T0byGr, 3 H2bynuQHD
     double Tau, aQGD, UQHD, T0, Gr;
+    // SRFQHDFoam (qgd_qhd_case_set_srf): the frame's angular velocity; BdFrc = beta*T*g - 2 (omega ^ U) [SRFQHDFoam/updateFields.H L73-74].
+    // No centrifugal term, as in the listing: p is the reduced pressure.  rotating: omega != 0, the launchers take the kernels'
+    // Coriolis instantiations; frozenT: the loop has no QHDTEqn.H [SRFQHDFoam.C L93-147], T and T.boundary are never written by a step
+    double omega[3];
+    int32_t rotating, frozenT;
+    // per-face velocities of fixedValue patches (qgd_qhd_case_set_bc_values), 3 per boundary face; read only on the faces of a patch whose
+    // PatchBCDev::valList has QGD_BC_LIST_U; nullptr = no patch of the case has a list
+    const double* bValU;
 };
 void launchQhdInit(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc, const double* U, const double* T, const double* p,
                    double* tauF, double* taubyrho);

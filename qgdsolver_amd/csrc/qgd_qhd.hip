@@ -8,6 +8,11 @@
 //   QHDTEqn.H L65-91           phiTf, phiTauTReg, fvc::laplacian(Hif, T)               face pass 2 + cell update
 //   QHDFoam.C L123-130         reference level of p
 //
+// SRFQHDFoam (SRFQHDFoam_8C_source.html L93-147; qgd_qhd_case_set_srf) is the same loop in a single rotating frame: the body force is
+// BdFrc = beta*T*g - 2 (omega ^ U) with U the relative velocity [SRFQHDFoam/updateFields.H L73-74], and QHDTEqn.H is not included, T stays
+// as read.  No centrifugal term, as in the listing: p is the reduced pressure.  Both are compile-time modes of the step kernels (QHD_ROT,
+// QHD_FROZEN below); qhdFusedAdvanceKernel knows QHDFoam's loop only.
+//
 // Thermo: rhoConst + constTransport (rho, mu, alpha = mu/Pr uniform; the QHD closures keep muQGD = alphauQGD = 0,
 // T0byGr_8C L62-72), not corrected inside the loop (the listing never calls thermo.correct() there), so tauQGDf and the
 // pressure matrix are those of start-up.  State: cell records {Ux,Uy,Uz,T} (32 B) and p separately (the solver's vector).
@@ -42,9 +47,34 @@ __device__ __forceinline__ void qhdBoundaryVals4(const MeshView& m, const PatchB
     if (perComponent && (bc.ptype == QGD_PATCH_SYMMETRYPLANE || bc.ptype == QGD_PATCH_SYMMETRY)) v.sn[0] = v.sn[1] = v.sn[2] = 0.0;
 }
 
+// Compile-time modes of the step kernels (template parameter MODE).  MODE 0 is QHDFoam as it always was, instruction for instruction; the
+// other instantiations are what qgd_qhd_case_set_srf / qgd_qhd_case_set_bc_values switch on: no uniform branch goes into the bodies.
+//   QHD_ROT     SRFQHDFoam's body force BdFrc = beta*T*g - 2 (omega ^ U) [SRFQHDFoam/updateFields.H L73-74] at all six sites: face passes 1 and
+//               2 (generic walk and LDS tiles), the explicit cell update, the right-hand sides of implicitDiffusion.  Per cell from the OLD U
+//               and T of that cell; internal faces lerpf(w, B_O, B_N); patch faces the same expression on the patch values U_b, T_b (BdFrc is
+//               a calculated field: qgdInterpolate takes its patch value).  No centrifugal term, as in the listing: p is the reduced pressure.
+//               gradWf = fvsc::grad(W) of updateFields.H L45 is not formed: nothing reads it.
+//   QHD_FROZEN  no QHDTEqn.H in the loop [SRFQHDFoam.C L93-147]: T and T.boundary are not written
+//   QHD_LIST    a fixedValue patch may carry one velocity per face (QhdView::bValU)
+enum : int { QHD_ROT = 1, QHD_FROZEN = 2, QHD_LIST = 4 };
+
+// BdFrc of one cell or patch face from its {Ux,Uy,Uz,T}
+__device__ __forceinline__ void qhdBdFrcRot(const QhdView& q, const double* u4, double B[3]) {
+    const double bT = q.beta * u4[3];
+    B[0] = bT * q.g[0] - 2.0 * (q.omega[1] * u4[2] - q.omega[2] * u4[1]);
+    B[1] = bT * q.g[1] - 2.0 * (q.omega[2] * u4[0] - q.omega[0] * u4[2]);
+    B[2] = bT * q.g[2] - 2.0 * (q.omega[0] * u4[1] - q.omega[1] * u4[0]);
+}
+// the velocity a fixedValue patch prescribes on boundary face b: the face's own entry where the patch carries a list
+template <int MODE>
+__device__ __forceinline__ void qhdFixedU(const QhdView& q, const PatchBCDev& bc, const int b, double vU[3]) {
+    if ((MODE & QHD_LIST) && (bc.valList & QGD_BC_LIST_U)) { vU[0] = q.bValU[3 * (size_t)b]; vU[1] = q.bValU[3 * (size_t)b + 1]; vU[2] = q.bValU[3 * (size_t)b + 2]; }
+    else { vU[0] = bc.vU[0]; vU[1] = bc.vU[1]; vU[2] = bc.vU[2]; }
+}
+
 // face pass 1 [updateFields.H L36-73, updateFluxes.H L33-38, QHDTEqn.H L66]
 // (tileList != nullptr: 128 threads per workgroup, the 128-face tiles the staged kernel leaves to this one; else the faces from fBegin on)
-template <int ST>
+template <int ST, int MODE>
 __global__ __launch_bounds__(QGD_BLOCK) void qhdFace1Kernel(const MeshView m, const QhdView q, const PatchBCDev* __restrict__ bcs,
                                                             const int32_t* __restrict__ tileList, const int fBegin) {
     const int f = tileList ? tileList[blockIdx.x] * 128 + (int)threadIdx.x
@@ -71,7 +101,13 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace1Kernel(const MeshView m, co
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         Uf[k] = internal ? lerpf(w, v.o[k], v.n[k]) : v.n[k];
-        Bf[k] = internal ? lerpf(w, (q.beta * v.o[3]) * gv[k], (q.beta * v.n[3]) * gv[k]) : (q.beta * v.n[3]) * gv[k];   // L66-67
+        if (!(MODE & QHD_ROT)) Bf[k] = internal ? lerpf(w, (q.beta * v.o[3]) * gv[k], (q.beta * v.n[3]) * gv[k]) : (q.beta * v.n[3]) * gv[k];   // L66-67
+    }
+    if (MODE & QHD_ROT) {   // SRFQHDFoam/updateFields.H L73-74
+        double Bo[3], Bn[3];
+        qhdBdFrcRot(q, v.o, Bo); qhdBdFrcRot(q, v.n, Bn);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Bf[k] = internal ? lerpf(w, Bo[k], Bn[k]) : Bn[k];
     }
     const double S[3] = {m.Sx[f], m.Sy[f], m.Sz[f]};
     const double tau = q.tauF[f];
@@ -99,8 +135,8 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdPressureBcKernel(const MeshView 
     const PatchBCDev bc = bcs[m.bPatch[b]];
     const double po = q.p[m.own[f]];
     double pb = po, gb = 0.0;
-    // (vU / vT / vP throughout this file: a QHDFoam case has one value per patch and entry; per-face lists, PatchBCDev::valList, belong to
-    // the QGDFoam case, whose set_bc_values is the only entry that raises the flag)
+    // (vT / vP throughout this file: a QHDFoam case has one value per patch for T and p; of PatchBCDev::valList it knows QGD_BC_LIST_U
+    // alone -- qgd_qhd_case_set_bc_values, read through qhdFixedU)
     if (bc.bcP == QGD_BC_FIXEDVALUE) pb = bc.vP;
     else if (bc.bcP == QGD_BC_QGDFLUX) { gb = bc.vP; pb = po + gb / m.dn[f]; }
     else if (bc.bcP == QGD_BC_QHDFLUX) { gb = -(q.phiwo[f] / q.tauF[f] * q.rho0 / m.magSf[f]); pb = po + gb / m.dn[f]; }
@@ -118,7 +154,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdCellGradKernel(const MeshView m,
 }
 
 // face pass 2 [QHDUEqn.H L36-84, QHDTEqn.H L65-91]: the net face terms of the U and T equations
-template <int ST>
+template <int ST, int MODE>
 __global__ __launch_bounds__(QGD_BLOCK) void qhdFace2Kernel(const MeshView m, const QhdView q, const PatchBCDev* __restrict__ bcs,
                                                             const int32_t* __restrict__ tileList, const int fBegin) {
     const int f = tileList ? tileList[blockIdx.x] * 128 + (int)threadIdx.x
@@ -189,11 +225,17 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace2Kernel(const MeshView m, co
     double gP[3];
     faceGradient<ST, 1, -1>(m, f, vp, q.p, q.ptp, gP);                                           // QHDUEqn.H L36
     const double tau = q.tauF[f], phi = q.phi[f];
-    double Uf[3], Wf[3];
+    double Uf[3], Wf[3], Bo[3], Bn[3];
+    if (MODE & QHD_ROT) {   // SRFQHDFoam/updateFields.H L73-74, as in face pass 1
+        const double o4[4] = {Uo[0], Uo[1], Uo[2], To}, n4[4] = {Un[0], Un[1], Un[2], Tn};
+        qhdBdFrcRot(q, o4, Bo); qhdBdFrcRot(q, n4, Bn);
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         Uf[k] = internal ? lerpf(w, Uo[k], Un[k]) : Un[k];
-        const double Bf = internal ? lerpf(w, (q.beta * To) * q.g[k], (q.beta * Tn) * q.g[k]) : (q.beta * Tn) * q.g[k];   // BdFrcf [updateFields.H L66-67], as in face pass 1
+        double Bf;
+        if (MODE & QHD_ROT) Bf = internal ? lerpf(w, Bo[k], Bn[k]) : Bn[k];
+        else Bf = internal ? lerpf(w, (q.beta * To) * q.g[k], (q.beta * Tn) * q.g[k]) : (q.beta * Tn) * q.g[k];   // BdFrcf [updateFields.H L66-67], as in face pass 1
         Wf[k] = tau * ((q.ugu[(size_t)k * nF + f] + gP[k] / q.rho0) - Bf);   // L37
     }
     const double Tf = internal ? lerpf(w, To, Tn) : Tn;
@@ -228,6 +270,7 @@ static_assert(2 * (kQhdFB + kQhdFB / 16) <= 3 * kQhdFB && 3 * (kQhdFB + kQhdFB /
               2 * (((kQhdFB * 23) / 16 + 7) / 8 * 8) <= 3 * kQhdFB && 3 * (((kQhdFB * 23) / 16 + 7) / 8 * 8) <= 5 * kQhdFB, "faceTileCap*");
 
 // face pass 1 on the staged tiles: the internal-face branch of qhdFace1Kernel
+template <int MODE>
 __global__ __launch_bounds__(kQhdFB) void qhdFace1TileKernel(const MeshView m, const QhdView q) {
     constexpr int FB = kQhdFB;
     extern __shared__ v2d qhdLds[];
@@ -279,7 +322,13 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace1TileKernel(const MeshView m, c
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         Uf[k] = lerpf(w, v.o[k], v.n[k]);
-        Bf[k] = lerpf(w, (q.beta * v.o[3]) * gv[k], (q.beta * v.n[3]) * gv[k]);   // L66-67
+        if (!(MODE & QHD_ROT)) Bf[k] = lerpf(w, (q.beta * v.o[3]) * gv[k], (q.beta * v.n[3]) * gv[k]);   // L66-67
+    }
+    if (MODE & QHD_ROT) {   // SRFQHDFoam/updateFields.H L73-74
+        double Bo[3], Bn[3];
+        qhdBdFrcRot(q, v.o, Bo); qhdBdFrcRot(q, v.n, Bn);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Bf[k] = lerpf(w, Bo[k], Bn[k]);
     }
     const size_t nF = (size_t)m.nF;
     const double phiu = S[0] * Uf[0] + S[1] * Uf[1] + S[2] * Uf[2];
@@ -296,6 +345,7 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace1TileKernel(const MeshView m, c
 }
 
 // face pass 2 on the staged tiles: the internal-face branch of qhdFace2Kernel
+template <int MODE>
 __global__ __launch_bounds__(kQhdFB) void qhdFace2TileKernel(const MeshView m, const QhdView q) {
     constexpr int FB = kQhdFB;
     extern __shared__ v2d qhdLds[];
@@ -361,11 +411,14 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace2TileKernel(const MeshView m, c
     if (kind == 2) faceGradient<ST_GVP3, 1, -1>(m, f, vp, q.p, q.ptp, gP);
     else gvp3GradCore<1, -1>(kind, true, l3(sC, lo), l3(sC, ln), l3(sX, v0), l3(sX, v1), l3(sX, v2), l3(sX, v3), vp.o, vp.n, sq + v0, sq + v1, sq + v2,
                              sq + v3, gP);                                                       // QHDUEqn.H L36
-    double Uf[3], Wf[3];
+    double Uf[3], Wf[3], Bo[3], Bn[3];
+    if (MODE & QHD_ROT) { qhdBdFrcRot(q, o4, Bo); qhdBdFrcRot(q, n4, Bn); }   // SRFQHDFoam/updateFields.H L73-74, as in face pass 1
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         Uf[k] = lerpf(w, Uo[k], Un[k]);
-        const double Bf = lerpf(w, (q.beta * To) * q.g[k], (q.beta * Tn) * q.g[k]);   // BdFrcf [updateFields.H L66-67], as in face pass 1
+        double Bf;
+        if (MODE & QHD_ROT) Bf = lerpf(w, Bo[k], Bn[k]);
+        else Bf = lerpf(w, (q.beta * To) * q.g[k], (q.beta * Tn) * q.g[k]);   // BdFrcf [updateFields.H L66-67], as in face pass 1
         Wf[k] = tau * ((ugu[k] + gP[k] / q.rho0) - Bf);   // L37
     }
     const double Tf = lerpf(w, To, Tn);
@@ -382,6 +435,7 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace2TileKernel(const MeshView m, c
 }
 
 // explicit Euler of the U and T equations [QHDUEqn.H L68-84, QHDTEqn.H L83-91]
+template <int MODE>
 __global__ __launch_bounds__(QGD_BLOCK) void qhdCellUpdateKernel(const MeshView m, const QhdView q) {
     const int c = xcdTile((int)gridDim.x, m.xcdRun) * QGD_BLOCK + threadIdx.x;   // runs of consecutive blocks per XCD: neighbours meet in one L2
     if (c >= m.nC) return;
@@ -432,9 +486,17 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdCellUpdateKernel(const MeshView 
     const double rV = 1.0 / m.V[c];
     double* rec = q.c4 + (size_t)c * 4;
     const double T = rec[3];
+    if (MODE & QHD_ROT) {   // BdFrc = beta*T*g - 2 (omega ^ U) of SRFQHDFoam/updateFields.H L73: the three OLD components are read before any is written
+        const double old[4] = {rec[0], rec[1], rec[2], T};
+        double B[3];
+        qhdBdFrcRot(q, old, B);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) rec[k] += q.dt * (-(s[k] * rV) + (q.beta * T) * q.g[k]);   // BdFrc = beta*T*g of updateFields.H L66
-    rec[3] = T + q.dt * (-(s[3] * rV));
+        for (int k = 0; k < 3; ++k) rec[k] = old[k] + q.dt * (-(s[k] * rV) + B[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rec[k] += q.dt * (-(s[k] * rV) + (q.beta * T) * q.g[k]);   // BdFrc = beta*T*g of updateFields.H L66
+    }
+    if (!(MODE & QHD_FROZEN)) rec[3] = T + q.dt * (-(s[3] * rV));
 }
 
 // ---------------------------------------------------------------------------
@@ -719,14 +781,18 @@ void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict
 // basicSymmetry (slip, U only): internal delta*|n_k|, source snGrad_k + delta*|n_k|*patchInternalField_k (transformFvPatchField);
 // zeroGradient: none.  ic[k] / bs[k] for k = Ux, Uy, Uz, T, in units of delta_f (the caller multiplies by gamma_k |Sf|); cur = the
 // owner's current {U, T} (nullptr: coefficients only)
-__device__ __forceinline__ void qhdPatchCoeffs(const MeshView& m, const PatchBCDev& bc, const int f, const double* cur, double ic[4], double bs[4]) {
+template <int MODE>
+__device__ __forceinline__ void qhdPatchCoeffs(const MeshView& m, const QhdView& q, const PatchBCDev& bc, const int f, const double* cur, double ic[4],
+                                               double bs[4]) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) ic[k] = bs[k] = 0.0;
     if (bc.ptype == QGD_PATCH_HALO || bc.ptype == QGD_PATCH_CYCLIC) return;
     const double dc = m.dn[f];
     if (bc.bcU == QGD_BC_FIXEDVALUE) {
+        double vU[3];
+        qhdFixedU<MODE>(q, bc, f - m.nIF, vU);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { ic[k] = dc; bs[k] = dc * bc.vU[k]; }
+        for (int k = 0; k < 3; ++k) { ic[k] = dc; bs[k] = dc * vU[k]; }
     } else if (bc.bcU == QGD_BC_SLIP) {
         double n[3];
         symmNormal(m, bc, f, n);
@@ -766,7 +832,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdImplicitDiagKernel(const MeshVie
         if (f < m.nIF) { inner += g; continue; }
         if (m.fkind[f] == 3) continue;
         double ic[4], bs[4];
-        qhdPatchCoeffs(m, bcs[m.bPatch[f - m.nIF]], f, nullptr, ic, bs);
+        qhdPatchCoeffs<0>(m, q, bcs[m.bPatch[f - m.nIF]], f, nullptr, ic, bs);   // (the coefficients only: they do not depend on the value)
         const double ms = m.magSf[f];
         for (int k = 0; k < 4; ++k) pc[k] += ms * ic[k];
     }
@@ -777,6 +843,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdImplicitDiagKernel(const MeshVie
     }
 }
 // right-hand sides and start values of the four systems: fvm::ddt's source + V (-div(face terms) + BdFrc) + the patch sources
+template <int MODE>
 __global__ __launch_bounds__(QGD_BLOCK) void qhdImplicitRhsKernel(const MeshView m, const QhdView q, const PatchBCDev* __restrict__ bcs) {
     const int c = xcdTile((int)gridDim.x, m.xcdRun) * QGD_BLOCK + threadIdx.x;
     if (c >= m.nC) return;
@@ -836,16 +903,23 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdImplicitRhsKernel(const MeshView
             const int f = it[u] >= 0 ? it[u] : ~it[u];
             if (f >= m.nIF && m.fkind[f] != 3) {
                 double ic[4], bs[4];
-                qhdPatchCoeffs(m, bcs[m.bPatch[f - m.nIF]], f, cur, ic, bs);
+                qhdPatchCoeffs<MODE>(m, q, bcs[m.bPatch[f - m.nIF]], f, cur, ic, bs);
                 const double ms = m.magSf[f];
                 for (int k = 0; k < 4; ++k) src[k] += ((k < 3 ? q.nu : q.Hi) * ms) * bs[k];
             }
         }
     }
     const double V = m.V[c], rV = 1.0 / V, rD = 1.0 / q.dt;
+    if (MODE & QHD_ROT) {
+        double B[3];
+        qhdBdFrcRot(q, cur, B);   // BdFrc = beta*T*g - 2 (omega ^ U) [SRFQHDFoam/updateFields.H L73]
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-        q.rhs4[(size_t)k * nC + c] = (rD * cur[k] * V + V * (-(s[k] * rV) + (q.beta * cur[3]) * q.g[k])) + src[k];   // BdFrc = beta*T*g [updateFields.H L66]
+        for (int k = 0; k < 3; ++k) q.rhs4[(size_t)k * nC + c] = (rD * cur[k] * V + V * (-(s[k] * rV) + B[k])) + src[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            q.rhs4[(size_t)k * nC + c] = (rD * cur[k] * V + V * (-(s[k] * rV) + (q.beta * cur[3]) * q.g[k])) + src[k];   // BdFrc = beta*T*g [updateFields.H L66]
+    }
     q.rhs4[3 * nC + c] = (rD * cur[3] * V + V * (-(s[3] * rV))) + src[3];
 }
 // the solution into the records (components that were not solved keep their values)
@@ -859,6 +933,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdImplicitStoreKernel(const MeshVi
 }
 
 // correctBoundaryConditions of U and T after their solves
+template <int MODE>
 __global__ __launch_bounds__(QGD_BLOCK) void qhdBcKernel(const MeshView m, const QhdView q, const PatchBCDev* __restrict__ bcs) {
     const int b = blockIdx.x * QGD_BLOCK + threadIdx.x;
     if (b >= m.nBF) return;
@@ -868,7 +943,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdBcKernel(const MeshView m, const
     if (bc.ptype == QGD_PATCH_HALO) return;
     const double* o4 = q.c4 + (size_t)m.own[f] * 4;
     double* b4 = q.b4 + (size_t)b * 4;
-    if (bc.bcU == QGD_BC_FIXEDVALUE) { b4[0] = bc.vU[0]; b4[1] = bc.vU[1]; b4[2] = bc.vU[2]; }
+    if (bc.bcU == QGD_BC_FIXEDVALUE) { double vU[3]; qhdFixedU<MODE>(q, bc, b, vU); b4[0] = vU[0]; b4[1] = vU[1]; b4[2] = vU[2]; }
     else if (bc.bcU == QGD_BC_SLIP) {
         double n[3];
         symmNormal(m, bc, f, n);
@@ -879,7 +954,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdBcKernel(const MeshView m, const
             b4[i] = (o4[i] + tv) / 2.0;
         }
     } else { b4[0] = o4[0]; b4[1] = o4[1]; b4[2] = o4[2]; }
-    b4[3] = bc.bcT == QGD_BC_FIXEDVALUE ? bc.vT : o4[3];
+    if (!(MODE & QHD_FROZEN)) b4[3] = bc.bcT == QGD_BC_FIXEDVALUE ? bc.vT : o4[3];
 }
 
 // p += pRefValue - p[pRefCell] when the field needs a reference level [QHDFoam.C L123-130]
@@ -969,23 +1044,39 @@ inline int gridOf(int64_t n) { return (int)((n + QGD_BLOCK - 1) / QGD_BLOCK); }
 // 3-D GaussVolPoint with face tiles of 128 (MeshView::qhdTiles): the staged kernels take the internal faces, the generic ones the
 // tiles beyond the caps and the boundary faces
 inline bool staged(int st, const MeshView& m) { return st == ST_GVP3 && m.qhdTiles != 0 && m.tileOff != nullptr && m.fblock == kQhdFB; }
+// (q.rotating: the same launches with the kernels' Coriolis instantiations, qgd_qhd_case_set_srf)
 template <int ST>
 void face1(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
+    const auto gen = q.rotating ? qhdFace1Kernel<ST, QHD_ROT> : qhdFace1Kernel<ST, 0>;
     if (staged(ST, m)) {
         const size_t lds = ((size_t)m.tileMaxC * 56 + (size_t)m.tileMaxV * 56 + 255) / 256 * 256;
-        qhdFace1TileKernel<<<(m.nIF + kQhdFB - 1) / kQhdFB, kQhdFB, lds, s>>>(m, q);
-        if (m.nTileSpill > 0) qhdFace1Kernel<ST><<<m.nTileSpill, 128, 0, s>>>(m, q, bc, m.tileSpill, 0);
-        if (m.nBF > 0) qhdFace1Kernel<ST><<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
-    } else qhdFace1Kernel<ST><<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, 0);
+        const auto tile = q.rotating ? qhdFace1TileKernel<QHD_ROT> : qhdFace1TileKernel<0>;
+        tile<<<(m.nIF + kQhdFB - 1) / kQhdFB, kQhdFB, lds, s>>>(m, q);
+        if (m.nTileSpill > 0) gen<<<m.nTileSpill, 128, 0, s>>>(m, q, bc, m.tileSpill, 0);
+        if (m.nBF > 0) gen<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
+    } else gen<<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, 0);
 }
 template <int ST>
 void face2(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
+    const auto gen = q.rotating ? qhdFace2Kernel<ST, QHD_ROT> : qhdFace2Kernel<ST, 0>;
     if (staged(ST, m)) {
         const size_t lds = ((size_t)m.tileMaxC * 136 + (size_t)m.tileMaxV * 32 + 255) / 256 * 256;
-        qhdFace2TileKernel<<<(m.nIF + kQhdFB - 1) / kQhdFB, kQhdFB, lds, s>>>(m, q);
-        if (m.nTileSpill > 0) qhdFace2Kernel<ST><<<m.nTileSpill, 128, 0, s>>>(m, q, bc, m.tileSpill, 0);
-        if (m.nBF > 0) qhdFace2Kernel<ST><<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
-    } else qhdFace2Kernel<ST><<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, 0);
+        const auto tile = q.rotating ? qhdFace2TileKernel<QHD_ROT> : qhdFace2TileKernel<0>;
+        tile<<<(m.nIF + kQhdFB - 1) / kQhdFB, kQhdFB, lds, s>>>(m, q);
+        if (m.nTileSpill > 0) gen<<<m.nTileSpill, 128, 0, s>>>(m, q, bc, m.tileSpill, 0);
+        if (m.nBF > 0) gen<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
+    } else gen<<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, 0);
+}
+// correctBoundaryConditions of U and T: the kernel of the case's mode (frozen: a step's call, not createFields')
+void bcValues(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc, const bool frozen) {
+    if (!m.nBF) return;
+    const int g = gridOf(m.nBF);
+    switch ((frozen ? QHD_FROZEN : 0) | (q.bValU ? QHD_LIST : 0)) {
+        case 0: qhdBcKernel<0><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
+        case QHD_FROZEN: qhdBcKernel<QHD_FROZEN><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
+        case QHD_LIST: qhdBcKernel<QHD_LIST><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
+        default: qhdBcKernel<QHD_FROZEN | QHD_LIST><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
+    }
 }
 
 }  // namespace
@@ -995,7 +1086,7 @@ void launchQhdInit(hipStream_t s, const MeshView& m, const QhdView& q, const Pat
     qhdInitKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m.nC, q, U, T, p);
     qhdTauKernel<<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q, tauF, taubyrho);
     if (m.nBF) {
-        qhdBcKernel<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc);
+        bcValues(s, m, q, bc, false);
         qhdPressureBcKernel<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc);
     }
 }
@@ -1066,6 +1157,7 @@ void launchQhdPostSolve(hipStream_t s, const MeshView& m, const QhdView& q, cons
 // {U,T} land in c4new and the caller swaps it with q.c4
 bool qhdFusedAdvanceEligible(int stencil, const MeshView& m, const QhdView& q, int* ldsBytes, int* ldsCell) {
     if (stencil != ST_GVP3 || m.fuBlocks <= 0 || m.fuHdr == nullptr || m.fuHdr2 == nullptr || m.ghost != nullptr || q.implicit || m.nGeomD != 3) return false;
+    if (q.rotating || q.frozenT) return false;   // qhdFusedAdvanceKernel knows QHDFoam's loop only: an SRFQHDFoam case runs the separate kernels
     if (m.fuMaxAll > kQhdFuCapC || m.fuMaxTot > kQhdFuCapTot || m.fuMaxV > kQhdFuCapV || m.fuMaxF > kQhdFuCapF) return false;
     const int cell = 7 * m.fuMaxAll + std::max(9 * m.fuMaxAll, 4 * m.fuMaxF) + m.fuMaxTot + 4 * m.fuMaxV;
     const int lds = 8 * cell + 6 * 128 * 4 + 4 * m.fuCapC;   // records, the own cells' parked face entries, the cell list
@@ -1079,11 +1171,11 @@ bool launchQhdAdvance(hipStream_t s, int stencil, bool usesPoints, const MeshVie
     int lds = 0, ldsCell = 0;
     if (c4new && qhdFusedAdvanceEligible(stencil, m, q, &lds, &ldsCell)) {
         if (m.nBP) boundaryPointKernel<1><<<gridOf(m.nBP), QGD_BLOCK, 0, s>>>(m, q.pb, 1, q.ptp, 1, 0, -1);
-        if (m.nBF > 0) qhdFace2Kernel<ST_GVP3><<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
+        if (m.nBF > 0) qhdFace2Kernel<ST_GVP3, 0><<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
         qhdFusedAdvanceKernel<<<m.fuBlocks, 256, lds, s>>>(m, q, c4new, ldsCell);
         QhdView q2 = q;
         q2.c4 = c4new;
-        if (m.nBF) qhdBcKernel<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q2, bc);
+        bcValues(s, m, q2, bc, false);
         if (needRef) qhdRefReadKernel<<<1, 1, 0, s>>>(q2, localRefCell, refValue, shift);
         return true;
     }
@@ -1097,8 +1189,13 @@ bool launchQhdAdvance(hipStream_t s, int stencil, bool usesPoints, const MeshVie
         case ST_GVP3: face2<ST_GVP3>(s, m, q, bc); break;
         default: face2<ST_GVP2>(s, m, q, bc); break;
     }
-    qhdCellUpdateKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q);
-    if (m.nBF) qhdBcKernel<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc);
+    switch ((q.rotating ? QHD_ROT : 0) | (q.frozenT ? QHD_FROZEN : 0)) {
+        case 0: qhdCellUpdateKernel<0><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
+        case QHD_ROT: qhdCellUpdateKernel<QHD_ROT><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
+        case QHD_FROZEN: qhdCellUpdateKernel<QHD_FROZEN><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
+        default: qhdCellUpdateKernel<QHD_ROT | QHD_FROZEN><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
+    }
+    bcValues(s, m, q, bc, q.frozenT != 0);
     if (needRef) qhdRefReadKernel<<<1, 1, 0, s>>>(q, localRefCell, refValue, shift);
     return false;
 }
@@ -1119,10 +1216,15 @@ void launchQhdImplicitAdvance(hipStream_t s, int stencil, bool usesPoints, const
             case ST_GVP3: face2<ST_GVP3>(s, m, q, bc); break;
             default: face2<ST_GVP2>(s, m, q, bc); break;
         }
-        qhdImplicitRhsKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc);
+        switch ((q.rotating ? QHD_ROT : 0) | (q.bValU ? QHD_LIST : 0)) {
+            case 0: qhdImplicitRhsKernel<0><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
+            case QHD_ROT: qhdImplicitRhsKernel<QHD_ROT><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
+            case QHD_LIST: qhdImplicitRhsKernel<QHD_LIST><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
+            default: qhdImplicitRhsKernel<QHD_ROT | QHD_LIST><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
+        }
     } else {
-        qhdImplicitStoreKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, validMask);
-        if (m.nBF) qhdBcKernel<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc);
+        qhdImplicitStoreKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, validMask);   // (frozen T: the caller's mask leaves T out)
+        bcValues(s, m, q, bc, q.frozenT != 0);
         if (needRef) qhdRefReadKernel<<<1, 1, 0, s>>>(q, localRefCell, refValue, shift);
     }
 }

@@ -1038,8 +1038,9 @@ def _bc_p_qhd(rec, what):
     raise FoamFileError(f"{what}: boundary condition '{t}' is not supported")
 
 
-def read_qhd_case_setup(case_dir, time="0"):
+def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
     """Read an OpenFOAM QHDFoam case directory [QHDFoam.C L63-72, QHDFoam/createFields.H L32-167].
+    (velocity / velocity_bc: the name of the velocity file and the reading of its patch entries, for read_srf_case_setup.)
 
     Returns (mesh, options dict for ``qhdfoam.qhd_options``, {'U','T','p'} internal arrays, per-patch BC triples).
     Entries read: constant/polyMesh; constant/thermophysicalProperties -- thermoType (equationOfState rhoConst, transport const),
@@ -1131,15 +1132,18 @@ def read_qhd_case_setup(case_dir, time="0"):
         if tols and opt["implicitDiffusion"]:
             opt["implicitTol"] = min(tols)
             opt["implicitMaxIter"] = max(iters)
-    U, bU = read_field(os.path.join(tdir, "U"), mesh)
+    if not _exists(os.path.join(tdir, velocity)):
+        raise FoamFileError(f"{tdir}: the velocity file '{velocity}' is missing")
+    U, bU = read_field(os.path.join(tdir, velocity), mesh)
     T, bT = read_field(os.path.join(tdir, "T"), mesh)
     p, bP = read_field(os.path.join(tdir, "p"), mesh)
     ptw = [PATCH_WORDS.get(int(t), "patch") for t in mesh.array("patchType")]
     bcs = []
     for i, name in enumerate(mesh.patch_names):
-        bu, bt = _bc(bU[name], True, ptw[i], f"U.{name}"), _bc(bT[name], False, ptw[i], f"T.{name}")
+        bu = (velocity_bc or _bc)(bU[name], True, ptw[i], f"{velocity}.{name}")
+        bt = _bc(bT[name], False, ptw[i], f"T.{name}")
         if bu[0] == "qgdFlux" or bt[0] in ("qgdFlux", "slip"):
-            raise FoamFileError(f"patch {name}: boundary condition not supported for U / T of a QHDFoam case")
+            raise FoamFileError(f"patch {name}: boundary condition not supported for {velocity} / T of a QHDFoam case")
         bcs.append({"U": bu, "T": bt, "p": _bc_p_qhd(bP[name], f"p.{name}")})
     return mesh, opt, {"U": U, "T": T[:, 0], "p": p[:, 0]}, bcs
 
@@ -1277,9 +1281,126 @@ def load_qhd_case(case_dir, time="0", device_id=0):
     return dev, case
 
 
-def write_qhd_time(case, case_dir, time_name, bcs=None):
+def read_srf_case_setup(case_dir, time="0"):
+    """Read an OpenFOAM SRFQHDFoam case directory [SRFQHDFoam.C L70-81, SRFQHDFoam/createFields.H L22-39]: what read_qhd_case_setup reads,
+    with the relative velocity ``Urel`` in place of ``U``, and constant/SRFProperties.
+
+    Returns (mesh, options dict, {'U' (= Urel),'T','p'}, per-patch BC triples, srf) with srf = {'omega', 'origin', 'axis', 'rpm'}.
+    SRFProperties: ``SRFModel rpm; origin (x y z); axis (x y z); rpmCoeffs { rpm N; }`` and omega = axis/|axis| * rpm * 2 pi / 60.
+    ASSUMPTION (L0): a restatement of OpenFOAM v2312's SRF::SRFModel (origin, axis normalised on reading) and SRF::rpm
+    (omega = axis * rpm * twoPi / 60); their sources are not among the reference's listings.
+    Patch entries of Urel: what QHDFoam's U takes, a fixedValue entry also as a value list, and ``SRFVelocity`` (OpenFOAM v2312
+    SRFVelocityFvPatchVectorField::updateCoeffs, L0): ``relative yes`` is fixedValue inletValue; ``relative no`` (a wall at rest in the
+    inertial frame) is one value per face, inletValue - omega ^ (Cf - origin), returned as an (nFaces, 3) array for
+    QHDFoamCase.set_bc_values.  Refused by name: any other SRFModel, SRFFreestreamVelocity, a missing Urel, a non-uniform inletValue."""
+    sp_path = os.path.join(case_dir, "constant", "SRFProperties")
+    if not _exists(sp_path):
+        raise FoamFileError(f"{sp_path}: SRFQHDFoam needs constant/SRFProperties")
+    sp = read_dict(sp_path)
+    model = str(sp.get("SRFModel", ""))
+    if model != "rpm":
+        raise FoamFileError(f"{sp_path}: SRFModel '{model}' is not supported (only rpm)")
+
+    def vec(key):
+        try:
+            v = np.asarray(sp[key], dtype=np.float64).reshape(-1)
+        except (KeyError, TypeError, ValueError):
+            v = np.zeros(0)
+        if v.size != 3 or not np.isfinite(v).all():
+            raise FoamFileError(f"{sp_path}: entry '{key}' must be a vector")
+        return v
+
+    origin, axis = vec("origin"), vec("axis")
+    if not np.linalg.norm(axis) > 0:
+        raise FoamFileError(f"{sp_path}: axis must not vanish")
+    coeffs = sp.get("rpmCoeffs", sp)
+    if not isinstance(coeffs, dict) or "rpm" not in coeffs:
+        raise FoamFileError(f"{sp_path}: rpmCoeffs.rpm is missing")
+    rpm = float(coeffs["rpm"])
+    omega = axis / np.linalg.norm(axis) * (rpm * 2.0 * np.pi / 60.0)
+    tdir = os.path.join(case_dir, str(time))
+    if not _exists(os.path.join(tdir, "Urel")):
+        raise FoamFileError(f"{tdir}: SRFQHDFoam reads the relative velocity from the file Urel [SRFQHDFoam/createFields.H L22-33]; there is none"
+                            + (" (the directory has a file U: rename it, and give the walls at rest the type SRFVelocity)"
+                               if _exists(os.path.join(tdir, "U")) else ""))
+    # (the patch geometry before the fields: the reading of a `relative no` entry needs the face centres)
+    geo = read_polymesh(os.path.join(case_dir, "constant", "polyMesh"))
+    names, Cf = list(geo.patch_names), geo.array("Cf").reshape(-1, 3)
+    start, size = [int(x) for x in geo.array("patchStart")], [int(x) for x in geo.array("patchSize")]
+
+    def urel_bc(rec, vector, patch_type_word, what):
+        t = rec["type"]
+        if t == "SRFFreestreamVelocity":
+            raise FoamFileError(f"{what}: boundary condition 'SRFFreestreamVelocity' is not supported")
+        if t != "SRFVelocity":
+            return _bc(rec, vector, patch_type_word, what, lists=True)
+        if patch_type_word in _CONSTRAINT_BCS:
+            raise FoamFileError(f"{what}: inconsistent patch and patchField types: the patch is '{patch_type_word}', the field says '{t}'")
+        if "inletValue" not in rec or "relative" not in rec:
+            raise FoamFileError(f"{what}: SRFVelocity needs the entries relative and inletValue")
+        iv = rec["inletValue"]
+        if not (isinstance(iv, list) and len(iv) == 2 and iv[0] == "uniform"):
+            raise FoamFileError(f"{what}: only a uniform inletValue is supported")
+        iv = np.asarray(iv[1], dtype=np.float64).reshape(-1)
+        if iv.size != 3:
+            raise FoamFileError(f"{what}: inletValue must be a vector")
+        if _truthy(rec["relative"]):
+            return ("fixedValue", iv)
+        i = names.index(what.split(".", 1)[1])
+        return ("fixedValue", iv[None, :] - np.cross(omega, Cf[start[i]: start[i] + size[i]] - origin))
+
+    mesh, opt, fields, bcs = read_qhd_case_setup(case_dir, time, velocity="Urel", velocity_bc=urel_bc)
+    return mesh, opt, fields, bcs, dict(omega=omega, origin=origin, axis=axis / np.linalg.norm(axis), rpm=rpm)
+
+
+def apply_qhd_bcs(case, bcs):
+    """the per-patch triples of read_qhd_case_setup / read_srf_case_setup onto a QHDFoamCase: a velocity given per face goes through
+    set_bc_values, after the patch's entry"""
+    for i, bc in enumerate(bcs):
+        u = bc["U"]
+        per_face = u[0] == "fixedValue" and np.ndim(u[1]) == 2
+        case.set_bc(i, U=("fixedValue", (0.0, 0.0, 0.0)) if per_face else u, T=bc["T"], p=bc["p"])
+        if per_face:
+            case.set_bc_values(i, u[1])
+
+
+def load_srf_case(case_dir, time="0", device_id=0, solve_T=False):
+    """Case directory -> (Device, QHDFoamCase in the rotating frame, srf) ready to ``step()``: SRFQHDFoam's createFields.H over the C-ABI"""
+    from .fvsc import Device
+    from .qhdfoam import QHDFoamCase, qhd_options
+
+    mesh, opt, fields, bcs, srf = read_srf_case_setup(case_dir, time)
+    dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}})
+    case = QHDFoamCase(dev, qhd_options(**opt))
+    case.set_srf(srf["omega"], solve_T=solve_T)
+    apply_qhd_bcs(case, bcs)
+    case.set_fields(fields["U"], fields["T"], fields["p"])
+    return dev, case, srf
+
+
+def write_srf_time(case, case_dir, time_name, srf, bcs=None):
+    """Urel, p, T (as read, unless the case solves it) and Uabs = Urel + omega ^ (C - origin) of a rotating QHDFoamCase into
+    <case_dir>/<time_name>/.  A patch whose velocity is given per face (SRFVelocity with `relative no`) is written as the fixedValue
+    list it evaluates to, which read_srf_case_setup reads back bit for bit; Uabs carries calculated patch values."""
+    mesh = case.mesh
+    write_qhd_time(case, case_dir, time_name, bcs, velocity="Urel")
+    omega, origin = np.asarray(srf["omega"], dtype=np.float64), np.asarray(srf["origin"], dtype=np.float64)
+    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
+    ps, pz, pt = mesh.array("patchStart"), mesh.array("patchSize"), mesh.array("patchType")
+    nIF = mesh.nInternalFaces
+    Uabs = case.field("U") + np.cross(omega, mesh.array("C").reshape(-1, 3) - origin)
+    Ub = case.field("U.boundary") + np.cross(omega, mesh.array("Cf").reshape(-1, 3)[nIF:] - origin)
+    patches = {}
+    for i, pn in enumerate(names):
+        word = PATCH_WORDS.get(int(pt[i]), "patch")
+        b0 = int(ps[i]) - nIF
+        patches[pn] = (word, None) if word in _CONSTRAINT_BCS else ("calculated", Ub[b0:b0 + int(pz[i])])
+    write_field(os.path.join(case_dir, str(time_name), "Uabs"), mesh, "Uabs", Uabs, patches, "[0 1 -1 0 0 0 0]")
+
+
+def write_qhd_time(case, case_dir, time_name, bcs=None, velocity="U"):
     """U, T, p of a QHDFoamCase into <case_dir>/<time_name>/ (the AUTO_WRITE fields of QHDFoam that this path carries); patch
-    entries carry the patch values as ``value`` (fixedGradient patches also their ``gradient``)."""
+    entries carry the patch values as ``value`` (fixedGradient patches also their ``gradient``).  velocity: the name of U's file."""
     mesh = case.mesh
     if hasattr(mesh, "file_mesh"):
         raise FoamFileError("write_time: a case with cyclic patches carries copies of its cells; python -m qgdsolver_amd.QGDFoam writes its time directories")
@@ -1305,7 +1426,8 @@ def write_qhd_time(case, case_dir, time_name, bcs=None):
                     extra = {"gradient": float(bcs[i][fname][1] or 0.0)}
             b0 = int(ps[i]) - nIF
             patches[pn] = (kind, bvals[b0:b0 + int(pz[i])]) if extra is None else (kind, bvals[b0:b0 + int(pz[i])], extra)
-        write_field(os.path.join(case_dir, str(time_name), fname), mesh, fname, internal, patches, dims[fname])
+        out_name = velocity if fname == "U" else fname
+        write_field(os.path.join(case_dir, str(time_name), out_name), mesh, out_name, internal, patches, dims[fname])
 
 
 def _patch_values(mesh, internal, patches, what):

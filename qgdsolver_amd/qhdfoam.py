@@ -186,6 +186,29 @@ class QHDFoamCase:
         L.check(L.lib.qgd_qhd_case_set_bc(self._h, int(patch), _BC[U[0]], vu.ctypes.data_as(L.c_double_p), _BC[T[0]], float(T[1] or 0.0),
                                           _BC[p[0]], float(p[1] or 0.0)), "qgd_qhd_case_set_bc")
 
+    def set_bc_values(self, patch, U):
+        """one velocity per face of a fixedValue patch (qgd_qhd_case_set_bc_values): (nFaces, 3) in the patch's face order; None returns
+        the patch to its one value.  set_fields follows, as after set_bc."""
+        if U is None:
+            L.check(L.lib.qgd_qhd_case_set_bc_values(self._h, int(patch), None, 0), "qgd_qhd_case_set_bc_values")
+            return
+        a = np.ascontiguousarray(U, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("set_bc_values: U must have shape (nFaces, 3)")
+        L.check(L.lib.qgd_qhd_case_set_bc_values(self._h, int(patch), a.ctypes.data_as(L.c_double_p), int(a.shape[0])), "qgd_qhd_case_set_bc_values")
+
+    # ---- SRFQHDFoam: the case in a single rotating frame (include/qgd_amd.h) ----
+    def set_srf(self, omega, solve_T=False):
+        """angular velocity of the frame (rad/s): BdFrc = beta*T*g - 2 (omega ^ U), U the relative velocity; T stays as read unless
+        solve_T (an extension: the reference's loop has no T equation).  After the constructor, before the first set_fields."""
+        w = np.ascontiguousarray(omega, dtype=np.float64).reshape(3)
+        L.check(L.lib.qgd_qhd_case_set_srf(self._h, w.ctypes.data_as(L.c_double_p), L.SRF_SOLVE_T if solve_T else 0), "qgd_qhd_case_set_srf")
+
+    def srf_info(self):
+        a = (C.c_double * 8)()
+        L.check(L.lib.qgd_qhd_case_srf_info(self._h, a), "qgd_qhd_case_srf_info")
+        return dict(omega=np.array(a[0:3]), rotating=bool(a[3]), frozenT=bool(a[4]))
+
     def set_fields(self, U, T, p):
         a = [np.ascontiguousarray(x, dtype=np.float64) for x in (U, T, p)]
         assert a[0].size == 3 * self.mesh.nCells and a[1].size == self.mesh.nCells and a[2].size == self.mesh.nCells

@@ -3,11 +3,13 @@
 
     python scripts/kernel_resources.py > profiles/kernel_resources.txt
         compiles qgdsolver_amd/csrc into a temporary directory with -Rpass-analysis=kernel-resource-usage and prints the table.
-    python scripts/kernel_resources.py --compare OLD.so NEW.so [--mnemonics]
+    python scripts/kernel_resources.py --compare OLD.so NEW.so [--mnemonics] [--gained-parameter]
         disassembles the gfx950 code objects of two builds of the library kernel by kernel: lists the kernels only one of them has and
         those whose instructions differ (encodings and operands; with --mnemonics the sequence of mnemonics only, for a change that
         moves kernel-argument offsets).  Exit status 1 when a common kernel differs.  How a refactor shows that it left the device
-        code alone.
+        code alone.  --gained-parameter: a kernel of OLD that NEW only has with one more, trailing template argument is compared with
+        the instantiation whose new argument is 0 (`k<3>` with `k<3, 0>`, `k` with `k<0>`): a compile-time flag was added and 0 is the
+        code as it was.
 
 No GPU needed.  ROCM_PATH (default /opt/rocm) locates hipcc and the LLVM tools."""
 import os
@@ -96,14 +98,39 @@ def kernel_disassembly(lib, mnemonics):
                     cur = kernels.setdefault(m.group(1), []) if m.group(1) in funcs else None
                 elif cur is not None and line.startswith("\t"):
                     ins, _, enc = line.strip().partition("//")
+                    if ins.strip() == "...":   # objdump's mark for zero bytes behind the last instruction (alignment of the next symbol)
+                        continue
                     # (the address in front of the encoding goes: a kernel may move inside its code object)
                     cur.append(ins.split()[0] if mnemonics else ins.strip() + " |" + enc.partition(":")[2])
     return kernels
 
 
-def compare(old, new, mnemonics):
+def as_before_the_flag(name):
+    """demangled `k<3, 0>(...)` -> `k<3>(...)`, `k<0>(...)` -> `k(...)` (an instantiated kernel template prints its return type)"""
+    m = re.search(r"<([^<>]*)>\(", name)   # the first `<...>(`: the kernel's own arguments, in front of its parameter list
+    if not m:
+        return None
+    args = m.group(1).split(", ")
+    if args[-1] != "0":
+        return None
+    head = re.sub(r"^void ", "", name[:m.start()]) + (f"<{', '.join(args[:-1])}>" if len(args) > 1 else "")
+    return head + name[m.end() - 1:]
+
+
+def compare(old, new, mnemonics, gained=False):
     a, b = kernel_disassembly(old, mnemonics), kernel_disassembly(new, mnemonics)
     names = demangle(sorted(set(a) | set(b)))
+    if gained:
+        plain = {re.sub(r"^void ", "", names[k]): k for k in set(a) - set(b)}
+        moved = {}
+        for k in set(b) - set(a):
+            was = as_before_the_flag(names[k])
+            if was in plain:
+                moved[k] = plain[was]
+        print(f"kernels of {old} found in {new} with a trailing template argument 0: {len(moved)}")
+        for k, ko in sorted(moved.items(), key=lambda kv: names[kv[0]]):
+            print("   ", names[ko], "->", names[k])
+            b[ko] = b.pop(k)
     for title, only in (("only in " + old, set(a) - set(b)), ("only in " + new, set(b) - set(a))):
         print(f"{title}: {len(only)}")
         for k in sorted(only, key=names.get):
@@ -118,5 +145,5 @@ def compare(old, new, mnemonics):
 
 if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "--compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3], "--mnemonics" in sys.argv[4:]))
+        sys.exit(compare(sys.argv[2], sys.argv[3], "--mnemonics" in sys.argv[4:], "--gained-parameter" in sys.argv[4:]))
     resource_table()
