@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <functional>
 
+#include "qgd_fused_caps.hpp"
+
 namespace qgd {
 
 // ---- gathered records (AoS, 16-B aligned so they move as dwordx4) ----------

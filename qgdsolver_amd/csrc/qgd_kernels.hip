@@ -606,7 +606,6 @@ void faceFluxGvp3Kernel(const MeshView m, const CaseView c, const GasModel gm, c
 // operation order, bit-identical fluxes.
 // ---------------------------------------------------------------------------
 typedef double v2d __attribute__((ext_vector_type(2)));   // one 16-B piece
-constexpr int kFusedCapCDev = 320, kFusedCapVDev = 256, kFusedCapFDev = 512, kFusedCapTotDev = 384;   // = kFusedCap{C,V,F,Tot} of qgd_setup.hpp
 // FIXED: the tile lists at a fixed stride (MeshView::tileCellsFix / tileVertsFix: every tile's list padded to the longest one by
 // repeating its last label, tileFlag = 1 for the tiles left to the gather kernel).  A tile's life is a chain of dependent memory
 // round trips -- list offsets -> labels -> pieces -> LDS -> algebra -- and with 6 workgroups per CU in flight the kernel's rate is
@@ -1127,11 +1126,11 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     __shared__ v2d sMon[9];
     __builtin_amdgcn_s_setprio(3);
     constexpr int NT = 256, KC = 5, KCC = 4, KB2 = 3, KV = 3, KF = 2, KE = 6, KP = 8, KG = 12;
-    static_assert(9 * kFusedCapCDev <= KG * NT, "caps");
+    static_assert(9 * kFusedCapC <= KG * NT, "caps");
     // piece loads per thread: RecA of <= 384 staged cells, centres and RecB of the <= 320 own + across-a-face cells, coordinates of <= 256
     // vertices; faces per thread; face entries of a cell / cells of a vertex held in registers
-    static_assert(3 * kFusedCapTotDev <= KC * NT && 3 * kFusedCapCDev <= KCC * NT && 2 * kFusedCapCDev <= KB2 * NT && 3 * kFusedCapVDev <= KV * NT &&
-                  kFusedCapFDev <= KF * NT && kFusedCapVDev <= NT, "caps");
+    static_assert(3 * kFusedCapTot <= KC * NT && 3 * kFusedCapC <= KCC * NT && 2 * kFusedCapC <= KB2 * NT && 3 * kFusedCapV <= KV * NT &&
+                  kFusedCapF <= KF * NT && kFusedCapV <= NT, "caps");
     // (the launcher has divided for the XCD order: a run that is a power of two costs shifts here, not two divisions in front of the first load)
     const int blk = firstBlock + xcdTileHost((int)gridDim.x, m.fuXcdRun, xcdFull, xcdShift);
     const int tid = (int)threadIdx.x;

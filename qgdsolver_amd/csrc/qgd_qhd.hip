@@ -11,7 +11,13 @@
 // SRFQHDFoam (SRFQHDFoam_8C_source.html L93-147; qgd_qhd_case_set_srf) is the same loop in a single rotating frame: the body force is
 // BdFrc = beta*T*g - 2 (omega ^ U) with U the relative velocity [SRFQHDFoam/updateFields.H L73-74], and QHDTEqn.H is not included, T stays
 // as read.  No centrifugal term, as in the listing: p is the reduced pressure.  Both are compile-time modes of the step kernels (QHD_ROT,
-// QHD_FROZEN below); qhdFusedAdvanceKernel knows QHDFoam's loop only.
+// QHD_FROZEN below).
+//
+// The formulas the kernels share are __device__ __forceinline__ functions: QhdBdFrc (the body force of either solver), qhdWf, qhdFaceTermU
+// and qhdFaceTermT (face pass 2, one component per call: the generic walk, the LDS tiles and the block-fused advance each keep the
+// component loops around them), qhdEulerCell, qhdReflected, qhdExtrapolated.  Face pass 1 is written out in its two kernels, as it was:
+// every shared form of it that was tried cost qhdFace1Kernel<ST_GVP2, QHD_ROT> a wave per SIMD or changed the last bits of phiwo
+// (profiles/qhd_shared_face_terms.txt).  qhdFusedAdvanceKernel is launched for QHDFoam's loop only (qhdFusedAdvanceEligible): MODE 0.
 //
 // Thermo: rhoConst + constTransport (rho, mu, alpha = mu/Pr uniform; the QHD closures keep muQGD = alphauQGD = 0,
 // T0byGr_8C L62-72), not corrected inside the loop (the listing never calls thermo.correct() there), so tauQGDf and the
@@ -20,9 +26,28 @@
 #include "qgd_device.hpp"
 #include "qgd_stencil_dev.hpp"
 
+#include <type_traits>
+
 namespace qgd {
 
 namespace {
+
+// component i of (I - 2 n n) . u: the velocity mirrored at a symmetry plane (basicSymmetry's transform, L0)
+__device__ __forceinline__ double qhdReflected(const double n[3], const double* u, const int i) {
+    return ((i == 0 ? 1.0 : 0.0) - 2.0 * (n[i] * n[0])) * u[0] + ((i == 1 ? 1.0 : 0.0) - 2.0 * (n[i] * n[1])) * u[1] +
+           ((i == 2 ? 1.0 : 0.0) - 2.0 * (n[i] * n[2])) * u[2];
+}
+// cur + the increment of the polynomial in time through the last k + 1 values (v[0..]: one, two, ... steps back; k = 1..4: linear
+// 2 x^n - x^(n-1), quadratic, cubic, quartic -- sum_j (-1)^j C(k+1, j+1) x^(n-j)), limited to twice the last increment
+__device__ __forceinline__ double qhdExtrapolated(const double cur, const double v[4], const int k) {
+    const double d0 = cur - v[0];
+    double e = d0;                                                                             // 2 x^n - x^(n-1)
+    if (k == 2) e = (2.0 * cur - 3.0 * v[0]) + v[1];                                           // 3, -3, 1
+    else if (k == 3) e = ((3.0 * cur - 6.0 * v[0]) + 4.0 * v[1]) - v[2];                       // 4, -6, 4, -1
+    else if (k >= 4) e = (((4.0 * cur - 10.0 * v[0]) + 10.0 * v[1]) - 5.0 * v[2]) + v[3];      // 5, -10, 10, -5, 1
+    const double lim = 2.0 * fabs(d0);
+    return cur + fmin(fmax(e, -lim), lim);
+}
 
 // patch snGrad of {U,T} (4 components) on boundary face f: fvPatchField::snGrad = deltaCoeffs*(value - internal) (L0);
 // basicSymmetry::snGrad for slip
@@ -37,33 +62,86 @@ __device__ __forceinline__ void qhdBoundaryVals4(const MeshView& m, const PatchB
         double n[3];
         symmNormal(m, bc, f, n);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double tv = ((i == 0 ? 1.0 : 0.0) - 2.0 * (n[i] * n[0])) * o4[0] + ((i == 1 ? 1.0 : 0.0) - 2.0 * (n[i] * n[1])) * o4[1] +
-                              ((i == 2 ? 1.0 : 0.0) - 2.0 * (n[i] * n[2])) * o4[2];
-            v.sn[i] = (tv - o4[i]) * (dc / 2.0);
-        }
+        for (int i = 0; i < 3; ++i) v.sn[i] = (qhdReflected(n, o4, i) - o4[i]) * (dc / 2.0);
     } else if (bc.bcU != QGD_BC_FIXEDVALUE) v.sn[0] = v.sn[1] = v.sn[2] = 0.0;
     if (bc.bcT != QGD_BC_FIXEDVALUE) v.sn[3] = 0.0;
     if (perComponent && (bc.ptype == QGD_PATCH_SYMMETRYPLANE || bc.ptype == QGD_PATCH_SYMMETRY)) v.sn[0] = v.sn[1] = v.sn[2] = 0.0;
 }
 
-// Compile-time modes of the step kernels (template parameter MODE).  MODE 0 is QHDFoam as it always was, instruction for instruction; the
-// other instantiations are what qgd_qhd_case_set_srf / qgd_qhd_case_set_bc_values switch on: no uniform branch goes into the bodies.
-//   QHD_ROT     SRFQHDFoam's body force BdFrc = beta*T*g - 2 (omega ^ U) [SRFQHDFoam/updateFields.H L73-74] at all six sites: face passes 1 and
-//               2 (generic walk and LDS tiles), the explicit cell update, the right-hand sides of implicitDiffusion.  Per cell from the OLD U
-//               and T of that cell; internal faces lerpf(w, B_O, B_N); patch faces the same expression on the patch values U_b, T_b (BdFrc is
-//               a calculated field: qgdInterpolate takes its patch value).  No centrifugal term, as in the listing: p is the reduced pressure.
+// Compile-time modes of the step kernels (template parameter MODE).  MODE 0 is QHDFoam; the other instantiations are what
+// qgd_qhd_case_set_srf / qgd_qhd_case_set_bc_values switch on: no uniform branch goes into the bodies.
+//   QHD_ROT     SRFQHDFoam's body force (QhdBdFrc).  No centrifugal term, as in the listing: p is the reduced pressure.
 //               gradWf = fvsc::grad(W) of updateFields.H L45 is not formed: nothing reads it.
 //   QHD_FROZEN  no QHDTEqn.H in the loop [SRFQHDFoam.C L93-147]: T and T.boundary are not written
 //   QHD_LIST    a fixedValue patch may carry one velocity per face (QhdView::bValU)
 enum : int { QHD_ROT = 1, QHD_FROZEN = 2, QHD_LIST = 4 };
 
-// BdFrc of one cell or patch face from its {Ux,Uy,Uz,T}
-__device__ __forceinline__ void qhdBdFrcRot(const QhdView& q, const double* u4, double B[3]) {
-    const double bT = q.beta * u4[3];
-    B[0] = bT * q.g[0] - 2.0 * (q.omega[1] * u4[2] - q.omega[2] * u4[1]);
-    B[1] = bT * q.g[1] - 2.0 * (q.omega[2] * u4[0] - q.omega[0] * u4[2]);
-    B[2] = bT * q.g[2] - 2.0 * (q.omega[0] * u4[1] - q.omega[1] * u4[0]);
+// BdFrc of one cell or patch face from its {Ux,Uy,Uz,T}: beta*T*g [updateFields.H L66], in the rotating frame beta*T*g - 2 (omega ^ U)
+// with U the relative velocity [SRFQHDFoam/updateFields.H L73].  Per cell from the OLD U and T of that cell; on a patch face the same
+// expression on the patch values U_b, T_b (BdFrc is a calculated field: qgdInterpolate takes its patch value).  The rotating form is
+// evaluated where the object is made, all three components; the plain one component by component where [k] asks for it: the order in which
+// the kernels always formed them (another order gives other registers and, in the rotating kernels, other FMA contractions)
+template <int MODE>
+struct QhdBdFrc {
+    const QhdView& q;
+    const double* u4;
+    double B[3];
+    static __device__ __forceinline__ void rot(const QhdView& q, const double* u4, double B[3]) {
+        const double bT = q.beta * u4[3];
+        B[0] = bT * q.g[0] - 2.0 * (q.omega[1] * u4[2] - q.omega[2] * u4[1]);
+        B[1] = bT * q.g[1] - 2.0 * (q.omega[2] * u4[0] - q.omega[0] * u4[2]);
+        B[2] = bT * q.g[2] - 2.0 * (q.omega[0] * u4[1] - q.omega[1] * u4[0]);
+    }
+    __device__ __forceinline__ QhdBdFrc(const QhdView& q_, const double* u4_) : q(q_), u4(u4_) {
+        if (MODE & QHD_ROT) rot(q, u4, B);
+    }
+    __device__ __forceinline__ double operator[](const int k) const { return (MODE & QHD_ROT) ? B[k] : (q.beta * u4[3]) * q.g[k]; }
+};
+// face pass 2 behind its operands [QHDUEqn.H L37-84, QHDTEqn.H L65-91], one component per call: the loops over the components stand in
+// the three kernels (measured: with the loops in one function here, qhdFusedAdvanceKernel spills 53 VGPRs for 6).  o4 / n4: {U,T} of the
+// owner and of the neighbour cell or patch face; implicit: implicitDiffusion, the laplacians sit in the matrix (fvm::laplacian, QHDUEqn.H L54, QHDTEqn.H L73-76)
+// Wf_k [QHDUEqn.H L37] from (Uf & gradUf)_k of face pass 1 and gradPf_k [QHDUEqn.H L36]; BdFrcf as in face pass 1
+__device__ __forceinline__ double qhdWf(const QhdView& q, const bool internal, const double w, const double BoK, const double BnK, const double tau,
+                                        const double uguK, const double gPK) {
+    const double Bf = internal ? lerpf(w, BoK, BnK) : BnK;
+    return tau * ((uguK + gPK / q.rho0) - Bf);
+}
+// the net face term of the U_j equation.  snUj: fvc::snGrad(U_j); pf: p at the face; gUT[3i+j] = lin(gradU)[3j+i], T(grad U) at the face
+__device__ __forceinline__ double qhdFaceTermU(const QhdView& q, const bool internal, const bool implicit, const double* o4, const double* n4,
+                                               const double Uf[3], const double Wf[3], const double snUj, const double pf, const double gUT[9],
+                                               const double S[3], const double magS, const double phi, const int j) {
+    const double uw = S[0] * (Uf[0] * Wf[j]) + S[1] * (Uf[1] * Wf[j]) + S[2] * (Uf[2] * Wf[j]);   // Sf & (Uf*Wf), L39
+    // qgdFlux(phi,U,Uf) [L41]: phi*Uf, or with `div(phi,U) Gauss upwind` fvc::flux = phi * (pos0(phi) (U_O - U_N) + U_N) inside,
+    // the patch value on patch faces [QGDInterpolate.H L86-104]
+    const double phiUf = phi * ((q.upwindU && internal) ? lerpf(phi >= 0.0 ? 1.0 : 0.0, o4[j], n4[j]) : Uf[j]) - uw;   // L41-43
+    const double lap = q.nu * snUj * magS;                                                       // fvc::laplacian(muf/rhof, U), L74
+    const double ext = S[0] * gUT[0 * 3 + j] + S[1] * gUT[1 * 3 + j] + S[2] * gUT[2 * 3 + j];    // Sf & lin(T(grad U)), L56 / L76
+    // the Gauss term of -fvc::grad(p)/rho (uniform rho) rides in the same face flux: S_j p_f / rho
+    return (implicit ? phiUf - q.nu * ext : (phiUf - lap) - q.nu * ext) + (S[j] * pf) / q.rho0;
+}
+// the net face term of the T equation [QHDTEqn.H L65-66, L73-76, L85-88].  phitr: phiTauTReg of face pass 1
+__device__ __forceinline__ double qhdFaceTermT(const QhdView& q, const bool internal, const bool implicit, const double w, const double To,
+                                               const double Tn, const double snT, const double magS, const double phi, const double phitr) {
+    const double Tf = (internal ? lerpf(w, To, Tn) : Tn);
+    const double phiTf = phi * ((q.upwindT && internal) ? lerpf(phi >= 0.0 ? 1.0 : 0.0, To, Tn) : Tf);   // qgdFlux(phi,T,Tf) [QHDTEqn.H L65]
+    return implicit ? phiTf - phitr : (phiTf - q.Hi * snT * magS) - phitr;
+}
+// explicit Euler of one cell's record [QHDUEqn.H L68-84, QHDTEqn.H L83-91] from the sums s of its net face terms: BdFrc from the OLD
+// components, all read before any is written
+template <int MODE>
+__device__ __forceinline__ void qhdEulerCell(const QhdView& q, const double s[4], const double rV, double rec[4]) {
+    const double old[4] = {rec[0], rec[1], rec[2], rec[3]};
+    const QhdBdFrc<MODE> B(q, old);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rec[k] = old[k] + q.dt * (-(s[k] * rV) + B[k]);
+    if (!(MODE & QHD_FROZEN)) rec[3] = old[3] + q.dt * (-(s[3] * rV));
+}
+// the records of an LDS tile: three doubles (a centre, a vertex), a {U,T} record as two 16-B pieces
+typedef double v2d __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ double4 l3(const double* p, const int i) { return make_double4(p[3 * i], p[3 * i + 1], p[3 * i + 2], 0.0); }
+__device__ __forceinline__ void l4(const v2d* p, const int i, double* o) {
+    const v2d a = p[2 * i], b = p[2 * i + 1];
+    o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
 }
 // the velocity a fixedValue patch prescribes on boundary face b: the face's own entry where the patch carries a list
 template <int MODE>
@@ -96,6 +174,8 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace1Kernel(const MeshView m, co
     }
     double g[12];
     faceGradient<ST, 4, 0>(m, f, v, q.c4, q.pt4, g);   // g[i*4 + k] = d_i {Ux,Uy,Uz,T}_k
+    // (the algebra from here on stands in qhdFace1TileKernel as well, statement for statement: keep the two alike.  BdFrcf's plain form is
+    // QhdBdFrc's beta*T*g written out; in any other statement order the rotating instantiations round phiwo differently)
     const double gv[3] = {q.g[0], q.g[1], q.g[2]};
     double Uf[3], Bf[3];
 #pragma unroll
@@ -105,7 +185,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace1Kernel(const MeshView m, co
     }
     if (MODE & QHD_ROT) {   // SRFQHDFoam/updateFields.H L73-74
         double Bo[3], Bn[3];
-        qhdBdFrcRot(q, v.o, Bo); qhdBdFrcRot(q, v.n, Bn);
+        QhdBdFrc<MODE>::rot(q, v.o, Bo); QhdBdFrc<MODE>::rot(q, v.n, Bn);
 #pragma unroll
         for (int k = 0; k < 3; ++k) Bf[k] = internal ? lerpf(w, Bo[k], Bn[k]) : Bn[k];
     }
@@ -117,7 +197,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace1Kernel(const MeshView m, co
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const double UgU = Uf[0] * g[0 * 4 + j] + Uf[1] * g[1 * 4 + j] + Uf[2] * g[2 * 4 + j];   // Uf & gradUf
-        q.ugu[(size_t)j * nF + f] = UgU;   // (BdFrcf is not stored: face pass 2 holds T of both cells and forms it again from the same expression)
+        q.ugu[(size_t)j * nF + f] = UgU;
         wo[j] = tau * (UgU - Bf[j]);
     }
     q.phiu[f] = phiu;
@@ -168,24 +248,22 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace2Kernel(const MeshView m, co
     const int o = m.own[f];
     const double S[3] = {m.Sx[f], m.Sy[f], m.Sz[f]};
     const double magS = m.magSf[f];
-    double Uo[3], Un[3], To, Tn, snU[3], snT, pf, w = 1.0;
+    double o4[4], n4[4], snU[3], snT, pf, w = 1.0;
     FaceVals<1> vp;
     vp.o[0] = q.p[o];
     double gUT[9];   // T(grad U) at the face: gUT[3i+j] = lin(gradU)[3j+i]
 #pragma unroll
-    for (int k = 0; k < 3; ++k) Uo[k] = q.c4[(size_t)o * 4 + k];
-    To = q.c4[(size_t)o * 4 + 3];
+    for (int k = 0; k < 4; ++k) o4[k] = q.c4[(size_t)o * 4 + k];
     if (internal) {
         const int n = m.nei[f];
         w = m.w[f];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) Un[k] = q.c4[(size_t)n * 4 + k];
-        Tn = q.c4[(size_t)n * 4 + 3];
+        for (int k = 0; k < 4; ++k) n4[k] = q.c4[(size_t)n * 4 + k];
         vp.n[0] = q.p[n]; vp.sn[0] = 0.0;
         const double dn = m.dn[f];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) snU[k] = dn * (Un[k] - Uo[k]);   // fvc::snGrad, uncorrected (L0)
-        snT = dn * (Tn - To);
+        for (int k = 0; k < 3; ++k) snU[k] = dn * (n4[k] - o4[k]);   // fvc::snGrad, uncorrected (L0)
+        snT = dn * (n4[3] - o4[3]);
         pf = lerpf(w, vp.o[0], vp.n[0]);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
@@ -197,8 +275,8 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace2Kernel(const MeshView m, co
         FaceVals<4> v4;
         qhdBoundaryVals4(m, bc, f, q.c4 + (size_t)o * 4, q.b4 + (size_t)b * 4, v4);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { Un[k] = v4.n[k]; snU[k] = v4.sn[k]; }
-        Tn = v4.n[3]; snT = v4.sn[3];
+        for (int k = 0; k < 3; ++k) { n4[k] = v4.n[k]; snU[k] = v4.sn[k]; }
+        n4[3] = v4.n[3]; snT = v4.sn[3];
         vp.n[0] = q.pb[b];
         vp.sn[0] = (bc.bcP == QGD_BC_QGDFLUX || bc.bcP == QGD_BC_QHDFLUX) ? q.pgb[b] : (bc.bcP == QGD_BC_FIXEDVALUE ? m.dn[f] * (vp.n[0] - vp.o[0]) : 0.0);
         pf = vp.n[0];
@@ -225,35 +303,16 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace2Kernel(const MeshView m, co
     double gP[3];
     faceGradient<ST, 1, -1>(m, f, vp, q.p, q.ptp, gP);                                           // QHDUEqn.H L36
     const double tau = q.tauF[f], phi = q.phi[f];
-    double Uf[3], Wf[3], Bo[3], Bn[3];
-    if (MODE & QHD_ROT) {   // SRFQHDFoam/updateFields.H L73-74, as in face pass 1
-        const double o4[4] = {Uo[0], Uo[1], Uo[2], To}, n4[4] = {Un[0], Un[1], Un[2], Tn};
-        qhdBdFrcRot(q, o4, Bo); qhdBdFrcRot(q, n4, Bn);
-    }
+    double Uf[3], Wf[3];
+    const QhdBdFrc<MODE> Bo(q, o4), Bn(q, n4);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        Uf[k] = internal ? lerpf(w, Uo[k], Un[k]) : Un[k];
-        double Bf;
-        if (MODE & QHD_ROT) Bf = internal ? lerpf(w, Bo[k], Bn[k]) : Bn[k];
-        else Bf = internal ? lerpf(w, (q.beta * To) * q.g[k], (q.beta * Tn) * q.g[k]) : (q.beta * Tn) * q.g[k];   // BdFrcf [updateFields.H L66-67], as in face pass 1
-        Wf[k] = tau * ((q.ugu[(size_t)k * nF + f] + gP[k] / q.rho0) - Bf);   // L37
+        Uf[k] = (internal ? lerpf(w, o4[k], n4[k]) : n4[k]);
+        Wf[k] = qhdWf(q, internal, w, Bo[k], Bn[k], tau, q.ugu[(size_t)k * nF + f], gP[k]);
     }
-    const double Tf = internal ? lerpf(w, To, Tn) : Tn;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double uw = S[0] * (Uf[0] * Wf[j]) + S[1] * (Uf[1] * Wf[j]) + S[2] * (Uf[2] * Wf[j]);   // Sf & (Uf*Wf), L39
-        // qgdFlux(phi,U,Uf) [L41]: phi*Uf, or with `div(phi,U) Gauss upwind` fvc::flux = phi * (pos0(phi) (U_O - U_N) + U_N) inside,
-        // the patch value on patch faces [QGDInterpolate.H L86-104]
-        const double phiUf = phi * ((q.upwindU && internal) ? lerpf(phi >= 0.0 ? 1.0 : 0.0, Uo[j], Un[j]) : Uf[j]) - uw;   // L41-43
-        const double lap = q.nu * snU[j] * magS;                                                     // fvc::laplacian(muf/rhof, U), L74
-        const double ext = S[0] * gUT[0 * 3 + j] + S[1] * gUT[1 * 3 + j] + S[2] * gUT[2 * 3 + j];    // Sf & lin(T(grad U)), L56 / L76
-        // the Gauss term of -fvc::grad(p)/rho (uniform rho) rides in the same face flux: S_j p_f / rho;
-        // implicitDiffusion: the laplacian sits in the matrix (fvm::laplacian, L54)
-        q.F[(size_t)j * nF + pos] = (q.implicit ? phiUf - q.nu * ext : (phiUf - lap) - q.nu * ext) + (S[j] * pf) / q.rho0;
-    }
-    const double phiTf = phi * ((q.upwindT && internal) ? lerpf(phi >= 0.0 ? 1.0 : 0.0, To, Tn) : Tf);   // qgdFlux(phi,T,Tf) [QHDTEqn.H L65]
-    q.F[3 * nF + pos] = q.implicit ? phiTf - q.phitr[f]                                                // QHDTEqn.H L73-76
-                                   : (phiTf - q.Hi * snT * magS) - q.phitr[f];                         // QHDTEqn.H L65-66, L85-88
+    for (int j = 0; j < 3; ++j) q.F[(size_t)j * nF + pos] = qhdFaceTermU(q, internal, q.implicit != 0, o4, n4, Uf, Wf, snU[j], pf, gUT, S, magS, phi, j);
+    q.F[3 * nF + pos] = qhdFaceTermT(q, internal, q.implicit != 0, w, o4[3], n4[3], snT, magS, phi, q.phitr[f]);
 }
 
 // ---------------------------------------------------------------------------
@@ -264,7 +323,6 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdFace2Kernel(const MeshView m, co
 // face as nine scattered doubles in the generic walk.  Same expressions as the generic kernels (which keep the boundary faces and
 // the tiles beyond the caps).
 // ---------------------------------------------------------------------------
-typedef double v2d __attribute__((ext_vector_type(2)));
 constexpr int kQhdFB = 128;
 static_assert(2 * (kQhdFB + kQhdFB / 16) <= 3 * kQhdFB && 3 * (kQhdFB + kQhdFB / 16) <= 4 * kQhdFB && 9 * (kQhdFB + kQhdFB / 16) <= 10 * kQhdFB &&
               2 * (((kQhdFB * 23) / 16 + 7) / 8 * 8) <= 3 * kQhdFB && 3 * (((kQhdFB * 23) / 16 + 7) / 8 * 8) <= 5 * kQhdFB, "faceTileCap*");
@@ -304,8 +362,6 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace1TileKernel(const MeshView m, c
     if (!active) return;
     const int lo = (int)(lc & 0xffffu), ln = (int)(lc >> 16);
     const int v0 = (int)(lv.x & 0xffffu), v1 = (int)(lv.x >> 16), v2 = (int)(lv.y & 0xffffu), v3 = (int)(lv.y >> 16);
-    auto l3 = [](const double* p, int i) { return make_double4(p[3 * i], p[3 * i + 1], p[3 * i + 2], 0.0); };
-    auto l4 = [](const v2d* p, int i, double* o) { const v2d a = p[2 * i], b = p[2 * i + 1]; o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y; };
     FaceVals<4> v;
     l4(s4, lo, v.o); l4(s4, ln, v.n);
 #pragma unroll
@@ -326,7 +382,7 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace1TileKernel(const MeshView m, c
     }
     if (MODE & QHD_ROT) {   // SRFQHDFoam/updateFields.H L73-74
         double Bo[3], Bn[3];
-        qhdBdFrcRot(q, v.o, Bo); qhdBdFrcRot(q, v.n, Bn);
+        QhdBdFrc<MODE>::rot(q, v.o, Bo); QhdBdFrc<MODE>::rot(q, v.n, Bn);
 #pragma unroll
         for (int k = 0; k < 3; ++k) Bf[k] = lerpf(w, Bo[k], Bn[k]);
     }
@@ -389,18 +445,15 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace2TileKernel(const MeshView m, c
     if (!active) return;
     const int lo = (int)(lc & 0xffffu), ln = (int)(lc >> 16);
     const int v0 = (int)(lv.x & 0xffffu), v1 = (int)(lv.x >> 16), v2 = (int)(lv.y & 0xffffu), v3 = (int)(lv.y >> 16);
-    auto l3 = [](const double* p, int i) { return make_double4(p[3 * i], p[3 * i + 1], p[3 * i + 2], 0.0); };
-    auto l4 = [](const v2d* p, int i, double* o) { const v2d a = p[2 * i], b = p[2 * i + 1]; o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y; };
     if (kind == 3) { for (int k = 0; k < 4; ++k) q.F[(size_t)k * nF + pos] = 0.0; return; }
     double o4[4], n4[4];
     l4(s4, lo, o4); l4(s4, ln, n4);
-    const double Uo[3] = {o4[0], o4[1], o4[2]}, Un[3] = {n4[0], n4[1], n4[2]}, To = o4[3], Tn = n4[3];
     FaceVals<1> vp;
     vp.o[0] = sp[lo]; vp.n[0] = sp[ln]; vp.sn[0] = 0.0;
     double snU[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) snU[k] = dn * (Un[k] - Uo[k]);   // fvc::snGrad, uncorrected (L0)
-    const double snT = dn * (Tn - To);
+    for (int k = 0; k < 3; ++k) snU[k] = dn * (n4[k] - o4[k]);   // fvc::snGrad, uncorrected (L0)
+    const double snT = dn * (n4[3] - o4[3]);
     const double pf = lerpf(w, vp.o[0], vp.n[0]);
     double gUT[9];   // T(grad U) at the face: gUT[3i+j] = lin(gradU)[3j+i]
 #pragma unroll
@@ -411,27 +464,16 @@ __global__ __launch_bounds__(kQhdFB) void qhdFace2TileKernel(const MeshView m, c
     if (kind == 2) faceGradient<ST_GVP3, 1, -1>(m, f, vp, q.p, q.ptp, gP);
     else gvp3GradCore<1, -1>(kind, true, l3(sC, lo), l3(sC, ln), l3(sX, v0), l3(sX, v1), l3(sX, v2), l3(sX, v3), vp.o, vp.n, sq + v0, sq + v1, sq + v2,
                              sq + v3, gP);                                                       // QHDUEqn.H L36
-    double Uf[3], Wf[3], Bo[3], Bn[3];
-    if (MODE & QHD_ROT) { qhdBdFrcRot(q, o4, Bo); qhdBdFrcRot(q, n4, Bn); }   // SRFQHDFoam/updateFields.H L73-74, as in face pass 1
+    double Uf[3], Wf[3];
+    const QhdBdFrc<MODE> Bo(q, o4), Bn(q, n4);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        Uf[k] = lerpf(w, Uo[k], Un[k]);
-        double Bf;
-        if (MODE & QHD_ROT) Bf = lerpf(w, Bo[k], Bn[k]);
-        else Bf = lerpf(w, (q.beta * To) * q.g[k], (q.beta * Tn) * q.g[k]);   // BdFrcf [updateFields.H L66-67], as in face pass 1
-        Wf[k] = tau * ((ugu[k] + gP[k] / q.rho0) - Bf);   // L37
+        Uf[k] = lerpf(w, o4[k], n4[k]);
+        Wf[k] = qhdWf(q, true, w, Bo[k], Bn[k], tau, ugu[k], gP[k]);
     }
-    const double Tf = lerpf(w, To, Tn);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double uw = S[0] * (Uf[0] * Wf[j]) + S[1] * (Uf[1] * Wf[j]) + S[2] * (Uf[2] * Wf[j]);   // Sf & (Uf*Wf), L39
-        const double phiUf = phi * (q.upwindU ? lerpf(phi >= 0.0 ? 1.0 : 0.0, Uo[j], Un[j]) : Uf[j]) - uw;   // L41-43 (upwind: see qhdFace2Kernel)
-        const double lap = q.nu * snU[j] * magS;                                                     // fvc::laplacian(muf/rhof, U), L74
-        const double ext = S[0] * gUT[0 * 3 + j] + S[1] * gUT[1 * 3 + j] + S[2] * gUT[2 * 3 + j];    // Sf & lin(T(grad U)), L56 / L76
-        q.F[(size_t)j * nF + pos] = (q.implicit ? phiUf - q.nu * ext : (phiUf - lap) - q.nu * ext) + (S[j] * pf) / q.rho0;
-    }
-    const double phiTf = phi * (q.upwindT ? lerpf(phi >= 0.0 ? 1.0 : 0.0, To, Tn) : Tf);
-    q.F[3 * nF + pos] = q.implicit ? phiTf - phitr : (phiTf - q.Hi * snT * magS) - phitr;   // QHDTEqn.H L65-66, L73-76, L85-88
+    for (int j = 0; j < 3; ++j) q.F[(size_t)j * nF + pos] = qhdFaceTermU(q, true, q.implicit != 0, o4, n4, Uf, Wf, snU[j], pf, gUT, S, magS, phi, j);
+    q.F[3 * nF + pos] = qhdFaceTermT(q, true, q.implicit != 0, w, o4[3], n4[3], snT, magS, phi, phitr);
 }
 
 // explicit Euler of the U and T equations [QHDUEqn.H L68-84, QHDTEqn.H L83-91]
@@ -484,19 +526,11 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdCellUpdateKernel(const MeshView 
         }
     }
     const double rV = 1.0 / m.V[c];
-    double* rec = q.c4 + (size_t)c * 4;
-    const double T = rec[3];
-    if (MODE & QHD_ROT) {   // BdFrc = beta*T*g - 2 (omega ^ U) of SRFQHDFoam/updateFields.H L73: the three OLD components are read before any is written
-        const double old[4] = {rec[0], rec[1], rec[2], T};
-        double B[3];
-        qhdBdFrcRot(q, old, B);
+    double* const dst = q.c4 + (size_t)c * 4;
+    double rec[4] = {dst[0], dst[1], dst[2], dst[3]};
+    qhdEulerCell<MODE>(q, s, rV, rec);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) rec[k] = old[k] + q.dt * (-(s[k] * rV) + B[k]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) rec[k] += q.dt * (-(s[k] * rV) + (q.beta * T) * q.g[k]);   // BdFrc = beta*T*g of updateFields.H L66
-    }
-    if (!(MODE & QHD_FROZEN)) rec[3] = T + q.dt * (-(s[3] * rV));
+    for (int k = 0; k < ((MODE & QHD_FROZEN) ? 3 : 4); ++k) dst[k] = rec[k];
 }
 
 // ---------------------------------------------------------------------------
@@ -505,18 +539,17 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdCellUpdateKernel(const MeshView 
 // QHDTEqn.H L65-91] without the 8 B per vertex and the 2 x 32 B per face the three kernels hand each other through device memory.  A workgroup
 // (256 threads) stages {U,T}, fvc::grad(U) and the centres of its own + across-a-face cells, p of those and of the edge / corner cells around
 // its vertices, the vertex coordinates; thread v forms p at vertex v (pointInterpFastKernel's sum, out of LDS; a patch point takes
-// boundaryPointKernel's value); every thread computes the net terms of two of the block's internal faces (qhdFace2TileKernel's expressions);
+// boundaryPointKernel's value); every thread computes the net terms of two of the block's internal faces (qhdWf, qhdFaceTermU, qhdFaceTermT);
 // the terms take the gradients' place in LDS and threads 0..127 advance one own cell each (qhdCellUpdateKernel's ordered sums; patch faces
 // from q.F, where qhdFace2Kernel put them).  The block reads the OLD {U,T} of its neighbours while other blocks write new ones: the update
 // goes to a second record array, the host swaps the two.  Unsharded cases, implicitDiffusion false.
 // ---------------------------------------------------------------------------
-constexpr int kQhdFuCapC = 320, kQhdFuCapV = 256, kQhdFuCapF = 512, kQhdFuCapTot = 384;   // = kFusedCap{C,V,F,Tot} of qgd_setup.hpp
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict__ c4new, const int ldsCell) {
     extern __shared__ v2d qhdLds[];
     constexpr int NT = 256, KB2 = 3, KCC = 4, KG = 12, KPC = 2, KV = 3, KF = 2, KE = 6, KP = 8;
-    static_assert(2 * kQhdFuCapC <= KB2 * NT && 3 * kQhdFuCapC <= KCC * NT && 9 * kQhdFuCapC <= KG * NT && kQhdFuCapTot <= KPC * NT &&
-                  3 * kQhdFuCapV <= KV * NT && kQhdFuCapF <= KF * NT && kQhdFuCapV <= NT, "caps");
+    static_assert(2 * kFusedCapC <= KB2 * NT && 3 * kFusedCapC <= KCC * NT && 9 * kFusedCapC <= KG * NT && kFusedCapTot <= KPC * NT &&
+                  3 * kFusedCapV <= KV * NT && kFusedCapF <= KF * NT && kFusedCapV <= NT, "caps");
     const int blk = xcdTile((int)gridDim.x, m.fuXcdRun);
     const int tid = (int)threadIdx.x;
     const int capC = m.fuCapC, capV = m.fuCapV, capF = m.fuCapF, capPE = m.fuCapPE;
@@ -654,9 +687,7 @@ void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict
         sq[tid] = acc;
     }
     __syncthreads();
-    // (2) the faces: qhdFace2TileKernel's expressions, the net terms into registers
-    auto l3 = [](const double* p, int i) { return make_double4(p[3 * i], p[3 * i + 1], p[3 * i + 2], 0.0); };
-    auto l4 = [](const v2d* p, int i, double* o) { const v2d a = p[2 * i], b = p[2 * i + 1]; o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y; };
+    // (2) the faces: the net terms into registers
     double out[KF][4];
 #pragma unroll
     for (int j = 0; j < KF; ++j) {
@@ -673,13 +704,12 @@ void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict
                 const double S[3] = {st[j].S[0], st[j].S[1], st[j].S[2]};
                 double o4[4], n4[4];
                 l4(s4, lo, o4); l4(s4, ln, n4);
-                const double Uo[3] = {o4[0], o4[1], o4[2]}, Un[3] = {n4[0], n4[1], n4[2]}, To = o4[3], Tn = n4[3];
                 FaceVals<1> vp;
                 vp.o[0] = sp[lo]; vp.n[0] = sp[ln]; vp.sn[0] = 0.0;
                 double snU[3];
 #pragma unroll
-                for (int k = 0; k < 3; ++k) snU[k] = dn * (Un[k] - Uo[k]);   // fvc::snGrad, uncorrected (L0)
-                const double snT = dn * (Tn - To);
+                for (int k = 0; k < 3; ++k) snU[k] = dn * (n4[k] - o4[k]);   // fvc::snGrad, uncorrected (L0)
+                const double snT = dn * (n4[3] - o4[3]);
                 const double pf = lerpf(w, vp.o[0], vp.n[0]);
                 double gUT[9];   // T(grad U) at the face: gUT[3i+j] = lin(gradU)[3j+i]
 #pragma unroll
@@ -695,24 +725,16 @@ void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict
                     loadStreams(st[j + 1], fl[j + 1]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                double Uf[3], Wf[3];
+                double Uf[3], Wf[3];   // (QHDFoam's loop, explicit only: MODE 0, implicit false)
+                const QhdBdFrc<0> Bo(q, o4), Bn(q, n4);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    Uf[k] = lerpf(w, Uo[k], Un[k]);
-                    const double Bf = lerpf(w, (q.beta * To) * q.g[k], (q.beta * Tn) * q.g[k]);   // BdFrcf [updateFields.H L66-67], as in face pass 1
-                    Wf[k] = tau * ((st[j].ugu[k] + gP[k] / q.rho0) - Bf);   // L37
+                    Uf[k] = lerpf(w, o4[k], n4[k]);
+                    Wf[k] = qhdWf(q, true, w, Bo[k], Bn[k], tau, st[j].ugu[k], gP[k]);
                 }
-                const double Tf = lerpf(w, To, Tn);
 #pragma unroll
-                for (int jj = 0; jj < 3; ++jj) {
-                    const double uw = S[0] * (Uf[0] * Wf[jj]) + S[1] * (Uf[1] * Wf[jj]) + S[2] * (Uf[2] * Wf[jj]);   // Sf & (Uf*Wf), L39
-                    const double phiUf = phi * (q.upwindU ? lerpf(phi >= 0.0 ? 1.0 : 0.0, Uo[jj], Un[jj]) : Uf[jj]) - uw;   // L41-43
-                    const double lap = q.nu * snU[jj] * magS;                                                      // fvc::laplacian(muf/rhof, U), L74
-                    const double ext = S[0] * gUT[0 * 3 + jj] + S[1] * gUT[1 * 3 + jj] + S[2] * gUT[2 * 3 + jj];   // Sf & lin(T(grad U)), L56 / L76
-                    out[j][jj] = ((phiUf - lap) - q.nu * ext) + (S[jj] * pf) / q.rho0;
-                }
-                const double phiTf = phi * (q.upwindT ? lerpf(phi >= 0.0 ? 1.0 : 0.0, To, Tn) : Tf);
-                out[j][3] = (phiTf - q.Hi * snT * magS) - phitr;   // QHDTEqn.H L65-66, L85-88
+                for (int jj = 0; jj < 3; ++jj) out[j][jj] = qhdFaceTermU(q, true, false, o4, n4, Uf, Wf, snU[jj], pf, gUT, S, magS, phi, jj);
+                out[j][3] = qhdFaceTermT(q, true, false, w, o4[3], n4[3], snT, magS, phi, phitr);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -766,10 +788,7 @@ void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict
         const double rV = 1.0 / Vc;
         double rec[4];
         l4(s4, tid, rec);
-        const double T = rec[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) rec[k] += q.dt * (-(s[k] * rV) + (q.beta * T) * q.g[k]);   // BdFrc = beta*T*g of updateFields.H L66
-        rec[3] = T + q.dt * (-(s[3] * rV));
+        qhdEulerCell<0>(q, s, rV, rec);
         v2d* const dst = reinterpret_cast<v2d*>(c4new) + 2 * (size_t)ci;
         dst[0] = v2d{rec[0], rec[1]};
         dst[1] = v2d{rec[2], rec[3]};
@@ -800,11 +819,7 @@ __device__ __forceinline__ void qhdPatchCoeffs(const MeshView& m, const QhdView&
         for (int k = 0; k < 3; ++k) ic[k] = dc * fabs(n[k]);
         if (cur) {
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const double tv = ((i == 0 ? 1.0 : 0.0) - 2.0 * (n[i] * n[0])) * cur[0] + ((i == 1 ? 1.0 : 0.0) - 2.0 * (n[i] * n[1])) * cur[1] +
-                                  ((i == 2 ? 1.0 : 0.0) - 2.0 * (n[i] * n[2])) * cur[2];
-                bs[i] = (tv - cur[i]) * (dc / 2.0) + ic[i] * cur[i];   // basicSymmetry::snGrad + gIC * patchInternalField
-            }
+            for (int i = 0; i < 3; ++i) bs[i] = (qhdReflected(n, cur, i) - cur[i]) * (dc / 2.0) + ic[i] * cur[i];   // basicSymmetry::snGrad + gIC * patchInternalField
         }
     }
     if (bc.bcT == QGD_BC_FIXEDVALUE) { ic[3] = dc; bs[3] = dc * bc.vT; }
@@ -863,15 +878,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdImplicitRhsKernel(const MeshView
             double v[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) v[t] = t < q.xOrder ? q.xd[t][j] : 0.0;
-            if (kk >= 1) {
-                const double d0 = cur[k] - v[0];
-                double e = d0;
-                if (kk == 2) e = (2.0 * cur[k] - 3.0 * v[0]) + v[1];
-                else if (kk == 3) e = ((3.0 * cur[k] - 6.0 * v[0]) + 4.0 * v[1]) - v[2];
-                else if (kk >= 4) e = (((4.0 * cur[k] - 10.0 * v[0]) + 10.0 * v[1]) - 5.0 * v[2]) + v[3];
-                const double lim = 2.0 * fabs(d0);     // limited like the pressure's (qhdExtrapolatePKernel)
-                q.x4[j] = cur[k] + fmin(fmax(e, -lim), lim);
-            }
+            if (kk >= 1) q.x4[j] = qhdExtrapolated(cur[k], v, kk);   // limited like the pressure's (qhdExtrapolatePKernel)
             q.xd[q.xOrder - 1][j] = cur[k];            // the current fields into the oldest slot (the host rotates the pointers)
         }
     }
@@ -910,16 +917,9 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdImplicitRhsKernel(const MeshView
         }
     }
     const double V = m.V[c], rV = 1.0 / V, rD = 1.0 / q.dt;
-    if (MODE & QHD_ROT) {
-        double B[3];
-        qhdBdFrcRot(q, cur, B);   // BdFrc = beta*T*g - 2 (omega ^ U) [SRFQHDFoam/updateFields.H L73]
+    const QhdBdFrc<MODE> B(q, cur);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) q.rhs4[(size_t)k * nC + c] = (rD * cur[k] * V + V * (-(s[k] * rV) + B[k])) + src[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            q.rhs4[(size_t)k * nC + c] = (rD * cur[k] * V + V * (-(s[k] * rV) + (q.beta * cur[3]) * q.g[k])) + src[k];   // BdFrc = beta*T*g [updateFields.H L66]
-    }
+    for (int k = 0; k < 3; ++k) q.rhs4[(size_t)k * nC + c] = (rD * cur[k] * V + V * (-(s[k] * rV) + B[k])) + src[k];
     q.rhs4[3 * nC + c] = (rD * cur[3] * V + V * (-(s[3] * rV))) + src[3];
 }
 // the solution into the records (components that were not solved keep their values)
@@ -948,11 +948,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdBcKernel(const MeshView m, const
         double n[3];
         symmNormal(m, bc, f, n);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double tv = ((i == 0 ? 1.0 : 0.0) - 2.0 * (n[i] * n[0])) * o4[0] + ((i == 1 ? 1.0 : 0.0) - 2.0 * (n[i] * n[1])) * o4[1] +
-                              ((i == 2 ? 1.0 : 0.0) - 2.0 * (n[i] * n[2])) * o4[2];
-            b4[i] = (o4[i] + tv) / 2.0;
-        }
+        for (int i = 0; i < 3; ++i) b4[i] = (o4[i] + qhdReflected(n, o4, i)) / 2.0;
     } else { b4[0] = o4[0]; b4[1] = o4[1]; b4[2] = o4[2]; }
     if (!(MODE & QHD_FROZEN)) b4[3] = bc.bcT == QGD_BC_FIXEDVALUE ? bc.vT : o4[3];
 }
@@ -1044,39 +1040,52 @@ inline int gridOf(int64_t n) { return (int)((n + QGD_BLOCK - 1) / QGD_BLOCK); }
 // 3-D GaussVolPoint with face tiles of 128 (MeshView::qhdTiles): the staged kernels take the internal faces, the generic ones the
 // tiles beyond the caps and the boundary faces
 inline bool staged(int st, const MeshView& m) { return st == ST_GVP3 && m.qhdTiles != 0 && m.tileOff != nullptr && m.fblock == kQhdFB; }
-// (q.rotating: the same launches with the kernels' Coriolis instantiations, qgd_qhd_case_set_srf)
-template <int ST>
-void face1(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
-    const auto gen = q.rotating ? qhdFace1Kernel<ST, QHD_ROT> : qhdFace1Kernel<ST, 0>;
-    if (staged(ST, m)) {
-        const size_t lds = ((size_t)m.tileMaxC * 56 + (size_t)m.tileMaxV * 56 + 255) / 256 * 256;
-        const auto tile = q.rotating ? qhdFace1TileKernel<QHD_ROT> : qhdFace1TileKernel<0>;
+// The kernel instantiation of a run-time choice: fn receives the stencil, or the MODE, as a std::integral_constant.  withMode<A> / <A, B>:
+// the one or two mode bits the kernel at hand is instantiated for -- the library holds these instantiations and no others
+template <class Fn>
+void withStencil(const int stencil, Fn&& fn) {
+    switch (stencil) {
+        case ST_REDUCED: fn(std::integral_constant<int, ST_REDUCED>{}); break;
+        case ST_LSQ: fn(std::integral_constant<int, ST_LSQ>{}); break;
+        case ST_GVP3: fn(std::integral_constant<int, ST_GVP3>{}); break;
+        default: fn(std::integral_constant<int, ST_GVP2>{}); break;
+    }
+}
+template <int A, class Fn>
+void withMode(const bool a, Fn&& fn) {
+    if (a) fn(std::integral_constant<int, A>{});
+    else fn(std::integral_constant<int, 0>{});
+}
+template <int A, int B, class Fn>
+void withMode(const bool a, const bool b, Fn&& fn) {
+    withMode<A>(a, [&](auto MA) { withMode<B>(b, [&](auto MB) { fn(std::integral_constant<int, MA | MB>{}); }); });
+}
+// a face pass: on the staged tiles (see staged) the tile kernel takes the internal faces, the generic one the tiles beyond the caps and the
+// boundary faces; else the generic kernel all faces.  (q.rotating: the kernels' Coriolis instantiations, qgd_qhd_case_set_srf)
+template <class Gen, class Tile>
+void facePass(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc, const bool tiles, const Gen gen, const Tile tile,
+              const size_t ldsPerCell, const size_t ldsPerVert) {
+    if (tiles) {
+        const size_t lds = ((size_t)m.tileMaxC * ldsPerCell + (size_t)m.tileMaxV * ldsPerVert + 255) / 256 * 256;
         tile<<<(m.nIF + kQhdFB - 1) / kQhdFB, kQhdFB, lds, s>>>(m, q);
         if (m.nTileSpill > 0) gen<<<m.nTileSpill, 128, 0, s>>>(m, q, bc, m.tileSpill, 0);
         if (m.nBF > 0) gen<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
     } else gen<<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, 0);
 }
-template <int ST>
-void face2(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
-    const auto gen = q.rotating ? qhdFace2Kernel<ST, QHD_ROT> : qhdFace2Kernel<ST, 0>;
-    if (staged(ST, m)) {
-        const size_t lds = ((size_t)m.tileMaxC * 136 + (size_t)m.tileMaxV * 32 + 255) / 256 * 256;
-        const auto tile = q.rotating ? qhdFace2TileKernel<QHD_ROT> : qhdFace2TileKernel<0>;
-        tile<<<(m.nIF + kQhdFB - 1) / kQhdFB, kQhdFB, lds, s>>>(m, q);
-        if (m.nTileSpill > 0) gen<<<m.nTileSpill, 128, 0, s>>>(m, q, bc, m.tileSpill, 0);
-        if (m.nBF > 0) gen<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, m.nIF);
-    } else gen<<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q, bc, nullptr, 0);
+void face1(hipStream_t s, const int stencil, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
+    withStencil(stencil, [&](auto ST) {
+        withMode<QHD_ROT>(q.rotating != 0, [&](auto M) { facePass(s, m, q, bc, staged(ST, m), qhdFace1Kernel<ST, M>, qhdFace1TileKernel<M>, 56, 56); });
+    });
+}
+void face2(hipStream_t s, const int stencil, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
+    withStencil(stencil, [&](auto ST) {
+        withMode<QHD_ROT>(q.rotating != 0, [&](auto M) { facePass(s, m, q, bc, staged(ST, m), qhdFace2Kernel<ST, M>, qhdFace2TileKernel<M>, 136, 32); });
+    });
 }
 // correctBoundaryConditions of U and T: the kernel of the case's mode (frozen: a step's call, not createFields')
 void bcValues(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc, const bool frozen) {
     if (!m.nBF) return;
-    const int g = gridOf(m.nBF);
-    switch ((frozen ? QHD_FROZEN : 0) | (q.bValU ? QHD_LIST : 0)) {
-        case 0: qhdBcKernel<0><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
-        case QHD_FROZEN: qhdBcKernel<QHD_FROZEN><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
-        case QHD_LIST: qhdBcKernel<QHD_LIST><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
-        default: qhdBcKernel<QHD_FROZEN | QHD_LIST><<<g, QGD_BLOCK, 0, s>>>(m, q, bc); break;
-    }
+    withMode<QHD_FROZEN, QHD_LIST>(frozen, q.bValU != nullptr, [&](auto M) { qhdBcKernel<M><<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc); });
 }
 
 }  // namespace
@@ -1096,12 +1105,7 @@ void launchQhdAssemble(hipStream_t s, int stencil, bool usesPoints, const MeshVi
         pointInterpFastKernel<4><<<gridOf(m.nP), QGD_BLOCK, 0, s>>>(m, q.c4, q.pt4);
         if (m.nBP) boundaryPointKernel<4><<<gridOf(m.nBP), QGD_BLOCK, 0, s>>>(m, q.b4, 4, q.pt4, 4, 0, m.nGeomD == 3 ? 0 : -1);
     }
-    switch (stencil) {
-        case ST_REDUCED: face1<ST_REDUCED>(s, m, q, bc); break;
-        case ST_LSQ: face1<ST_LSQ>(s, m, q, bc); break;
-        case ST_GVP3: face1<ST_GVP3>(s, m, q, bc); break;
-        default: face1<ST_GVP2>(s, m, q, bc); break;
-    }
+    face1(s, stencil, m, q, bc);
     if (m.nBF) qhdPressureBcKernel<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc);   // p.correctBoundaryConditions() [QHDpEqn.H L35]
     // fvc::grad(U) of QHDUEqn.H L76, formed here: U does not change before the U equation, and a shard's ghost cells hold the new
     // velocity now (their own gradient travels with the pressure message, after the solve)
@@ -1125,16 +1129,7 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdExtrapolatePKernel(const int n, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = (j < H.order && H.h[j]) ? H.h[j][i] : 0.0;
     const int k = H.have < H.order ? H.have : H.order;
-    if (k >= 1) {
-        const double d0 = pn - v[0];
-        double e = d0;                                                                             // 2 p^n - p^(n-1)
-        if (k == 2) e = (2.0 * pn - 3.0 * v[0]) + v[1];                                            // 3, -3, 1
-        else if (k == 3) e = ((3.0 * pn - 6.0 * v[0]) + 4.0 * v[1]) - v[2];                        // 4, -6, 4, -1
-        else if (k >= 4) e = (((4.0 * pn - 10.0 * v[0]) + 10.0 * v[1]) - 5.0 * v[2]) + v[3];       // 5, -10, 10, -5, 1
-        const double lim = 2.0 * fabs(d0);
-        e = fmin(fmax(e, -lim), lim);
-        p[i] = pn + e;
-    }
+    if (k >= 1) p[i] = qhdExtrapolated(pn, v, k);
     // the ring: h[j] <- h[j-1], h[0] <- p^n (each lane moves its own entries; no other lane reads them)
 #pragma unroll
     for (int j = 3; j >= 1; --j) if (j < H.order && H.h[j]) H.h[j][i] = v[j - 1];
@@ -1158,7 +1153,7 @@ void launchQhdPostSolve(hipStream_t s, const MeshView& m, const QhdView& q, cons
 bool qhdFusedAdvanceEligible(int stencil, const MeshView& m, const QhdView& q, int* ldsBytes, int* ldsCell) {
     if (stencil != ST_GVP3 || m.fuBlocks <= 0 || m.fuHdr == nullptr || m.fuHdr2 == nullptr || m.ghost != nullptr || q.implicit || m.nGeomD != 3) return false;
     if (q.rotating || q.frozenT) return false;   // qhdFusedAdvanceKernel knows QHDFoam's loop only: an SRFQHDFoam case runs the separate kernels
-    if (m.fuMaxAll > kQhdFuCapC || m.fuMaxTot > kQhdFuCapTot || m.fuMaxV > kQhdFuCapV || m.fuMaxF > kQhdFuCapF) return false;
+    if (m.fuMaxAll > kFusedCapC || m.fuMaxTot > kFusedCapTot || m.fuMaxV > kFusedCapV || m.fuMaxF > kFusedCapF) return false;
     const int cell = 7 * m.fuMaxAll + std::max(9 * m.fuMaxAll, 4 * m.fuMaxF) + m.fuMaxTot + 4 * m.fuMaxV;
     const int lds = 8 * cell + 6 * 128 * 4 + 4 * m.fuCapC;   // records, the own cells' parked face entries, the cell list
     if (lds > 65536) return false;
@@ -1183,18 +1178,8 @@ bool launchQhdAdvance(hipStream_t s, int stencil, bool usesPoints, const MeshVie
         pointInterpFastKernel<1><<<gridOf(m.nP), QGD_BLOCK, 0, s>>>(m, q.p, q.ptp);
         if (m.nBP) boundaryPointKernel<1><<<gridOf(m.nBP), QGD_BLOCK, 0, s>>>(m, q.pb, 1, q.ptp, 1, 0, -1);
     }
-    switch (stencil) {
-        case ST_REDUCED: face2<ST_REDUCED>(s, m, q, bc); break;
-        case ST_LSQ: face2<ST_LSQ>(s, m, q, bc); break;
-        case ST_GVP3: face2<ST_GVP3>(s, m, q, bc); break;
-        default: face2<ST_GVP2>(s, m, q, bc); break;
-    }
-    switch ((q.rotating ? QHD_ROT : 0) | (q.frozenT ? QHD_FROZEN : 0)) {
-        case 0: qhdCellUpdateKernel<0><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
-        case QHD_ROT: qhdCellUpdateKernel<QHD_ROT><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
-        case QHD_FROZEN: qhdCellUpdateKernel<QHD_FROZEN><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
-        default: qhdCellUpdateKernel<QHD_ROT | QHD_FROZEN><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); break;
-    }
+    face2(s, stencil, m, q, bc);
+    withMode<QHD_ROT, QHD_FROZEN>(q.rotating != 0, q.frozenT != 0, [&](auto M) { qhdCellUpdateKernel<M><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q); });
     bcValues(s, m, q, bc, q.frozenT != 0);
     if (needRef) qhdRefReadKernel<<<1, 1, 0, s>>>(q, localRefCell, refValue, shift);
     return false;
@@ -1210,18 +1195,8 @@ void launchQhdImplicitAdvance(hipStream_t s, int stencil, bool usesPoints, const
             pointInterpFastKernel<1><<<gridOf(m.nP), QGD_BLOCK, 0, s>>>(m, q.p, q.ptp);
             if (m.nBP) boundaryPointKernel<1><<<gridOf(m.nBP), QGD_BLOCK, 0, s>>>(m, q.pb, 1, q.ptp, 1, 0, -1);
         }
-        switch (stencil) {
-            case ST_REDUCED: face2<ST_REDUCED>(s, m, q, bc); break;
-            case ST_LSQ: face2<ST_LSQ>(s, m, q, bc); break;
-            case ST_GVP3: face2<ST_GVP3>(s, m, q, bc); break;
-            default: face2<ST_GVP2>(s, m, q, bc); break;
-        }
-        switch ((q.rotating ? QHD_ROT : 0) | (q.bValU ? QHD_LIST : 0)) {
-            case 0: qhdImplicitRhsKernel<0><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
-            case QHD_ROT: qhdImplicitRhsKernel<QHD_ROT><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
-            case QHD_LIST: qhdImplicitRhsKernel<QHD_LIST><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
-            default: qhdImplicitRhsKernel<QHD_ROT | QHD_LIST><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); break;
-        }
+        face2(s, stencil, m, q, bc);
+        withMode<QHD_ROT, QHD_LIST>(q.rotating != 0, q.bValU != nullptr, [&](auto M) { qhdImplicitRhsKernel<M><<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc); });
     } else {
         qhdImplicitStoreKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, validMask);   // (frozen T: the caller's mask leaves T out)
         bcValues(s, m, q, bc, q.frozenT != 0);

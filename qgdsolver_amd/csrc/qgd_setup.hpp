@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "qgd_fused_caps.hpp"
 #include "qgd_mesh.hpp"
 
 namespace qgd {
@@ -180,7 +181,6 @@ struct FusedBlocks {
 };
 // LDS a block's records may take so that three blocks (+ 3 KB of parked face entries each) share a CU's 160 KB: what an 8x4x4 brick needs
 constexpr int32_t kFusedLdsTarget = 48 * 360 + 32 * 288 + 72 * 225 + 24 * 288;
-constexpr int32_t kFusedCells = 128, kFusedCapC = 320, kFusedCapV = 256, kFusedCapF = 512, kFusedCapTot = 384;   // kFusedCapC: own + across-a-face cells
 FusedBlocks buildFusedBlocks(const StaticData& s);
 
 }  // namespace qgd

@@ -3,15 +3,18 @@
 
     python scripts/kernel_resources.py > profiles/kernel_resources.txt
         compiles qgdsolver_amd/csrc into a temporary directory with -Rpass-analysis=kernel-resource-usage and prints the table.
-    python scripts/kernel_resources.py --compare OLD.so NEW.so [--mnemonics] [--gained-parameter]
+    python scripts/kernel_resources.py --compare OLD.so NEW.so [--mnemonics] [--gained-parameter] [--multiset]
         disassembles the gfx950 code objects of two builds of the library kernel by kernel: lists the kernels only one of them has and
         those whose instructions differ (encodings and operands; with --mnemonics the sequence of mnemonics only, for a change that
         moves kernel-argument offsets).  Exit status 1 when a common kernel differs.  How a refactor shows that it left the device
         code alone.  --gained-parameter: a kernel of OLD that NEW only has with one more, trailing template argument is compared with
         the instantiation whose new argument is 0 (`k<3>` with `k<3, 0>`, `k` with `k<0>`): a compile-time flag was added and 0 is the
-        code as it was.
+        code as it was.  --multiset: also compares, for every common kernel, HOW MANY of each mnemonic it has (s_waitcnt and s_nop
+        left out) and lists the kernels where the counts differ: a change that shares or moves code without touching the arithmetic keeps
+        every count (the same FMA / mul / add instructions: the same contraction, the same bits).
 
 No GPU needed.  ROCM_PATH (default /opt/rocm) locates hipcc and the LLVM tools."""
+import collections
 import os
 import re
 import shutil
@@ -117,7 +120,7 @@ def as_before_the_flag(name):
     return head + name[m.end() - 1:]
 
 
-def compare(old, new, mnemonics, gained=False):
+def compare(old, new, mnemonics, gained=False, multiset=False):
     a, b = kernel_disassembly(old, mnemonics), kernel_disassembly(new, mnemonics)
     names = demangle(sorted(set(a) | set(b)))
     if gained:
@@ -140,10 +143,16 @@ def compare(old, new, mnemonics, gained=False):
     print(f"in both: {len(set(a) & set(b))}; same {what}: {len(set(a) & set(b)) - len(differ)}; different: {len(differ)}")
     for k in differ:
         print("   ", names[k], f"({len(a[k])} -> {len(b[k])} instructions)")
+    if multiset:
+        count = lambda ins: collections.Counter(i.split()[0] for i in ins if i.split()[0] not in ("s_waitcnt", "s_nop"))
+        odd = [(k, count(a[k]), count(b[k])) for k in differ if count(a[k]) != count(b[k])]
+        print(f"different multiset of mnemonics (s_waitcnt, s_nop left out): {len(odd)}")
+        for k, ca, cb in odd:
+            print("   ", names[k], " ".join(f"{m} {ca[m]}->{cb[m]}" for m in sorted(set(ca) | set(cb)) if ca[m] != cb[m]))
     return 1 if differ else 0
 
 
 if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "--compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3], "--mnemonics" in sys.argv[4:], "--gained-parameter" in sys.argv[4:]))
+        sys.exit(compare(sys.argv[2], sys.argv[3], "--mnemonics" in sys.argv[4:], "--gained-parameter" in sys.argv[4:], "--multiset" in sys.argv[4:]))
     resource_table()

@@ -160,27 +160,38 @@ def test_multigrid_and_jacobi_preconditioners_agree():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("implicit", [0, 1])
-def test_staged_face_passes_are_the_generic_walk_bit_for_bit(implicit, monkeypatch):
+@pytest.mark.parametrize("implicit,rotating", [pytest.param(0, False, id="0"), pytest.param(1, False, id="1"),
+                                               pytest.param(0, True, id="0-rotating"), pytest.param(1, True, id="1-rotating")])
+def test_staged_face_passes_are_the_generic_walk_bit_for_bit(implicit, rotating, monkeypatch):
     """qhdFace1/2TileKernel (the internal faces of a 128-face tile out of LDS, QGD_QHD_TILES default 1) against the generic
     qhdFace1/2Kernel (QGD_QHD_TILES=0): same expressions on the same values -- U, T, p and phi after 5 steps agree bit for bit on
     hexahedra (with a ragged last tile and row ends beyond the caps), on a jittered mesh with triangles and polygon faces, and on a
-    scrambled numbering (most tiles left to the generic kernel)."""
+    scrambled numbering (most tiles left to the generic kernel).  rotating: the kernels' Coriolis instantiations (set_srf with an
+    oblique omega; T is frozen there: it stays the initial field) on the first and the third of these meshes."""
     from test_config5_gpu import c5_mesh
-    scr = q.PolyMesh.box(12, 10, 8)
-    scr.renumber(np.random.default_rng(5).permutation(scr.nCells).astype(np.int32))
-    for tag, mesh in (("hex 37x11x5", q.PolyMesh.box(37, 11, 5)), ("hex 20^3 jittered", q.PolyMesh.box(20, 20, 20).jitter(0.15, seed=4)),
-                      ("triangles + polygons, Morton order", c5_mesh(16, 8 ** 3, poly=True)), ("scrambled labels", scr)):
+    meshes = [("hex 37x11x5", q.PolyMesh.box(37, 11, 5)), ("triangles + polygons, Morton order", c5_mesh(16, 8 ** 3, poly=True))]
+    if not rotating:
+        scr = q.PolyMesh.box(12, 10, 8)
+        scr.renumber(np.random.default_rng(5).permutation(scr.nCells).astype(np.int32))
+        meshes[1:1] = [("hex 20^3 jittered", q.PolyMesh.box(20, 20, 20).jitter(0.15, seed=4))]
+        meshes.append(("scrambled labels", scr))
+    for tag, mesh in meshes:
         res = {}
         for tiles in (0, 1):
             monkeypatch.setenv("QGD_QHD_TILES", str(tiles))
             dev = q.Device(mesh)
             ft = dev.face_tiles()
             c = qhdfoam.QHDFoamCase(dev, options(deltaT=1e-3, pTol=1e-10, implicitDiffusion=implicit))
+            if rotating:
+                c.set_srf((0.3, -0.5, 0.8))
+                assert c.srf_info()["rotating"] and c.srf_info()["frozenT"]
             cavity_bcs(c, mesh)
             c.set_fields(*initial(mesh))
+            T0 = c.field("T")
             c.step(5)
             res[tiles] = {k: c.field(k) for k in ("U", "T", "p", "phi")}
+            if rotating:
+                assert np.array_equal(res[tiles]["T"], T0), tag
             c.close(); dev.close()
         if not tag.startswith("scrambled"):
             assert ft["facesPerTile"] == 128 and ft["gatherTiles"] < ft["tiles"], (tag, ft)
