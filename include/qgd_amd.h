@@ -451,7 +451,7 @@ int qgd_qhd_case_set_bc(qgd_qhd_case_t c, int32_t patch, int32_t bcU, const doub
                         int32_t bcP, double valueP);
 int qgd_qhd_case_set_fields(qgd_qhd_case_t c, const double* U, const double* T, const double* p);
 int qgd_qhd_case_step(qgd_qhd_case_t c, int32_t nSteps);
-/* "U","T","p" (+ ".boundary"), face fields "phi","phiu","phiwo","tauQGDf" */
+/* "U","T","p" (+ ".boundary"), face fields "phi","phiu","phiwo","tauQGDf", "faceTerms" (4 nF, after a step: see the QHD run monitor) */
 int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int64_t outDoubles);
 /* info[0]=time, [1]=deltaT, [2..4]= iterations / initial / final normalised residual of the last pressure solve,
  * [5]=steps, [6]=multigrid levels, [7]=milliseconds of the last pressure solve */
@@ -1065,6 +1065,37 @@ int qgd_monitor_enable_species(qgd_monitor_t m);
 int qgd_monitor_species_layout(qgd_monitor_t m, int64_t offsets[QGD_MONITOR_SECTIONS], int64_t* nDoubles);
 /* Waits for the slot's event only (the one qgd_monitor_read waits for). */
 int qgd_monitor_species_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap);
+
+/* ---- run monitor of a QHD case (QHDFoam, SRFQHDFoam; qgd_qhd_monitor.hip) ------ */
+/* The same handle and the same rules for a resident QHD case: three launches and one small copy per sample on the device's stream,
+ * nothing written that the case reads, none of its launches changed, every sum a fixed tree (two samples of one state are bitwise
+ * equal), owned cells only (ghost cells of a shard are never counted, nor are patch faces they own), labels of the unsharded mesh as
+ * doubles.  qgd_monitor_layout / _sample / _read / _free serve the handle unchanged; qgd_monitor_enable_species on it is
+ * QGD_ERR_INVALID (a QHD case carries no species).  qgd_qhd_case_free frees the monitors still open on the case first (a later
+ * qgd_monitor_free of such a handle does nothing).  On a sharded case (qgd_qhd_case_step_sharded, qgd_qhd_case_step_phase) a sample
+ * between whole steps reports this shard's owned cells.
+ *
+ * Result block (doubles; qgd_monitor_layout gives the offsets of its QGD_MONITOR_SECTIONS sections):
+ *   0 header (8):     owned cells | flux state | nProbes | nPatches | cells with a non-finite value in any of U, T, p | lowest label
+ *                     among them (-1: none) | deltaT | flags: bit 0 rotating, bit 1 T frozen (qgd_qhd_case_set_srf)
+ *                     flux state 0: no step since qgd_qhd_case_set_fields -- patch fluxes and the continuity entries are NaN;
+ *                     1: explicit branch -- everything is reported; 2: implicitDiffusion -- the face terms hold the explicit part only:
+ *                     the volumetric flux and the continuity entries are reported, the four U / T flux columns are NaN
+ *   1 integrals (12): V | U_x V, U_y V, U_z V | T V | |U|^2/2 V | p V | B_x V, B_y V, B_z V | sum_c d_c | sum_c |d_c|, summed over the owned
+ *                     cells.  B is the body force as the NEXT step's cell update forms it from this state: beta T g, minus 2 omega ^ U on
+ *                     a rotating case.  d_c is the signed sum of phi over all faces of cell c (+ where the cell owns the face): entries
+ *                     10 and 11 are OpenFOAM's global and local continuity errors before the factor deltaT / sum V
+ *   2 extrema (16):   {min, its cell, max, its cell} of |U|, T, p and |d_c| / V_c over the owned cells whose state is finite; ties go to
+ *                     the lowest label; NaN and -1 when there is no such cell, and for the continuity row under flux state 0
+ *   3 probes (5 each):  Ux, Uy, Uz, T, p of the probe's cell (NaN where the label is -1)
+ *   4 patches (9 each): sum |Sf| | sum phi | the totals of the three net face terms of the U equation | that of the T equation (NaN when
+ *                     T is frozen) | sum p_b Sf (3).  The face terms are what the cell update of the last step consumed, so that with the
+ *                     integrals of successive samples and the body force they close the discrete balances of U and T to rounding.
+ * qgd_qhd_case_get_field knows "faceTerms" for the checks of these totals: the four net face terms by face label, 4 nF doubles,
+ * component-major; valid after a step (QGD_ERR_INVALID before); under implicitDiffusion the explicit part.
+ * This entry and that name were added without a change of QGD_ABI_VERSION (it stays 9: no struct grew, no existing entry changed its
+ * meaning); a host that must run against older builds looks the symbol up. */
+int qgd_qhd_monitor_create(qgd_qhd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,9 @@ directory on one MI355X.
 What the reference's ``main`` does per step -- updateFields.H, updateFluxes.H, QHDpEqn.H, QHDUEqn.H, QHDTEqn.H (either branch of
 implicitDiffusion; the reference's default is true), the reference level of p, runTime.write() -- is ``QHDFoamCase.step`` plus
 ``foamfile.write_qhd_time`` here.  Read from system/controlDict: startFrom/startTime, endTime, deltaT, writeControl (timeStep, or
-runTime/adjustableRunTime), writeInterval, timePrecision; adjustTimeStep is refused (the path's matrices are built once for the
-fixed deltaT).  One rank; a decomposed run goes through ``bench.py --workload qhd --gpus N`` / ``qgd_qhd_case_step_sharded``.
+runTime/adjustableRunTime), writeInterval, timePrecision, and of ``functions{}`` the types probes, fieldMinMax, qhdIntegrals, qhdPatchFluxes and
+qhdContinuityErrors (foamfile.read_qhd_functions; files under postProcessing/); adjustTimeStep is refused (the path's matrices are
+built once for the fixed deltaT).  One rank; a decomposed run goes through ``bench.py --workload qhd --gpus N`` / ``qgd_qhd_case_step_sharded``.
 """
 import argparse
 import os
@@ -16,6 +17,28 @@ import numpy as np
 
 from . import foamfile as ff
 from .QGDFoam import find_start_time, time_name
+
+
+def open_functions(cd, case, mesh, case_dir, t0_name, t0, log):
+    """(advance, functions) for the served entries of ``functions{}`` (foamfile.read_qhd_functions; shared with SRFQHDFoam): advance(n)
+    takes n steps, cut at the steps at which a function is due, each followed by one sample of the device monitor
+    (monitor.QHDFunctionObjects; read two samples late, flushed by functions.finish()).  Without served functions advance is the
+    case's own step and functions is None."""
+    specs = ff.read_qhd_functions(cd, warn=log)
+    if not specs:
+        return case.step, None
+    from .monitor import QHDFunctionObjects
+    functions = QHDFunctionObjects(case, specs, mesh, case_dir, t0_name, lambda g: g, np.arange(mesh.nCells), log=log)
+    taken = [0]
+
+    def advance(n):
+        while n > 0:
+            k = min(n, functions.next_due(taken[0]))
+            case.step(k)
+            taken[0] += k
+            n -= k
+            functions.after_step(taken[0], t0)
+    return advance, functions
 
 
 def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
@@ -56,12 +79,13 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
             + ", not from the old field as OpenFOAM does [QHDpEqn.H L45]: same systems, same tolerances, same answer to those tolerances -- but "
             "'Initial residual' and 'No Iterations' below are NOT comparable with a reference QHDFoam log.  QGD_QHD_PEXTRAP=0 "
             "QGD_IMPL_XEXTRAP=0 restore OpenFOAM's start values.")
+    advance, functions = open_functions(cd, case, mesh, case_dir, t0_name, t0, log)
     done = 0
     wall0 = _time.perf_counter()
     written = []
     while done < total:
         n = min(chunk, total - done)
-        case.step(n)
+        advance(n)
         done += n
         info = case.info()
         t = t0 + info["time"]
@@ -85,6 +109,8 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
             name = time_name(t, precision)
             ff.write_qhd_time(case, case_dir, name, bcs)
             written.append(name)
+    if functions is not None:
+        functions.finish()
     log("End")
     return dev, case, written
 

@@ -6,8 +6,8 @@ QHDpEqn.H, QHDUEqn.H (either branch of implicitDiffusion), the reference level o
 ``set_srf`` plus ``foamfile.write_srf_time`` here.  The loop has no QHDTEqn.H: T stays as read.  There is no centrifugal term, as in
 the reference: p is the reduced pressure.  Read from constant/SRFProperties: SRFModel rpm, origin, axis, rpmCoeffs.rpm; the velocity
 file is Urel; walls at rest in the inertial frame are SRFVelocity patches with ``relative no``.  system/controlDict as for QHDFoam:
-startFrom/startTime, endTime, deltaT, writeControl (timeStep, or runTime/adjustableRunTime), writeInterval, timePrecision;
-adjustTimeStep is refused.  Written per time: Urel, T, p and Uabs = Urel + omega ^ (C - origin).  One rank.
+startFrom/startTime, endTime, deltaT, writeControl (timeStep, or runTime/adjustableRunTime), writeInterval, timePrecision,
+``functions{}`` as QHDFoam serves it; adjustTimeStep is refused.  Written per time: Urel, T, p and Uabs = Urel + omega ^ (C - origin).  One rank.
 """
 import argparse
 import os
@@ -18,6 +18,7 @@ import numpy as np
 
 from . import foamfile as ff
 from .QGDFoam import find_start_time, time_name
+from .QHDFoam import open_functions
 
 
 def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
@@ -57,12 +58,13 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
             + ", not from the old field as OpenFOAM does [QHDpEqn.H L45]: same systems, same tolerances, same answer to those tolerances -- but "
             "'Initial residual' and 'No Iterations' below are NOT comparable with a reference SRFQHDFoam log.  QGD_QHD_PEXTRAP=0 "
             "QGD_IMPL_XEXTRAP=0 restore OpenFOAM's start values.")
+    advance, functions = open_functions(cd, case, mesh, case_dir, t0_name, t0, log)
     done = 0
     wall0 = _time.perf_counter()
     written = []
     while done < total:
         n = min(chunk, total - done)
-        case.step(n)
+        advance(n)
         done += n
         info = case.info()
         t = t0 + info["time"]
@@ -86,6 +88,8 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
             name = time_name(t, precision)
             ff.write_srf_time(case, case_dir, name, srf, bcs)
             written.append(name)
+    if functions is not None:
+        functions.finish()
     log("End")
     return dev, case, written
 

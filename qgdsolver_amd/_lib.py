@@ -236,6 +236,7 @@ SIGNATURES = {
     "qgd_case_timing_reset": (C.c_int, [handle]),
     "qgd_case_device_bytes": (C.c_int, [handle, c_int64_p]),
     "qgd_monitor_create": (C.c_int, [handle, C.POINTER(MonitorSpec), handle_p]),
+    "qgd_qhd_monitor_create": (C.c_int, [handle, C.POINTER(MonitorSpec), handle_p]),
     "qgd_monitor_layout": (C.c_int, [handle, c_int64_p, c_int64_p, c_int32_p]),
     "qgd_monitor_sample": (C.c_int, [handle, C.c_int32]),
     "qgd_monitor_read": (C.c_int, [handle, C.c_int32, c_double_p, C.c_int64, c_double_p, c_int64_p]),

@@ -1678,8 +1678,10 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
     QGD_CATCH
 }
 // the handle of a run monitor (its entries: "run monitors" below); here because a case frees the monitors still open on it
+struct qgd_qhd_case_s;
 struct qgd_monitor_s {
     qgd_case_s* c = nullptr;
+    qgd_qhd_case_s* qc = nullptr;   // the kind of the handle: a monitor of a QHD case (qgd_qhd_monitor_create) has qc and no c
     MonitorView view{};
     DeviceArena arena;
     double* result = nullptr;    // device: one result block (the copy into a slot follows the fold in stream order)
@@ -1703,12 +1705,13 @@ static void monitorDestroy(qgd_monitor_s* m) {
     g_monitors.erase(std::remove(g_monitors.begin(), g_monitors.end(), m), g_monitors.end());
     delete m;
 }
-static void freeMonitorsOf(qgd_case_s* c) {
-    if (c->monitors.empty()) return;
-    (void)hipStreamSynchronize(c->stream());
-    for (qgd_monitor_s* m : c->monitors) monitorDestroy(m);
-    c->monitors.clear();
+static void freeMonitors(std::vector<qgd_monitor_s*>& monitors, hipStream_t stream) {
+    if (monitors.empty()) return;
+    (void)hipStreamSynchronize(stream);
+    for (qgd_monitor_s* m : monitors) monitorDestroy(m);
+    monitors.clear();
 }
+static void freeMonitorsOf(qgd_case_s* c) { freeMonitors(c->monitors, c->stream()); }
 int qgd_case_free(qgd_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
@@ -2791,7 +2794,12 @@ struct qgd_qhd_case_s {
     double time = 0, lastIter = 0, lastRes0 = 0, lastRes = 0, lastSolveMs = 0;
     int64_t steps = 0;
     double* bValUDev = nullptr;            // qgd_qhd_case_set_bc_values: 3 per boundary face (view.bValU while some patch's valList names U)
+    std::vector<qgd_monitor_s*> monitors;  // qgd_qhd_monitor_create: freed with the case where still open
 };
+// what the entries of a monitor need of its case, whichever kind it is
+static qgd_device_s* monitorDevice(const qgd_monitor_s* m) { return m->qc ? m->qc->dev : m->c->dev; }
+static hipStream_t monitorStream(const qgd_monitor_s* m) { return m->qc ? m->qc->dev->stream : m->c->stream(); }
+static std::vector<qgd_monitor_s*>& monitorsOfCase(qgd_monitor_s* m) { return m->qc ? m->qc->monitors : m->c->monitors; }
 
 int qgd_qhd_options_default(qgd_qhd_options* o) {
     if (!o) return fail(QGD_ERR_INVALID, "null argument");
@@ -2875,6 +2883,7 @@ int qgd_qhd_case_create(qgd_device_t d, const qgd_qhd_options* opt, qgd_qhd_case
 int qgd_qhd_case_free(qgd_qhd_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
+    freeMonitors(c->monitors, c->dev->stream);
     if (c->solver) pressureSolverFree(c->solver);
     if (c->implSolver) { (void)hipStreamSynchronize(c->dev->stream); implicitSolverFree(c->implSolver); }
     c->arena.release();
@@ -3353,6 +3362,20 @@ int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int6
     else if (!bnd && s == "phiu") { direct = q.phiu; count = m.nF; }
     else if (!bnd && s == "phiwo") { direct = q.phiwo; count = m.nF; }
     else if (!bnd && s == "tauQGDf") { direct = c->tauF; count = m.nF; }
+    else if (!bnd && s == "faceTerms") {
+        // QhdView::F by face label: the four net face terms of the U (3) and T equations, component-major (an internal face keeps its
+        // terms at its slot-major position MeshView::fpos, a patch face at its label); under implicitDiffusion the explicit part
+        if (c->steps == 0) return fail(QGD_ERR_INVALID, "qgd_qhd_case_get_field: faceTerms hold nothing before the first step after qgd_qhd_case_set_fields");
+        const size_t nF = (size_t)m.nF;
+        if ((int64_t)(4 * nF) > outDoubles) return fail(QGD_ERR_INVALID, "output too small");
+        std::vector<double> F(4 * nF);
+        std::vector<int32_t> fpos((size_t)m.nIF);
+        if (nF) HIP_CHECK(hipMemcpy(F.data(), q.F, sizeof(double) * 4 * nF, hipMemcpyDeviceToHost));
+        if (m.nIF) HIP_CHECK(hipMemcpy(fpos.data(), m.fpos, sizeof(int32_t) * (size_t)m.nIF, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 4; ++k)
+            for (size_t f = 0; f < nF; ++f) out[(size_t)k * nF + f] = F[(size_t)k * nF + (f < (size_t)m.nIF ? (size_t)fpos[f] : f)];
+        return QGD_OK;
+    }
     if (direct) {
         if (count > outDoubles) return fail(QGD_ERR_INVALID, "output too small");
         if (count) d->ws.d2h(out, direct, sizeof(double) * (size_t)count, d->stream);
@@ -4016,25 +4039,25 @@ static const char* patchTypeWord(int t) {
     }
 }
 
-int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
-    QGD_TRY
-    if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_monitor_create: null argument");
-    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_create: call qgd_case_set_fields first (a monitor samples the state the case holds)");
+// the widths of a monitor's rows: the QGD block's, or the QHD block's (qgd_qhd_monitor.hip)
+struct MonitorShape { int sums, extrema, cellRow, probeRow, patchRow; };
+// the checks of a specification and the handle both kinds of monitor share; `who` names the entry in the messages.  Returns an error code
+// (out untouched) or QGD_OK with the handle filled in but for its case.
+static int monitorBuild(const std::string& who, qgd_device_s* d, const qgd_monitor_spec* spec, const MonitorShape& shape, qgd_monitor_s** out) {
     if (spec->nProbes < 0 || spec->nPatches < 0 || (spec->nProbes > 0 && !spec->probeCells) || (spec->nPatches > 0 && !spec->patches))
-        return fail(QGD_ERR_INVALID, "qgd_monitor_create: bad specification (negative count or null list)");
-    const qgd_device_s* d = c->dev;
+        return fail(QGD_ERR_INVALID, who + ": bad specification (negative count or null list)");
     const MeshView& m = d->view;
     for (int32_t i = 0; i < spec->nProbes; ++i)
         if (spec->probeCells[i] < -1 || spec->probeCells[i] >= m.nC)
-            return fail(QGD_ERR_INVALID, "qgd_monitor_create: probe " + std::to_string(i) + ": cell label " + std::to_string(spec->probeCells[i]) +
+            return fail(QGD_ERR_INVALID, who + ": probe " + std::to_string(i) + ": cell label " + std::to_string(spec->probeCells[i]) +
                                              " is out of range [0, " + std::to_string(m.nC) + ") (-1 = not on this rank)");
     for (int32_t i = 0; i < spec->nPatches; ++i) {
         const int32_t p = spec->patches[i];
         if (p < 0 || p >= (int32_t)d->patches.size())
-            return fail(QGD_ERR_INVALID, "qgd_monitor_create: patch index " + std::to_string(p) + " is out of range [0, " + std::to_string(d->patches.size()) + ")");
+            return fail(QGD_ERR_INVALID, who + ": patch index " + std::to_string(p) + " is out of range [0, " + std::to_string(d->patches.size()) + ")");
         const int t = d->patches[p].type;
         if (t == QGD_PATCH_HALO || t == QGD_PATCH_EMPTY || t == QGD_PATCH_CYCLIC || t == QGD_PATCH_WEDGE)
-            return fail(QGD_ERR_INVALID, "qgd_monitor_create: patch " + std::to_string(p) + " ('" + d->patches[p].name + "') is a " + patchTypeWord(t) +
+            return fail(QGD_ERR_INVALID, who + ": patch " + std::to_string(p) + " ('" + d->patches[p].name + "') is a " + patchTypeWord(t) +
                                              " patch: it carries no boundary fluxes of its own (patch totals are formed on real patches only)");
     }
     HIP_CHECK(hipSetDevice(d->deviceId));
@@ -4052,7 +4075,7 @@ int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t
         int32_t inChunk = 0;
         for (int32_t f = pt.start; f < pt.start + pt.size; ++f) {
             const int32_t b = f - m.nIF;
-            if (b < 0 || b >= m.nBF) throw std::invalid_argument("qgd_monitor_create: patch '" + pt.name + "' has faces outside the boundary range");
+            if (b < 0 || b >= m.nBF) throw std::invalid_argument(who + ": patch '" + pt.name + "' has faces outside the boundary range");
             if (fkind[b] == FK_SKIP || own[b] < d->ownedBegin || own[b] >= d->ownedEnd) continue;
             if (inChunk == 256) { chunkStart.push_back((int32_t)faceList.size()); inChunk = 0; }
             faceList.push_back(b);
@@ -4063,20 +4086,19 @@ int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t
     }
     qgd_monitor_s* mo = new qgd_monitor_s();
     try {
-        mo->c = c;
         MonitorView& v = mo->view;
         DeviceArena& a = mo->arena;
         v.ownedBegin = d->ownedBegin; v.ownedEnd = d->ownedEnd;
         v.cellGlobal = a.upload(d->cellGlobal); v.cellGlobalOffset = d->cellGlobalOffset;
-        v.cellPart = a.alloc<double>((size_t)QGD_MONITOR_BLOCKS * QGD_MONITOR_CELL_ROW);
+        v.cellPart = a.alloc<double>((size_t)QGD_MONITOR_BLOCKS * shape.cellRow);
         v.nProbes = spec->nProbes;
         v.probeCell = a.upload(std::vector<int32_t>(spec->probeCells, spec->probeCells + spec->nProbes));
         v.nPatches = spec->nPatches; v.nChunks = (int32_t)chunkStart.size() - 1;
         v.faceList = a.upload(faceList); v.chunkStart = a.upload(chunkStart); v.patchChunk = a.upload(patchChunk);
-        v.patchPart = a.alloc<double>((size_t)std::max(1, v.nChunks) * QGD_MONITOR_PATCH_ROW);
-        v.off[0] = 0; v.off[1] = 8; v.off[2] = v.off[1] + QGD_MONITOR_SUMS; v.off[3] = v.off[2] + 4 * QGD_MONITOR_EXTREMA;
-        v.off[4] = v.off[3] + (int64_t)QGD_MONITOR_PROBE_ROW * v.nProbes;
-        mo->nDoubles = v.off[4] + (int64_t)QGD_MONITOR_PATCH_ROW * v.nPatches;
+        v.patchPart = a.alloc<double>((size_t)std::max(1, v.nChunks) * shape.patchRow);
+        v.off[0] = 0; v.off[1] = 8; v.off[2] = v.off[1] + shape.sums; v.off[3] = v.off[2] + 4 * shape.extrema;
+        v.off[4] = v.off[3] + (int64_t)shape.probeRow * v.nProbes;
+        mo->nDoubles = v.off[4] + (int64_t)shape.patchRow * v.nPatches;
         mo->result = a.alloc<double>((size_t)mo->nDoubles);
         HIP_CHECK(hipHostMalloc((void**)&mo->host, sizeof(double) * (size_t)mo->nDoubles * QGD_MONITOR_SLOTS, hipHostMallocDefault));
         for (int k = 0; k < QGD_MONITOR_SLOTS; ++k) HIP_CHECK(hipEventCreateWithFlags(&mo->ev[k], hipEventDisableTiming));
@@ -4087,6 +4109,35 @@ int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t
         delete mo;
         throw;
     }
+    *out = mo;
+    return QGD_OK;
+}
+int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
+    QGD_TRY
+    if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_monitor_create: null argument");
+    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_create: call qgd_case_set_fields first (a monitor samples the state the case holds)");
+    static const MonitorShape shape{QGD_MONITOR_SUMS, QGD_MONITOR_EXTREMA, QGD_MONITOR_CELL_ROW, QGD_MONITOR_PROBE_ROW, QGD_MONITOR_PATCH_ROW};
+    qgd_monitor_s* mo = nullptr;
+    const int rc = monitorBuild("qgd_monitor_create", c->dev, spec, shape, &mo);
+    if (rc) return rc;
+    mo->c = c;
+    g_monitors.push_back(mo);
+    c->monitors.push_back(mo);
+    *out = mo;
+    return QGD_OK;
+    QGD_CATCH
+}
+// the monitor of a QHD case (qgd_qhd_monitor.hip): the same handle, served by the entries below
+int qgd_qhd_monitor_create(qgd_qhd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
+    QGD_TRY
+    if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_qhd_monitor_create: null argument");
+    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_qhd_monitor_create: call qgd_qhd_case_set_fields first (a monitor samples the state the case holds)");
+    static const MonitorShape shape{QGD_QHD_MONITOR_SUMS, QGD_QHD_MONITOR_EXTREMA, QGD_QHD_MONITOR_CELL_ROW, QGD_QHD_MONITOR_PROBE_ROW,
+                                    QGD_QHD_MONITOR_PATCH_ROW};
+    qgd_monitor_s* mo = nullptr;
+    const int rc = monitorBuild("qgd_qhd_monitor_create", c->dev, spec, shape, &mo);
+    if (rc) return rc;
+    mo->qc = c;
     g_monitors.push_back(mo);
     c->monitors.push_back(mo);
     *out = mo;
@@ -4104,6 +4155,20 @@ int qgd_monitor_sample(qgd_monitor_t m, int32_t slot) {
     QGD_TRY
     if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: not an open monitor (a monitor is freed with its case)");
     if (slot < 0 || slot >= QGD_MONITOR_SLOTS) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: slot must be 0.." + std::to_string(QGD_MONITOR_SLOTS - 1));
+    if (m->qc) {   // a QHD case: three launches and the copy on the device's stream
+        qgd_qhd_case_s* qc = m->qc;
+        if (!qc->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: the case's boundary conditions changed: call qgd_qhd_case_set_fields first");
+        HIP_CHECK(hipSetDevice(qc->dev->deviceId));
+        const int fluxState = qc->steps == 0 ? 0 : (qc->view.implicit ? 2 : 1);
+        hipStream_t st = qc->dev->stream;
+        (void)hipGetLastError();
+        launchQhdMonitorSample(st, m->view, qc->dev->view, qc->view, fluxState, m->result);   // (the view as it stands now: the fused advance swaps c4)
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(m->host + (size_t)slot * (size_t)m->nDoubles, m->result, sizeof(double) * (size_t)m->nDoubles, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipEventRecord(m->ev[slot], st));
+        m->sampled[slot] = true; m->time[slot] = qc->time; m->step[slot] = qc->steps;
+        return QGD_OK;
+    }
     qgd_case_s* c = m->c;
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: the case's boundary conditions or coefficients changed: call qgd_case_set_fields first");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
@@ -4130,11 +4195,11 @@ int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, do
     if (slot < 0 || slot >= QGD_MONITOR_SLOTS) return fail(QGD_ERR_INVALID, "qgd_monitor_read: slot must be 0.." + std::to_string(QGD_MONITOR_SLOTS - 1));
     if (!out || cap < m->nDoubles) return fail(QGD_ERR_INVALID, "qgd_monitor_read: output too small (qgd_monitor_layout gives the doubles of a result block)");
     if (!m->sampled[slot]) return fail(QGD_ERR_INVALID, "qgd_monitor_read: slot " + std::to_string(slot) + " was never sampled");
-    HIP_CHECK(hipSetDevice(m->c->dev->deviceId));
+    HIP_CHECK(hipSetDevice(monitorDevice(m)->deviceId));
     HIP_CHECK(hipEventSynchronize(m->ev[slot]));
     const double* src = m->host + (size_t)slot * (size_t)(m->nDoubles + m->spDoubles);
     std::copy(src, src + m->nDoubles, out);
-    if (time) *time = m->c->opt.adjustTimeStep ? src[7] : m->time[slot];
+    if (time) *time = (m->c && m->c->opt.adjustTimeStep) ? src[7] : m->time[slot];   // (a QHD case steps at a fixed deltaT; its header[7] holds flags)
     if (step) *step = m->step[slot];
     return QGD_OK;
     QGD_CATCH
@@ -4143,6 +4208,7 @@ int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, do
 int qgd_monitor_enable_species(qgd_monitor_t m) {
     QGD_TRY
     if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: not an open monitor (a monitor is freed with its case)");
+    if (m->qc) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: the monitor of a QHD case has no species block (QHDFoam and SRFQHDFoam carry no species)");
     qgd_case_s* c = m->c;
     if (!c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: the case carries no species (qgd_case_set_species)");
     if (m->spDoubles) return QGD_OK;
@@ -4195,10 +4261,10 @@ int qgd_monitor_species_read(qgd_monitor_t m, int32_t slot, double* out, int64_t
 }
 int qgd_monitor_free(qgd_monitor_t m) {
     if (!monitorLive(m)) return QGD_OK;   // null, or freed with its case
-    qgd_case_s* c = m->c;
-    (void)hipSetDevice(c->dev->deviceId);
-    (void)hipStreamSynchronize(c->stream());
-    c->monitors.erase(std::remove(c->monitors.begin(), c->monitors.end(), m), c->monitors.end());
+    (void)hipSetDevice(monitorDevice(m)->deviceId);
+    (void)hipStreamSynchronize(monitorStream(m));
+    std::vector<qgd_monitor_s*>& open = monitorsOfCase(m);
+    open.erase(std::remove(open.begin(), open.end(), m), open.end());
     monitorDestroy(m);
     return QGD_OK;
 }

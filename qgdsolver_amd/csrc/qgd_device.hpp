@@ -458,6 +458,16 @@ void launchQhdHalo(hipStream_t s, const QhdView& q, double* direction, int kind,
                    double* buf, bool pack);
 void launchQhdHaloFloat(hipStream_t s, float* vec, const int32_t* cells, int nCells, double* buf, bool pack);
 void launchQhdExtract(hipStream_t s, int64_t n, const double* rec4, int field, double* out);
+// ---- run monitor of a QHD case (qgd_qhd_monitor.hip; qgd_qhd_monitor_create of include/qgd_amd.h) -----------------------
+// MonitorView as for the QGD monitor (owned range, labels, probe cells, face list and chunk table), with rows of these widths
+#define QGD_QHD_MONITOR_SUMS 12          // V, U V (3), T V, |U|^2/2 V, p V, BdFrc V (3), sum d_c, sum |d_c|
+#define QGD_QHD_MONITOR_EXTREMA 4        // |U|, T, p, |d_c| / V_c: {min, label, max, label} each
+#define QGD_QHD_MONITOR_CELL_ROW (QGD_QHD_MONITOR_SUMS + 4 * QGD_QHD_MONITOR_EXTREMA + 2)
+#define QGD_QHD_MONITOR_PROBE_ROW 5      // Ux, Uy, Uz, T, p
+#define QGD_QHD_MONITOR_PATCH_ROW 9      // |Sf|, phi, the four net face terms of QhdView::F, p_b Sf (3)
+// fluxState: 0 no step since set_fields (phi and F hold nothing: patch fluxes and continuity entries NaN), 1 explicit branch,
+// 2 implicitDiffusion (F holds the explicit part only: its four columns NaN)
+void launchQhdMonitorSample(hipStream_t s, const MonitorView& mv, const MeshView& m, const QhdView& q, int fluxState, double* out);
 
 // ---- scalarTransportQHDFoam case resident on the device (qgd_scalar.hip) ------------------------------------------------
 // U, rho and tauQGDf never change [scalarTransportQHDFoam.C L86-125: thermo.correct() and updateFluxes.H run once], so everything that

@@ -24,6 +24,7 @@
 // pressure matrix are those of start-up.  State: cell records {Ux,Uy,Uz,T} (32 B) and p separately (the solver's vector).
 #include "../../include/qgd_amd.h"
 #include "qgd_device.hpp"
+#include "qgd_qhd_dev.hpp"
 #include "qgd_stencil_dev.hpp"
 
 #include <type_traits>
@@ -68,35 +69,8 @@ __device__ __forceinline__ void qhdBoundaryVals4(const MeshView& m, const PatchB
     if (perComponent && (bc.ptype == QGD_PATCH_SYMMETRYPLANE || bc.ptype == QGD_PATCH_SYMMETRY)) v.sn[0] = v.sn[1] = v.sn[2] = 0.0;
 }
 
-// Compile-time modes of the step kernels (template parameter MODE).  MODE 0 is QHDFoam; the other instantiations are what
-// qgd_qhd_case_set_srf / qgd_qhd_case_set_bc_values switch on: no uniform branch goes into the bodies.
-//   QHD_ROT     SRFQHDFoam's body force (QhdBdFrc).  No centrifugal term, as in the listing: p is the reduced pressure.
-//               gradWf = fvsc::grad(W) of updateFields.H L45 is not formed: nothing reads it.
-//   QHD_FROZEN  no QHDTEqn.H in the loop [SRFQHDFoam.C L93-147]: T and T.boundary are not written
-//   QHD_LIST    a fixedValue patch may carry one velocity per face (QhdView::bValU)
-enum : int { QHD_ROT = 1, QHD_FROZEN = 2, QHD_LIST = 4 };
-
-// BdFrc of one cell or patch face from its {Ux,Uy,Uz,T}: beta*T*g [updateFields.H L66], in the rotating frame beta*T*g - 2 (omega ^ U)
-// with U the relative velocity [SRFQHDFoam/updateFields.H L73].  Per cell from the OLD U and T of that cell; on a patch face the same
-// expression on the patch values U_b, T_b (BdFrc is a calculated field: qgdInterpolate takes its patch value).  The rotating form is
-// evaluated where the object is made, all three components; the plain one component by component where [k] asks for it: the order in which
-// the kernels always formed them (another order gives other registers and, in the rotating kernels, other FMA contractions)
-template <int MODE>
-struct QhdBdFrc {
-    const QhdView& q;
-    const double* u4;
-    double B[3];
-    static __device__ __forceinline__ void rot(const QhdView& q, const double* u4, double B[3]) {
-        const double bT = q.beta * u4[3];
-        B[0] = bT * q.g[0] - 2.0 * (q.omega[1] * u4[2] - q.omega[2] * u4[1]);
-        B[1] = bT * q.g[1] - 2.0 * (q.omega[2] * u4[0] - q.omega[0] * u4[2]);
-        B[2] = bT * q.g[2] - 2.0 * (q.omega[0] * u4[1] - q.omega[1] * u4[0]);
-    }
-    __device__ __forceinline__ QhdBdFrc(const QhdView& q_, const double* u4_) : q(q_), u4(u4_) {
-        if (MODE & QHD_ROT) rot(q, u4, B);
-    }
-    __device__ __forceinline__ double operator[](const int k) const { return (MODE & QHD_ROT) ? B[k] : (q.beta * u4[3]) * q.g[k]; }
-};
+// The compile-time modes of the step kernels (QHD_ROT, QHD_FROZEN, QHD_LIST) and QhdBdFrc, the body force of either solver, stand in
+// qgd_qhd_dev.hpp: the QHD run monitor forms the same force.
 // face pass 2 behind its operands [QHDUEqn.H L37-84, QHDTEqn.H L65-91], one component per call: the loops over the components stand in
 // the three kernels (measured: with the loops in one function here, qhdFusedAdvanceKernel spills 53 VGPRs for 6).  o4 / n4: {U,T} of the
 // owner and of the neighbour cell or patch face; implicit: implicitDiffusion, the laplacians sit in the matrix (fvm::laplacian, QHDUEqn.H L54, QHDTEqn.H L73-76)

@@ -270,6 +270,25 @@ def read_functions(control_dict, warn=print, species=None):
     in ``fields`` next to the flow fields, and ``qgdSpeciesIntegrals`` and ``qgdSpeciesPatchFluxes`` (patches) are served; in a case
     without species those two types are an error that names the function (a species name among ``fields`` is then just a field that is
     not served: warned about by name and left out, as any unknown field is)."""
+    return _read_functions(control_dict, warn, FUNCTION_TYPES, ("qgdPatchFluxes", "qgdSpeciesPatchFluxes"), species)
+
+
+# the function objects the QHDFoam and SRFQHDFoam applications serve (monitor.QHDFunctionObjects): type -> the fields it may name
+QHD_FUNCTION_TYPES = {"probes": ("U", "T", "p"), "fieldMinMax": ("U", "mag(U)", "T", "p", "contErr"), "qhdIntegrals": (), "qhdPatchFluxes": (),
+                      "qhdContinuityErrors": ()}
+
+
+def read_qhd_functions(control_dict, warn=print):
+    """``read_functions`` for a QHDFoam or SRFQHDFoam case: ``probes`` (fields out of U T p, probeLocations), ``fieldMinMax`` (fields out
+    of U T p contErr; U is its magnitude, contErr is |sum of phi over the cell's faces| / V), and the project's own ``qhdIntegrals``,
+    ``qhdPatchFluxes`` (patches) and ``qhdContinuityErrors``, each every ``writeInterval`` steps.  Anything else gets one warning line
+    that names it and is skipped."""
+    return _read_functions(control_dict, warn, QHD_FUNCTION_TYPES, ("qhdPatchFluxes",), None)
+
+
+def _read_functions(control_dict, warn, types, patch_types, species):
+    """the parsing read_functions and read_qhd_functions share: ``types`` maps a served type to the fields it may name, ``patch_types``
+    are the types that need ``patches``"""
     species = [str(n) for n in (species or [])]
     funcs = control_dict.get("functions", {})
     out = []
@@ -279,8 +298,8 @@ def read_functions(control_dict, warn=print, species=None):
         if not isinstance(d, dict):
             continue
         typ = str(d.get("type", ""))
-        if typ not in FUNCTION_TYPES:
-            warn(f"functions: '{name}' has type '{typ}', which is not served (served: {', '.join(FUNCTION_TYPES)}): skipped")
+        if typ not in types:
+            warn(f"functions: '{name}' has type '{typ}', which is not served (served: {', '.join(types)}): skipped")
             continue
         if not _truthy(d.get("enabled", "yes")):
             continue
@@ -294,10 +313,10 @@ def read_functions(control_dict, warn=print, species=None):
         if typ in SPECIES_FUNCTION_TYPES and not species:
             raise FoamFileError(f"functions: '{name}': type {typ} needs a case with species (thermophysicalProperties lists none)")
         spec = dict(name=str(name), type=typ, interval=interval)
-        if FUNCTION_TYPES[typ]:
+        if types[typ]:
             fields = d.get("fields", [])
             fields = [str(f) for f in (fields if isinstance(fields, (list, tuple)) else [fields])]
-            can = FUNCTION_TYPES[typ] + tuple(n for n in species if n not in FUNCTION_TYPES[typ])
+            can = types[typ] + tuple(n for n in species if n not in types[typ])
             served = [f for f in fields if f in can]
             for f in fields:
                 if f not in served:
@@ -316,7 +335,7 @@ def read_functions(control_dict, warn=print, species=None):
                 warn(f"functions: '{name}': no probeLocations: skipped")
                 continue
             spec["probeLocations"] = locs
-        if typ in ("qgdPatchFluxes", "qgdSpeciesPatchFluxes"):
+        if typ in patch_types:
             patches = d.get("patches", [])
             patches = [str(p) for p in (patches if isinstance(patches, (list, tuple)) else [patches])]
             if not patches:

@@ -9,6 +9,11 @@ With ``species=True`` on a case that carries species every sample holds the spec
 ``read()`` then also gives, per species in the case's order and with the inert one included, ``speciesMass`` [nS], ``speciesMin`` /
 ``speciesMinCell`` / ``speciesMax`` / ``speciesMaxCell`` [nS], ``speciesProbes`` [nProbes, nS], ``speciesPatchFlux`` [nPatches, nS], and
 the scalars ``speciesFluxState``, ``speciesSumDefect``, ``speciesNonFinite``, ``speciesFirstNonFinite``.
+
+A resident QHDFoam / SRFQHDFoam case has a ``QHDMonitor`` (``QHDFoamCase.monitor``; qgd_qhd_monitor_create) on the same slot ring: its
+samples (``unpack_qhd``) carry the integrals of U, T, kinetic energy, p and of the body force, the continuity errors of the pressure solve,
+the extrema of |U|, T, p and of the cells' continuity error, probes, and per patch the totals of phi and of the net face terms;
+``QHDFunctionObjects`` serves the ``functions{}`` of the two applications from it.
 """
 import collections
 import ctypes as C
@@ -23,12 +28,21 @@ EXTREMA_FIELDS = ("rho", "p", "T", "magU", "Mach")
 PROBE_COLUMNS = ("rho", "Ux", "Uy", "Uz", "p", "T", "e")
 PATCH_COLUMNS = ("area", "massFlux", "momentumFlux_x", "momentumFlux_y", "momentumFlux_z", "energyFlux",
                  "pressureForce_x", "pressureForce_y", "pressureForce_z")
+# the result block of a QHD monitor (QHDMonitor, unpack_qhd)
+QHD_INTEGRALS = ("volume", "U_x", "U_y", "U_z", "T", "kineticEnergy", "p", "bodyForce_x", "bodyForce_y", "bodyForce_z",
+                 "continuityGlobal", "continuityLocal")
+QHD_EXTREMA_FIELDS = ("magU", "T", "p", "contErr")
+QHD_PROBE_COLUMNS = ("Ux", "Uy", "Uz", "T", "p")
+QHD_PATCH_COLUMNS = ("area", "volumetricFlux", "UFlux_x", "UFlux_y", "UFlux_z", "TFlux",
+                     "pressureForce_x", "pressureForce_y", "pressureForce_z")
 
 
-class Monitor:
-    def __init__(self, case, probes=None, patches=None, species=False):
-        """probes: cell labels of the case's device mesh (-1: not on this rank, its row reads NaN); patches: patch indices; species: the
-        samples carry the species block too (a case with set_species)"""
+class _MonitorBase:
+    """what the monitors of either case kind share: the handle, the layout and the ring of four slots.  ``_create`` names the entry that
+    makes the handle; qgd_monitor_layout / _sample / _read / _free serve both kinds."""
+    _create = None
+
+    def __init__(self, case, probes=None, patches=None):
         self.case = case
         self.probes = np.ascontiguousarray(probes if probes is not None else [], dtype=np.int32).reshape(-1)
         self.patches = np.ascontiguousarray(patches if patches is not None else [], dtype=np.int32).reshape(-1)
@@ -37,7 +51,7 @@ class Monitor:
         spec.probeCells = self.probes.ctypes.data_as(L.c_int32_p) if self.probes.size else None
         spec.patches = self.patches.ctypes.data_as(L.c_int32_p) if self.patches.size else None
         h = C.c_void_p()
-        L.check(L.lib.qgd_monitor_create(case._h, C.byref(spec), C.byref(h)), "qgd_monitor_create")
+        L.check(getattr(L.lib, self._create)(case._h, C.byref(spec), C.byref(h)), self._create)
         self._handle = L.NativeHandle(h, L.lib.qgd_monitor_free)
         off = (C.c_int64 * L.MONITOR_SECTIONS)()
         n, cap = C.c_int64(), C.c_int32()
@@ -45,15 +59,6 @@ class Monitor:
         self.offsets, self.n_doubles, self.grid_cap = [int(x) for x in off], int(n.value), int(cap.value)
         self._pending = collections.deque()   # sampled and not yet read, oldest first
         self._last = -1
-        self.species, self.species_offsets, self.species_doubles = bool(species), None, 0
-        if self.species:
-            try:
-                L.check(L.lib.qgd_monitor_enable_species(h), "qgd_monitor_enable_species")
-                L.check(L.lib.qgd_monitor_species_layout(h, off, C.byref(n)), "qgd_monitor_species_layout")
-            except Exception:
-                self._handle.free()
-                raise
-            self.species_offsets, self.species_doubles = [int(x) for x in off], int(n.value)
 
     @property
     def _h(self):
@@ -84,6 +89,35 @@ class Monitor:
             self._pending.remove(slot)
         return out, t.value, int(step.value)
 
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._handle.free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Monitor(_MonitorBase):
+    _create = "qgd_monitor_create"
+
+    def __init__(self, case, probes=None, patches=None, species=False):
+        """probes: cell labels of the case's device mesh (-1: not on this rank, its row reads NaN); patches: patch indices; species: the
+        samples carry the species block too (a case with set_species)"""
+        super().__init__(case, probes, patches)
+        h, off, n = self._h, (C.c_int64 * L.MONITOR_SECTIONS)(), C.c_int64()
+        self.species, self.species_offsets, self.species_doubles = bool(species), None, 0
+        if self.species:
+            try:
+                L.check(L.lib.qgd_monitor_enable_species(h), "qgd_monitor_enable_species")
+                L.check(L.lib.qgd_monitor_species_layout(h, off, C.byref(n)), "qgd_monitor_species_layout")
+            except Exception:
+                self._handle.free()
+                raise
+            self.species_offsets, self.species_doubles = [int(x) for x in off], int(n.value)
+
     def read_species_raw(self, slot):
         """the species block of a slot (the sample qgd_monitor_read of that slot gives)"""
         out = np.empty(max(self.species_doubles, 1))[:self.species_doubles]
@@ -99,15 +133,15 @@ class Monitor:
             s.update(unpack_species(self.read_species_raw(slot), self.species_offsets))
         return s
 
-    def close(self):
-        if getattr(self, "_handle", None):
-            self._handle.free()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class QHDMonitor(_MonitorBase):
+    """the run monitor of a resident QHDFoam / SRFQHDFoam case (``QHDFoamCase.monitor``; qgd_qhd_monitor_create): the same ring of four
+    slots, the QHD result block (``unpack_qhd``)"""
+    _create = "qgd_qhd_monitor_create"
+
+    def read(self, slot=None):
+        raw, t, step = self.read_raw(slot)
+        return unpack_qhd(raw, self.offsets, t, step)
 
 
 def unpack(raw, offsets, time, step):
@@ -123,6 +157,26 @@ def unpack(raw, offsets, time, step):
                 nonFinite=int(hd[4]), firstNonFinite=int(hd[5]),
                 integrals=integ.copy(), volume=float(integ[0]), mass=float(integ[1]), momentum=integ[2:5].copy(),
                 totalEnergy=float(integ[5]), internalEnergy=float(integ[6]), kineticEnergy=float(integ[7]),
+                min=ex[:, 0].copy(), minCell=ex[:, 1].astype(np.int64), max=ex[:, 2].copy(), maxCell=ex[:, 3].astype(np.int64),
+                probes=probes.copy(), patchArea=patches[:, 0].copy(), patchFlux=patches[:, 1:6].copy(),
+                patchPressureForce=patches[:, 6:9].copy(), raw=raw)
+
+
+def unpack_qhd(raw, offsets, time, step):
+    """named arrays of one result block of a QHD monitor (the layout of include/qgd_amd.h, qgd_qhd_monitor_create); the keys are those of
+    ``unpack`` wherever the meaning is the same"""
+    o = offsets
+    hd, integ = raw[o[0]:o[1]], raw[o[1]:o[2]]
+    ex = raw[o[2]:o[3]].reshape(len(QHD_EXTREMA_FIELDS), 4)
+    n_probes, n_patches = int(hd[2]), int(hd[3])
+    probes = raw[o[3]:o[4]].reshape(n_probes, len(QHD_PROBE_COLUMNS))
+    patches = raw[o[4]:o[4] + n_patches * len(QHD_PATCH_COLUMNS)].reshape(n_patches, len(QHD_PATCH_COLUMNS))
+    flags = int(hd[7])
+    return dict(kind="qhd", time=time, step=step, deltaT=float(hd[6]), ownedCells=int(hd[0]), fluxState=int(hd[1]),
+                # fluxState 0: no step yet (patch fluxes and continuity entries NaN); 1: everything; 2: implicitDiffusion (the U / T flux columns NaN)
+                nonFinite=int(hd[4]), firstNonFinite=int(hd[5]), rotating=bool(flags & 1), frozenT=bool(flags & 2),
+                integrals=integ.copy(), volume=float(integ[0]), momentum=integ[1:4].copy(), bodyForce=integ[7:10].copy(),
+                continuityGlobal=float(integ[10]), continuityLocal=float(integ[11]),
                 min=ex[:, 0].copy(), minCell=ex[:, 1].astype(np.int64), max=ex[:, 2].copy(), maxCell=ex[:, 3].astype(np.int64),
                 probes=probes.copy(), patchArea=patches[:, 0].copy(), patchFlux=patches[:, 1:6].copy(),
                 patchPressureForce=patches[:, 6:9].copy(), raw=raw)
@@ -157,6 +211,12 @@ def combine(parts):
     if len(parts) == 1:
         return out
     _combine_block(out, parts, _FLOW_KEYS)
+    if parts[0].get("kind") == "qhd":   # the derived keys of unpack_qhd; the flags and the flux state are the same on every shard
+        integ = out["integrals"]
+        out.update(volume=float(integ[0]), bodyForce=integ[7:10].copy(), continuityGlobal=float(integ[10]), continuityLocal=float(integ[11]),
+                   ownedCells=sum(p["ownedCells"] for p in parts))
+        out.pop("raw", None)
+        return out
     for key in ("volume", "mass", "totalEnergy", "internalEnergy", "kineticEnergy"):
         out[key] = float(out["integrals"][INTEGRALS.index(key)])
     out["ownedCells"] = sum(p["ownedCells"] for p in parts)
@@ -337,10 +397,27 @@ class FunctionObjects:
     it back to the label in the case files; ``gather`` (None on one rank) is all_gather_object.  ``species``: the case's species names;
     a function that names one of them, or one of SPECIES_TYPES, makes the monitor carry the species block."""
 
+    _PROBES, _MINMAX = ProbesWriter, FieldMinMaxWriter      # the writers of the two types every application serves
+
+    def _open_monitor(self, case, probes, patches, species):
+        return Monitor(case, probes=probes, patches=patches, species=species)
+
+    def _own_writer(self, s, out_dir, file_label, patch_rows, species):
+        """the writer of one of the application's own types (root only)"""
+        if s["type"] == "qgdIntegrals":
+            return IntegralsWriter(out_dir, s, file_label)
+        if s["type"] == "qgdPatchFluxes":
+            return PatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]])
+        if s["type"] == "qgdSpeciesIntegrals":
+            return SpeciesIntegralsWriter(out_dir, s, file_label, species)
+        if s["type"] == "qgdSpeciesPatchFluxes":
+            return SpeciesPatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]], species)
+        return None
+
     def __init__(self, case, specs, file_mesh, case_dir, start_name, local_of, file_label, is_root=True, gather=None, log=print, species=None):
         self.specs, self.is_root, self.gather = specs, is_root, gather
         species = list(species or [])
-        flow_fields = set(ProbesWriter._COLS) | set(FieldMinMaxWriter._INDEX)
+        flow_fields = set(self._PROBES._COLS) | set(self._MINMAX._INDEX)
         wanted = [(s["name"], f) for s in specs for f in s.get("fields", []) if f not in flow_fields] + [(s["name"], s["type"]) for s in specs if s["type"] in SPECIES_TYPES]
         for name, what in wanted:
             if what not in species and what not in SPECIES_TYPES:
@@ -358,7 +435,7 @@ class FunctionObjects:
                 if p not in patch_rows:
                     patch_rows[p] = len(patches)
                     patches.append(names.index(p))
-        self.monitor = Monitor(case, probes=[local_of(int(c)) if c >= 0 else -1 for c in cells], patches=patches, species=bool(wanted))
+        self.monitor = self._open_monitor(case, [local_of(int(c)) if c >= 0 else -1 for c in cells], patches, bool(wanted))
         self.writers = []
         centres = file_mesh.array("C").reshape(-1, 3)
         at = 0
@@ -373,20 +450,14 @@ class FunctionObjects:
                     for i, c in enumerate(cells[rows]):
                         if c < 0:
                             log(f"functions: '{s['name']}': probe {i} is outside the mesh: its column reads nan")
-                    w = ProbesWriter(out_dir, s, cells[rows] >= 0, species)
+                    w = self._PROBES(out_dir, s, cells[rows] >= 0, species)
                     w.rows = rows
             elif not is_root:
                 pass
             elif s["type"] == "fieldMinMax":
-                w = FieldMinMaxWriter(out_dir, s, centres, file_label, species)
-            elif s["type"] == "qgdIntegrals":
-                w = IntegralsWriter(out_dir, s, file_label)
-            elif s["type"] == "qgdPatchFluxes":
-                w = PatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]])
-            elif s["type"] == "qgdSpeciesIntegrals":
-                w = SpeciesIntegralsWriter(out_dir, s, file_label, species)
-            elif s["type"] == "qgdSpeciesPatchFluxes":
-                w = SpeciesPatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]], species)
+                w = self._MINMAX(out_dir, s, centres, file_label, species)
+            else:
+                w = self._own_writer(s, out_dir, file_label, patch_rows, species)
             self.writers.append(w)
         self._waiting = collections.deque()   # (due specs) of the samples not read yet
 
@@ -424,3 +495,83 @@ class FunctionObjects:
         while self._waiting:
             self._flush_one()
         self.monitor.close()
+
+
+# ---- the function objects of a QHDFoam / SRFQHDFoam case (foamfile.read_qhd_functions gives the specifications) ---------------------------
+class QHDProbesWriter(ProbesWriter):
+    """the probes layout on the probe rows of a QHD sample"""
+    _COLS = {"U": (0, 1, 2), "T": (3,), "p": (4,)}
+
+
+class QHDFieldMinMaxWriter(FieldMinMaxWriter):
+    """fieldMinMax.dat on the extrema of a QHD sample; contErr is |sum of phi over the cell's faces| / V"""
+    _INDEX = {"U": 0, "mag(U)": 0, "T": 1, "p": 2, "contErr": 3}
+
+
+class QHDIntegralsWriter:
+    """volIntegrals.dat: the time, the twelve integrals of the QHD block, the count of non-finite cells and the first of them (-1: none)"""
+
+    def __init__(self, out_dir, spec, file_label):
+        self.file_label = file_label
+        self.table = _Table(os.path.join(out_dir, "volIntegrals.dat"),
+                            ["# Volume integrals over the mesh", "# " + "\t".join(("Time",) + QHD_INTEGRALS + ("nonFiniteCells", "firstNonFiniteCell"))])
+
+    def write(self, t, s):
+        first = int(self.file_label[s["firstNonFinite"]]) if s["firstNonFinite"] >= 0 else -1
+        self.table.row("\t".join([_num(t)] + [_num(v) for v in s["integrals"]] + [str(int(s["nonFinite"])), str(first)]))
+
+
+class QHDPatchFluxWriter:
+    """patchFluxes.dat: the time, then per patch its area, the volumetric flux, the totals of the net face terms of the U (3) and T
+    equations (what the cell update consumed in the step that produced the state) and sum p_b Sf"""
+
+    def __init__(self, out_dir, spec, rows):
+        self.rows = rows                    # rows of the monitor's patch table, in the order of spec["patches"]
+        cols = ["Time"] + [f"{p}:{c}" for p in spec["patches"] for c in QHD_PATCH_COLUMNS]
+        self.table = _Table(os.path.join(out_dir, "patchFluxes.dat"), ["# Patch totals of phi and of the net face terms", "# " + "\t".join(cols)])
+
+    def write(self, t, s):
+        row = [_num(t)]
+        for r in self.rows:
+            row += [_num(s["patchArea"][r])] + [_num(v) for v in s["patchFlux"][r]] + [_num(v) for v in s["patchPressureForce"][r]]
+        self.table.row("\t".join(row))
+
+
+class ContinuityErrorsWriter:
+    """continuityErrors.dat, what OpenFOAM's continuityErrs.H prints: the time, sum local = deltaT sum |d_c| / sum V, global =
+    deltaT sum d_c / sum V, the cumulative global error over the rows written, and the largest |d_c| / V_c with its cell
+    (d_c: the signed sum of phi over the faces of cell c)"""
+
+    def __init__(self, out_dir, spec, file_label):
+        self.file_label, self.cumulative = file_label, 0.0
+        cols = ("Time", "sumLocal", "global", "cumulative", "max(contErr)", "cell(max)")
+        self.table = _Table(os.path.join(out_dir, "continuityErrors.dat"), ["# Continuity errors of the pressure solve", "# " + "\t".join(cols)])
+
+    def write(self, t, s):
+        local, glob = continuity_errors(s)
+        self.cumulative += glob
+        c = int(s["maxCell"][3])
+        self.table.row("\t".join([_num(t), _num(local), _num(glob), _num(self.cumulative), _num(s["max"][3]), str(int(self.file_label[c]) if c >= 0 else -1)]))
+
+
+def continuity_errors(s):
+    """(sum local, global) continuity errors of a QHD sample, as OpenFOAM scales them"""
+    scale = s["deltaT"] / s["volume"]
+    return scale * s["continuityLocal"], scale * s["continuityGlobal"]
+
+
+class QHDFunctionObjects(FunctionObjects):
+    """FunctionObjects for a QHDFoam or SRFQHDFoam run: one QHDMonitor, the QHD writers"""
+    _PROBES, _MINMAX = QHDProbesWriter, QHDFieldMinMaxWriter
+
+    def _open_monitor(self, case, probes, patches, species):
+        return QHDMonitor(case, probes=probes, patches=patches)
+
+    def _own_writer(self, s, out_dir, file_label, patch_rows, species):
+        if s["type"] == "qhdIntegrals":
+            return QHDIntegralsWriter(out_dir, s, file_label)
+        if s["type"] == "qhdPatchFluxes":
+            return QHDPatchFluxWriter(out_dir, s, [patch_rows[p] for p in s["patches"]])
+        if s["type"] == "qhdContinuityErrors":
+            return ContinuityErrorsWriter(out_dir, s, file_label)
+        return None

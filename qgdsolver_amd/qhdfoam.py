@@ -180,6 +180,7 @@ class QHDFoamCase:
         L.check(L.lib.qgd_qhd_case_create(dev._h, C.byref(self.options), C.byref(h)), "qgd_qhd_case_create")
         self._handle = L.NativeHandle(h, L.lib.qgd_qhd_case_free)
         dev.adopt(self._handle)
+        self._monitor_handles = []
 
     def set_bc(self, patch, U=("zeroGradient", None), T=("zeroGradient", None), p=("zeroGradient", None)):
         vu = np.asarray(U[1] if U[1] is not None else (0.0, 0.0, 0.0), dtype=np.float64)
@@ -218,6 +219,10 @@ class QHDFoamCase:
         L.check(L.lib.qgd_qhd_case_step(self._h, int(n)), "qgd_qhd_case_step")
 
     def field(self, name):
+        if name == "faceTerms":   # the four net face terms of the U (3) and T equations by face label, after a step: (4, nFaces)
+            out = np.zeros((4, self.mesh.nFaces))
+            L.check(L.lib.qgd_qhd_case_get_field(self._h, name.encode(), out.ctypes.data_as(L.c_double_p), out.size), f"qgd_qhd_case_get_field({name})")
+            return out
         base = name[:-len(".boundary")] if name.endswith(".boundary") else name
         nc = 3 if base == "U" else 1
         n = self.mesh.nBoundaryFaces if name.endswith(".boundary") else (self.mesh.nFaces if base in ("phi", "phiu", "phiwo", "tauQGDf")
@@ -366,6 +371,17 @@ class QHDFoamCase:
     def halo_unpack(self, slot, kind, dev_ptr):
         L.check(L.lib.qgd_qhd_case_halo_unpack(self._h, int(slot), int(kind), C.c_void_p(dev_ptr)), "qgd_qhd_case_halo_unpack")
 
+    def monitor(self, probes=None, patches=None):
+        """a run monitor of this case (monitor.QHDMonitor; qgd_qhd_monitor_create): volume integrals of U, T, |U|^2/2, p and of the body
+        force the next step applies, the continuity error of the pressure solve, extrema with their cells, the first non-finite cell, the
+        values at ``probes`` (cell labels of this device's mesh, -1 = not on this rank) and, over ``patches`` (indices of real patches), the
+        totals of phi and of the net face terms of the U and T equations, formed on the device by ``sample()`` and fetched by ``read()``.
+        After set_fields.  The monitor is freed with the case where still open."""
+        from .monitor import QHDMonitor
+        m = QHDMonitor(self, probes=probes, patches=patches)
+        self._monitor_handles = [h for h in self._monitor_handles if h.value] + [m._handle]
+        return m
+
     def info(self):
         a = (C.c_double * 8)()
         L.check(L.lib.qgd_qhd_case_info(self._h, a), "qgd_qhd_case_info")
@@ -384,6 +400,9 @@ class QHDFoamCase:
 
     def close(self):
         if getattr(self, "_handle", None):
+            for h in getattr(self, "_monitor_handles", ()):   # a monitor keeps a pointer to its case: freed before it (NativeHandle: once)
+                h.free()
+            self._monitor_handles = []
             self._handle.free()
 
     def __del__(self):
