@@ -4039,8 +4039,6 @@ static const char* patchTypeWord(int t) {
     }
 }
 
-// the widths of a monitor's rows: the QGD block's, or the QHD block's (qgd_qhd_monitor.hip)
-struct MonitorShape { int sums, extrema, cellRow, probeRow, patchRow; };
 // the checks of a specification and the handle both kinds of monitor share; `who` names the entry in the messages.  Returns an error code
 // (out untouched) or QGD_OK with the handle filled in but for its case.
 static int monitorBuild(const std::string& who, qgd_device_s* d, const qgd_monitor_spec* spec, const MonitorShape& shape, qgd_monitor_s** out) {
@@ -4090,7 +4088,7 @@ static int monitorBuild(const std::string& who, qgd_device_s* d, const qgd_monit
         DeviceArena& a = mo->arena;
         v.ownedBegin = d->ownedBegin; v.ownedEnd = d->ownedEnd;
         v.cellGlobal = a.upload(d->cellGlobal); v.cellGlobalOffset = d->cellGlobalOffset;
-        v.cellPart = a.alloc<double>((size_t)QGD_MONITOR_BLOCKS * shape.cellRow);
+        v.cellPart = a.alloc<double>((size_t)QGD_MONITOR_BLOCKS * shape.cellRow());
         v.nProbes = spec->nProbes;
         v.probeCell = a.upload(std::vector<int32_t>(spec->probeCells, spec->probeCells + spec->nProbes));
         v.nPatches = spec->nPatches; v.nChunks = (int32_t)chunkStart.size() - 1;
@@ -4112,36 +4110,33 @@ static int monitorBuild(const std::string& who, qgd_device_s* d, const qgd_monit
     *out = mo;
     return QGD_OK;
 }
+// what the two create entries share: `who` names the entry, `setFields` the call it asks for first; `monitors` is the case's own list
+static int monitorCreate(const char* who, const char* setFields, qgd_device_s* d, bool fieldsSet, std::vector<qgd_monitor_s*>& monitors,
+                         const qgd_monitor_spec* spec, const MonitorShape& shape, qgd_monitor_s** out) {
+    if (!fieldsSet) return fail(QGD_ERR_INVALID, std::string(who) + ": call " + setFields + " first (a monitor samples the state the case holds)");
+    qgd_monitor_s* mo = nullptr;
+    const int rc = monitorBuild(who, d, spec, shape, &mo);
+    if (rc) return rc;
+    g_monitors.push_back(mo);
+    monitors.push_back(mo);
+    *out = mo;
+    return QGD_OK;
+}
 int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
     QGD_TRY
     if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_monitor_create: null argument");
-    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_create: call qgd_case_set_fields first (a monitor samples the state the case holds)");
-    static const MonitorShape shape{QGD_MONITOR_SUMS, QGD_MONITOR_EXTREMA, QGD_MONITOR_CELL_ROW, QGD_MONITOR_PROBE_ROW, QGD_MONITOR_PATCH_ROW};
-    qgd_monitor_s* mo = nullptr;
-    const int rc = monitorBuild("qgd_monitor_create", c->dev, spec, shape, &mo);
-    if (rc) return rc;
-    mo->c = c;
-    g_monitors.push_back(mo);
-    c->monitors.push_back(mo);
-    *out = mo;
-    return QGD_OK;
+    const int rc = monitorCreate("qgd_monitor_create", "qgd_case_set_fields", c->dev, c->fieldsSet, c->monitors, spec, kFlowMonitorShape, out);
+    if (rc == QGD_OK) (*out)->c = c;
+    return rc;
     QGD_CATCH
 }
 // the monitor of a QHD case (qgd_qhd_monitor.hip): the same handle, served by the entries below
 int qgd_qhd_monitor_create(qgd_qhd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
     QGD_TRY
     if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_qhd_monitor_create: null argument");
-    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_qhd_monitor_create: call qgd_qhd_case_set_fields first (a monitor samples the state the case holds)");
-    static const MonitorShape shape{QGD_QHD_MONITOR_SUMS, QGD_QHD_MONITOR_EXTREMA, QGD_QHD_MONITOR_CELL_ROW, QGD_QHD_MONITOR_PROBE_ROW,
-                                    QGD_QHD_MONITOR_PATCH_ROW};
-    qgd_monitor_s* mo = nullptr;
-    const int rc = monitorBuild("qgd_qhd_monitor_create", c->dev, spec, shape, &mo);
-    if (rc) return rc;
-    mo->qc = c;
-    g_monitors.push_back(mo);
-    c->monitors.push_back(mo);
-    *out = mo;
-    return QGD_OK;
+    const int rc = monitorCreate("qgd_qhd_monitor_create", "qgd_qhd_case_set_fields", c->dev, c->fieldsSet, c->monitors, spec, kQhdMonitorShape, out);
+    if (rc == QGD_OK) (*out)->qc = c;
+    return rc;
     QGD_CATCH
 }
 int qgd_monitor_layout(qgd_monitor_t m, int64_t offsets[QGD_MONITOR_SECTIONS], int64_t* nDoubles, int32_t* gridCap) {

@@ -256,22 +256,25 @@ void launchSpeciesAdvanceImplicit(hipStream_t s, int stencil, const MeshView& m,
 int speciesBatchWidth();
 
 // ---- run monitors (qgd_monitor.hip; qgd_monitor_* of include/qgd_amd.h) ---------------------------------------------------------
-#define QGD_MONITOR_BLOCKS 1024      // most workgroups of monitorCellKernel (its lanes stride over the owned cells beyond that)
-#define QGD_MONITOR_SUMS 8           // V, rho V, rho U V (3), rho E V, rho e V, rho |U|^2/2 V
-#define QGD_MONITOR_EXTREMA 5        // rho, p, T, |U|, Mach: {min, label, max, label} each
-#define QGD_MONITOR_CELL_ROW (QGD_MONITOR_SUMS + 4 * QGD_MONITOR_EXTREMA + 2)
-#define QGD_MONITOR_PROBE_ROW 7      // rho, Ux, Uy, Uz, p, T, e
-#define QGD_MONITOR_PATCH_ROW 9      // |Sf|, the five net fluxes, p_b Sf (3)
+#define QGD_MONITOR_BLOCKS 1024      // most workgroups of a cell kernel (its lanes stride over the owned cells beyond that)
+// the widths of a block's rows: what the kernels of a kind are instantiated with and what qgd_capi.cpp sizes the handle by
+struct MonitorShape {
+    int sums, extrema, probeRow, patchRow;   // integrals; fields with {min, label, max, label} each; columns of a probe row, of a patch row
+    constexpr int cellRow() const { return sums + 4 * extrema + 2; }   // a workgroup's partial row: + non-finite count, lowest label
+};
+// sums: V, rho V, rho U V (3), rho E V, rho e V, rho |U|^2/2 V; extrema: rho, p, T, |U|, Mach; probes: rho, Ux, Uy, Uz, p, T, e;
+// patches: |Sf|, the five net fluxes, p_b Sf (3)
+constexpr MonitorShape kFlowMonitorShape{8, 5, 7, 9};
 struct MonitorView {
     int32_t ownedBegin, ownedEnd;
     const int32_t* cellGlobal; int64_t cellGlobalOffset;   // labels of the unsharded mesh (nullptr: local label + offset)
-    double* cellPart;                                      // QGD_MONITOR_BLOCKS rows of QGD_MONITOR_CELL_ROW
+    double* cellPart;                                      // QGD_MONITOR_BLOCKS rows of MonitorShape::cellRow()
     int32_t nProbes; const int32_t* probeCell;             // local labels, -1: not on this device
     int32_t nPatches, nChunks;
     const int32_t* faceList;                               // boundary-face indices, sorted by requested patch
     const int32_t* chunkStart;                             // nChunks + 1 offsets into faceList: <= 256 faces of one patch each
     const int32_t* patchChunk;                             // nPatches + 1: the chunks of a patch are consecutive
-    double* patchPart;                                     // nChunks rows of QGD_MONITOR_PATCH_ROW
+    double* patchPart;                                     // nChunks rows of MonitorShape::patchRow
     int64_t off[5];                                        // sections of the result block: header, integrals, extrema, probes, patches
 };
 // fluxState: 0 no assembly yet (patch fluxes NaN), 1 all five, 2 implicitDiffusion (mass only)
@@ -460,11 +463,9 @@ void launchQhdHaloFloat(hipStream_t s, float* vec, const int32_t* cells, int nCe
 void launchQhdExtract(hipStream_t s, int64_t n, const double* rec4, int field, double* out);
 // ---- run monitor of a QHD case (qgd_qhd_monitor.hip; qgd_qhd_monitor_create of include/qgd_amd.h) -----------------------
 // MonitorView as for the QGD monitor (owned range, labels, probe cells, face list and chunk table), with rows of these widths
-#define QGD_QHD_MONITOR_SUMS 12          // V, U V (3), T V, |U|^2/2 V, p V, BdFrc V (3), sum d_c, sum |d_c|
-#define QGD_QHD_MONITOR_EXTREMA 4        // |U|, T, p, |d_c| / V_c: {min, label, max, label} each
-#define QGD_QHD_MONITOR_CELL_ROW (QGD_QHD_MONITOR_SUMS + 4 * QGD_QHD_MONITOR_EXTREMA + 2)
-#define QGD_QHD_MONITOR_PROBE_ROW 5      // Ux, Uy, Uz, T, p
-#define QGD_QHD_MONITOR_PATCH_ROW 9      // |Sf|, phi, the four net face terms of QhdView::F, p_b Sf (3)
+// sums: V, U V (3), T V, |U|^2/2 V, p V, BdFrc V (3), sum d_c, sum |d_c|; extrema: |U|, T, p, |d_c| / V_c; probes: Ux, Uy, Uz, T, p;
+// patches: |Sf|, phi, the four net face terms of QhdView::F, p_b Sf (3)
+constexpr MonitorShape kQhdMonitorShape{12, 4, 5, 9};
 // fluxState: 0 no step since set_fields (phi and F hold nothing: patch fluxes and continuity entries NaN), 1 explicit branch,
 // 2 implicitDiffusion (F holds the explicit part only: its four columns NaN)
 void launchQhdMonitorSample(hipStream_t s, const MonitorView& mv, const MeshView& m, const QhdView& q, int fluxState, double* out);

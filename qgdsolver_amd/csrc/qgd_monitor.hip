@@ -13,20 +13,23 @@
 #include <cstdint>
 
 #include "qgd_device.hpp"
-#include "qgd_monitor_dev.hpp"   // the folds and the {value, label} pairs, shared with the species block
+#include "qgd_monitor_dev.hpp"   // the row stores, the folds and the "none" rules every block shares
 
 namespace qgd {
 
+namespace {
+constexpr MonitorShape SH = kFlowMonitorShape;
+}
+
 // ---- cells -------------------------------------------------------------------------------------------------------------------------
-// row of QGD_MONITOR_CELL_ROW doubles per workgroup: 8 sums | 5 x {min, label, max, label} | non-finite count, lowest label
+// row of SH.cellRow() doubles per workgroup: 8 sums | 5 x {min, label, max, label} | non-finite count, lowest label
 __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorCellKernel(const MonitorView mv, const MeshView m, const CaseView c, const GasModel g) {
     __shared__ double sh[8];
-    double s[QGD_MONITOR_SUMS];
+    double s[SH.sums];
 #pragma unroll
-    for (int k = 0; k < QGD_MONITOR_SUMS; ++k) s[k] = 0.0;
-    ArgVal lo[QGD_MONITOR_EXTREMA], hi[QGD_MONITOR_EXTREMA];
-#pragma unroll
-    for (int k = 0; k < QGD_MONITOR_EXTREMA; ++k) { lo[k] = ArgVal{INFINITY, QGD_MON_NOLABEL}; hi[k] = ArgVal{-INFINITY, QGD_MON_NOLABEL}; }
+    for (int k = 0; k < SH.sums; ++k) s[k] = 0.0;
+    ArgVal lo[SH.extrema], hi[SH.extrema];
+    noExtrema(lo, hi);
     double bad = 0.0, badLabel = QGD_MON_NOLABEL;
     const int64_t stride = (int64_t)gridDim.x * QGD_MON_BLOCK;
     for (int64_t i = (int64_t)mv.ownedBegin + (int64_t)blockIdx.x * QGD_MON_BLOCK + threadIdx.x; i < mv.ownedEnd; i += stride) {
@@ -45,48 +48,26 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorCellKernel(const Monitor
         s[6] += a.rho * a.e * V;
         s[7] += a.rho * ke * V;
         if (!(isFiniteD(a.rho) && isFiniteD(a.p) && isFiniteD(a.e) && isFiniteD(a.ux) && isFiniteD(a.uy) && isFiniteD(a.uz))) {
-            bad += 1.0;
-            badLabel = fmin(badLabel, label);
+            markNonFinite(bad, badLabel, label);
             continue;   // extrema are taken over the cells whose state is finite
         }
         const double magU = sqrt(u2);
-        const double val[QGD_MONITOR_EXTREMA] = {a.rho, a.p, a.e / g.Cv, magU, magU / cs};
+        const double val[SH.extrema] = {a.rho, a.p, a.e / g.Cv, magU, magU / cs};
 #pragma unroll
-        for (int k = 0; k < QGD_MONITOR_EXTREMA; ++k) {
-            if (!isFiniteD(val[k])) continue;
-            if (val[k] < lo[k].v) lo[k] = ArgVal{val[k], label};   // ascending labels per lane: the first one met stays on a tie
-            if (val[k] > hi[k].v) hi[k] = ArgVal{val[k], label};
-        }
+        for (int k = 0; k < SH.extrema; ++k) keepFinite(lo[k], hi[k], val[k], label);
     }
-    double* row = mv.cellPart + (size_t)blockIdx.x * QGD_MONITOR_CELL_ROW;
-#pragma unroll
-    for (int k = 0; k < QGD_MONITOR_SUMS; ++k) {
-        const double r = blockFold<OpSum>(s[k], sh);
-        if (threadIdx.x == 0) row[k] = r;
-    }
-#pragma unroll
-    for (int k = 0; k < QGD_MONITOR_EXTREMA; ++k) {
-        const ArgVal a = blockFoldArg<false>(lo[k], sh);
-        const ArgVal b = blockFoldArg<true>(hi[k], sh);
-        if (threadIdx.x == 0) {
-            double* e = row + QGD_MONITOR_SUMS + 4 * k;
-            e[0] = a.v; e[1] = a.l; e[2] = b.v; e[3] = b.l;
-        }
-    }
-    const double nb = blockFold<OpSum>(bad, sh);
-    const double lb = blockFold<OpMin>(badLabel, sh);
-    if (threadIdx.x == 0) { row[QGD_MONITOR_SUMS + 4 * QGD_MONITOR_EXTREMA] = nb; row[QGD_MONITOR_SUMS + 4 * QGD_MONITOR_EXTREMA + 1] = lb; }
+    storeCellRow(s, lo, hi, bad, badLabel, mv.cellPart + (size_t)blockIdx.x * SH.cellRow(), sh);
 }
 
 // ---- patch faces -------------------------------------------------------------------------------------------------------------------
-// one workgroup per chunk (<= 256 consecutive entries of the face list, all of one patch); row of QGD_MONITOR_PATCH_ROW doubles:
+// one workgroup per chunk (<= 256 consecutive entries of the face list, all of one patch); row of SH.patchRow doubles:
 // |Sf|, the five net fluxes, p_b Sf
 __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorPatchKernel(const MonitorView mv, const MeshView m, const CaseView c) {
     __shared__ double sh[4];
     const int first = mv.chunkStart[blockIdx.x], n = mv.chunkStart[blockIdx.x + 1] - first;
-    double s[QGD_MONITOR_PATCH_ROW];
+    double s[SH.patchRow];
 #pragma unroll
-    for (int k = 0; k < QGD_MONITOR_PATCH_ROW; ++k) s[k] = 0.0;
+    for (int k = 0; k < SH.patchRow; ++k) s[k] = 0.0;
     if ((int)threadIdx.x < n) {
         const int b = mv.faceList[first + threadIdx.x];   // boundary face index
         const size_t f = (size_t)m.nIF + b;
@@ -96,93 +77,48 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorPatchKernel(const Monito
         const double pb = c.bA[b].p;
         s[6] = pb * m.Sx[f]; s[7] = pb * m.Sy[f]; s[8] = pb * m.Sz[f];
     }
-    double* row = mv.patchPart + (size_t)blockIdx.x * QGD_MONITOR_PATCH_ROW;
-#pragma unroll
-    for (int k = 0; k < QGD_MONITOR_PATCH_ROW; ++k) {
-        const double r = blockFold<OpSum>(s[k], sh);
-        if (threadIdx.x == 0) row[k] = r;
-    }
+    storePatchRow(s, mv.patchPart + (size_t)blockIdx.x * SH.patchRow, sh);
 }
 
 // ---- fold --------------------------------------------------------------------------------------------------------------------------
-// thread t takes rows t, t + 256, ... in ascending order, then the block tree: fixed for a given grid and chunk table
+// header: owned cells, fluxState, probes, patches, non-finite cells, the first of them | deltaT, the one before
 __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorFoldKernel(const MonitorView mv, const CaseView c, const GasModel g, const int nCellRows,
                                                                   const int fluxState, double* __restrict__ out) {
     __shared__ double sh[8];
     const int t = threadIdx.x;
-    const double nan = __builtin_nan("");
-    // header
     double* hd = out + mv.off[0];
     double* in = out + mv.off[1];
-    for (int k = 0; k < QGD_MONITOR_SUMS; ++k) {
-        double x = 0.0;
-        for (int r = t; r < nCellRows; r += QGD_MON_BLOCK) x += mv.cellPart[(size_t)r * QGD_MONITOR_CELL_ROW + k];
-        x = blockFold<OpSum>(x, sh);
+    for (int k = 0; k < SH.sums; ++k) {
+        const double x = foldColumn<OpSum>(mv.cellPart, SH.cellRow(), k, 0, nCellRows, 0.0, sh);
         if (t == 0) in[k] = x;
     }
     double* ex = out + mv.off[2];
-    for (int k = 0; k < QGD_MONITOR_EXTREMA; ++k) {
-        ArgVal a{INFINITY, QGD_MON_NOLABEL}, b{-INFINITY, QGD_MON_NOLABEL};
-        for (int r = t; r < nCellRows; r += QGD_MON_BLOCK) {
-            const double* e = mv.cellPart + (size_t)r * QGD_MONITOR_CELL_ROW + QGD_MONITOR_SUMS + 4 * k;
-            a = argMin(a, ArgVal{e[0], e[1]});
-            b = argMax(b, ArgVal{e[2], e[3]});
-        }
-        a = blockFoldArg<false>(a, sh);
-        b = blockFoldArg<true>(b, sh);
-        if (t == 0) {
-            const bool none = a.l >= QGD_MON_NOLABEL;   // no cell with a finite value
-            ex[4 * k] = none ? nan : a.v; ex[4 * k + 1] = none ? -1.0 : a.l;
-            ex[4 * k + 2] = none ? nan : b.v; ex[4 * k + 3] = none ? -1.0 : b.l;
-        }
+    for (int k = 0; k < SH.extrema; ++k) {
+        const MinMax e = foldExtremum(mv.cellPart, SH.cellRow(), SH.sums + 4 * k, 0, nCellRows, sh);
+        if (t == 0) storeExtremum(ex + 4 * k, e, false);
     }
-    {
-        double nb = 0.0, lb = QGD_MON_NOLABEL;
-        for (int r = t; r < nCellRows; r += QGD_MON_BLOCK) {
-            const double* e = mv.cellPart + (size_t)r * QGD_MONITOR_CELL_ROW + QGD_MONITOR_SUMS + 4 * QGD_MONITOR_EXTREMA;
-            nb += e[0];
-            lb = fmin(lb, e[1]);
-        }
-        nb = blockFold<OpSum>(nb, sh);
-        lb = blockFold<OpMin>(lb, sh);
-        if (t == 0) {
-            hd[0] = (double)(mv.ownedEnd - mv.ownedBegin);
-            hd[1] = (double)fluxState;
-            hd[2] = (double)mv.nProbes;
-            hd[3] = (double)mv.nPatches;
-            hd[4] = nb;
-            hd[5] = lb >= QGD_MON_NOLABEL ? -1.0 : lb;
-            hd[6] = c.dt[0];
-            hd[7] = c.dt[1];
-        }
+    const NonFinite nf = foldNonFinite(mv.cellPart, SH.cellRow(), SH.sums + 4 * SH.extrema, 0, nCellRows, sh);
+    if (t == 0) {
+        monitorHeader(hd, mv, fluxState, nf);
+        hd[6] = c.dt[0];
+        hd[7] = c.dt[1];
     }
     // probes: rho, Ux, Uy, Uz, p, T, e
     double* pr = out + mv.off[3];
     for (int i = t; i < mv.nProbes; i += QGD_MON_BLOCK) {
         const int cell = mv.probeCell[i];
-        double* o = pr + (size_t)i * QGD_MONITOR_PROBE_ROW;
+        double* o = pr + (size_t)i * SH.probeRow;
         if (cell < 0) {
 #pragma unroll
-            for (int k = 0; k < QGD_MONITOR_PROBE_ROW; ++k) o[k] = nan;
+            for (int k = 0; k < SH.probeRow; ++k) o[k] = __builtin_nan("");
         } else {
             const RecA a = c.A[cell];
             o[0] = a.rho; o[1] = a.ux; o[2] = a.uy; o[3] = a.uz; o[4] = a.p; o[5] = a.e / g.Cv; o[6] = a.e;
         }
     }
-    // patches: their chunks are consecutive rows
-    double* pa = out + mv.off[4];
-    for (int p = 0; p < mv.nPatches; ++p) {
-        const int r0 = mv.patchChunk[p], r1 = mv.patchChunk[p + 1];
-        for (int k = 0; k < QGD_MONITOR_PATCH_ROW; ++k) {
-            double x = 0.0;
-            for (int r = r0 + t; r < r1; r += QGD_MON_BLOCK) x += mv.patchPart[(size_t)r * QGD_MONITOR_PATCH_ROW + k];
-            x = blockFold<OpSum>(x, sh);
-            // fluxState 0: nothing assembled yet; 2: implicitDiffusion, where flux[1..4] hold the explicit part only
-            const bool isFlux = k >= 1 && k <= 5;
-            if (isFlux && (fluxState == 0 || (fluxState == 2 && k >= 2))) x = nan;
-            if (t == 0) pa[(size_t)p * QGD_MONITOR_PATCH_ROW + k] = x;
-        }
-    }
+    // patches.  The flux columns 1..5 -- fluxState 0: nothing assembled yet; 2: implicitDiffusion, where flux[1..4] hold the explicit part only
+    foldPatches(mv, mv.patchPart, SH.patchRow, out + mv.off[4], sh,
+                [=](int k) { return k >= 1 && k <= 5 && (fluxState == 0 || (fluxState == 2 && k >= 2)); });
 }
 
 void launchMonitorSample(hipStream_t s, const MonitorView& mv, const MeshView& m, const CaseView& c, const GasModel& g, int fluxState, double* out) {

@@ -29,8 +29,6 @@
 
 namespace qgd {
 
-struct OpMax { __device__ static double f(double a, double b) { return fmax(a, b); } };
-
 // ---- cells -------------------------------------------------------------------------------------------------------------------------
 // row of 5 nS + 3 doubles per workgroup: nS sums of (rho Y_i) V | nS x {min, label, max, label} | cells with a non-finite Y_i, the lowest
 // label among them, max |sum_i Y_i - 1| over the cells whose Y_i are all finite (-1: no such cell).
@@ -82,8 +80,8 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorSpeciesCellKernel(const 
 #pragma unroll
             for (int k = 0; k < W; ++k) {
                 s[k] = 0.0;
-                lo[k] = ArgVal{INFINITY, QGD_MON_NOLABEL};
-                hi[k] = ArgVal{-INFINITY, QGD_MON_NOLABEL};
+                lo[k] = noMin();
+                hi[k] = noMax();
 #pragma unroll
                 for (int j = 0; j < K; ++j) {
                     if (!(on >> j & 1u) || s0 + k >= nS) continue;
@@ -91,8 +89,7 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorSpeciesCellKernel(const 
                     s[k] += (rho[j] * v) * V[j];
                     ysum[j] += v;
                     if (!isFiniteD(v)) { bad |= 1u << j; continue; }   // the extrema of a species are taken over the cells where it is finite
-                    if (v < lo[k].v) lo[k] = ArgVal{v, label[j]};      // ascending labels per lane: the first one met stays on a tie
-                    if (v > hi[k].v) hi[k] = ArgVal{v, label[j]};
+                    keepExtrema(lo[k], hi[k], v, label[j]);
                 }
             }
 #pragma unroll
@@ -181,6 +178,7 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorSpeciesPatchKernel(const
 }
 
 // ---- fold --------------------------------------------------------------------------------------------------------------------------
+// header: nS, the inert species, fluxState, cells with a non-finite Y_i, the first of them, max |sum_i Y_i - 1|, probes, patches
 __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorSpeciesFoldKernel(const MonitorView mv, const SpeciesMonitorView sm, const SpeciesView sv, const int nC,
                                                                          const int fluxState, double* __restrict__ out) {
     __shared__ double sh[8];
@@ -191,46 +189,21 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorSpeciesFoldKernel(const 
     double* in = out + sm.off[1];
     double* ex = out + sm.off[2];
     for (int i = 0; i < nS; ++i) {
-        double x = 0.0;
-        ArgVal a{INFINITY, QGD_MON_NOLABEL}, b{-INFINITY, QGD_MON_NOLABEL};
-        for (int r = t; r < sm.nRows; r += QGD_MON_BLOCK) {
-            const double* p = sm.cellPart + (size_t)r * rowLen;
-            x += p[i];
-            const double* e = p + nS + 4 * i;
-            a = argMin(a, ArgVal{e[0], e[1]});
-            b = argMax(b, ArgVal{e[2], e[3]});
-        }
-        x = blockFold<OpSum>(x, sh);
-        a = blockFoldArg<false>(a, sh);
-        b = blockFoldArg<true>(b, sh);
-        if (t == 0) {
-            in[i] = x;
-            const bool none = a.l >= QGD_MON_NOLABEL;   // no cell with a finite value
-            ex[4 * i] = none ? nan : a.v; ex[4 * i + 1] = none ? -1.0 : a.l;
-            ex[4 * i + 2] = none ? nan : b.v; ex[4 * i + 3] = none ? -1.0 : b.l;
-        }
+        const double x = foldColumn<OpSum>(sm.cellPart, rowLen, i, 0, sm.nRows, 0.0, sh);
+        const MinMax e = foldExtremum(sm.cellPart, rowLen, nS + 4 * i, 0, sm.nRows, sh);
+        if (t == 0) { in[i] = x; storeExtremum(ex + 4 * i, e, false); }
     }
-    {
-        double nb = 0.0, lb = QGD_MON_NOLABEL, defect = -1.0;
-        for (int r = t; r < sm.nRows; r += QGD_MON_BLOCK) {
-            const double* e = sm.cellPart + (size_t)r * rowLen + 5 * (size_t)nS;
-            nb += e[0];
-            lb = fmin(lb, e[1]);
-            defect = fmax(defect, e[2]);
-        }
-        nb = blockFold<OpSum>(nb, sh);
-        lb = blockFold<OpMin>(lb, sh);
-        defect = blockFold<OpMax>(defect, sh);
-        if (t == 0) {
-            hd[0] = (double)nS;
-            hd[1] = (double)sv.inert;
-            hd[2] = (double)fluxState;
-            hd[3] = nb;
-            hd[4] = lb >= QGD_MON_NOLABEL ? -1.0 : lb;
-            hd[5] = defect < 0.0 ? nan : defect;   // no owned cell whose Y_i are all finite
-            hd[6] = (double)mv.nProbes;
-            hd[7] = (double)mv.nPatches;
-        }
+    const NonFinite nf = foldNonFinite(sm.cellPart, rowLen, 5 * nS, 0, sm.nRows, sh);
+    const double defect = foldColumn<OpMax>(sm.cellPart, rowLen, 5 * nS + 2, 0, sm.nRows, -1.0, sh);
+    if (t == 0) {
+        hd[0] = (double)nS;
+        hd[1] = (double)sv.inert;
+        hd[2] = (double)fluxState;
+        hd[3] = nf.count;
+        hd[4] = nf.first();
+        hd[5] = defect < 0.0 ? nan : defect;   // no owned cell whose Y_i are all finite
+        hd[6] = (double)mv.nProbes;
+        hd[7] = (double)mv.nPatches;
     }
     // probes: Y_i of the probe's cell, all species
     double* pr = out + sm.off[3];
@@ -238,17 +211,8 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void monitorSpeciesFoldKernel(const 
         const int cell = mv.probeCell[i];
         for (int k = 0; k < nS; ++k) pr[(size_t)i * nS + k] = cell < 0 ? nan : sv.Y[(size_t)k * nC + cell];
     }
-    // patches: their chunks are consecutive rows
-    double* pa = out + sm.off[4];
-    for (int p = 0; p < mv.nPatches; ++p) {
-        const int r0 = mv.patchChunk[p], r1 = mv.patchChunk[p + 1];
-        for (int k = 0; k < nS; ++k) {
-            double x = 0.0;
-            for (int r = r0 + t; r < r1; r += QGD_MON_BLOCK) x += sm.patchPart[(size_t)r * nS + k];
-            x = blockFold<OpSum>(x, sh);
-            if (t == 0) pa[(size_t)p * nS + k] = fluxState == 0 ? nan : x;   // nothing assembled yet
-        }
-    }
+    // patches: every column NaN while nothing is assembled yet
+    foldPatches(mv, sm.patchPart, nS, out + sm.off[4], sh, [=](int) { return fluxState == 0; });
 }
 
 void launchMonitorSpeciesSample(hipStream_t s, const MonitorView& mv, const SpeciesMonitorView& sm, const MeshView& m, const CaseView& c,

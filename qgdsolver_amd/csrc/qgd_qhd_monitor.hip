@@ -14,27 +14,27 @@
 #include <cstdint>
 
 #include "qgd_device.hpp"
-#include "qgd_monitor_dev.hpp"   // the folds and the {value, label} pairs
+#include "qgd_monitor_dev.hpp"   // the row stores, the folds and the "none" rules every block shares
 #include "qgd_qhd_dev.hpp"       // QhdBdFrc: the body force as the step kernels form it
 
 namespace qgd {
 
 namespace {
 typedef double mon2d __attribute__((ext_vector_type(2)));
+constexpr MonitorShape SH = kQhdMonitorShape;
 }
 
 // ---- cells -------------------------------------------------------------------------------------------------------------------------
-// row of QGD_QHD_MONITOR_CELL_ROW doubles per workgroup: 12 sums | 4 x {min, label, max, label} | non-finite count, lowest label
+// row of SH.cellRow() doubles per workgroup: 12 sums | 4 x {min, label, max, label} | non-finite count, lowest label
 // ROT: the case rotates (QhdBdFrc<QHD_ROT>); FLUX: a step has run, phi holds the flux of the last pressure solve
 template <int ROT, bool FLUX>
 __global__ __launch_bounds__(QGD_MON_BLOCK) void qhdMonitorCellKernel(const MonitorView mv, const MeshView m, const QhdView q) {
     __shared__ double sh[8];
-    double s[QGD_QHD_MONITOR_SUMS];
+    double s[SH.sums];
 #pragma unroll
-    for (int k = 0; k < QGD_QHD_MONITOR_SUMS; ++k) s[k] = 0.0;
-    ArgVal lo[QGD_QHD_MONITOR_EXTREMA], hi[QGD_QHD_MONITOR_EXTREMA];
-#pragma unroll
-    for (int k = 0; k < QGD_QHD_MONITOR_EXTREMA; ++k) { lo[k] = ArgVal{INFINITY, QGD_MON_NOLABEL}; hi[k] = ArgVal{-INFINITY, QGD_MON_NOLABEL}; }
+    for (int k = 0; k < SH.sums; ++k) s[k] = 0.0;
+    ArgVal lo[SH.extrema], hi[SH.extrema];
+    noExtrema(lo, hi);
     double bad = 0.0, badLabel = QGD_MON_NOLABEL;
     const mon2d* const c4 = reinterpret_cast<const mon2d*>(q.c4);
     const int64_t stride = (int64_t)gridDim.x * QGD_MON_BLOCK;
@@ -75,48 +75,26 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void qhdMonitorCellKernel(const Moni
         s[10] += d;
         s[11] += fabs(d);
         if (!(isFiniteD(u4[0]) && isFiniteD(u4[1]) && isFiniteD(u4[2]) && isFiniteD(u4[3]) && isFiniteD(p))) {
-            bad += 1.0;
-            badLabel = fmin(badLabel, label);
+            markNonFinite(bad, badLabel, label);
             continue;   // extrema are taken over the cells whose state is finite
         }
-        const double val[QGD_QHD_MONITOR_EXTREMA] = {sqrt(u2), u4[3], p, fabs(d) / V};
+        const double val[SH.extrema] = {sqrt(u2), u4[3], p, fabs(d) / V};
 #pragma unroll
-        for (int k = 0; k < QGD_QHD_MONITOR_EXTREMA; ++k) {
-            if (!isFiniteD(val[k])) continue;
-            if (val[k] < lo[k].v) lo[k] = ArgVal{val[k], label};   // ascending labels per lane: the first one met stays on a tie
-            if (val[k] > hi[k].v) hi[k] = ArgVal{val[k], label};
-        }
+        for (int k = 0; k < SH.extrema; ++k) keepFinite(lo[k], hi[k], val[k], label);
     }
-    double* row = mv.cellPart + (size_t)blockIdx.x * QGD_QHD_MONITOR_CELL_ROW;
-#pragma unroll
-    for (int k = 0; k < QGD_QHD_MONITOR_SUMS; ++k) {
-        const double r = blockFold<OpSum>(s[k], sh);
-        if (threadIdx.x == 0) row[k] = r;
-    }
-#pragma unroll
-    for (int k = 0; k < QGD_QHD_MONITOR_EXTREMA; ++k) {
-        const ArgVal a = blockFoldArg<false>(lo[k], sh);
-        const ArgVal b = blockFoldArg<true>(hi[k], sh);
-        if (threadIdx.x == 0) {
-            double* e = row + QGD_QHD_MONITOR_SUMS + 4 * k;
-            e[0] = a.v; e[1] = a.l; e[2] = b.v; e[3] = b.l;
-        }
-    }
-    const double nb = blockFold<OpSum>(bad, sh);
-    const double lb = blockFold<OpMin>(badLabel, sh);
-    if (threadIdx.x == 0) { row[QGD_QHD_MONITOR_SUMS + 4 * QGD_QHD_MONITOR_EXTREMA] = nb; row[QGD_QHD_MONITOR_SUMS + 4 * QGD_QHD_MONITOR_EXTREMA + 1] = lb; }
+    storeCellRow(s, lo, hi, bad, badLabel, mv.cellPart + (size_t)blockIdx.x * SH.cellRow(), sh);
 }
 
 // ---- patch faces -------------------------------------------------------------------------------------------------------------------
-// one workgroup per chunk (<= 256 consecutive entries of the face list, all of one patch); row of QGD_QHD_MONITOR_PATCH_ROW doubles:
+// one workgroup per chunk (<= 256 consecutive entries of the face list, all of one patch); row of SH.patchRow doubles:
 // |Sf|, phi, the four net face terms (patch faces keep them at their label), p_b Sf
 template <bool FLUX>
 __global__ __launch_bounds__(QGD_MON_BLOCK) void qhdMonitorPatchKernel(const MonitorView mv, const MeshView m, const QhdView q) {
     __shared__ double sh[4];
     const int first = mv.chunkStart[blockIdx.x], n = mv.chunkStart[blockIdx.x + 1] - first;
-    double s[QGD_QHD_MONITOR_PATCH_ROW];
+    double s[SH.patchRow];
 #pragma unroll
-    for (int k = 0; k < QGD_QHD_MONITOR_PATCH_ROW; ++k) s[k] = 0.0;
+    for (int k = 0; k < SH.patchRow; ++k) s[k] = 0.0;
     if ((int)threadIdx.x < n) {
         const int b = mv.faceList[first + threadIdx.x];   // boundary face index
         const size_t f = (size_t)m.nIF + b;
@@ -129,16 +107,11 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void qhdMonitorPatchKernel(const Mon
         const double pb = q.pb[b];
         s[6] = pb * m.Sx[f]; s[7] = pb * m.Sy[f]; s[8] = pb * m.Sz[f];
     }
-    double* row = mv.patchPart + (size_t)blockIdx.x * QGD_QHD_MONITOR_PATCH_ROW;
-#pragma unroll
-    for (int k = 0; k < QGD_QHD_MONITOR_PATCH_ROW; ++k) {
-        const double r = blockFold<OpSum>(s[k], sh);
-        if (threadIdx.x == 0) row[k] = r;
-    }
+    storePatchRow(s, mv.patchPart + (size_t)blockIdx.x * SH.patchRow, sh);
 }
 
 // ---- fold --------------------------------------------------------------------------------------------------------------------------
-// thread t takes rows t, t + 256, ... in ascending order, then the block tree: fixed for a given grid and chunk table
+// header: owned cells, fluxState, probes, patches, non-finite cells, the first of them | deltaT, flags (1: rotating, 2: frozen T)
 __global__ __launch_bounds__(QGD_MON_BLOCK) void qhdMonitorFoldKernel(const MonitorView mv, const QhdView q, const int nCellRows, const int fluxState,
                                                                      double* __restrict__ out) {
     __shared__ double sh[8];
@@ -146,77 +119,40 @@ __global__ __launch_bounds__(QGD_MON_BLOCK) void qhdMonitorFoldKernel(const Moni
     const double nan = __builtin_nan("");
     double* hd = out + mv.off[0];
     double* in = out + mv.off[1];
-    for (int k = 0; k < QGD_QHD_MONITOR_SUMS; ++k) {
-        double x = 0.0;
-        for (int r = t; r < nCellRows; r += QGD_MON_BLOCK) x += mv.cellPart[(size_t)r * QGD_QHD_MONITOR_CELL_ROW + k];
-        x = blockFold<OpSum>(x, sh);
-        if (k >= 10 && fluxState == 0) x = nan;   // no pressure solve yet: phi holds nothing
-        if (t == 0) in[k] = x;
+    for (int k = 0; k < SH.sums; ++k) {
+        const double x = foldColumn<OpSum>(mv.cellPart, SH.cellRow(), k, 0, nCellRows, 0.0, sh);
+        if (t == 0) in[k] = k >= 10 && fluxState == 0 ? nan : x;   // no pressure solve yet: phi holds nothing
     }
     double* ex = out + mv.off[2];
-    for (int k = 0; k < QGD_QHD_MONITOR_EXTREMA; ++k) {
-        ArgVal a{INFINITY, QGD_MON_NOLABEL}, b{-INFINITY, QGD_MON_NOLABEL};
-        for (int r = t; r < nCellRows; r += QGD_MON_BLOCK) {
-            const double* e = mv.cellPart + (size_t)r * QGD_QHD_MONITOR_CELL_ROW + QGD_QHD_MONITOR_SUMS + 4 * k;
-            a = argMin(a, ArgVal{e[0], e[1]});
-            b = argMax(b, ArgVal{e[2], e[3]});
-        }
-        a = blockFoldArg<false>(a, sh);
-        b = blockFoldArg<true>(b, sh);
-        if (t == 0) {
-            const bool none = a.l >= QGD_MON_NOLABEL || (k == 3 && fluxState == 0);   // no cell with a finite value; no continuity error yet
-            ex[4 * k] = none ? nan : a.v; ex[4 * k + 1] = none ? -1.0 : a.l;
-            ex[4 * k + 2] = none ? nan : b.v; ex[4 * k + 3] = none ? -1.0 : b.l;
-        }
+    for (int k = 0; k < SH.extrema; ++k) {
+        const MinMax e = foldExtremum(mv.cellPart, SH.cellRow(), SH.sums + 4 * k, 0, nCellRows, sh);
+        if (t == 0) storeExtremum(ex + 4 * k, e, k == 3 && fluxState == 0);   // no continuity error yet
     }
-    {
-        double nb = 0.0, lb = QGD_MON_NOLABEL;
-        for (int r = t; r < nCellRows; r += QGD_MON_BLOCK) {
-            const double* e = mv.cellPart + (size_t)r * QGD_QHD_MONITOR_CELL_ROW + QGD_QHD_MONITOR_SUMS + 4 * QGD_QHD_MONITOR_EXTREMA;
-            nb += e[0];
-            lb = fmin(lb, e[1]);
-        }
-        nb = blockFold<OpSum>(nb, sh);
-        lb = blockFold<OpMin>(lb, sh);
-        if (t == 0) {
-            hd[0] = (double)(mv.ownedEnd - mv.ownedBegin);
-            hd[1] = (double)fluxState;
-            hd[2] = (double)mv.nProbes;
-            hd[3] = (double)mv.nPatches;
-            hd[4] = nb;
-            hd[5] = lb >= QGD_MON_NOLABEL ? -1.0 : lb;
-            hd[6] = q.dt;
-            hd[7] = (double)((q.rotating ? 1 : 0) | (q.frozenT ? 2 : 0));
-        }
+    const NonFinite nf = foldNonFinite(mv.cellPart, SH.cellRow(), SH.sums + 4 * SH.extrema, 0, nCellRows, sh);
+    if (t == 0) {
+        monitorHeader(hd, mv, fluxState, nf);
+        hd[6] = q.dt;
+        hd[7] = (double)((q.rotating ? 1 : 0) | (q.frozenT ? 2 : 0));
     }
     // probes: Ux, Uy, Uz, T, p
     double* pr = out + mv.off[3];
     for (int i = t; i < mv.nProbes; i += QGD_MON_BLOCK) {
         const int cell = mv.probeCell[i];
-        double* o = pr + (size_t)i * QGD_QHD_MONITOR_PROBE_ROW;
+        double* o = pr + (size_t)i * SH.probeRow;
         if (cell < 0) {
 #pragma unroll
-            for (int k = 0; k < QGD_QHD_MONITOR_PROBE_ROW; ++k) o[k] = nan;
+            for (int k = 0; k < SH.probeRow; ++k) o[k] = nan;
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = q.c4[(size_t)cell * 4 + k];
             o[4] = q.p[cell];
         }
     }
-    // patches: their chunks are consecutive rows
-    double* pa = out + mv.off[4];
-    for (int p = 0; p < mv.nPatches; ++p) {
-        const int r0 = mv.patchChunk[p], r1 = mv.patchChunk[p + 1];
-        for (int k = 0; k < QGD_QHD_MONITOR_PATCH_ROW; ++k) {
-            double x = 0.0;
-            for (int r = r0 + t; r < r1; r += QGD_MON_BLOCK) x += mv.patchPart[(size_t)r * QGD_QHD_MONITOR_PATCH_ROW + k];
-            x = blockFold<OpSum>(x, sh);
-            // fluxState 0: no step yet; 2: implicitDiffusion, where F holds the explicit part only; a frozen T has no equation, so no flux
-            const bool isTerm = k >= 2 && k <= 5;
-            if ((k == 1 && fluxState == 0) || (isTerm && fluxState != 1) || (k == 5 && q.frozenT)) x = nan;
-            if (t == 0) pa[(size_t)p * QGD_QHD_MONITOR_PATCH_ROW + k] = x;
-        }
-    }
+    // patches.  phi (column 1) -- fluxState 0: no step yet; the terms 2..5 -- 2: implicitDiffusion, where F holds the explicit part only; a
+    // frozen T has no equation, so no flux
+    const bool frozenT = q.frozenT;
+    foldPatches(mv, mv.patchPart, SH.patchRow, out + mv.off[4], sh,
+                [=](int k) { return (k == 1 && fluxState == 0) || (k >= 2 && k <= 5 && fluxState != 1) || (k == 5 && frozenT); });
 }
 
 void launchQhdMonitorSample(hipStream_t s, const MonitorView& mv, const MeshView& m, const QhdView& q, int fluxState, double* out) {

@@ -144,42 +144,46 @@ class QHDMonitor(_MonitorBase):
         return unpack_qhd(raw, self.offsets, t, step)
 
 
-def unpack(raw, offsets, time, step):
-    """named arrays of one result block (the layout of include/qgd_amd.h)"""
+def _sections(raw, offsets, time, step, extrema_fields, probe_columns, patch_columns):
+    """the five sections of a flow or QHD result block (header, integrals, extrema, probes, patches) and the keys both blocks name alike"""
     o = offsets
     hd, integ = raw[o[0]:o[1]], raw[o[1]:o[2]]
-    ex = raw[o[2]:o[3]].reshape(len(EXTREMA_FIELDS), 4)
+    ex = raw[o[2]:o[3]].reshape(len(extrema_fields), 4)
     n_probes, n_patches = int(hd[2]), int(hd[3])
-    probes = raw[o[3]:o[4]].reshape(n_probes, len(PROBE_COLUMNS))
-    patches = raw[o[4]:o[4] + n_patches * len(PATCH_COLUMNS)].reshape(n_patches, len(PATCH_COLUMNS))
-    return dict(time=time, step=step, deltaT=float(hd[6]), ownedCells=int(hd[0]), fluxState=int(hd[1]),
-                # fluxState 0: no assembly yet (patch fluxes NaN); 1: all five; 2: implicitDiffusion (mass flux only, the other four NaN)
-                nonFinite=int(hd[4]), firstNonFinite=int(hd[5]),
-                integrals=integ.copy(), volume=float(integ[0]), mass=float(integ[1]), momentum=integ[2:5].copy(),
-                totalEnergy=float(integ[5]), internalEnergy=float(integ[6]), kineticEnergy=float(integ[7]),
-                min=ex[:, 0].copy(), minCell=ex[:, 1].astype(np.int64), max=ex[:, 2].copy(), maxCell=ex[:, 3].astype(np.int64),
-                probes=probes.copy(), patchArea=patches[:, 0].copy(), patchFlux=patches[:, 1:6].copy(),
-                patchPressureForce=patches[:, 6:9].copy(), raw=raw)
+    probes = raw[o[3]:o[4]].reshape(n_probes, len(probe_columns))
+    patches = raw[o[4]:o[4] + n_patches * len(patch_columns)].reshape(n_patches, len(patch_columns))
+    return hd, integ, dict(time=time, step=step, deltaT=float(hd[6]), ownedCells=int(hd[0]), fluxState=int(hd[1]),
+                           nonFinite=int(hd[4]), firstNonFinite=int(hd[5]), integrals=integ.copy(),
+                           min=ex[:, 0].copy(), minCell=ex[:, 1].astype(np.int64), max=ex[:, 2].copy(), maxCell=ex[:, 3].astype(np.int64),
+                           probes=probes.copy(), patchArea=patches[:, 0].copy(), patchFlux=patches[:, 1:6].copy(),
+                           patchPressureForce=patches[:, 6:9].copy(), raw=raw)
+
+
+# the keys a sample derives from its integrals: a scalar by its index, a vector by its slice (unpack, unpack_qhd and combine)
+_FLOW_DERIVED = dict(volume=0, mass=1, momentum=slice(2, 5), totalEnergy=5, internalEnergy=6, kineticEnergy=7)
+_QHD_DERIVED = dict(volume=0, momentum=slice(1, 4), bodyForce=slice(7, 10), continuityGlobal=10, continuityLocal=11)
+
+
+def _derived(integ, table):
+    return {key: integ[at].copy() if isinstance(at, slice) else float(integ[at]) for key, at in table.items()}
+
+
+def unpack(raw, offsets, time, step):
+    """named arrays of one result block (the layout of include/qgd_amd.h)"""
+    # fluxState 0: no assembly yet (patch fluxes NaN); 1: all five; 2: implicitDiffusion (mass flux only, the other four NaN)
+    hd, integ, s = _sections(raw, offsets, time, step, EXTREMA_FIELDS, PROBE_COLUMNS, PATCH_COLUMNS)
+    s.update(_derived(integ, _FLOW_DERIVED))
+    return s
 
 
 def unpack_qhd(raw, offsets, time, step):
     """named arrays of one result block of a QHD monitor (the layout of include/qgd_amd.h, qgd_qhd_monitor_create); the keys are those of
     ``unpack`` wherever the meaning is the same"""
-    o = offsets
-    hd, integ = raw[o[0]:o[1]], raw[o[1]:o[2]]
-    ex = raw[o[2]:o[3]].reshape(len(QHD_EXTREMA_FIELDS), 4)
-    n_probes, n_patches = int(hd[2]), int(hd[3])
-    probes = raw[o[3]:o[4]].reshape(n_probes, len(QHD_PROBE_COLUMNS))
-    patches = raw[o[4]:o[4] + n_patches * len(QHD_PATCH_COLUMNS)].reshape(n_patches, len(QHD_PATCH_COLUMNS))
+    # fluxState 0: no step yet (patch fluxes and continuity entries NaN); 1: everything; 2: implicitDiffusion (the U / T flux columns NaN)
+    hd, integ, s = _sections(raw, offsets, time, step, QHD_EXTREMA_FIELDS, QHD_PROBE_COLUMNS, QHD_PATCH_COLUMNS)
     flags = int(hd[7])
-    return dict(kind="qhd", time=time, step=step, deltaT=float(hd[6]), ownedCells=int(hd[0]), fluxState=int(hd[1]),
-                # fluxState 0: no step yet (patch fluxes and continuity entries NaN); 1: everything; 2: implicitDiffusion (the U / T flux columns NaN)
-                nonFinite=int(hd[4]), firstNonFinite=int(hd[5]), rotating=bool(flags & 1), frozenT=bool(flags & 2),
-                integrals=integ.copy(), volume=float(integ[0]), momentum=integ[1:4].copy(), bodyForce=integ[7:10].copy(),
-                continuityGlobal=float(integ[10]), continuityLocal=float(integ[11]),
-                min=ex[:, 0].copy(), minCell=ex[:, 1].astype(np.int64), max=ex[:, 2].copy(), maxCell=ex[:, 3].astype(np.int64),
-                probes=probes.copy(), patchArea=patches[:, 0].copy(), patchFlux=patches[:, 1:6].copy(),
-                patchPressureForce=patches[:, 6:9].copy(), raw=raw)
+    s.update(_derived(integ, _QHD_DERIVED), kind="qhd", rotating=bool(flags & 1), frozenT=bool(flags & 2))
+    return s
 
 
 def unpack_species(raw, offsets):
@@ -211,15 +215,9 @@ def combine(parts):
     if len(parts) == 1:
         return out
     _combine_block(out, parts, _FLOW_KEYS)
-    if parts[0].get("kind") == "qhd":   # the derived keys of unpack_qhd; the flags and the flux state are the same on every shard
-        integ = out["integrals"]
-        out.update(volume=float(integ[0]), bodyForce=integ[7:10].copy(), continuityGlobal=float(integ[10]), continuityLocal=float(integ[11]),
-                   ownedCells=sum(p["ownedCells"] for p in parts))
-        out.pop("raw", None)
-        return out
-    for key in ("volume", "mass", "totalEnergy", "internalEnergy", "kineticEnergy"):
-        out[key] = float(out["integrals"][INTEGRALS.index(key)])
-    out["ownedCells"] = sum(p["ownedCells"] for p in parts)
+    # the derived keys of the kind; the flags and the flux state of a QHD sample are the same on every shard
+    out.update(_derived(out["integrals"], _QHD_DERIVED if parts[0].get("kind") == "qhd" else _FLOW_DERIVED),
+               ownedCells=sum(p["ownedCells"] for p in parts))
     if "speciesMass" in parts[0]:
         _combine_block(out, parts, _SPECIES_KEYS)
         defects = [p["speciesSumDefect"] for p in parts if not np.isnan(p["speciesSumDefect"])]
@@ -330,12 +328,14 @@ class FieldMinMaxWriter:
 
 
 class IntegralsWriter:
-    """volIntegrals.dat: the time, the eight volume integrals, the count of non-finite cells and the first of them (-1: none)"""
+    """volIntegrals.dat: the time, the volume integrals of the block (``COLUMNS``: the eight of a QGDFoam case), the count of non-finite
+    cells and the first of them (-1: none)"""
+    COLUMNS = INTEGRALS
 
     def __init__(self, out_dir, spec, file_label):
         self.file_label = file_label
         self.table = _Table(os.path.join(out_dir, "volIntegrals.dat"),
-                            ["# Volume integrals over the mesh", "# " + "\t".join(("Time",) + INTEGRALS + ("nonFiniteCells", "firstNonFiniteCell"))])
+                            ["# Volume integrals over the mesh", "# " + "\t".join(("Time",) + self.COLUMNS + ("nonFiniteCells", "firstNonFiniteCell"))])
 
     def write(self, t, s):
         first = int(self.file_label[s["firstNonFinite"]]) if s["firstNonFinite"] >= 0 else -1
@@ -343,13 +343,15 @@ class IntegralsWriter:
 
 
 class PatchFluxWriter:
-    """patchFluxes.dat: the time, then per patch its area, the five net fluxes out of the domain (mass, momentum, total energy: what the
-    cell update consumed in the step that produced the state) and sum p_b Sf"""
+    """patchFluxes.dat: the time, then per patch the columns of the block's patch row (``COLUMNS``) -- for a QGDFoam case its area, the
+    five net fluxes out of the domain (mass, momentum, total energy: what the cell update consumed in the step that produced the state)
+    and sum p_b Sf"""
+    COLUMNS, TITLE = PATCH_COLUMNS, "# Patch totals of the net face fluxes"
 
     def __init__(self, out_dir, spec, rows):
         self.rows = rows                    # rows of the monitor's patch table, in the order of spec["patches"]
-        cols = ["Time"] + [f"{p}:{c}" for p in spec["patches"] for c in PATCH_COLUMNS]
-        self.table = _Table(os.path.join(out_dir, "patchFluxes.dat"), ["# Patch totals of the net face fluxes", "# " + "\t".join(cols)])
+        cols = ["Time"] + [f"{p}:{c}" for p in spec["patches"] for c in self.COLUMNS]
+        self.table = _Table(os.path.join(out_dir, "patchFluxes.dat"), [self.TITLE, "# " + "\t".join(cols)])
 
     def write(self, t, s):
         row = [_num(t)]
@@ -508,33 +510,15 @@ class QHDFieldMinMaxWriter(FieldMinMaxWriter):
     _INDEX = {"U": 0, "mag(U)": 0, "T": 1, "p": 2, "contErr": 3}
 
 
-class QHDIntegralsWriter:
-    """volIntegrals.dat: the time, the twelve integrals of the QHD block, the count of non-finite cells and the first of them (-1: none)"""
-
-    def __init__(self, out_dir, spec, file_label):
-        self.file_label = file_label
-        self.table = _Table(os.path.join(out_dir, "volIntegrals.dat"),
-                            ["# Volume integrals over the mesh", "# " + "\t".join(("Time",) + QHD_INTEGRALS + ("nonFiniteCells", "firstNonFiniteCell"))])
-
-    def write(self, t, s):
-        first = int(self.file_label[s["firstNonFinite"]]) if s["firstNonFinite"] >= 0 else -1
-        self.table.row("\t".join([_num(t)] + [_num(v) for v in s["integrals"]] + [str(int(s["nonFinite"])), str(first)]))
+class QHDIntegralsWriter(IntegralsWriter):
+    """volIntegrals.dat with the twelve integrals of the QHD block"""
+    COLUMNS = QHD_INTEGRALS
 
 
-class QHDPatchFluxWriter:
-    """patchFluxes.dat: the time, then per patch its area, the volumetric flux, the totals of the net face terms of the U (3) and T
+class QHDPatchFluxWriter(PatchFluxWriter):
+    """patchFluxes.dat of a QHD sample: per patch its area, the volumetric flux, the totals of the net face terms of the U (3) and T
     equations (what the cell update consumed in the step that produced the state) and sum p_b Sf"""
-
-    def __init__(self, out_dir, spec, rows):
-        self.rows = rows                    # rows of the monitor's patch table, in the order of spec["patches"]
-        cols = ["Time"] + [f"{p}:{c}" for p in spec["patches"] for c in QHD_PATCH_COLUMNS]
-        self.table = _Table(os.path.join(out_dir, "patchFluxes.dat"), ["# Patch totals of phi and of the net face terms", "# " + "\t".join(cols)])
-
-    def write(self, t, s):
-        row = [_num(t)]
-        for r in self.rows:
-            row += [_num(s["patchArea"][r])] + [_num(v) for v in s["patchFlux"][r]] + [_num(v) for v in s["patchPressureForce"][r]]
-        self.table.row("\t".join(row))
+    COLUMNS, TITLE = QHD_PATCH_COLUMNS, "# Patch totals of phi and of the net face terms"
 
 
 class ContinuityErrorsWriter:

@@ -226,9 +226,10 @@ def check_patches(s, case, mesh, patches, faces_of=None, what=""):
             sum_ok(s["patchPressureForce"][row, k], pb[f - nif] * Sf[f, k], tag + f" p Sf {k}")
 
 
-@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly"])
+@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly", "box257_257_1"])
 def test_patch_totals_against_the_face_fields(kind):
-    mesh = {"box111": lambda: q.PolyMesh.box(1, 1, 1), "box20_17_3": lambda: q.PolyMesh.box(20, 17, 3)}.get(kind, lambda: make_mesh(kind))()
+    dims = {"box111": (1, 1, 1), "box20_17_3": (20, 17, 3), "box257_257_1": (257, 257, 1)}
+    mesh = q.PolyMesh.box(*dims[kind]) if kind in dims else make_mesh(kind)
     dev, case = open_case(mesh, bc_fn=io_bcs)
     patches = [5, 0, 1, 2, 3, 4, 0]                  # any order, one of them twice
     m = case.monitor(patches=patches)
@@ -242,6 +243,8 @@ def test_patch_totals_against_the_face_fields(kind):
     assert s["fluxState"] == 1
     if kind == "box20_17_3":
         assert mesh.array("patchSize")[4] == 340     # more than one chunk of 256
+    if kind == "box257_257_1":
+        assert list(mesh.array("patchSize")[4:6]) == [66049] * 2     # 259 chunks: the fold's threads take a second trip over a patch's rows
     if kind == "box111":
         assert list(mesh.array("patchSize")) == [1] * 6
     check_patches(s, case, mesh, patches, what=kind)

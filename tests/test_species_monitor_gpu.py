@@ -212,9 +212,11 @@ def check_species_patches(s, case, mesh, patches, nS, inert, phiJm, Yb_old, impl
 
 
 @pytest.mark.parametrize("implicit", [False, True])
-@pytest.mark.parametrize("kind", ["box654_poly", "plane2d_jitter"])
+@pytest.mark.parametrize("kind", ["box654_poly", "plane2d_jitter", "box257_257_1"])
 def test_patch_totals_against_the_kept_face_fields(kind, implicit):
-    mesh = make_mesh(kind)
+    mesh = q.PolyMesh.box(257, 257, 1) if kind == "box257_257_1" else make_mesh(kind)
+    if kind == "box257_257_1":
+        assert list(mesh.array("patchSize")[4:6]) == [66049] * 2     # 259 chunks: the fold's threads take a second trip over a patch's rows
     nS, inert = 6, 2
     # species 0: fixedValue at the inlet, zero-gradient at the outlet; species 3: the other way round; species 5: fixedValue on a wall
     sbcs = [(0, 0, ("fixedValue", 0.3)), (3, 1, ("fixedValue", 0.05)), (5, 2, ("fixedValue", 0.2)), (1, 0, ("fixedValue", 0.1))]
