@@ -97,7 +97,7 @@ def test_layout_and_grid_cap():
     case.close(); dev.close()
 
 
-@pytest.mark.parametrize("kind", ["box111", "box5_3_17", "box488", "box257_1_1", "box654_poly", "box64_64_65"])
+@pytest.mark.parametrize("kind", ["box111", "box5_3_17", "box488", "box257_1_1", "box654_poly", "box64_64_65", "tet433", "prism543", "mix643"])
 def test_integrals_extrema_and_probes_against_numpy(kind):
     dims = {"box111": (1, 1, 1), "box5_3_17": (5, 3, 17), "box488": (4, 8, 8), "box257_1_1": (257, 1, 1), "box64_64_65": (64, 64, 65)}
     mesh = make_mesh(kind) if kind not in dims else q.PolyMesh.box(*dims[kind])
@@ -166,11 +166,15 @@ def test_one_nan_cell_is_counted_named_and_kept_out_of_the_extrema():
 
 
 # ---- 3. balance ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("arm,adjust", [("fused", 0), ("kernels", 0), ("kernels", 1), ("fusedAdjust", 1)])
-def test_patch_fluxes_close_the_balance_of_mass_momentum_and_energy(arm, adjust):
+BALANCE = [pytest.param(arm, adjust, None, id=f"{arm}-{adjust}") for arm, adjust in (("fused", 0), ("kernels", 0), ("kernels", 1), ("fusedAdjust", 1))]
+BALANCE += [pytest.param(arm, 0, kind, id=f"{arm}-0-{kind}") for kind in ("tet433", "prism543", "mix643") for arm in ("fused", "kernels")]
+
+
+@pytest.mark.parametrize("arm,adjust,kind", BALANCE)
+def test_patch_fluxes_close_the_balance_of_mass_momentum_and_energy(arm, adjust, kind):
     """|Q_n - Q_(n-1) + deltaT_n sum F| <= (nCells + nFaces) 2^-52 (sum |q V| + deltaT_n sum |F|) after each of 5 steps, for mass, the three
     momentum components and rho E; F over all patches, deltaT_n from info()"""
-    mesh = q.PolyMesh.box(10, 9, 8)
+    mesh = make_mesh(kind) if kind else q.PolyMesh.box(10, 9, 8)
     dev, case = open_case(mesh, fused_tables=False if arm == "kernels" else "any", bc_fn=io_bcs, adjustTimeStep=adjust, maxCo=0.3)
     assert_path(case, arm, arm)
     m = case.monitor(patches=range(6))
@@ -226,7 +230,7 @@ def check_patches(s, case, mesh, patches, faces_of=None, what=""):
             sum_ok(s["patchPressureForce"][row, k], pb[f - nif] * Sf[f, k], tag + f" p Sf {k}")
 
 
-@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly", "box257_257_1"])
+@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly", "box257_257_1", "tet433", "prism543", "mix643"])
 def test_patch_totals_against_the_face_fields(kind):
     dims = {"box111": (1, 1, 1), "box20_17_3": (20, 17, 3), "box257_257_1": (257, 257, 1)}
     mesh = q.PolyMesh.box(*dims[kind]) if kind in dims else make_mesh(kind)

@@ -221,7 +221,8 @@ def test_scalar_reader_refuses_what_the_path_does_not_do(tmp_path):
 PARITY = [("line1d", "reduced", 1e-2, False), ("line1d", "GaussVolPoint", 1e-2, False),
           ("plane2d_jitter", "GaussVolPoint", 1e-2, False), ("plane2d_jitter", "leastSquares", 1e-2, False),
           ("box654_jitter", "GaussVolPoint", 1e-2, False), ("box654_jitter", "reduced", 1e-2, False),
-          ("box654_jitter", "GaussVolPoint", 0.0, False), ("plane2d_jitter", "GaussVolPoint", 1e-2, True)]
+          ("box654_jitter", "GaussVolPoint", 0.0, False), ("plane2d_jitter", "GaussVolPoint", 1e-2, True),
+          ("tet433", "GaussVolPoint", 1e-2, False), ("mix643", "reduced", 1e-2, False), ("prism543", "GaussVolPoint", 1e-2, True)]
 
 
 @pytest.mark.gpu
@@ -259,7 +260,7 @@ def test_device_case_steps_like_the_restatement(kind, stencil, mu, upwind):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,stencil", [("line1d", "reduced"), ("plane2d_jitter", "GaussVolPoint"), ("plane2d_jitter", "leastSquares"),
-                                          ("box654_jitter", "GaussVolPoint")])
+                                          ("box654_jitter", "GaussVolPoint"), ("tet433", "GaussVolPoint"), ("mix643", "GaussVolPoint")])
 def test_device_face_fields_of_the_initial_state(kind, stencil):
     """before any solve the device and the restatement hold the same T bit for bit: phiu, phiTauTReg, gradTf to the face-field bound"""
     mesh = make_mesh(kind)

@@ -101,7 +101,7 @@ def check_species_probes(s, case, cells, nS):
 
 # ---- 1. integrals, extrema and probes against numpy -----------------------------------------------------------------------------------------
 CELL_CASES = [(k, 6) for k in ("box111", "box5_3_17", "box257_1_1", "box488", "box654_poly", "box64_64_65")]
-CELL_CASES += [("box5_3_17", 2), ("box654_poly", 2), ("box5_3_17", 5), ("box654_poly", 5), ("box5_3_17", 32), ("box128_128_65", 2)]
+CELL_CASES += [("box5_3_17", 2), ("box654_poly", 2), ("box5_3_17", 5), ("box654_poly", 5), ("box5_3_17", 32), ("box128_128_65", 2), ("tet433", 6), ("mix643", 5)]
 
 
 @pytest.mark.parametrize("kind,nS", CELL_CASES)
@@ -212,7 +212,7 @@ def check_species_patches(s, case, mesh, patches, nS, inert, phiJm, Yb_old, impl
 
 
 @pytest.mark.parametrize("implicit", [False, True])
-@pytest.mark.parametrize("kind", ["box654_poly", "plane2d_jitter", "box257_257_1"])
+@pytest.mark.parametrize("kind", ["box654_poly", "plane2d_jitter", "box257_257_1", "tet433"])
 def test_patch_totals_against_the_kept_face_fields(kind, implicit):
     mesh = q.PolyMesh.box(257, 257, 1) if kind == "box257_257_1" else make_mesh(kind)
     if kind == "box257_257_1":

@@ -11,7 +11,14 @@ the implicitDiffusion branch on these meshes is in tests/test_implicit_diffusion
 Tolerances are those of the files whose patterns are reused: 1e-12 for the fvsc operators (test_fvsc_parity_gpu), 1e-13 / 1e-11 / 1e-10 for
 initial state / face fields / states (test_case_parity_gpu), 1e-11 for deltaT and the Courant number, 1e-9 and pFinalResidual < 1e-12 for
 QHDFoam (test_qhd_case), 1e-12 against the unsharded device and 1e-10 against the oracle for shards (test_partition_gpu), 1e-13 for the
-mass balance (test_cyclic_patches).  Each test prints its worst error (pytest -s)."""
+mass balance (test_cyclic_patches).  Each test prints its worst error (pytest -s).
+
+The other families on these meshes: species (explicit, implicitDiffusion, range shards), varScModel7, QHDFoam with implicitDiffusion true,
+QHDFoam and QGDFoam-implicit on range cuts, symmetry and cyclic patches in tests/test_unstructured_families_gpu.py; the run monitors
+(tests/test_monitor_gpu.py, test_species_monitor_gpu.py, test_qhd_monitor_gpu.py) and scalarTransportQHDFoam
+(tests/test_scalar_transport_case.py) as rows of their own files; SRFQHDFoam on tet433 in tests/test_srf_qhd_gpu.py.  The table of all of them
+is tests/test_unstructured_meshes.py::test_every_family_has_an_unstructured_row.  Not on these meshes yet: SRFQHDFoam beyond that one arm,
+species on cyclic patches, varScModel7 on shards, the applications on a written case, 2:1 refined cells with hanging nodes."""
 import numpy as np
 import pytest
 

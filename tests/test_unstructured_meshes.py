@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import qgdsolver_amd as q
+from qgdsolver_amd import _lib as L
 
 import cases
 import unstructured
@@ -67,6 +68,144 @@ def test_morton_ordered_shards(kind, world):
         seen[cg[own]] += 1
         assert 0 < (~own).sum() and s.halo_slots >= 1
     assert np.all(seen == 1)
+
+
+# ---- cyclic patches: the six sides of the lattice paired, tetrahedra and prisms copied behind sides, edges and corners ----------------------
+PERIODIC_KINDS = {"tet433": 816, "prism543": 410}      # kind: cells of the unrolled mesh.  (mix643: triangles face quadrilaterals, refused)
+PERIODIC_OPT = dict(deltaT=2e-4, mu=2e-3)
+
+
+def periodic_mesh(kind):
+    """(the mesh with its six sides cyclic, its unrolled form).  The jitter of unstructured.lattice_points keeps the boundary points where
+    they are, and every cube is cut the same way: the halves of a pair match point by point, triangle for triangle"""
+    g = make_mesh(kind, [L.PATCH_CYCLIC] * 6)
+    return g, g.unroll_cyclic()
+
+
+def periodic_fields(C):
+    """the state of test_cyclic_patches.test_triply_periodic_box_conserves_mass_momentum_and_energy"""
+    from test_cyclic_patches import smooth_fields
+    U, T, p = smooth_fields(C)
+    U[:, 2] += 0.04 * np.sin(2 * np.pi * C[:, 1])
+    return U, T + 0.03 * np.sin(2 * np.pi * C[:, 2]), p
+
+
+def conservation_defect(before, after):
+    """|change| of (mass, momentum x y z, energy) relative to (mass, mass, mass, mass, energy): test_cyclic_patches"""
+    return np.abs(after - before) / np.array([before[0], before[0], before[0], before[0], before[4]])
+
+
+@pytest.mark.parametrize("kind", sorted(PERIODIC_KINDS))
+def test_triply_periodic_unroll_keeps_the_real_mesh_and_mirrors_its_sides(kind):
+    """the assertions of test_cyclic_patches.test_unrolled_mesh_keeps_the_real_mesh_and_mirrors_its_sides, with all three directions paired:
+    26 slots (6 sides, 12 edges, 8 corners), every real label kept, each slot's ghosts its partner's send list moved by one lattice vector"""
+    g, ext = periodic_mesh(kind)
+    assert np.array_equal(unstructured.primitives(kind)["patchType"], np.zeros(6))        # the cached primitives were not written
+    n = g.nCells
+    assert ext.nCells == PERIODIC_KINDS[kind] > n and np.array_equal(ext.array("cellGlobal")[:n], np.arange(n))
+    assert np.array_equal(ext.array("points")[:3 * g.nPoints], g.array("points"))
+    ps, pz, pty = ext.array("patchStart"), ext.array("patchSize"), ext.array("patchType")
+    assert ext.nPatches == 7 and pty[-1] == L.PATCH_HALO and pz[-1] > 0 and all(pz[i] == 0 for i in range(6))
+    self_slot = ext.array("haloSelf")
+    assert ext.halo_slots == 26 and sorted(self_slot) == list(range(26)) and all(self_slot[self_slot[k]] == k for k in range(26))
+    cg, C = ext.array("cellGlobal"), ext.array("C").reshape(-1, 3)
+    for k in range(26):
+        ghost, send = ext.array(f"haloGhost{k}"), ext.array(f"haloSend{int(self_slot[k])}")
+        assert ghost.size > 0 and np.array_equal(cg[ghost], send)
+        shift = C[ghost] - C[send]
+        assert np.abs(shift - shift[0]).max() < 1e-12 and np.abs(shift[0]).max() > 0.5
+    assert (ext.array("owner")[ps[-1]: ps[-1] + pz[-1]] >= n).all()        # nothing of the real cells is left on the halo patch
+    # the copies are tetrahedra / prisms like their originals
+    per_cell = np.bincount(ext.array("owner"), minlength=ext.nCells) + np.bincount(ext.array("neighbour"), minlength=ext.nCells)
+    assert np.array_equal(per_cell[n:], per_cell[cg[n:]]) and set(per_cell) == set(EXPECT[kind][2])
+
+
+@pytest.mark.parametrize("scheme", ["GaussVolPoint", "reduced"])
+@pytest.mark.parametrize("kind", sorted(PERIODIC_KINDS))
+def test_triply_periodic_oracle_conserves_mass_momentum_and_energy(kind, scheme):
+    from test_cyclic_patches import OraclePeriodic, conserved
+    g, ext = periodic_mesh(kind)
+    per = OraclePeriodic(ext, q.default_options(stencil=scheme, **PERIODIC_OPT))
+    per.set_fields(*periodic_fields(g.array("C").reshape(-1, 3)))
+    V, n = g.array("V"), g.nCells
+    rho0 = per.field("rho", n).copy()
+    before = conserved(per.case, V, n)
+    per.step(10)
+    defect = conservation_defect(before, conserved(per.case, V, n))
+    assert (defect <= 1e-13).all(), (kind, scheme, defect)
+    assert np.abs(per.field("rho", n) - rho0).max() > 1e-3                   # (something happened)
+
+
+def test_mixed_halves_are_refused_by_name():
+    """mix643 periodic in x: the prisms' rectangles on xMin face the hexahedra's on xMax, but their neighbours' layers differ (triangles
+    against quadrilaterals on the sides next to them)"""
+    g = make_mesh("mix643", [L.PATCH_CYCLIC, L.PATCH_CYCLIC, 0, 0, 0, 0])
+    with pytest.raises(q.QgdError, match="do not match point by point"):
+        g.unroll_cyclic()
+
+
+# ---- which family runs on which of these meshes ------------------------------------------------------------------------------------------
+def _kinds(module, test, argnames, column=0, where=lambda row: True):
+    """the unstructured kinds among the rows of one parametrisation of module.test (util.param_rows), optionally of the rows `where` keeps"""
+    import importlib
+    from util import param_rows
+    rows = param_rows(getattr(importlib.import_module(module), test), argnames)
+    rows = [row if isinstance(row, (tuple, list)) else (row,) for row in rows]
+    return {row[column] for row in rows if row[column] in unstructured.KINDS and where(row)}
+
+
+def test_every_family_has_an_unstructured_row():
+    """family -> (file, test, parametrisation) and the meshes it must hold: an edit that drops a row fails here, without a GPU.  (What runs on
+    these meshes elsewhere: the fvsc operators, the explicit step, adjustTimeStep, explicit QHDFoam and explicit shards in
+    tests/test_unstructured_gpu.py, the block tables in tests/test_fused_blocks_host.py, implicitDiffusion in tests/test_implicit_diffusion.py,
+    the multigrid cycle in tests/test_mg_cycle_gpu.py, SRFQHDFoam on tet433 in tests/test_srf_qhd_gpu.py.)"""
+    fam = "test_unstructured_families_gpu"
+    tets, three = {"tet433", "mix643"}, {"tet433", "prism543", "mix643"}
+    table = [
+        ("species, explicit", fam, "test_species_explicit_match_the_replay", "kind,scheme", three, {}),
+        ("species, explicit, shards", fam, "test_species_on_range_shards_of_tetrahedra", None, {"tet433"}, {}),
+        ("species, implicitDiffusion", fam, "test_species_implicit_match_the_replay", "kind", tets, {}),
+        ("varScModel7 sensor", fam, "test_var_sc_sensor_matches_the_restatement", "kind", three, {}),
+        ("varScModel7 first step", fam, "test_var_sc_first_step_matches_the_oracle_fed_by_the_restatement", "kind,arm", tets, {}),
+        ("varScModel7 every step", fam, "test_var_sc_every_step_takes_the_restatement_of_its_pressures", "kind,arm", tets, {}),
+        ("monitor cell rows", "test_monitor_gpu", "test_integrals_extrema_and_probes_against_numpy", "kind", three, {}),
+        ("monitor patch totals", "test_monitor_gpu", "test_patch_totals_against_the_face_fields", "kind", three, {}),
+        ("monitor balance, fused", "test_monitor_gpu", "test_patch_fluxes_close_the_balance_of_mass_momentum_and_energy", "arm,adjust,kind", three,
+         dict(column=2, where=lambda row: row[0] == "fused")),
+        ("monitor balance, kernels", "test_monitor_gpu", "test_patch_fluxes_close_the_balance_of_mass_momentum_and_energy", "arm,adjust,kind", three,
+         dict(column=2, where=lambda row: row[0] == "kernels")),
+        ("species monitor cell rows", "test_species_monitor_gpu", "test_masses_extrema_and_probes_against_numpy", "kind,nS", tets, {}),
+        ("species monitor patch fluxes", "test_species_monitor_gpu", "test_patch_totals_against_the_kept_face_fields", "kind", {"tet433"}, {}),
+        ("QHD monitor cell rows", "test_qhd_monitor_gpu", "test_integrals_extrema_and_probes_against_numpy", "kind", three, {}),
+        ("QHD monitor patch totals and continuity", "test_qhd_monitor_gpu", "test_patch_totals_against_the_face_fields", "kind", {"tet433"}, {}),
+        ("scalarTransportQHDFoam steps", "test_scalar_transport_case", "test_device_case_steps_like_the_restatement", "kind,stencil,mu,upwind", three, {}),
+        ("scalarTransportQHDFoam face fields", "test_scalar_transport_case", "test_device_face_fields_of_the_initial_state", "kind,stencil", tets, {}),
+        ("QHDFoam implicitDiffusion", fam, "test_qhd_implicit_branch_matches_oracle", "kind", tets, {}),
+        ("QHDFoam shards", fam, "test_qhd_shards_match_unsharded_device_and_oracle", "kind,world", {"tet433", "tet866"}, {}),
+        ("QGDFoam implicitDiffusion shards", fam, "test_implicit_shards_match_unsharded_device_and_oracle", "kind,world", {"tet433", "tet866"}, {}),
+        ("symmetry QGDFoam", fam, "test_symmetry_patches_match_the_oracle", "kind", {"tet433", "prism543"}, {}),
+        ("symmetry QHDFoam", fam, "test_qhd_case_on_symmetry_patches", "kind", {"tet433", "prism543"}, {}),
+        ("cyclic", fam, "test_triply_periodic_case_matches_the_oracle_and_conserves", "kind", set(PERIODIC_KINDS), {}),
+        ("cyclic, oracle", "test_unstructured_meshes", "test_triply_periodic_oracle_conserves_mass_momentum_and_energy", "kind", set(PERIODIC_KINDS), {}),
+    ]
+    import test_unstructured_families_gpu as families
+    from util import param_rows
+    for family, module, test, argnames, want, how in table:
+        if argnames is None:          # one mesh, named by the module
+            assert families.SPECIES_SHARDS[0] in want and hasattr(families, test), family
+            continue
+        got = _kinds(module, test, argnames, **how)
+        assert want <= got, (family, module, test, sorted(want - got))
+    assert set(PERIODIC_KINDS) == {"tet433", "prism543"}
+    # ... and the arms
+    for test in (families.test_var_sc_first_step_matches_the_oracle_fed_by_the_restatement, families.test_var_sc_every_step_takes_the_restatement_of_its_pressures):
+        for kind in tets:
+            assert {arm for k, arm in param_rows(test, "kind,arm") if k == kind} == {"fused", "kernels", "fusedAdjust", "implicitDiffusion"}, (test.__name__, kind)
+    assert set(param_rows(families.test_symmetry_patches_match_the_oracle, "arm")) == {"fused", "kernels", "implicitDiffusion"}
+    assert set(param_rows(families.test_triply_periodic_case_matches_the_oracle_and_conserves, "arm")) == {"fused", "kernels"}
+    assert {("tet433", "GaussVolPoint"), ("mix643", "GaussVolPoint"), ("prism543", "reduced")} <= set(param_rows(families.test_species_explicit_match_the_replay, "kind,scheme"))
+    assert set(param_rows(families.test_species_explicit_match_the_replay, "adjust")) == {0, 1}
+    assert set(param_rows(families.test_species_on_range_shards_of_tetrahedra, "layer_first")) == {False, True}
 
 
 @pytest.mark.parametrize("kind", sorted(EXPECT))

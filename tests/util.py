@@ -16,9 +16,12 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / scale) if b.size else 0.0
 
 
-def make_mesh(kind):
-    """Named test meshes.  Returns a PolyMesh."""
+def make_mesh(kind, patch_types=None):
+    """Named test meshes.  Returns a PolyMesh.  patch_types (the unstructured kinds only): the types of the six sides instead of generic
+    patches, put on a copy of the cached primitives, which stay as they are"""
     G, E = L.PATCH_GENERIC, L.PATCH_EMPTY
+    if patch_types is not None and kind not in unstructured.KINDS:
+        raise KeyError((kind, "patch_types belongs to the unstructured kinds"))
     if kind == "box654":
         return q.PolyMesh.box(6, 5, 4)
     if kind == "box654_jitter":
@@ -41,9 +44,21 @@ def make_mesh(kind):
         return q.PolyMesh.box(6, 5, 1, hi=(1.0, 1.0, 0.1), patch_types=[G, G, L.PATCH_SYMMETRYPLANE, G, E, E])
     if kind in unstructured.KINDS:  # tetrahedra / prisms / prisms + hexahedra: point valence 24 / 12 / 12, cells of 4 / 5 / 5 + 6 faces
         a = unstructured.primitives(kind)
+        if patch_types is not None:
+            a = dict(a, patchType=np.array(patch_types, dtype=np.int32))
+            assert a["patchType"].shape == (6,)
         return q.PolyMesh.from_arrays(a["points"], a["faceOffsets"], a["facePoints"], a["owner"], a["neighbour"], a["nCells"], a["patchStart"],
                                       a["patchSize"], a["patchType"])
     raise KeyError(kind)
+
+
+def param_rows(test_fn, argnames):
+    """the rows of the pytest.mark.parametrize(argnames, ...) decoration of a test function, as the decorator was given them (pytest.param
+    rows by their values): for tests that take over another test's cases, and for tables that say which cases a test has"""
+    for mark in getattr(test_fn, "pytestmark", []):
+        if mark.name == "parametrize" and mark.args[0] == argnames:
+            return [row.values if hasattr(row, "marks") else row for row in mark.args[1]]
+    raise KeyError((test_fn.__name__, argnames))
 
 
 def oracle_mesh_of(mesh):
