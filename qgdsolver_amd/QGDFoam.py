@@ -3,50 +3,23 @@
 
 What the reference's ``main`` does per step -- updateFields.H, updateFluxes.H, QGDCourantNo.H,
 setDeltaT-QGDQHD.H, the three explicit equations, thermo.correct(), runTime.write() -- is
-``QGDFoamCase.step`` plus ``foamfile.write_time`` here.  Read from system/controlDict:
+``QGDFoamCase.step`` plus ``foamfile.write_cell_fields`` (write_time's job from gathered fields) here, inside ``apprun.step_chunks``;
+the run control, the stepping around the function objects and the report of the implicit solves are apprun's too.  Read from system/controlDict:
 startFrom/startTime, endTime, deltaT, writeControl (timeStep, or runTime/adjustableRunTime with a
 fixed deltaT), writeInterval, adjustTimeStep/maxCo/maxDeltaT, timePrecision, and of ``functions{}`` the types
 probes, fieldMinMax, qgdIntegrals and qgdPatchFluxes, with species names among the fields and qgdSpeciesIntegrals and
 qgdSpeciesPatchFluxes in a case with species (foamfile.read_functions; files under postProcessing/).
 """
-import argparse
 import os
 import sys
 import time as _time
 
 import numpy as np
 
+from . import apprun
 from . import foamfile as ff
-
-
-def time_name(t, precision=6):
-    """Time::timeName(): general format with timePrecision significant digits (L0)"""
-    s = f"{t:.{precision}g}"
-    if "e" in s:
-        m, e = s.split("e")
-        s = f"{m}e{int(e):+03d}"
-    return s
-
-
-def find_start_time(case_dir, cd):
-    start_from = str(cd.get("startFrom", "startTime"))
-    times = []
-    for d in os.listdir(case_dir):
-        try:
-            times.append((float(d), d))
-        except ValueError:
-            pass
-    if not times:
-        raise ff.FoamFileError(f"{case_dir}: no time directory")
-    if start_from == "latestTime":
-        return max(times)
-    if start_from == "firstTime":
-        return min(times)
-    want = float(cd.get("startTime", 0))
-    for t, d in times:
-        if abs(t - want) <= 1e-12 * max(1.0, abs(want)):
-            return t, d
-    raise ff.FoamFileError(f"{case_dir}: no time directory for startTime {want}")
+from .apprun import find_start_time, time_name                     # (their names here: they lived in this module before apprun)
+from .foamfile import write_cell_fields as _write_cell_fields      # (likewise)
 
 
 def _distributed():
@@ -124,8 +97,7 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
     case = QGDFoamCase(dev, default_options(**opt))
     # value lists of fixedValue entries follow the device mesh's patch faces (a shard's through faceGlobal, the copies behind cyclic halves
     # take their originals' values); the case files keep theirs for the writer
-    for i, bc in enumerate(ff.device_bcs(gmesh, mesh, bcs)):
-        case.set_bc(i, U=bc["U"], T=bc["T"], p=bc["p"])
+    ff.apply_bcs(case, gmesh, mesh, bcs)
     if "alphaQGD" in fields or "ScQGD" in fields:
         # non-uniform alphaQGD / ScQGD files: cell values follow the relabelling; boundary faces keep their labels under
         # renumbering, a shard's real patch faces are found through faceGlobal (cut faces carry no patch value)
@@ -212,18 +184,6 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             local_of, gather_parts = (lambda g: g), None
         functions = FunctionObjects(case, func_specs, gmesh, case_dir, t0_name, local_of, old_of_new, is_root=rank == 0,
                                     gather=gather_parts, log=log, species=species["names"] if species else None)
-    steps_taken = [0]
-
-    def advance(n):
-        if functions is None:
-            advance_plain(n)
-            return
-        while n > 0:
-            k = min(n, functions.next_due(steps_taken[0]))
-            advance_plain(k)
-            steps_taken[0] += k
-            n -= k
-            functions.after_step(steps_taken[0], t0)
 
     def advance_plain(n):
         if world == 1:
@@ -252,18 +212,7 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             out[idx] = vals
         return out
 
-    dt = float(cd["deltaT"])
-    end_time = float(cd["endTime"])
-    control = str(cd.get("writeControl", "timeStep"))
-    interval = float(cd.get("writeInterval", 1))
-    precision = int(cd.get("timePrecision", 6))
-    if control == "timeStep":
-        chunk = max(1, int(round(interval)))
-    elif control in ("runTime", "adjustableRunTime") and not adjust:
-        chunk = max(1, int(round(interval / dt)))
-    else:
-        raise ff.FoamFileError(f"writeControl '{control}' with adjustTimeStep is not supported (use writeControl timeStep)")
-    total = n_steps if n_steps is not None else (None if adjust else int(round((end_time - t0) / dt)))
+    dt, end_time, chunk, precision, total = apprun.run_control(cd, t0, n_steps, adjust, apprun.ADJUST_REFUSAL, run_time=not adjust)
     branch = "implicitDiffusion true" if opt.get("implicitDiffusion") else "explicit branch"
     log(f"QGDFoam (qgdsolver_amd, {branch}): {n_global} cells on {world} rank(s), fvsc {opt['stencil']}, "
         f"deltaT {dt:g}, start {t0_name}, cell order {renumber}")
@@ -280,43 +229,18 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
                 + "limited per value), not from the predictor alone as OpenFOAM does: same systems, same tolerance, same answer to that "
                 "tolerance -- but the 'initial' residuals and iteration counts below are NOT comparable with a reference QGDFoam log.  "
                 "QGD_IMPL_XEXTRAP=0 restores OpenFOAM's start values.")
-    done = 0
     wall0 = _time.perf_counter()
-    written = []
-    while True:
-        if total is not None and done >= total:
-            break
-        n = chunk if total is None else min(chunk, total - done)
-        if total is None:
-            # adjustTimeStep: runTime.run() is asked after every step [QGDFoam.C L90]; the write cadence stays `chunk`
-            n_done = 0
-            while n_done < n:
-                advance(1)
-                n_done += 1
-                if t0 + case.info()["time"] >= end_time - 1e-12 * max(1.0, abs(end_time)):
-                    break
-            n = n_done
-        else:
-            advance(n)
-        done += n
-        info = case.info()
+
+    def report(done, t, info):
         if world > 1:
             mins = [None] * world
             dist.all_gather_object(mins, (info["minRho"], info["minE"], info["CoNum"]))
             info["minRho"], info["minE"] = min(m[0] for m in mins), min(m[1] for m in mins)
             info["CoNum"] = max(m[2] for m in mins)
-        t = t0 + info["time"]
         log(f"Time = {time_name(t, precision)}  steps {done}  deltaT {info['deltaT']:.6g}  Courant max {info['CoNum']:.6g}  "
             f"min rho {info['minRho']:.6g}  min e {info['minE']:.6g}  ClockTime {_time.perf_counter() - wall0:.2f} s")
         if opt.get("implicitDiffusion"):
-            ii = case.implicit_info()
-            log("  " + "  ".join(f"{k}: {v['initial']:.3g} -> {v['final']:.3g} in {v['iterations']}" for k, v in ii["solves"].items()))
-            if ii["unconverged_steps"]:
-                log(f"  WARNING: {ii['unconverged_steps']} step(s) so far in which an implicit solve stopped above its tolerance "
-                    f"(implicitTol {case.options.implicitTol:g}, maxIter {case.options.implicitMaxIter})")
-            if ii["stalled_steps"]:
-                log(f"  NOTE: {ii['stalled_steps']} step(s) so far in which a Chebyshev solve ended at the rounding floor of its residual, above "
-                    f"implicitTol {case.options.implicitTol:g} (OpenFOAM would have iterated on to maxIter)")
+            apprun.log_implicit_solves(log, case.implicit_info(), case.options)
         if species and opt.get("implicitDiffusion"):
             si = case.species_implicit_info()
             log("  " + "  ".join(f"{k}: {v['initial']:.3g} -> {v['final']:.3g} in {v['iterations']}" for k, v in si["species"].items()))
@@ -335,19 +259,20 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
             log(f"max/min ScQGD: {sc_hi:.6g}/{sc_lo:.6g}")     # [varScModel7.C L256-259]
         if not np.isfinite(info["minRho"]) or info["minRho"] <= 0:
             raise FloatingPointError(f"density lost positivity at time {t:g}")
-        if write:
-            name = time_name(t, precision)
-            data = {f: gather(f) for f in ("U", "T", "p", "rho") + (("ScQGD",) if var_sc else ())}
+
+    def write_time(name):
+        data = {f: gather(f) for f in ("U", "T", "p", "rho") + (("ScQGD",) if var_sc else ())}
+        if rank == 0:
+            _write_cell_fields(case_dir, name, data, bcs, gmesh, var_sc)
+        if species:
+            # (gathered from the owned cells like the flow fields: the real cells only of a mesh with cyclic patches)
+            Y = {sn: gather(sn, case.species_field(sn)) for sn in species["names"]}
             if rank == 0:
-                _write_cell_fields(case_dir, name, data, bcs, gmesh, var_sc)
-            if species:
-                # (gathered from the owned cells like the flow fields: the real cells only of a mesh with cyclic patches)
-                Y = {sn: gather(sn, case.species_field(sn)) for sn in species["names"]}
-                if rank == 0:
-                    ff.write_species_fields(case_dir, name, gmesh, species, Y)
-            written.append(name)
-        if total is None and t >= end_time - 1e-12 * max(1.0, abs(end_time)):
-            break
+                ff.write_species_fields(case_dir, name, gmesh, species, Y)
+
+    # (adjustTimeStep without -nSteps: total is None and the loop runs to endTime, the write cadence stays `chunk`)
+    written = apprun.step_chunks(case, apprun.stepping(advance_plain, functions, t0), t0, chunk, total, precision, report, write_time if write else None,
+                                 end_time)
     if functions is not None:
         functions.finish()
     log("End")
@@ -357,50 +282,12 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print, renumber="no
     return dev, case, written
 
 
-def _write_cell_fields(case_dir, name, data, bcs, file_mesh, var_sc=None):
-    """Time directory from gathered cell fields.  Patch entries carry the BC type; values of fixedValue patches are
-    the prescribed ones, the others are written without a value (the solver evaluates them at start-up).  ScQGD (varScModel7) has
-    calculated patches with the dictionary's value, clipped like the field [varScModel7.C L237-244]."""
-    dims = {"U": "[0 1 -1 0 0 0 0]", "T": "[0 0 0 1 0 0 0]", "p": "[1 -1 -2 0 0 0 0]", "rho": "[1 -3 0 0 0 0 0]", "ScQGD": "[0 0 0 0 0 0 0]"}
-    sc_b = None
-    if var_sc:
-        sc_b = var_sc["ScQGD"]
-        sc_b = max(sc_b, var_sc["minSc"]) if var_sc["minSc"] >= 0 else sc_b
-        sc_b = min(sc_b, var_sc["maxSc"]) if var_sc["maxSc"] >= 0 else sc_b
-    names = file_mesh.patch_names
-    pt = file_mesh.array("patchType")
-    for fname, values in data.items():
-        patches = {}
-        for i, pn in enumerate(names):
-            word = ff.PATCH_WORDS.get(int(pt[i]), "patch")
-            if word in ff._CONSTRAINT_BCS:
-                patches[pn] = (word, None)
-                continue
-            if fname == "ScQGD":
-                patches[pn] = ("calculated", np.float64(sc_b))
-                continue
-            kind, val = bcs[i].get(fname, ("calculated", None)) if fname != "rho" else ("calculated", None)
-            if kind == "none":
-                kind = "calculated"
-            patches[pn] = (kind, np.asarray(val, dtype=np.float64) if (kind == "fixedValue" and val is not None) else None)
-        ff.write_field(os.path.join(case_dir, str(name), fname), file_mesh, fname, values, patches, dims[fname])
-
-
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog="QGDFoam", description=__doc__.split("\n\n")[0])
-    ap.add_argument("-case", dest="case", default=".")
-    ap.add_argument("-nSteps", dest="n_steps", type=int, default=None, help="run this many steps instead of up to endTime")
-    ap.add_argument("-device", dest="device", type=int, default=0)
-    ap.add_argument("-noWrite", dest="no_write", action="store_true")
-    ap.add_argument("-renumber", dest="renumber", default="none", choices=["none", "rcm", "morton"],
-                    help="relabel the cells on the device side (results are written in the case's own order)")
-    ap.add_argument("-backend", dest="backend", default="nccl", choices=["nccl", "gloo"],
-                    help="multi-rank transport; gloo = host-staged messages, all ranks on GPU 0 (debugging)")
-    a = ap.parse_args(argv)
-    dev, case, _ = run(a.case, a.n_steps, a.device, not a.no_write, renumber=a.renumber, backend=a.backend)
-    case.close()
-    dev.close()
-    return 0
+    return apprun.main("QGDFoam", __doc__, run, argv=argv, extra_args=(
+        ("-renumber", dict(dest="renumber", default="none", choices=["none", "rcm", "morton"],
+                           help="relabel the cells on the device side (results are written in the case's own order)")),
+        ("-backend", dict(dest="backend", default="nccl", choices=["nccl", "gloo"],
+                          help="multi-rank transport; gloo = host-staged messages, all ranks on GPU 0 (debugging)"))))
 
 
 if __name__ == "__main__":

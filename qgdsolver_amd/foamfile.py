@@ -6,6 +6,12 @@ entries QGDFoam reads (QGDFoam/createFields.H, thermophysicalProperties, fvSchem
 ``fvsc`` [fvsc.C L47-58], controlDict), so that a case prepared for the reference
 solver can be loaded into a ``QGDFoamCase`` and its result written back.
 
+The same for the QHD family: ``read_qhd_case_setup`` / ``read_srf_case_setup`` / ``read_scalar_case_setup`` (their common thermo block is
+``_read_qhd_thermo``, every reader's walk over fvSolution.solvers ``_solver_entries``), ``assemble_qhd_case`` / ``assemble_scalar_case``
+(what a reader returned -> Device and case; ``load_*`` and the applications call them), and the writers ``write_time``,
+``write_cell_fields``, ``write_qhd_time``, ``write_srf_time``, ``write_scalar_time``, ``write_species_fields``, which share one patch
+table (``_patch_table``).  ``read_run_control`` is controlDict's run control for ``apprun.run_control``.
+
 Only the ASCII stream format is handled (``format binary`` is refused loudly).
 The file grammar is OpenFOAM's (L0: OpenFOAM itself is not part of the reference
 tree); nothing in here is on the timed path.
@@ -592,6 +598,31 @@ def write_field(path, mesh, name, internal, patches, dimensions="[0 0 0 0 0 0 0]
         f.write("}\n")
 
 
+# dimensions of the written fields; the p of the QHD family is kinematic
+_DIMS = {"U": "[0 1 -1 0 0 0 0]", "T": "[0 0 0 1 0 0 0]", "p": "[1 -1 -2 0 0 0 0]", "rho": "[1 -3 0 0 0 0 0]", "ScQGD": "[0 0 0 0 0 0 0]"}
+_QHD_DIMS = dict(_DIMS, p="[0 2 -2 0 0 0 0]")
+
+
+def _patch_table(mesh, entry):
+    """the ``patches`` of write_field for one field: a constraint patch is written as its own word, without a value; any other patch as
+    entry(i, patch name, sl) -> (kind, value[, extra]), sl being the patch's slice of an array over the boundary faces"""
+    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
+    ps, pz, pt = mesh.array("patchStart"), mesh.array("patchSize"), mesh.array("patchType")
+    table = {}
+    for i, pn in enumerate(names):
+        word = PATCH_WORDS.get(int(pt[i]), "patch")
+        b0 = int(ps[i]) - mesh.nInternalFaces
+        table[pn] = (word, None) if word in _CONSTRAINT_BCS else entry(i, pn, slice(b0, b0 + int(pz[i])))
+    return table
+
+
+def _written_kind(bcs, i, fname):
+    """the type word a resident case's writer gives patch i of field fname: the kind of its boundary condition, ``calculated`` where there
+    is none"""
+    kind = bcs[i][fname][0] if bcs is not None and fname in bcs[i] else "calculated"
+    return "calculated" if kind == "none" else kind
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # case set-up (what QGDFoam's createFields.H reads)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -803,10 +834,10 @@ def read_case_setup(case_dir, time="0"):
     opt["Pr"] = float(mix["transport"]["Pr"])
     qgd = tp["QGD"]
     # QGDThermo::read(): implicitDiffusion defaults to true when absent [QGDThermo.C L70-82]
-    opt["implicitDiffusion"] = 1 if str(qgd.get("implicitDiffusion", "true")) in ("true", "on", "yes", "1") else 0
+    opt["implicitDiffusion"] = 1 if _truthy(qgd.get("implicitDiffusion", "true")) else 0
     # not a reference entry: selects the physically consistent explicit energy update (qgd_case_options::consistentEnergy)
     if "consistentEnergy" in qgd:
-        opt["consistentEnergy"] = 1 if str(qgd["consistentEnergy"]) in ("true", "on", "yes", "1") else 0
+        opt["consistentEnergy"] = 1 if _truthy(qgd["consistentEnergy"]) else 0
     model = str(qgd["QGDCoeffs"])
     if model not in ("constScPrModel1", "varScModel7"):
         raise FoamFileError(f"QGDCoeffs '{model}' is not supported (served: constScPrModel1, varScModel7)")
@@ -874,7 +905,7 @@ def read_case_setup(case_dir, time="0"):
                                 "entry defaults to true when absent")
     cd = read_dict(os.path.join(case_dir, "system", "controlDict"))
     opt["deltaT"] = float(cd["deltaT"])
-    opt["adjustTimeStep"] = 1 if str(cd.get("adjustTimeStep", "no")) in ("yes", "on", "true", "1") else 0
+    opt["adjustTimeStep"] = 1 if _truthy(cd.get("adjustTimeStep", "no")) else 0
     # createTimeControls.H (L0): maxCo defaults to 1, maxDeltaT to GREAT; setDeltaT-QGDQHD.H L45: cTau defaults to 0.75
     opt["maxCo"] = float(cd.get("maxCo", 1.0))
     opt["maxDeltaT"] = float(cd.get("maxDeltaT", 1e300))
@@ -883,18 +914,10 @@ def read_case_setup(case_dir, time="0"):
     # the linear solves of the implicitDiffusion branch take fvSolution's controls of U and e [QGDUEqn.H L66, QGDEEqn.H
     # L61: solve(...) looks up solvers.<field>]; the tighter of the two tolerances and the larger maxIter serve both
     # (qgd_case_options has one pair).  OpenFOAM's defaults when an entry is absent: tolerance 1e-6, maxIter 1000.
-    fsol_path = os.path.join(case_dir, "system", "fvSolution")
-    if opt["implicitDiffusion"] and _exists(fsol_path):
-        solvers = read_dict(fsol_path).get("solvers", {})
-        tols, iters = [], []
-        for key, entry in solvers.items() if isinstance(solvers, dict) else ():
-            names = str(key).strip('"()').replace("|", " ").split()
-            if isinstance(entry, dict) and any(n in ("U", "e", "Ux", "Uy", "Uz") or n.startswith(("U.", "e.")) for n in names):
-                tols.append(float(entry.get("tolerance", 1e-6)))
-                iters.append(int(float(entry.get("maxIter", 1000))))
-        if tols:
-            opt["implicitTol"] = min(tols)
-            opt["implicitMaxIter"] = max(iters)
+    if opt["implicitDiffusion"]:
+        pairs = [_tol_iter(e) for e in _solver_entries(_fv_solvers(case_dir), ("U", "e", "Ux", "Uy", "Uz"), prefixes=("U.", "e."))]
+        if pairs:
+            opt["implicitTol"], opt["implicitMaxIter"] = min(t for t, _ in pairs), max(i for _, i in pairs)
 
     U, bU = read_field(os.path.join(tdir, "U"), mesh)
     T, bT = read_field(os.path.join(tdir, "T"), mesh)
@@ -911,11 +934,33 @@ def read_case_setup(case_dir, time="0"):
         if opt["implicitDiffusion"]:
             # YEqn.solve() [QGDYEqn.H L62] looks up solvers.<species name>: the tightest tolerance and the largest maxIter of the transported
             # species serve them all (QGDFoamCase.set_species_solver has one pair)
-            solvers = read_dict(fsol_path).get("solvers", {}) if _exists(fsol_path) else {}
+            solvers = _fv_solvers(case_dir)
             sp = opt["species"]
             pairs = [_solver_controls(solvers, n) for n in sp["names"] if n != sp["inert"]]
             sp["tolerance"], sp["maxIter"] = min(t for t, _ in pairs), max(i for _, i in pairs)
     return mesh, opt, fields, bcs
+
+
+def _fv_solvers(case_dir):
+    """the `solvers` dictionary of system/fvSolution ({} without the file)"""
+    path = os.path.join(case_dir, "system", "fvSolution")
+    return read_dict(path).get("solvers", {}) if _exists(path) else {}
+
+
+def _solver_entries(solvers, fields, prefixes=()):
+    """the entries of fvSolution.solvers that name one of ``fields``, in the file's order: a key names the words between its quotes,
+    parentheses and `|` ("(U|e)" names U and e); with ``prefixes`` also a word that starts with one of them"""
+    out = []
+    for key, entry in solvers.items() if isinstance(solvers, dict) else ():
+        names = str(key).strip('"()').replace("|", " ").split()
+        if isinstance(entry, dict) and any(n in fields or n.startswith(tuple(prefixes)) for n in names):
+            out.append(entry)
+    return out
+
+
+def _tol_iter(entry):
+    """(tolerance, maxIter) of a solver entry; OpenFOAM's defaults 1e-6 and 1000 where it has none"""
+    return float(entry.get("tolerance", 1e-6)), int(float(entry.get("maxIter", 1000)))
 
 
 def _solver_controls(solvers, name):
@@ -934,8 +979,7 @@ def _solver_controls(solvers, name):
                     hit = False
                 if hit:
                     entry = e
-    entry = entry or {}
-    return float(entry.get("tolerance", 1e-6)), int(float(entry.get("maxIter", 1000)))
+    return _tol_iter(entry or {})
 
 
 def _species_mixture(tp, names):
@@ -1016,15 +1060,11 @@ def apply_species(case, species, cells=None, halo=False):
 
 def write_species_fields(case_dir, time_name, mesh, species, values):
     """the Y_i files of a time directory: values {name: cell values}; patch entries carry each species' own boundary condition"""
-    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
-    pt = mesh.array("patchType")
     for n in species["names"]:
-        patches = {}
-        for i, pn in enumerate(names):
-            word = PATCH_WORDS.get(int(pt[i]), "patch")
+        def entry(i, pn, sl):
             kind, val = species["bcs"][n][i]
-            patches[pn] = (word, None) if word in _CONSTRAINT_BCS else (("fixedValue", np.float64(val)) if kind == "fixedValue" else ("zeroGradient", None))
-        write_field(os.path.join(case_dir, str(time_name), n), mesh, n, values[n], patches)
+            return ("fixedValue", np.float64(val)) if kind == "fixedValue" else ("zeroGradient", None)
+        write_field(os.path.join(case_dir, str(time_name), n), mesh, n, values[n], _patch_table(mesh, entry))
 
 
 def _truthy(v):
@@ -1057,6 +1097,64 @@ def _bc_p_qhd(rec, what):
     raise FoamFileError(f"{what}: boundary condition '{t}' is not supported")
 
 
+def _read_qhd_thermo(case_dir, time, mesh, app):
+    """What the QHD family (QHDFoam, SRFQHDFoam, scalarTransportQHDFoam) reads of constant/thermophysicalProperties and <time>/alphaQGD
+    alike -> (options, the thermophysicalProperties dictionary): thermoType (equationOfState rhoConst, transport const),
+    mixture.equationOfState.rho, mixture.transport.{mu, Pr}, QGD{implicitDiffusion (default true, QGDThermo.C L70-82), QGDCoeffs
+    constTau | HbyUQHD | T0byGr | H2bynuQHD with the keys of <model>Dict or of QGD itself [QGDCoeffs.C L81-116; constTau.C L71,
+    HbyUQHD.C L61, T0byGr.C L74-75]}; alphaQGD when present and uniform [QGDCoeffs.C L119-160, default 0.5].  ``app`` names the
+    application in the refusals."""
+    opt = {}
+    tp = read_dict(os.path.join(case_dir, "constant", "thermophysicalProperties"))
+    tt = tp.get("thermoType", {})
+    for key, want in (("equationOfState", "rhoConst"), ("transport", "const")):
+        if isinstance(tt, dict) and key in tt and str(tt[key]) != want:
+            raise FoamFileError(f"thermoType.{key} '{tt[key]}' is not supported by the {app} path (only {want})")
+    mix = tp["mixture"]
+    opt["rho0"] = float(mix["equationOfState"]["rho"])
+    opt["mu"], opt["Pr"] = float(mix["transport"]["mu"]), float(mix["transport"]["Pr"])
+    qgd = tp["QGD"]
+    opt["implicitDiffusion"] = 1 if _truthy(qgd.get("implicitDiffusion", "true")) else 0
+    model = str(qgd["QGDCoeffs"])
+    if model not in ("constTau", "HbyUQHD", "T0byGr", "H2bynuQHD"):
+        raise FoamFileError(f"QGDCoeffs '{model}' is not a closure of the {app} path (constTau, HbyUQHD, T0byGr, H2bynuQHD)")
+    opt["tauModel"] = model
+    md = qgd.get(model + "Dict", qgd)
+    for key, needed in (("Tau", model == "constTau"), ("UQHD", model == "HbyUQHD"), ("T0", model == "T0byGr"), ("Gr", model == "T0byGr")):
+        if needed:
+            if key not in md:
+                raise FoamFileError(f"QGD.{model}: entry '{key}' is missing")
+            opt[key] = float(md[key])
+    opt["aQGD"] = 0.5
+    apath = os.path.join(case_dir, str(time), "alphaQGD")
+    if _exists(apath):
+        vals, _ = read_field(apath, mesh)
+        if not np.all(vals == vals[0]):
+            raise FoamFileError(f"{apath}: a non-uniform alphaQGD is not supported by the {app} path")
+        opt["aQGD"] = float(vals[0, 0])
+    return opt, tp
+
+
+def _qhd_patch_bcs(mesh, bU, bT, app, velocity="U", velocity_bc=None, bP=None):
+    """per patch {'U': ..., 'T': ...[, 'p': ...]} of a QHD-family case from the patch records of its velocity, T and (QHDFoam) p files;
+    qgdFlux, and slip on T, are refused"""
+    ptw = [PATCH_WORDS.get(int(t), "patch") for t in mesh.array("patchType")]
+    bcs = []
+    for i, name in enumerate(mesh.patch_names):
+        bu = (velocity_bc or _bc)(bU[name], True, ptw[i], f"{velocity}.{name}")
+        bt = _bc(bT[name], False, ptw[i], f"T.{name}")
+        if bu[0] == "qgdFlux" or bt[0] in ("qgdFlux", "slip"):
+            raise FoamFileError(f"patch {name}: boundary condition not supported for {velocity} / T of a {app} case")
+        bcs.append({"U": bu, "T": bt} if bP is None else {"U": bu, "T": bt, "p": _bc_p_qhd(bP[name], f"p.{name}")})
+    return bcs
+
+
+def read_run_control(cd):
+    """the run control of system/controlDict: {endTime, writeInterval, writeControl, timePrecision} with OpenFOAM's defaults"""
+    return {"endTime": float(cd["endTime"]), "writeInterval": float(cd.get("writeInterval", 1)),
+            "writeControl": str(cd.get("writeControl", "timeStep")), "timePrecision": int(cd.get("timePrecision", 6))}
+
+
 def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
     """Read an OpenFOAM QHDFoam case directory [QHDFoam.C L63-72, QHDFoam/createFields.H L32-167].
     (velocity / velocity_bc: the name of the velocity file and the reading of its patch entries, for read_srf_case_setup.)
@@ -1071,28 +1169,9 @@ def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
     maxIter} and, with implicitDiffusion, solvers.(U|T) {tolerance, maxIter}; <time>/{U,T,p}."""
     mesh = read_polymesh(os.path.join(case_dir, "constant", "polyMesh"))
     _refuse_unserved_patches(mesh, case_dir)
-    opt = {}
-    tp = read_dict(os.path.join(case_dir, "constant", "thermophysicalProperties"))
-    tt = tp.get("thermoType", {})
-    for key, want in (("equationOfState", "rhoConst"), ("transport", "const")):
-        if isinstance(tt, dict) and key in tt and str(tt[key]) != want:
-            raise FoamFileError(f"thermoType.{key} '{tt[key]}' is not supported by the QHDFoam path (only {want})")
-    mix = tp["mixture"]
-    opt["rho0"] = float(mix["equationOfState"]["rho"])
-    tr = mix["transport"]
-    opt["mu"], opt["Pr"], opt["beta"] = float(tr["mu"]), float(tr["Pr"]), float(tr["beta"])
+    opt, tp = _read_qhd_thermo(case_dir, time, mesh, "QHDFoam")
+    opt["beta"] = float(tp["mixture"]["transport"]["beta"])
     qgd = tp["QGD"]
-    opt["implicitDiffusion"] = 1 if _truthy(qgd.get("implicitDiffusion", "true")) else 0
-    model = str(qgd["QGDCoeffs"])
-    if model not in ("constTau", "HbyUQHD", "T0byGr", "H2bynuQHD"):
-        raise FoamFileError(f"QGDCoeffs '{model}' is not a closure of the QHDFoam path (constTau, HbyUQHD, T0byGr, H2bynuQHD)")
-    opt["tauModel"] = model
-    md = qgd.get(model + "Dict", qgd)
-    for key, needed in (("Tau", model == "constTau"), ("UQHD", model == "HbyUQHD"), ("T0", model == "T0byGr"), ("Gr", model == "T0byGr")):
-        if needed:
-            if key not in md:
-                raise FoamFileError(f"QGD.{model}: entry '{key}' is missing")
-            opt[key] = float(md[key])
     opt["pRefCell"] = int(float(qgd.get("pRefCell", 0)))      # setRefCell(p, thermo.subDict("QGD"), ...) [createFields.H L165]
     opt["pRefValue"] = float(qgd.get("pRefValue", 0.0))
     gp = read_dict(os.path.join(case_dir, "constant", "gravitationalProperties"))
@@ -1110,13 +1189,6 @@ def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
         raise FoamFileError(f"{case_dir}/constant/gravitationalProperties: cannot read the vector g")
     opt["g"] = tuple(vec)
     tdir = os.path.join(case_dir, str(time))
-    opt["aQGD"] = 0.5
-    apath = os.path.join(tdir, "alphaQGD")
-    if _exists(apath):
-        vals, _ = read_field(apath, mesh)
-        if not np.all(vals == vals[0]):
-            raise FoamFileError(f"{apath}: a non-uniform alphaQGD is not supported by the QHDFoam path")
-        opt["aQGD"] = float(vals[0, 0])
     fs_path = os.path.join(case_dir, "system", "fvSchemes")
     fs = read_dict(fs_path)
     # fvsc::grad of U, W, T [QHDFoam/updateFields.H L36-40] and p [QHDUEqn.H L36]; qgdFlux(phi,U,Uf) [QHDUEqn.H L41], qgdFlux(phi,T,Tf) [QHDTEqn.H L65]
@@ -1133,37 +1205,19 @@ def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
     opt["deltaT"] = float(cd["deltaT"])
     if _truthy(cd.get("adjustTimeStep", "no")):
         raise FoamFileError("adjustTimeStep yes: the QHDFoam path runs with the fixed deltaT of controlDict (its matrices are built once)")
-    fsol_path = os.path.join(case_dir, "system", "fvSolution")
-    if _exists(fsol_path):
-        solvers = read_dict(fsol_path).get("solvers", {})
-        tols, iters = [], []
-        for key, entry in solvers.items() if isinstance(solvers, dict) else ():
-            names = str(key).strip('"()').replace("|", " ").split()
-            if not isinstance(entry, dict):
-                continue
-            if "p" in names:
-                opt["pTol"] = float(entry.get("tolerance", 1e-6))
-                opt["pRelTol"] = float(entry.get("relTol", 0.0))
-                opt["pMaxIter"] = int(float(entry.get("maxIter", 1000)))
-            if any(n in ("U", "T", "Ux", "Uy", "Uz") for n in names):
-                tols.append(float(entry.get("tolerance", 1e-6)))
-                iters.append(int(float(entry.get("maxIter", 1000))))
-        if tols and opt["implicitDiffusion"]:
-            opt["implicitTol"] = min(tols)
-            opt["implicitMaxIter"] = max(iters)
+    solvers = _fv_solvers(case_dir)
+    for entry in _solver_entries(solvers, ("p",)):      # (the last entry that names p wins, key by key)
+        opt["pTol"], opt["pMaxIter"] = _tol_iter(entry)
+        opt["pRelTol"] = float(entry.get("relTol", 0.0))
+    pairs = [_tol_iter(e) for e in _solver_entries(solvers, ("U", "T", "Ux", "Uy", "Uz"))]
+    if pairs and opt["implicitDiffusion"]:
+        opt["implicitTol"], opt["implicitMaxIter"] = min(t for t, _ in pairs), max(i for _, i in pairs)
     if not _exists(os.path.join(tdir, velocity)):
         raise FoamFileError(f"{tdir}: the velocity file '{velocity}' is missing")
     U, bU = read_field(os.path.join(tdir, velocity), mesh)
     T, bT = read_field(os.path.join(tdir, "T"), mesh)
     p, bP = read_field(os.path.join(tdir, "p"), mesh)
-    ptw = [PATCH_WORDS.get(int(t), "patch") for t in mesh.array("patchType")]
-    bcs = []
-    for i, name in enumerate(mesh.patch_names):
-        bu = (velocity_bc or _bc)(bU[name], True, ptw[i], f"{velocity}.{name}")
-        bt = _bc(bT[name], False, ptw[i], f"T.{name}")
-        if bu[0] == "qgdFlux" or bt[0] in ("qgdFlux", "slip"):
-            raise FoamFileError(f"patch {name}: boundary condition not supported for {velocity} / T of a QHDFoam case")
-        bcs.append({"U": bu, "T": bt, "p": _bc_p_qhd(bP[name], f"p.{name}")})
+    bcs = _qhd_patch_bcs(mesh, bU, bT, "QHDFoam", velocity, velocity_bc, bP)
     return mesh, opt, {"U": U, "T": T[:, 0], "p": p[:, 0]}, bcs
 
 
@@ -1180,36 +1234,8 @@ def read_scalar_case_setup(case_dir, time="0"):
     is refused by name."""
     mesh = read_polymesh(os.path.join(case_dir, "constant", "polyMesh"))
     _refuse_unserved_patches(mesh, case_dir)
-    opt = {}
-    tp = read_dict(os.path.join(case_dir, "constant", "thermophysicalProperties"))
-    tt = tp.get("thermoType", {})
-    for key, want in (("equationOfState", "rhoConst"), ("transport", "const")):
-        if isinstance(tt, dict) and key in tt and str(tt[key]) != want:
-            raise FoamFileError(f"thermoType.{key} '{tt[key]}' is not supported by the scalarTransportQHDFoam path (only {want})")
-    mix = tp["mixture"]
-    opt["rho0"] = float(mix["equationOfState"]["rho"])
-    tr = mix["transport"]
-    opt["mu"], opt["Pr"] = float(tr["mu"]), float(tr["Pr"])
-    qgd = tp["QGD"]
-    opt["implicitDiffusion"] = 1 if _truthy(qgd.get("implicitDiffusion", "true")) else 0
-    model = str(qgd["QGDCoeffs"])
-    if model not in ("constTau", "HbyUQHD", "T0byGr", "H2bynuQHD"):
-        raise FoamFileError(f"QGDCoeffs '{model}' is not a closure of the scalarTransportQHDFoam path (constTau, HbyUQHD, T0byGr, H2bynuQHD)")
-    opt["tauModel"] = model
-    md = qgd.get(model + "Dict", qgd)
-    for key, needed in (("Tau", model == "constTau"), ("UQHD", model == "HbyUQHD"), ("T0", model == "T0byGr"), ("Gr", model == "T0byGr")):
-        if needed:
-            if key not in md:
-                raise FoamFileError(f"QGD.{model}: entry '{key}' is missing")
-            opt[key] = float(md[key])
+    opt, _ = _read_qhd_thermo(case_dir, time, mesh, "scalarTransportQHDFoam")
     tdir = os.path.join(case_dir, str(time))
-    opt["aQGD"] = 0.5
-    apath = os.path.join(tdir, "alphaQGD")
-    if _exists(apath):
-        vals, _ = read_field(apath, mesh)
-        if not np.all(vals == vals[0]):
-            raise FoamFileError(f"{apath}: a non-uniform alphaQGD is not supported by the scalarTransportQHDFoam path")
-        opt["aQGD"] = float(vals[0, 0])
     fs_path = os.path.join(case_dir, "system", "fvSchemes")
     fs = read_dict(fs_path)
     words, flux = read_face_schemes(fs, ("div(phiu,T)",), ("grad(T)",), fs_path)   # fvsc::grad(T) [updateFields.H L1], qgdFlux(phiu,T,Tf) [.C L110]
@@ -1223,34 +1249,20 @@ def read_scalar_case_setup(case_dir, time="0"):
         opt["maxCo"] = float(cd.get("maxCo", 1.0))                 # runTime.controlDict().lookupOrDefault [readTimeControls.H, L0]
         opt["maxDeltaT"] = float(cd.get("maxDeltaT", 1e300))       # GREAT
         opt["cTau"] = float(cd.get("cTau", 0.75))
-    control = {"endTime": float(cd["endTime"]), "writeInterval": float(cd.get("writeInterval", 1)),
-               "writeControl": str(cd.get("writeControl", "timeStep")), "timePrecision": int(cd.get("timePrecision", 6))}
-    fsol_path = os.path.join(case_dir, "system", "fvSolution")
-    if _exists(fsol_path):
-        solvers = read_dict(fsol_path).get("solvers", {})
-        for key, entry in solvers.items() if isinstance(solvers, dict) else ():
-            names = str(key).strip('"()').replace("|", " ").split()
-            if isinstance(entry, dict) and "T" in names:
-                opt["implicitTol"] = float(entry.get("tolerance", 1e-6))
-                opt["implicitMaxIter"] = int(float(entry.get("maxIter", 1000)))
+    control = read_run_control(cd)
+    for entry in _solver_entries(_fv_solvers(case_dir), ("T",)):      # (the last entry that names T wins)
+        opt["implicitTol"], opt["implicitMaxIter"] = _tol_iter(entry)
     U, bU = read_field(os.path.join(tdir, "U"), mesh)
     T, bT = read_field(os.path.join(tdir, "T"), mesh)
-    ptw = [PATCH_WORDS.get(int(t), "patch") for t in mesh.array("patchType")]
-    bcs = []
-    for i, name in enumerate(mesh.patch_names):
-        bu, bt = _bc(bU[name], True, ptw[i], f"U.{name}"), _bc(bT[name], False, ptw[i], f"T.{name}")
-        if bu[0] == "qgdFlux" or bt[0] in ("qgdFlux", "slip"):
-            raise FoamFileError(f"patch {name}: boundary condition not supported for U / T of a scalarTransportQHDFoam case")
-        bcs.append({"U": bu, "T": bt})
+    bcs = _qhd_patch_bcs(mesh, bU, bT, "scalarTransportQHDFoam")
     return mesh, opt, {"U": U, "T": T[:, 0]}, bcs, control
 
 
-def load_scalar_case(case_dir, time="0", device_id=0):
-    """Case directory -> (Device, ScalarTransportQHDCase) ready to ``step()``"""
+def assemble_scalar_case(mesh, opt, fields, bcs, device_id=0):
+    """what read_scalar_case_setup returned -> (Device, ScalarTransportQHDCase) ready to ``step()``"""
     from .fvsc import Device
     from .scalarfoam import ScalarTransportQHDCase, scalar_options
 
-    mesh, opt, fields, bcs, _ = read_scalar_case_setup(case_dir, time)
     dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}}, fused_tables=False)
     case = ScalarTransportQHDCase(dev, scalar_options(**opt))
     for i, bc in enumerate(bcs):
@@ -1259,45 +1271,52 @@ def load_scalar_case(case_dir, time="0", device_id=0):
     return dev, case
 
 
+def load_scalar_case(case_dir, time="0", device_id=0):
+    """Case directory -> (Device, ScalarTransportQHDCase) ready to ``step()``"""
+    return assemble_scalar_case(*read_scalar_case_setup(case_dir, time)[:4], device_id)
+
+
 def write_scalar_time(case, case_dir, time_name, U, bcs=None, rho0=None):
     """T of a ScalarTransportQHDCase, the frozen U it was started with and the uniform rho into <case_dir>/<time_name>/ (the AUTO_WRITE
     fields of scalarTransportQHDFoam); T's patch entries carry the patch values as ``value``"""
     mesh = case.mesh
-    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
-    ps, pz, pt = mesh.array("patchStart"), mesh.array("patchSize"), mesh.array("patchType")
-    nIF = mesh.nInternalFaces
     Tb = case.field("T.boundary")
     rho = float(rho0 if rho0 is not None else case.options.rho0)
-    pT, pU, pR = {}, {}, {}
-    for i, pn in enumerate(names):
-        word = PATCH_WORDS.get(int(pt[i]), "patch")
-        if word in _CONSTRAINT_BCS:
-            pT[pn] = pU[pn] = pR[pn] = (word, None)
-            continue
-        b0 = int(ps[i]) - nIF
+
+    def entry_T(i, pn, sl):
         kT = bcs[i]["T"][0] if bcs is not None else "calculated"
-        pT[pn] = ("calculated" if kT == "none" else kT, Tb[b0:b0 + int(pz[i])])
+        return ("calculated" if kT == "none" else kT, Tb[sl])
+
+    def entry_U(i, pn, sl):
         kU, vU = bcs[i]["U"] if bcs is not None else ("zeroGradient", None)
-        pU[pn] = (kU, np.asarray(vU, dtype=np.float64)) if kU == "fixedValue" else (kU, None)
-        pR[pn] = ("calculated", np.float64(rho))
+        return (kU, np.asarray(vU, dtype=np.float64)) if kU == "fixedValue" else (kU, None)
+
     d = os.path.join(case_dir, str(time_name))
-    write_field(os.path.join(d, "T"), mesh, "T", case.field("T"), pT, "[0 0 0 1 0 0 0]")
-    write_field(os.path.join(d, "U"), mesh, "U", np.asarray(U, dtype=np.float64).reshape(-1, 3), pU, "[0 1 -1 0 0 0 0]")
-    write_field(os.path.join(d, "rho"), mesh, "rho", np.full(mesh.nCells, rho), pR, "[1 -3 0 0 0 0 0]")
+    write_field(os.path.join(d, "T"), mesh, "T", case.field("T"), _patch_table(mesh, entry_T), _DIMS["T"])
+    write_field(os.path.join(d, "U"), mesh, "U", np.asarray(U, dtype=np.float64).reshape(-1, 3), _patch_table(mesh, entry_U), _DIMS["U"])
+    write_field(os.path.join(d, "rho"), mesh, "rho", np.full(mesh.nCells, rho), _patch_table(mesh, lambda i, pn, sl: ("calculated", np.float64(rho))),
+                _DIMS["rho"])
+
+
+def assemble_qhd_case(mesh, opt, fields, bcs, device_id=0, fused_tables=True, omega=None, solve_T=False):
+    """what read_qhd_case_setup / read_srf_case_setup returned -> (Device, QHDFoamCase) ready to ``step()``: the createFields.H sequence
+    of QHDFoam -- with ``omega``, of SRFQHDFoam: the case in the rotating frame -- over the C-ABI.  A velocity given per face
+    (read_srf_case_setup) goes through set_bc_values, after the patch's entry."""
+    from .fvsc import Device
+    from .qhdfoam import QHDFoamCase, qhd_options
+
+    dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}}, fused_tables=fused_tables)
+    case = QHDFoamCase(dev, qhd_options(**opt))
+    if omega is not None:
+        case.set_srf(omega, solve_T=solve_T)
+    apply_qhd_bcs(case, bcs)
+    case.set_fields(fields["U"], fields["T"], fields["p"])
+    return dev, case
 
 
 def load_qhd_case(case_dir, time="0", device_id=0):
     """Case directory -> (Device, QHDFoamCase) ready to ``step()``: the createFields.H sequence of QHDFoam over the C-ABI."""
-    from .fvsc import Device
-    from .qhdfoam import QHDFoamCase, qhd_options
-
-    mesh, opt, fields, bcs = read_qhd_case_setup(case_dir, time)
-    dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}})
-    case = QHDFoamCase(dev, qhd_options(**opt))
-    for i, bc in enumerate(bcs):
-        case.set_bc(i, U=bc["U"], T=bc["T"], p=bc["p"])
-    case.set_fields(fields["U"], fields["T"], fields["p"])
-    return dev, case
+    return assemble_qhd_case(*read_qhd_case_setup(case_dir, time), device_id)
 
 
 def read_srf_case_setup(case_dir, time="0"):
@@ -1385,16 +1404,8 @@ def apply_qhd_bcs(case, bcs):
 
 def load_srf_case(case_dir, time="0", device_id=0, solve_T=False):
     """Case directory -> (Device, QHDFoamCase in the rotating frame, srf) ready to ``step()``: SRFQHDFoam's createFields.H over the C-ABI"""
-    from .fvsc import Device
-    from .qhdfoam import QHDFoamCase, qhd_options
-
     mesh, opt, fields, bcs, srf = read_srf_case_setup(case_dir, time)
-    dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}})
-    case = QHDFoamCase(dev, qhd_options(**opt))
-    case.set_srf(srf["omega"], solve_T=solve_T)
-    apply_qhd_bcs(case, bcs)
-    case.set_fields(fields["U"], fields["T"], fields["p"])
-    return dev, case, srf
+    return assemble_qhd_case(mesh, opt, fields, bcs, device_id, omega=srf["omega"], solve_T=solve_T) + (srf,)
 
 
 def write_srf_time(case, case_dir, time_name, srf, bcs=None):
@@ -1404,17 +1415,10 @@ def write_srf_time(case, case_dir, time_name, srf, bcs=None):
     mesh = case.mesh
     write_qhd_time(case, case_dir, time_name, bcs, velocity="Urel")
     omega, origin = np.asarray(srf["omega"], dtype=np.float64), np.asarray(srf["origin"], dtype=np.float64)
-    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
-    ps, pz, pt = mesh.array("patchStart"), mesh.array("patchSize"), mesh.array("patchType")
-    nIF = mesh.nInternalFaces
     Uabs = case.field("U") + np.cross(omega, mesh.array("C").reshape(-1, 3) - origin)
-    Ub = case.field("U.boundary") + np.cross(omega, mesh.array("Cf").reshape(-1, 3)[nIF:] - origin)
-    patches = {}
-    for i, pn in enumerate(names):
-        word = PATCH_WORDS.get(int(pt[i]), "patch")
-        b0 = int(ps[i]) - nIF
-        patches[pn] = (word, None) if word in _CONSTRAINT_BCS else ("calculated", Ub[b0:b0 + int(pz[i])])
-    write_field(os.path.join(case_dir, str(time_name), "Uabs"), mesh, "Uabs", Uabs, patches, "[0 1 -1 0 0 0 0]")
+    Ub = case.field("U.boundary") + np.cross(omega, mesh.array("Cf").reshape(-1, 3)[mesh.nInternalFaces:] - origin)
+    write_field(os.path.join(case_dir, str(time_name), "Uabs"), mesh, "Uabs", Uabs, _patch_table(mesh, lambda i, pn, sl: ("calculated", Ub[sl])),
+                _DIMS["U"])
 
 
 def write_qhd_time(case, case_dir, time_name, bcs=None, velocity="U"):
@@ -1423,30 +1427,16 @@ def write_qhd_time(case, case_dir, time_name, bcs=None, velocity="U"):
     mesh = case.mesh
     if hasattr(mesh, "file_mesh"):
         raise FoamFileError("write_time: a case with cyclic patches carries copies of its cells; python -m qgdsolver_amd.QGDFoam writes its time directories")
-    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
-    ps, pz, pt = mesh.array("patchStart"), mesh.array("patchSize"), mesh.array("patchType")
-    nIF = mesh.nInternalFaces
-    dims = {"U": "[0 1 -1 0 0 0 0]", "T": "[0 0 0 1 0 0 0]", "p": "[0 2 -2 0 0 0 0]"}
     for fname in ("U", "T", "p"):
-        internal = case.field(fname)
         bvals = case.field(fname + ".boundary")
-        patches = {}
-        for i, pn in enumerate(names):
-            word = PATCH_WORDS.get(int(pt[i]), "patch")
-            if word in _CONSTRAINT_BCS:
-                patches[pn] = (word, None)
-                continue
-            kind, extra = "calculated", None
-            if bcs is not None and fname in bcs[i]:
-                kind = bcs[i][fname][0]
-                if kind == "none":
-                    kind = "calculated"
-                if kind == "fixedGradient":
-                    extra = {"gradient": float(bcs[i][fname][1] or 0.0)}
-            b0 = int(ps[i]) - nIF
-            patches[pn] = (kind, bvals[b0:b0 + int(pz[i])]) if extra is None else (kind, bvals[b0:b0 + int(pz[i])], extra)
+
+        def entry(i, pn, sl):
+            kind = _written_kind(bcs, i, fname)
+            if kind == "fixedGradient":
+                return (kind, bvals[sl], {"gradient": float(bcs[i][fname][1] or 0.0)})
+            return (kind, bvals[sl])
         out_name = velocity if fname == "U" else fname
-        write_field(os.path.join(case_dir, str(time_name), out_name), mesh, out_name, internal, patches, dims[fname])
+        write_field(os.path.join(case_dir, str(time_name), out_name), mesh, out_name, case.field(fname), _patch_table(mesh, entry), _QHD_DIMS[fname])
 
 
 def _patch_values(mesh, internal, patches, what):
@@ -1502,28 +1492,32 @@ def device_bcs(file_mesh, mesh, bcs):
     return out
 
 
+def apply_bcs(case, file_mesh, mesh, bcs):
+    """the per-patch BC triples of read_case_setup onto a QGDFoamCase on ``mesh`` (file_mesh itself, or cut or unrolled from it: device_bcs)"""
+    for i, bc in enumerate(device_bcs(file_mesh, mesh, bcs)):
+        case.set_bc(i, U=bc["U"], T=bc["T"], p=bc["p"])
+
+
 def load_case(case_dir, time="0", device_id=0):
     """Case directory -> (Device, QGDFoamCase) ready to ``step()``: the createFields.H sequence of QGDFoam over the
     C-ABI.  Needs the HIP device (there is no CPU fallback)."""
     from .fvsc import Device
     from .qgdfoam import QGDFoamCase, default_options
 
-    mesh, opt, fields, bcs = read_case_setup(case_dir, time)
-    if getattr(mesh, "cyclic_pairs", None):
+    file_mesh, opt, fields, bcs = read_case_setup(case_dir, time)
+    mesh = file_mesh
+    if getattr(file_mesh, "cyclic_pairs", None):
         # translational cyclic pairs: glued, with translated copies of the cells behind either half (PolyMesh.unroll_cyclic); the real cells
         # keep their labels, case.field(...)[:case.mesh.file_mesh.nCells] are theirs
         if opt.get("implicitDiffusion") or "alphaQGD" in fields or "ScQGD" in fields:
             raise FoamFileError(f"{case_dir}: a case with cyclic patches runs the explicit branch (QGD {{ implicitDiffusion false; }}) with uniform alphaQGD / ScQGD")
-        file_mesh = mesh
         mesh = file_mesh.unroll_cyclic(file_mesh.cyclic_pairs)
         mesh.file_mesh = file_mesh
         cg = mesh.array("cellGlobal")
         fields = {k: v[cg] for k, v in fields.items()}
-        bcs = device_bcs(file_mesh, mesh, bcs)
     dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}})
     case = QGDFoamCase(dev, default_options(**opt))
-    for i, bc in enumerate(bcs):
-        case.set_bc(i, U=bc["U"], T=bc["T"], p=bc["p"])
+    apply_bcs(case, file_mesh, mesh, bcs)
     if "alphaQGD" in fields or "ScQGD" in fields:
         case.set_qgd_coeffs(alphaQGD=fields.get("alphaQGD"), ScQGD=fields.get("ScQGD"))
     if opt.get("varSc"):
@@ -1544,32 +1538,34 @@ def write_time(case, case_dir, time_name, bcs=None, species=None):
     mesh = case.mesh
     if hasattr(mesh, "file_mesh"):
         raise FoamFileError("write_time: a case with cyclic patches carries copies of its cells; python -m qgdsolver_amd.QGDFoam writes its time directories")
-    names = getattr(mesh, "patch_names", None) or [f"patch{i}" for i in range(mesh.nPatches)]
-    ps, pz, pt = mesh.array("patchStart"), mesh.array("patchSize"), mesh.array("patchType")
-    nIF = mesh.nInternalFaces
-    dims = {"U": "[0 1 -1 0 0 0 0]", "T": "[0 0 0 1 0 0 0]", "p": "[1 -1 -2 0 0 0 0]", "rho": "[1 -3 0 0 0 0 0]"}
     for fname in ("U", "T", "p", "rho"):
-        internal = case.field(fname)
         bvals = case.field(fname + ".boundary")
-        patches = {}
-        for i, pn in enumerate(names):
-            word = PATCH_WORDS.get(int(pt[i]), "patch")
-            if word in _CONSTRAINT_BCS:
-                patches[pn] = (word, None)
-                continue
-            kind = "calculated"
-            if bcs is not None and fname in bcs[i]:
-                kind = bcs[i][fname][0]
-                if kind == "none":
-                    kind = "calculated"
-            b0 = int(ps[i]) - nIF
+
+        def entry(i, pn, sl):
+            kind = _written_kind(bcs, i, fname)
             if kind == "fixedValue" and fname != "rho":
                 vals, is_list = case.get_bc_values(i, fname)
-                patches[pn] = (kind, vals if is_list or not len(vals) else vals[0])
-            elif kind in ("zeroGradient", "slip", "qgdFlux"):
-                patches[pn] = (kind, None)
-            else:
-                patches[pn] = (kind, bvals[b0:b0 + int(pz[i])])
-        write_field(os.path.join(case_dir, str(time_name), fname), mesh, fname, internal, patches, dims[fname])
+                return (kind, vals if is_list or not len(vals) else vals[0])
+            return (kind, None) if kind in ("zeroGradient", "slip", "qgdFlux") else (kind, bvals[sl])
+        write_field(os.path.join(case_dir, str(time_name), fname), mesh, fname, case.field(fname), _patch_table(mesh, entry), _DIMS[fname])
     if species:
         write_species_fields(case_dir, time_name, mesh, species, {n: case.species_field(n) for n in species["names"]})
+
+
+def write_cell_fields(case_dir, name, data, bcs, file_mesh, var_sc=None):
+    """Time directory from gathered cell fields (the QGDFoam application: write_time's job for a run whose cells are relabelled, cut into
+    shards or carry cyclic copies).  Patch entries carry the BC type; values of fixedValue patches are
+    the prescribed ones, the others are written without a value (the solver evaluates them at start-up).  ScQGD (varScModel7) has
+    calculated patches with the dictionary's value, clipped like the field [varScModel7.C L237-244]."""
+    sc_b = None
+    if var_sc:
+        sc_b = var_sc["ScQGD"]
+        sc_b = max(sc_b, var_sc["minSc"]) if var_sc["minSc"] >= 0 else sc_b
+        sc_b = min(sc_b, var_sc["maxSc"]) if var_sc["maxSc"] >= 0 else sc_b
+    for fname, values in data.items():
+        def entry(i, pn, sl):
+            if fname == "ScQGD":
+                return ("calculated", np.float64(sc_b))
+            kind, val = bcs[i].get(fname, ("calculated", None)) if fname != "rho" else ("calculated", None)
+            return ("calculated" if kind == "none" else kind, np.asarray(val, dtype=np.float64) if (kind == "fixedValue" and val is not None) else None)
+        write_field(os.path.join(case_dir, str(name), fname), file_mesh, fname, values, _patch_table(file_mesh, entry), _DIMS[fname])

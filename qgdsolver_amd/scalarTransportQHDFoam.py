@@ -3,46 +3,34 @@ L60-135) run from an OpenFOAM case directory on one MI355X.
 
 What the reference's ``main`` does -- thermo.correct() and updateFluxes.H once, then per step the Courant number and setDeltaT-QGDQHD.H
 (adjustTimeStep), updateFields.H, the T equation, runTime.write() -- is ``ScalarTransportQHDCase.set_fields`` / ``step`` plus
-``foamfile.write_scalar_time`` here.  Read from system/controlDict: startFrom/startTime, endTime, deltaT, writeControl timeStep,
+``foamfile.write_scalar_time`` here (the case is put together by ``foamfile.assemble_scalar_case``; the loop is this module's own: it logs
+every step and writes on a counter).  Read from system/controlDict (apprun.run_control): startFrom/startTime, endTime, deltaT, writeControl timeStep,
 writeInterval, timePrecision, adjustTimeStep, maxCo, maxDeltaT, cTau.  The run restarts from the latest time directory (startFrom
 latestTime) or from startTime.
 """
-import argparse
+import os
 import sys
 import time as _time
 
 import numpy as np
 
+from . import apprun
 from . import foamfile as ff
-from .QGDFoam import find_start_time, time_name
+from .apprun import time_name
 
 
 def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
-    import os
-
     cd = ff.read_dict(os.path.join(case_dir, "system", "controlDict"))
-    t0, t0_name = find_start_time(case_dir, cd)
-    from .fvsc import Device
-    from .scalarfoam import ScalarTransportQHDCase, scalar_options
-
-    mesh, opt, fields, bcs, control = ff.read_scalar_case_setup(case_dir, t0_name)
-    if control["writeControl"] != "timeStep":
-        raise ff.FoamFileError(f"writeControl '{control['writeControl']}' is not supported (timeStep)")
-    dev = Device(mesh, device_id, fv_schemes={"fvsc": {"default": opt["stencil"]}}, fused_tables=False)
-    case = ScalarTransportQHDCase(dev, scalar_options(**opt))
-    for i, bc in enumerate(bcs):
-        case.set_bc(i, U=bc["U"], T=bc["T"])
-    case.set_fields(fields["U"], fields["T"])
-    chunk = max(1, int(round(control["writeInterval"])))
-    precision = control["timePrecision"]
-    end_time = control["endTime"]
+    t0, t0_name = apprun.find_start_time(case_dir, cd)
+    mesh, opt, fields, bcs, _ = ff.read_scalar_case_setup(case_dir, t0_name)
     adjust = bool(opt["adjustTimeStep"])
+    _, end_time, chunk, precision, total = apprun.run_control(cd, t0, n_steps, adjust, "is not supported (timeStep)", run_time=False)
+    dev, case = ff.assemble_scalar_case(mesh, opt, fields, bcs, device_id)
     log(f"scalarTransportQHDFoam (qgdsolver_amd, implicitDiffusion {'true' if opt['implicitDiffusion'] else 'false'}): {mesh.nCells} cells, "
         f"fvsc {opt['stencil']}, QGDCoeffs {opt['tauModel']}, deltaT {opt['deltaT']:g}{' (adjustTimeStep)' if adjust else ''}, start {t0_name}")
     if not opt["implicitDiffusion"]:
         log("  WARNING: implicitDiffusion false: scalarTransportQHDFoam.C L113 solves the T equation only under implicitDiffusion and has no "
             "else branch -- T stays as it is and only time advances (reproduced as listed)")
-    total = n_steps if n_steps is not None else (None if adjust else int(round((end_time - t0) / opt["deltaT"])))
     done, since_write = 0, 0
     wall0 = _time.perf_counter()
     written = []
@@ -76,16 +64,7 @@ def run(case_dir, n_steps=None, device_id=0, write=True, log=print):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog="scalarTransportQHDFoam", description=__doc__.split("\n\n")[0])
-    ap.add_argument("-case", dest="case", default=".")
-    ap.add_argument("-nSteps", dest="n_steps", type=int, default=None, help="run this many steps instead of up to endTime")
-    ap.add_argument("-device", dest="device", type=int, default=0)
-    ap.add_argument("-noWrite", dest="no_write", action="store_true")
-    a = ap.parse_args(argv)
-    dev, case, _ = run(a.case, a.n_steps, a.device, not a.no_write)
-    case.close()
-    dev.close()
-    return 0
+    return apprun.main("scalarTransportQHDFoam", __doc__, run, argv=argv)
 
 
 if __name__ == "__main__":
