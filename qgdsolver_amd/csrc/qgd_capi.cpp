@@ -366,17 +366,86 @@ struct HaloBuffers {
     }
 };
 
-struct qgd_case_s {
+// What the three resident cases (qgd_case_s, qgd_qhd_case_s, qgd_scalar_case_s) share, and what the entries that work on these members
+// alone take: the patch table, the per-face value lists, the implicit solve's accessors, the stream wait, the public halo entries, the
+// monitors and the teardown.  A plain base: the handles stay the three structs, which add their own members.
+struct qgd_monitor_s;
+struct CaseCore {
     qgd_device_s* dev = nullptr;
+    int stencil = ST_GVP3;      // device stencil kind
+    bool usesPoints = true;
+    bool fieldsSet = false;
+    bool counted = false;       // dev->liveCases counts this case (the last thing a create does)
+    std::vector<PatchBCDev> bc;
+    PatchBCDev* bcDev = nullptr;
+    DeviceArena arena;
+    double time = 0;
+    int64_t steps = 0;
+    // the implicitDiffusion branch's linear solver (device-scalar multi-right-hand-side): the U and e solves of a QGD case, the four systems
+    // {Ux, Uy, Uz, T} of a QHD case as one solve, the T equation of a scalar case; nullptr without the branch
+    ImplicitSolver* implSolver = nullptr;
+    HaloBuffers haloBuf;        // native halo transport (exchangeOn): the message buffers
+    std::vector<qgd_monitor_s*> monitors;   // qgd_monitor_create / qgd_qhd_monitor_create: freed with the case where still open
+    // optional caller-owned stream (e.g. the one RCCL transfers are ordered on): qgd_case_set_stream, a QGD case only
+    hipStream_t userStream = nullptr;
+    bool useUserStream = false;
+    hipStream_t stream() const { return useUserStream ? userStream : dev->stream; }
+};
+
+// the handle of a run monitor (its entries: "run monitors" below); here because a case frees the monitors still open on it
+struct qgd_monitor_s {
+    CaseCore* c = nullptr;
+    bool qhd = false;            // the kind of the handle: c is a qgd_qhd_case_s (qgd_qhd_monitor_create), else a qgd_case_s
+    MonitorView view{};
+    DeviceArena arena;
+    double* result = nullptr;    // device: one result block (the copy into a slot follows the fold in stream order)
+    double* host = nullptr;      // pinned: QGD_MONITOR_SLOTS slots of nDoubles + spDoubles: the flow block, the species block behind it
+    int64_t nDoubles = 0;
+    // the species block (qgd_monitor_enable_species; qgd_monitor_species.hip): spDoubles == 0 until it is enabled
+    SpeciesMonitorView spView{};
+    int64_t spDoubles = 0;
+    hipEvent_t ev[QGD_MONITOR_SLOTS] = {};
+    bool sampled[QGD_MONITOR_SLOTS] = {};
+    double time[QGD_MONITOR_SLOTS] = {};
+    int64_t step[QGD_MONITOR_SLOTS] = {};
+};
+// the open monitors of this process: a handle whose case was freed first is no longer among them
+static std::vector<qgd_monitor_s*> g_monitors;
+static bool monitorLive(const qgd_monitor_s* m) { return m && std::find(g_monitors.begin(), g_monitors.end(), m) != g_monitors.end(); }
+static void monitorDestroy(qgd_monitor_s* m) {
+    for (hipEvent_t e : m->ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
+    if (m->host) (void)hipHostFree(m->host);
+    m->arena.release();
+    g_monitors.erase(std::remove(g_monitors.begin(), g_monitors.end(), m), g_monitors.end());
+    delete m;
+}
+// The one teardown of a case's core, from the catch of a create and from a free alike, after the kind's own extras (pressure solver, timing
+// events, own halo stream): the monitors still open and the solver once the stream has drained, the arena, the device's count.  The caller
+// deletes the handle.
+static void caseTeardown(CaseCore* c) {
+    if (!c->monitors.empty() || c->implSolver) (void)hipStreamSynchronize(c->stream());
+    for (qgd_monitor_s* m : c->monitors) monitorDestroy(m);
+    c->monitors.clear();
+    if (c->implSolver) implicitSolverFree(c->implSolver);
+    c->arena.release();
+    if (c->counted) c->dev->liveCases--;
+}
+// every exit of a create after `new` that does not hand the case out
+template <class Case>
+static int caseAbandon(Case* c, int rc) {
+    caseTeardown(c);
+    delete c;
+    return rc;
+}
+
+struct qgd_case_s : CaseCore {
     qgd_case_options opt{};
     GasModel gas{};
-    int stencil = ST_GVP3;      // device stencil kind
     // per-term fvsc entries (qgd_case_options::termStencil): mixB >= 0: the case walks its faces with the two stencils stencil < mixB, the
     // gradient components in mixMask by mixB (bit k: rho, Ux, Uy, Uz, p, e)
     int mixB = -1, mixMask = 0;
     int implXOrder = 0;         // QGD_IMPL_XEXTRAP: order of the start-value extrapolation of the implicit branch's solves (ImplView::have counts up to it)
     bool pRefresh = true;       // grad(p)'s word is GaussVolPoint: p's boundary conditions are re-evaluated inside it [GaussVolPointStencil_8C L73] (quirk B6)
-    bool usesPoints = true;
     bool fused = false;         // qgd_case_step advances with fusedFaceCellKernel (QGD_FUSED)
     bool fusedAdj = false;      // adjustTimeStep: the blocks run up to their flux sums + Courant partials, cellFinishKernel advances once deltaT is known (QGD_FUSED_ADJUST)
     bool fusedImpl = false;     // implicitDiffusion: vertex values, QGD fluxes, tauMC and the U systems' rows are one launch on the same blocks (QGD_IMPL_FUSED)
@@ -384,21 +453,15 @@ struct qgd_case_s {
                                     //     clear fieldsSet), set by qgd_case_step and qgd_case_update_fluxes, which refresh the copies first; qgd_case_step_phase is refused
     bool hasQgdFlux = false;
     bool phiwRegistered = false;
-    bool fieldsSet = false;
     bool fluxAssembled = false;     // CaseView::flux holds the fluxes of an assembly of this case's fields (what a monitor reports per patch)
-    std::vector<struct qgd_monitor_s*> monitors;   // qgd_monitor_create: freed with the case where still open
-    std::vector<PatchBCDev> bc;
-    PatchBCDev* bcDev = nullptr;
     // per-face values of fixedValue patches (qgd_case_set_bc_values), field 0 U (3 per boundary face), 1 T, 2 p: the host copy serves
     // qgd_case_get_bc_values, the device copy is CaseView::bValU / bValT / bValP while some patch's valList names the field; both empty /
     // nullptr until the first list arrives
     std::vector<double> bcValHost[3];
     double* bcValDev[3] = {nullptr, nullptr, nullptr};
-    DeviceArena arena;
     CaseView view{};
     double* dbgBuf = nullptr;
-    ImplView impl{};            // implicitDiffusion branch: its face / cell work arrays
-    ImplicitSolver* implSolver = nullptr;   // the two linear solves of the branch (device-scalar multi-right-hand-side PCG)
+    ImplView impl{};            // implicitDiffusion branch: its face / cell work arrays (CaseCore::implSolver runs its two linear solves)
     int implSolveIndex = 0;                 // 0: the U solve is the one in flight, 1: the e solve
     bool reuseGradU = true;                 // QGD_IMPL_REUSE_GRADU (default 1)
     bool gradUValid = false;                // implicit branch, unsharded: fvc::grad(U) of phase 29 is still that of the records (phase 20 of the next step skips it)
@@ -424,8 +487,6 @@ struct qgd_case_s {
     int spBatches = 0;
     double spTol = -1.0;
     int32_t spMaxIter = -1;
-    double time = 0;
-    int64_t steps = 0;
     // timing
     bool timing = false;
     std::vector<TimedLaunch> pending;
@@ -433,14 +494,9 @@ struct qgd_case_s {
     double totalMs[QGD_K_COUNT] = {};
     int64_t launches[QGD_K_COUNT] = {};
     hipEvent_t curStart = nullptr;
-    // optional caller-owned stream (e.g. the one RCCL transfers are ordered on)
-    hipStream_t userStream = nullptr;
-    bool useUserStream = false;
-    hipStream_t stream() const { return useUserStream ? userStream : dev->stream; }
     hipStream_t haloStream = nullptr;  // pack/unpack stream (defaults to stream())
     bool useHaloStream = false;
-    // native halo transport (qgd_case_halo_exchange, qgd_case_step_sharded, selfHaloExchange): message buffers, events ordering the two streams
-    HaloBuffers haloBuf;
+    // native halo transport (qgd_case_halo_exchange, qgd_case_step_sharded, selfHaloExchange): CaseCore::haloBuf, and the events ordering the two streams
     hipStream_t ownHaloStream = nullptr;
     hipEvent_t evLayerDone = nullptr, evUnpacked = nullptr;
 };
@@ -1560,6 +1616,32 @@ int qgd_case_options_default(qgd_case_options* o) {
     return QGD_OK;
 }
 
+// ---- what the three creates share -------------------------------------------------------------------------------------------------------
+// after an entry's own option checks: the device's refusal of resident cases, the stencil of the options, the device made current
+static int caseCreatePreamble(const char* who, qgd_device_s* d, int stencilId, int* st) {
+    if (!d->caseRefusal.empty()) return fail(d->caseRefusalCode, std::string(who) + ": " + d->caseRefusal);
+    const int rc = deviceStencil(d, stencilId, st);
+    if (rc) return rc;
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    return QGD_OK;
+}
+static void caseCoreInit(CaseCore* c, qgd_device_s* d, int st) {
+    c->dev = d; c->stencil = st;
+    c->usesPoints = (st == ST_GVP3 || st == ST_GVP2);
+}
+// the patch table: every patch zeroGradient or its constraint's own kinds, and the device copy set_fields fills
+static void casePatchTable(CaseCore* c) {
+    const std::vector<Patch>& patches = c->dev->patches;
+    c->bc.resize(patches.size());
+    for (size_t i = 0; i < patches.size(); ++i) initPatchBC(c->bc[i], patches[i]);
+    c->bcDev = c->arena.alloc<PatchBCDev>(std::max<size_t>(1, c->bc.size()));
+}
+// the last step of a create: the device counts the case (qgd_device_free refuses while one is open)
+static void caseCount(CaseCore* c) {
+    c->dev->liveCases++;
+    c->counted = true;
+}
+
 int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out) {
     QGD_TRY
     if (!d || !opt || !out) return fail(QGD_ERR_INVALID, "qgd_case_create: null argument");
@@ -1569,15 +1651,13 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
         return fail(QGD_ERR_INVALID, "qgd_case_create: R, Cv, Pr, PrQGD, deltaT must be positive");
     if ((opt->fluxSchemeU != QGD_FLUX_LINEAR && opt->fluxSchemeU != QGD_FLUX_UPWIND) || (opt->fluxSchemeH != QGD_FLUX_LINEAR && opt->fluxSchemeH != QGD_FLUX_UPWIND))
         return fail(QGD_ERR_INVALID, "qgd_case_create: fluxSchemeU / fluxSchemeH must be QGD_FLUX_LINEAR or QGD_FLUX_UPWIND");
-    if (!d->caseRefusal.empty()) return fail(d->caseRefusalCode, "qgd_case_create: " + d->caseRefusal);
     int st = 0;
-    int rc = deviceStencil(d, opt->stencil, &st);
+    const int rc = caseCreatePreamble("qgd_case_create", d, opt->stencil, &st);
     if (rc) return rc;
-    HIP_CHECK(hipSetDevice(d->deviceId));
     qgd_case_s* c = new qgd_case_s();
     try {
-        c->dev = d; c->opt = *opt; c->stencil = st;
-        c->usesPoints = (st == ST_GVP3 || st == ST_GVP2);
+        caseCoreInit(c, d, st);
+        c->opt = *opt;
         c->pRefresh = c->usesPoints;
         {   // per-term entries [fvsc_8C L51-58]: grad(U), grad(e), grad(rho), grad(p) -> components (Ux,Uy,Uz), e, rho, p of the face gradient
             static const int kBits[4] = {0x0e, 0x20, 0x01, 0x10};
@@ -1586,12 +1666,13 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
                 term[t] = st;
                 if (opt->termStencil[t] != 0) {
                     const int r2 = deviceStencil(d, opt->termStencil[t] - 1, &term[t]);   // the checks of fvscOpName apply per term
-                    if (r2) { delete c; return r2; }
+                    if (r2) return caseAbandon(c, r2);
                 }
                 lo = std::min(lo, term[t]); hi = std::max(hi, term[t]);
             }
             for (int t = 0; t < 4; ++t)
-                if (term[t] != lo && term[t] != hi) { delete c; return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_create: more than two distinct fvsc stencils in one case"); }
+                if (term[t] != lo && term[t] != hi)
+                    return caseAbandon(c, fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_case_create: more than two distinct fvsc stencils in one case"));
             if (lo != hi) {
                 c->stencil = lo; c->mixB = hi; c->mixMask = 0;
                 for (int t = 0; t < 4; ++t) if (term[t] == hi) c->mixMask |= kBits[t];
@@ -1666,66 +1747,24 @@ int qgd_case_create(qgd_device_t d, const qgd_case_options* opt, qgd_case_t* out
                 if (c->implXOrder > 0 && opt->adjustTimeStep) { iv.w = a.alloc<double>(4); iv.dtHist = a.alloc<double>(8); }   // (zero-filled)
             }
         }
-        c->bc.resize(d->patches.size());
-        for (size_t i = 0; i < d->patches.size(); ++i) initPatchBC(c->bc[i], d->patches[i]);
-        c->bcDev = a.alloc<PatchBCDev>(std::max<size_t>(1, c->bc.size()));
+        casePatchTable(c);
         const double dt0[8] = {opt->deltaT, 0, 0, 0, 0, 0, 0, 0};
         HIP_CHECK(hipMemcpy(cv.dt, dt0, sizeof(dt0), hipMemcpyHostToDevice));
-    } catch (...) { c->arena.release(); delete c; throw; }
-    d->liveCases++;
+    } catch (...) { caseAbandon(c, 0); throw; }
+    caseCount(c);
     *out = c;
     return QGD_OK;
     QGD_CATCH
 }
-// the handle of a run monitor (its entries: "run monitors" below); here because a case frees the monitors still open on it
-struct qgd_qhd_case_s;
-struct qgd_monitor_s {
-    qgd_case_s* c = nullptr;
-    qgd_qhd_case_s* qc = nullptr;   // the kind of the handle: a monitor of a QHD case (qgd_qhd_monitor_create) has qc and no c
-    MonitorView view{};
-    DeviceArena arena;
-    double* result = nullptr;    // device: one result block (the copy into a slot follows the fold in stream order)
-    double* host = nullptr;      // pinned: QGD_MONITOR_SLOTS slots of nDoubles + spDoubles: the flow block, the species block behind it
-    int64_t nDoubles = 0;
-    // the species block (qgd_monitor_enable_species; qgd_monitor_species.hip): spDoubles == 0 until it is enabled
-    SpeciesMonitorView spView{};
-    int64_t spDoubles = 0;
-    hipEvent_t ev[QGD_MONITOR_SLOTS] = {};
-    bool sampled[QGD_MONITOR_SLOTS] = {};
-    double time[QGD_MONITOR_SLOTS] = {};
-    int64_t step[QGD_MONITOR_SLOTS] = {};
-};
-// the open monitors of this process: a handle whose case was freed first is no longer among them
-static std::vector<qgd_monitor_s*> g_monitors;
-static bool monitorLive(const qgd_monitor_s* m) { return m && std::find(g_monitors.begin(), g_monitors.end(), m) != g_monitors.end(); }
-static void monitorDestroy(qgd_monitor_s* m) {
-    for (hipEvent_t e : m->ev) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
-    if (m->host) (void)hipHostFree(m->host);
-    m->arena.release();
-    g_monitors.erase(std::remove(g_monitors.begin(), g_monitors.end(), m), g_monitors.end());
-    delete m;
-}
-static void freeMonitors(std::vector<qgd_monitor_s*>& monitors, hipStream_t stream) {
-    if (monitors.empty()) return;
-    (void)hipStreamSynchronize(stream);
-    for (qgd_monitor_s* m : monitors) monitorDestroy(m);
-    monitors.clear();
-}
-static void freeMonitorsOf(qgd_case_s* c) { freeMonitors(c->monitors, c->stream()); }
 int qgd_case_free(qgd_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
-    freeMonitorsOf(c);
     harvestTiming(c);
     for (hipEvent_t e : c->freeEvents) (void)hipEventDestroy(e);
-    if (c->implSolver) { (void)hipStreamSynchronize(c->stream()); implicitSolverFree(c->implSolver); }
     if (c->ownHaloStream) { (void)hipStreamSynchronize(c->ownHaloStream); (void)hipStreamDestroy(c->ownHaloStream); }
     if (c->evLayerDone) (void)hipEventDestroy(c->evLayerDone);
     if (c->evUnpacked) (void)hipEventDestroy(c->evUnpacked);
-    c->arena.release();
-    c->dev->liveCases--;
-    delete c;
-    return QGD_OK;
+    return caseAbandon(c, QGD_OK);
 }
 
 // CaseView::bValU / bValT / bValP follow the patches' flags: a field no patch has a list for reads nothing (nullptr)
@@ -1740,21 +1779,32 @@ static void bcValuePointers(qgd_case_s* c) {
 // fusedFaceCellKernel<..., IMPL>): a case with per-face velocities assembles with implCellUKernel, which reads the list
 static bool implFusedNow(const qgd_case_s* c) { return c->fusedImpl && !c->view.bValU; }
 
-int qgd_case_set_bc(qgd_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT, int32_t bcP, double valueP) {
-    QGD_TRY
+// The write of one patch's table entry behind the three set_bc: `who` names the entry.  pKinds: the p kinds the case admits on top of
+// zeroGradient / fixedValue / none -- 0: a case without p (its entry keeps zeroGradient, or the constraint's kind), 1: qgdFlux, 2: and qhdFlux
+static int casePatchEntry(CaseCore* c, const char* who, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT, int pKinds,
+                          int32_t bcP, double valueP) {
     if (!c) return fail(QGD_ERR_INVALID, "null case");
-    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, "qgd_case_set_bc: patch out of range");
+    const std::string w(who);
+    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, w + ": patch out of range");
     auto okU = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_SLIP || k == QGD_BC_NONE; };
     auto okT = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_NONE; };
-    auto okP = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_QGDFLUX || k == QGD_BC_NONE; };
-    if (!okU(bcU) || !okT(bcT) || !okP(bcP)) return fail(QGD_ERR_INVALID, "qgd_case_set_bc: unsupported boundary-condition kind");
+    auto okP = [pKinds](int k) {
+        return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_NONE || (pKinds >= 1 && k == QGD_BC_QGDFLUX) || (pKinds >= 2 && k == QGD_BC_QHDFLUX);
+    };
+    if (!okU(bcU) || !okT(bcT) || !okP(bcP)) return fail(QGD_ERR_INVALID, w + ": unsupported boundary-condition kind");
     PatchBCDev& b = c->bc[patch];
     constraintKinds(b.ptype, bcU, bcT, bcP);   // a constraint patch keeps its own field type whatever the caller asks for
     b.bcU = bcU; b.bcT = bcT; b.bcP = bcP; b.vT = valueT; b.vP = valueP;
     if (valueU) for (int k = 0; k < 3; ++k) b.vU[k] = valueU[k];
-    b.valList = 0;   // the patch is uniform again: a value list follows its entry (qgd_case_set_bc_values comes after this call)
-    bcValuePointers(c);
+    b.valList = 0;   // the patch is uniform again: a value list follows its entry (*_set_bc_values comes after this call)
     c->fieldsSet = false;
+    return QGD_OK;
+}
+int qgd_case_set_bc(qgd_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT, int32_t bcP, double valueP) {
+    QGD_TRY
+    const int rc = casePatchEntry(c, "qgd_case_set_bc", patch, bcU, valueU, bcT, valueT, 1, bcP, valueP);
+    if (rc) return rc;
+    bcValuePointers(c);
     c->gradUValid = false;
     return QGD_OK;
     QGD_CATCH
@@ -1762,7 +1812,10 @@ int qgd_case_set_bc(qgd_case_t c, int32_t patch, int32_t bcU, const double* valu
 
 // field 0 U, 1 T, 2 p of a patch's table entry
 static int32_t bcKindOf(const PatchBCDev& b, int field) { return field == 0 ? b.bcU : (field == 1 ? b.bcT : b.bcP); }
-static int bcValuesCheck(qgd_case_t c, const char* who, int32_t patch, int32_t field, int64_t nFaces) {
+// The checks of a per-face value list of a fixedValue entry (both set_bc_values, qgd_case_get_bc_values).  counted: nFaces has to be the
+// patch's (a null list, which clears the flag, comes with any).  noEntry: the one text an entry has for a halo, cyclic or constraint patch
+// (behind the patch's name), nullptr: one text per kind of patch.
+static int bcValuesCheck(CaseCore* c, const char* who, int32_t patch, int32_t field, int64_t nFaces, bool counted, const char* noEntry = nullptr) {
     const std::string w(who);
     if (!c) return fail(QGD_ERR_INVALID, w + ": null case");
     if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, w + ": patch out of range");
@@ -1770,41 +1823,54 @@ static int bcValuesCheck(qgd_case_t c, const char* who, int32_t patch, int32_t f
     const Patch& pt = c->dev->patches[patch];
     const PatchBCDev& b = c->bc[patch];
     static const char* kFieldName[3] = {"U", "T", "p"};
+    if (pt.type != QGD_PATCH_GENERIC && noEntry) return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + noEntry);
     if (pt.type == QGD_PATCH_HALO) return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a halo patch (its faces carry no boundary condition)");
     if (pt.type == QGD_PATCH_CYCLIC) return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a cyclic patch (its faces carry no boundary condition)");
     if (pt.type != QGD_PATCH_GENERIC)
         return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a constraint patch (empty / symmetryPlane / symmetry / wedge): it keeps its own field type");
     if (bcKindOf(b, field) != QGD_BC_FIXEDVALUE)
         return fail(QGD_ERR_INVALID, w + ": the " + kFieldName[field] + " entry of patch '" + pt.name + "' is not fixedValue (per-face values belong to fixedValue entries only)");
-    if (nFaces != (int64_t)pt.size)
+    if (counted && nFaces != (int64_t)pt.size)
         return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' has " + std::to_string(pt.size) + " faces on this device's mesh, nFaces = " + std::to_string(nFaces));
+    return QGD_OK;
+}
+// The store behind both set_bc_values, after the check: the list of `field` (3 per face for U, else 1) goes into devList, one entry per
+// boundary face of the device's mesh and made on first use, and into hostList where the case keeps a host copy; a null list clears the
+// patch's flag.  finite: a non-finite value is refused.  The caller refreshes its view's pointers.
+static int bcValuesStore(CaseCore* c, const char* who, int32_t patch, int32_t field, const double* values, bool finite, double*& devList,
+                         std::vector<double>* hostList) {
+    const std::string w(who);
+    const Patch& pt = c->dev->patches[patch];
+    const int32_t bit = 1 << field;
+    if (!values) c->bc[patch].valList &= ~bit;
+    else {
+        HIP_CHECK(hipSetDevice(c->dev->deviceId));
+        const MeshView& m = c->dev->view;
+        const size_t nw = field == 0 ? 3 : 1, nB = (size_t)m.nBF, first = (size_t)(pt.start - m.nIF);
+        if (first + (size_t)pt.size > nB) return fail(QGD_ERR_INVALID, w + ": the patch's faces lie outside the device's boundary faces");
+        if (finite)
+            for (size_t i = 0; i < nw * (size_t)pt.size; ++i)
+                if (!std::isfinite(values[i])) return fail(QGD_ERR_INVALID, w + ": non-finite value");
+        if (hostList && hostList->empty()) hostList->assign(nw * std::max<size_t>(nB, 1), 0.0);
+        if (!devList) devList = c->arena.alloc<double>(nw * std::max<size_t>(nB, 1));   // (zero-filled)
+        if (pt.size > 0) {
+            if (hostList) std::memcpy(hostList->data() + nw * first, values, sizeof(double) * nw * (size_t)pt.size);
+            HIP_CHECK(hipStreamSynchronize(c->stream()));   // (no kernel of an earlier step still reads the old values)
+            HIP_CHECK(hipMemcpy(devList + nw * first, values, sizeof(double) * nw * (size_t)pt.size, hipMemcpyHostToDevice));
+        }
+        c->bc[patch].valList |= bit;
+    }
+    c->fieldsSet = false;   // like set_bc: the patch records are evaluated again by set_fields
     return QGD_OK;
 }
 
 int qgd_case_set_bc_values(qgd_case_t c, int32_t patch, int32_t field, const double* values, int64_t nFaces) {
     QGD_TRY
-    const int rc = bcValuesCheck(c, "qgd_case_set_bc_values", patch, field, values ? nFaces : (c && patch >= 0 && patch < (int32_t)c->bc.size() ? (int64_t)c->dev->patches[patch].size : nFaces));
+    int rc = bcValuesCheck(c, "qgd_case_set_bc_values", patch, field, nFaces, values != nullptr);
+    if (rc == QGD_OK) rc = bcValuesStore(c, "qgd_case_set_bc_values", patch, field, values, false, c->bcValDev[field], &c->bcValHost[field]);
     if (rc) return rc;
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    const MeshView& m = c->dev->view;
-    const Patch& pt = c->dev->patches[patch];
-    const int32_t bit = 1 << field;
-    if (!values) c->bc[patch].valList &= ~bit;
-    else {
-        const size_t w = field == 0 ? 3 : 1, nB = (size_t)m.nBF, first = (size_t)(pt.start - m.nIF);
-        if (first + (size_t)pt.size > nB) return fail(QGD_ERR_INVALID, "qgd_case_set_bc_values: the patch's faces lie outside the device's boundary faces");
-        if (c->bcValHost[field].empty()) c->bcValHost[field].assign(w * std::max<size_t>(nB, 1), 0.0);
-        if (!c->bcValDev[field]) c->bcValDev[field] = c->arena.alloc<double>(w * std::max<size_t>(nB, 1));   // (zero-filled)
-        if (pt.size > 0) {
-            std::memcpy(c->bcValHost[field].data() + w * first, values, sizeof(double) * w * (size_t)pt.size);
-            HIP_CHECK(hipStreamSynchronize(c->stream()));   // (no kernel of an earlier step still reads the old values)
-            HIP_CHECK(hipMemcpy(c->bcValDev[field] + w * first, values, sizeof(double) * w * (size_t)pt.size, hipMemcpyHostToDevice));
-        }
-        c->bc[patch].valList |= bit;
-    }
     bcValuePointers(c);
-    c->fieldsSet = false;      // like qgd_case_set_bc: the patch records are evaluated again by qgd_case_set_fields,
-    c->ghostsCurrent = false;  // and the copies behind cyclic halves take their originals' records after it
+    c->ghostsCurrent = false;  // the copies behind cyclic halves take their originals' records after qgd_case_set_fields
     c->gradUValid = false;
     return QGD_OK;
     QGD_CATCH
@@ -1812,7 +1878,7 @@ int qgd_case_set_bc_values(qgd_case_t c, int32_t patch, int32_t field, const dou
 
 int qgd_case_get_bc_values(qgd_case_t c, int32_t patch, int32_t field, double* values, int64_t nFaces, int32_t* isList) {
     QGD_TRY
-    const int rc = bcValuesCheck(c, "qgd_case_get_bc_values", patch, field, nFaces);
+    const int rc = bcValuesCheck(c, "qgd_case_get_bc_values", patch, field, nFaces, true);
     if (rc) return rc;
     if (!values && nFaces > 0) return fail(QGD_ERR_INVALID, "qgd_case_get_bc_values: null argument");
     const MeshView& m = c->dev->view;
@@ -2675,7 +2741,8 @@ int qgd_case_set_stream(qgd_case_t c, void* hipStream) {
     c->useUserStream = true;
     return QGD_OK;
 }
-int qgd_case_stream_sync(qgd_case_t c) {
+// the wait behind qgd_case_stream_sync, qgd_qhd_case_sync and qgd_scalar_case_sync
+static int caseSync(CaseCore* c) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
@@ -2683,6 +2750,7 @@ int qgd_case_stream_sync(qgd_case_t c) {
     return QGD_OK;
     QGD_CATCH
 }
+int qgd_case_stream_sync(qgd_case_t c) { return caseSync(c); }
 
 int qgd_device_alloc(qgd_device_t d, int64_t bytes, void** devicePtr) {
     QGD_TRY
@@ -2703,38 +2771,46 @@ int qgd_device_release(qgd_device_t d, void* devicePtr) {
     QGD_CATCH
 }
 
-static int caseHaloCount(qgd_case_s* c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
+// ---- the public halo entries of both case kinds, after their own argument checks: the doubles of message m for a slot (none beyond the
+// device's slots), and its pack / unpack on a stream
+static int caseHaloCount(const CaseCore* c, int slot, const HaloMessage& m, int64_t* sendCount, int64_t* recvCount) {
     *sendCount = *recvCount = 0;
     if (slot >= (int)c->dev->halo.size()) return QGD_OK;
-    const HaloMessage m = haloMessage(c, kind, true);
     *sendCount = (int64_t)m.sendCount(c->dev->halo[slot]);
     *recvCount = (int64_t)m.recvCount(c->dev->halo[slot]);
     return QGD_OK;
 }
-// the public pack / unpack of message `kind`: the state message honours qgd_case_set_halo_stream, the others run on the case's stream
-static int caseHaloMovePublic(qgd_case_s* c, int slot, int kind, const double* buf, bool pack) {
+static int caseHaloMovePublic(const CaseCore* c, int slot, const HaloMessage& m, const double* buf, bool pack, hipStream_t stream) {
     QGD_TRY
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return caseHaloMove(c, slot, kind, const_cast<double*>(buf), pack, kind == 0 && c->useHaloStream ? c->haloStream : c->stream());
+    return m.move(slot, const_cast<double*>(buf), pack, stream);
     QGD_CATCH
+}
+// of a QGD case: counts with room for the widest solve (haloMessage's forCount); the state message honours qgd_case_set_halo_stream, the
+// others run on the case's stream
+static int qgdHaloCount(qgd_case_s* c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
+    return caseHaloCount(c, slot, haloMessage(c, kind, true), sendCount, recvCount);
+}
+static int qgdHaloMove(qgd_case_s* c, int slot, int kind, const double* buf, bool pack) {
+    return caseHaloMovePublic(c, slot, haloMessage(c, kind), buf, pack, kind == 0 && c->useHaloStream ? c->haloStream : c->stream());
 }
 int qgd_case_halo_count(qgd_case_t c, int slot, int64_t* count) {
     int64_t recv;
     if (!c || !count || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloCount(c, slot, 0, count, &recv);
+    return qgdHaloCount(c, slot, 0, count, &recv);
 }
 int qgd_case_halo_recv_count(qgd_case_t c, int slot, int64_t* count) {
     int64_t send;
     if (!c || !count || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloCount(c, slot, 0, &send, count);
+    return qgdHaloCount(c, slot, 0, &send, count);
 }
 int qgd_case_halo_pack(qgd_case_t c, int slot, double* sendBufDevice) {
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloMovePublic(c, slot, 0, sendBufDevice, true);
+    return qgdHaloMove(c, slot, 0, sendBufDevice, true);
 }
 int qgd_case_halo_unpack(qgd_case_t c, int slot, const double* recvBufDevice) {
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloMovePublic(c, slot, 0, recvBufDevice, false);
+    return qgdHaloMove(c, slot, 0, recvBufDevice, false);
 }
 int qgd_case_mid_exchange_needed(qgd_case_t c, int32_t* needed) {
     if (!c || !needed) return fail(QGD_ERR_INVALID, "bad argument");
@@ -2743,63 +2819,49 @@ int qgd_case_mid_exchange_needed(qgd_case_t c, int32_t* needed) {
 }
 int qgd_case_mid_halo_count(qgd_case_t c, int slot, int64_t* sendCount, int64_t* recvCount) {
     if (!c || slot < 0 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloCount(c, slot, 5, sendCount, recvCount);
+    return qgdHaloCount(c, slot, 5, sendCount, recvCount);
 }
 int qgd_case_mid_halo_pack(qgd_case_t c, int slot, double* sendBufDevice) {
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloMovePublic(c, slot, 5, sendBufDevice, true);
+    return qgdHaloMove(c, slot, 5, sendBufDevice, true);
 }
 int qgd_case_mid_halo_unpack(qgd_case_t c, int slot, const double* recvBufDevice) {
     if (!c || slot < 0) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloMovePublic(c, slot, 5, recvBufDevice, false);
+    return qgdHaloMove(c, slot, 5, recvBufDevice, false);
 }
 // the branch's own messages on a shard (kinds 1 grad U, 2 U, 3 search direction, 4 guess): counts in doubles
 int qgd_case_implicit_halo_count(qgd_case_t c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
     if (!c || slot < 0 || kind < 1 || kind > 4 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
     *sendCount = *recvCount = 0;
     if (!c->implSolver) return fail(QGD_ERR_INVALID, "qgd_case_implicit_halo_count: not an implicitDiffusion case");
-    return caseHaloCount(c, slot, kind, sendCount, recvCount);
+    return qgdHaloCount(c, slot, kind, sendCount, recvCount);
 }
 int qgd_case_implicit_halo_pack(qgd_case_t c, int slot, int kind, double* sendBufDevice) {
     if (!c || slot < 0 || kind < 1 || kind > 4 || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloMovePublic(c, slot, kind, sendBufDevice, true);
+    return qgdHaloMove(c, slot, kind, sendBufDevice, true);
 }
 int qgd_case_implicit_halo_unpack(qgd_case_t c, int slot, int kind, const double* recvBufDevice) {
     if (!c || slot < 0 || kind < 1 || kind > 4 || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
-    return caseHaloMovePublic(c, slot, kind, recvBufDevice, false);
+    return qgdHaloMove(c, slot, kind, recvBufDevice, false);
 }
 
 // ---- QHDFoam case resident on the device -------------------------------------------------------------------------------
-struct qgd_qhd_case_s {
-    qgd_device_s* dev = nullptr;
+struct qgd_qhd_case_s : CaseCore {   // (implSolver: the four systems {Ux, Uy, Uz, T} as one multi-right-hand-side solve; haloBuf: qgd_qhd_case_halo_exchange, qgd_qhd_case_step_sharded)
     qgd_qhd_options opt{};
-    int stencil = ST_GVP3;
-    bool usesPoints = true, fieldsSet = false;
     double* pHist[4] = {nullptr, nullptr, nullptr, nullptr}; int pOrder = 0, pPrevHave = 0;   // QGD_QHD_PEXTRAP: p of the steps before (start value of the pressure solve, qgd_qhd.hip)
     int implXOrder = 0;         // QGD_IMPL_XEXTRAP (QhdView::xHave counts up to it)   // QGD_QHD_PEXTRAP: p of the step before (start value of the pressure solve, qgd_qhd.hip)
-    std::vector<PatchBCDev> bc;
-    PatchBCDev* bcDev = nullptr;
-    DeviceArena arena;
     QhdView view{};
     double* c4b = nullptr;      // QGD_QHD_FUSED: the second {U,T} array of the block-fused U / T equations (qgd_qhd.hip qhdFusedAdvanceKernel); swapped with view.c4 every step
     double *tauF = nullptr, *tbr = nullptr, *scratch = nullptr;
     uint8_t* bKind = nullptr;
     PressureSolver* solver = nullptr;
-    ImplicitSolver* implSolver = nullptr;  // implicitDiffusion: the four systems {Ux, Uy, Uz, T} as one multi-right-hand-side solve
     int implMask = 15;                     // components that are solved (validComponents: not those along empty directions)
     bool needRef = false;
     int localRefCell = -1;                 // local label of pRefCell when this shard owns it
     std::vector<int32_t> bcPRequested;     // p kinds as the caller set them (a box slab's cut plane hides the patch's own kind)
-    HaloBuffers haloBuf;                   // native transport (qgd_qhd_case_halo_exchange, qgd_qhd_case_step_sharded)
-    double time = 0, lastIter = 0, lastRes0 = 0, lastRes = 0, lastSolveMs = 0;
-    int64_t steps = 0;
+    double lastIter = 0, lastRes0 = 0, lastRes = 0, lastSolveMs = 0;
     double* bValUDev = nullptr;            // qgd_qhd_case_set_bc_values: 3 per boundary face (view.bValU while some patch's valList names U)
-    std::vector<qgd_monitor_s*> monitors;  // qgd_qhd_monitor_create: freed with the case where still open
 };
-// what the entries of a monitor need of its case, whichever kind it is
-static qgd_device_s* monitorDevice(const qgd_monitor_s* m) { return m->qc ? m->qc->dev : m->c->dev; }
-static hipStream_t monitorStream(const qgd_monitor_s* m) { return m->qc ? m->qc->dev->stream : m->c->stream(); }
-static std::vector<qgd_monitor_s*>& monitorsOfCase(qgd_monitor_s* m) { return m->qc ? m->qc->monitors : m->c->monitors; }
 
 int qgd_qhd_options_default(qgd_qhd_options* o) {
     if (!o) return fail(QGD_ERR_INVALID, "null argument");
@@ -2823,18 +2885,16 @@ int qgd_qhd_case_create(qgd_device_t d, const qgd_qhd_options* opt, qgd_qhd_case
         return fail(QGD_ERR_INVALID, "qgd_qhd_case_create: rho0, Pr, deltaT must be positive, tauModel in 0..3");
     if ((opt->fluxSchemeU != QGD_FLUX_LINEAR && opt->fluxSchemeU != QGD_FLUX_UPWIND) || (opt->fluxSchemeT != QGD_FLUX_LINEAR && opt->fluxSchemeT != QGD_FLUX_UPWIND))
         return fail(QGD_ERR_INVALID, "qgd_qhd_case_create: fluxSchemeU / fluxSchemeT must be QGD_FLUX_LINEAR or QGD_FLUX_UPWIND");
-    if (!d->caseRefusal.empty()) return fail(d->caseRefusalCode, "qgd_qhd_case_create: " + d->caseRefusal);
     int st = 0;
-    int rc = deviceStencil(d, opt->stencil, &st);
+    const int rc = caseCreatePreamble("qgd_qhd_case_create", d, opt->stencil, &st);
     if (rc) return rc;
-    HIP_CHECK(hipSetDevice(d->deviceId));
     qgd_qhd_case_s* c = new qgd_qhd_case_s();
     try {
-        c->dev = d; c->opt = *opt; c->stencil = st;
-        c->usesPoints = (st == ST_GVP3 || st == ST_GVP2);
+        caseCoreInit(c, d, st);
+        c->opt = *opt;
         d->ensureFaceGeoPos();
         const MeshView& v = d->view;
-        if (!d->sharded() && opt->pRefCell >= v.nC) { delete c; return fail(QGD_ERR_INVALID, "qgd_qhd_case_create: pRefCell out of range"); }
+        if (!d->sharded() && opt->pRefCell >= v.nC) return caseAbandon(c, fail(QGD_ERR_INVALID, "qgd_qhd_case_create: pRefCell out of range"));
         DeviceArena& a = c->arena;
         QhdView& q = c->view;
         const size_t nC = (size_t)v.nC, nB = (size_t)std::max(v.nBF, 1), nF = (size_t)v.nF, nP = (size_t)std::max(v.nP, 1);
@@ -2864,18 +2924,16 @@ int qgd_qhd_case_create(qgd_device_t d, const qgd_qhd_options* opt, qgd_qhd_case
         q.rho0 = opt->rho0; q.nu = opt->mu / opt->rho0; q.Hi = (opt->mu / opt->Pr) / opt->rho0; q.beta = opt->beta;
         for (int k = 0; k < 3; ++k) q.g[k] = opt->g[k];
         q.dt = opt->deltaT; q.tauModel = opt->tauModel; q.Tau = opt->Tau; q.aQGD = opt->aQGD; q.UQHD = opt->UQHD; q.T0 = opt->T0; q.Gr = opt->Gr;
-        c->bc.resize(d->patches.size());
         c->bcPRequested.assign(d->patches.size(), QGD_BC_ZEROGRADIENT);
-        for (size_t i = 0; i < d->patches.size(); ++i) initPatchBC(c->bc[i], d->patches[i]);
-        c->bcDev = a.alloc<PatchBCDev>(std::max<size_t>(1, c->bc.size()));
+        casePatchTable(c);
         c->bKind = a.alloc<uint8_t>(nB);
         {
             static const int kModes[] = {0, 1, 2, 3, 4};
             c->pOrder = envChoice("QGD_QHD_PEXTRAP", 4, kModes, 5);   // 0: OpenFOAM's start value p^n; k: extrapolation of order k in time (qgd_qhd.hip)
             for (int j = 0; j < c->pOrder; ++j) c->pHist[j] = a.alloc<double>(nC);
         }
-    } catch (...) { if (c->implSolver) implicitSolverFree(c->implSolver); c->arena.release(); delete c; throw; }
-    d->liveCases++;
+    } catch (...) { caseAbandon(c, 0); throw; }
+    caseCount(c);
     *out = c;
     return QGD_OK;
     QGD_CATCH
@@ -2883,13 +2941,8 @@ int qgd_qhd_case_create(qgd_device_t d, const qgd_qhd_options* opt, qgd_qhd_case
 int qgd_qhd_case_free(qgd_qhd_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
-    freeMonitors(c->monitors, c->dev->stream);
     if (c->solver) pressureSolverFree(c->solver);
-    if (c->implSolver) { (void)hipStreamSynchronize(c->dev->stream); implicitSolverFree(c->implSolver); }
-    c->arena.release();
-    c->dev->liveCases--;
-    delete c;
-    return QGD_OK;
+    return caseAbandon(c, QGD_OK);
 }
 // QhdView::bValU follows the patches' flags: without a list the kernels read nothing (nullptr) and keep their list-free instantiations
 static void qhdBcValuePointer(qgd_qhd_case_s* c) {
@@ -2900,51 +2953,21 @@ static void qhdBcValuePointer(qgd_qhd_case_s* c) {
 int qgd_qhd_case_set_bc(qgd_qhd_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT, int32_t bcP,
                         double valueP) {
     QGD_TRY
-    if (!c) return fail(QGD_ERR_INVALID, "null case");
-    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_bc: patch out of range");
-    auto okU = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_SLIP || k == QGD_BC_NONE; };
-    auto okT = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_NONE; };
-    auto okP = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_QGDFLUX || k == QGD_BC_QHDFLUX || k == QGD_BC_NONE; };
-    if (!okU(bcU) || !okT(bcT) || !okP(bcP)) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_bc: unsupported boundary-condition kind");
-    PatchBCDev& b = c->bc[patch];
+    const int rc = casePatchEntry(c, "qgd_qhd_case_set_bc", patch, bcU, valueU, bcT, valueT, 2, bcP, valueP);
+    if (rc) return rc;
     c->bcPRequested[patch] = bcP;
-    constraintKinds(b.ptype, bcU, bcT, bcP);   // a constraint patch keeps its own field type whatever the caller asks for
-    b.bcU = bcU; b.bcT = bcT; b.bcP = bcP; b.vT = valueT; b.vP = valueP;
-    if (valueU) for (int k = 0; k < 3; ++k) b.vU[k] = valueU[k];
-    b.valList = 0;   // the patch is uniform again (qgd_qhd_case_set_bc_values comes after this call)
     qhdBcValuePointer(c);
-    c->fieldsSet = false;
     return QGD_OK;
     QGD_CATCH
 }
 // one velocity per face of a fixedValue patch: the contract of qgd_case_set_bc_values
 int qgd_qhd_case_set_bc_values(qgd_qhd_case_t c, int32_t patch, const double* U, int64_t nFaces) {
     QGD_TRY
-    const std::string w = "qgd_qhd_case_set_bc_values";
-    if (!c) return fail(QGD_ERR_INVALID, w + ": null case");
-    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, w + ": patch out of range");
-    const Patch& pt = c->dev->patches[patch];
-    if (pt.type != QGD_PATCH_GENERIC)
-        return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' is a halo, cyclic or constraint patch: its faces carry no fixedValue entry");
-    if (c->bc[patch].bcU != QGD_BC_FIXEDVALUE)
-        return fail(QGD_ERR_INVALID, w + ": the U entry of patch '" + pt.name + "' is not fixedValue (per-face values belong to fixedValue entries only)");
-    if (!U) { c->bc[patch].valList &= ~QGD_BC_LIST_U; qhdBcValuePointer(c); c->fieldsSet = false; return QGD_OK; }
-    if (nFaces != (int64_t)pt.size)
-        return fail(QGD_ERR_INVALID, w + ": patch '" + pt.name + "' has " + std::to_string(pt.size) + " faces on this device's mesh, nFaces = " + std::to_string(nFaces));
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    const MeshView& m = c->dev->view;
-    const size_t nB = (size_t)m.nBF, first = (size_t)(pt.start - m.nIF);
-    if (first + (size_t)pt.size > nB) return fail(QGD_ERR_INVALID, w + ": the patch's faces lie outside the device's boundary faces");
-    for (int64_t i = 0; i < 3 * nFaces; ++i)
-        if (!std::isfinite(U[i])) return fail(QGD_ERR_INVALID, w + ": non-finite value");
-    if (!c->bValUDev) c->bValUDev = c->arena.alloc<double>(3 * std::max<size_t>(nB, 1));   // (zero-filled)
-    if (pt.size > 0) {
-        HIP_CHECK(hipStreamSynchronize(c->dev->stream));   // (no kernel of an earlier step still reads the old values)
-        HIP_CHECK(hipMemcpy(c->bValUDev + 3 * first, U, sizeof(double) * 3 * (size_t)pt.size, hipMemcpyHostToDevice));
-    }
-    c->bc[patch].valList |= QGD_BC_LIST_U;
+    int rc = bcValuesCheck(c, "qgd_qhd_case_set_bc_values", patch, 0, nFaces, U != nullptr,
+                           "' is a halo, cyclic or constraint patch: its faces carry no fixedValue entry");
+    if (rc == QGD_OK) rc = bcValuesStore(c, "qgd_qhd_case_set_bc_values", patch, 0, U, true, c->bValUDev, nullptr);
+    if (rc) return rc;
     qhdBcValuePointer(c);
-    c->fieldsSet = false;   // like qgd_qhd_case_set_bc: the patch values are evaluated again by qgd_qhd_case_set_fields
     return QGD_OK;
     QGD_CATCH
 }
@@ -3215,49 +3238,71 @@ int qgd_qhd_case_control(qgd_qhd_case_t c, double control[16], int set) {
     return QGD_OK;
     QGD_CATCH
 }
-// the control block (68 doubles) and the state of the implicitDiffusion solve in flight
-int qgd_qhd_case_implicit_control(qgd_qhd_case_t c, double control[68], int set) {
+// ---- the accessors of the implicitDiffusion solve, of a QGD and of a QHD case: `refusal` is the entry's text for a null argument or a case
+// without the branch.  The control block (68 doubles, slot-major: control[slot * 4 + component]) and the state of the solve in flight
+static int caseImplicitControl(CaseCore* c, const char* refusal, double* control, int set) {
     QGD_TRY
-    if (!c || !control || !c->implSolver) return fail(QGD_ERR_INVALID, "qgd_qhd_case_implicit_control: an implicitDiffusion case is needed");
+    if (!c || !control || !c->implSolver) return fail(QGD_ERR_INVALID, refusal);
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    hipStream_t st = c->dev->stream;
+    hipStream_t st = c->stream();
     if (set) HIP_CHECK(hipMemcpyAsync(implicitSolverCtl(c->implSolver), control, 68 * sizeof(double), hipMemcpyHostToDevice, st));
     else HIP_CHECK(hipMemcpyAsync(control, implicitSolverCtl(c->implSolver), 68 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     return QGD_OK;
     QGD_CATCH
 }
-int qgd_qhd_case_implicit_control_ptr(qgd_qhd_case_t c, void** devicePtr) {
-    if (!c || !devicePtr || !c->implSolver) return fail(QGD_ERR_INVALID, "qgd_qhd_case_implicit_control_ptr: an implicitDiffusion case is needed");
+static int caseImplicitControlPtr(CaseCore* c, const char* refusal, void** devicePtr) {
+    if (!c || !devicePtr || !c->implSolver) return fail(QGD_ERR_INVALID, refusal);
     *devicePtr = implicitSolverCtl(c->implSolver);
     return QGD_OK;
 }
-int qgd_qhd_case_implicit_info(qgd_qhd_case_t c, double info[16]) {
+// status: {all components done, right-hand sides of the solve in flight}; maxRhs: 3 (a QGD case's solves) or 4 (the QHD case's) are read
+static int caseImplicitSolveStatus(CaseCore* c, const char* refusal, int maxRhs, double status[2]) {
     QGD_TRY
-    if (!c || !info) return fail(QGD_ERR_INVALID, "bad argument");
-    for (int i = 0; i < 16; ++i) info[i] = 0.0;
-    if (!c->implSolver) return QGD_OK;
+    if (!c || !status || !c->implSolver) return fail(QGD_ERR_INVALID, refusal);
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    double allDone = 0;
+    implicitSolverSetStream(c->implSolver, c->stream());
     int it[4];
     double r0[4], r1[4];
-    implicitSolveStatus4(c->implSolver, &allDone, it, r0, r1);
-    for (int k = 0; k < 4; ++k) { info[k] = it[k]; info[4 + k] = r0[k]; info[8 + k] = r1[k]; }
-    info[12] = implicitSolverUnconverged(c->implSolver, &info[14]);
-    info[13] = implicitSolverChebyshev(c->implSolver) ? 2.0 : 1.0;
-    return QGD_OK;
-    QGD_CATCH
-}
-int qgd_qhd_case_implicit_solve_status(qgd_qhd_case_t c, double status[2]) {
-    QGD_TRY
-    if (!c || !status || !c->implSolver) return fail(QGD_ERR_INVALID, "qgd_qhd_case_implicit_solve_status: an implicitDiffusion case is needed");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    int it[4];
-    double r0[4], r1[4];
-    implicitSolveStatus4(c->implSolver, &status[0], it, r0, r1);
+    if (maxRhs == 3) implicitSolveStatus(c->implSolver, &status[0], it, r0, r1);
+    else implicitSolveStatus4(c->implSolver, &status[0], it, r0, r1);
     status[1] = implicitSolverRhs(c->implSolver);
     return QGD_OK;
     QGD_CATCH
+}
+// info: iterations [0..4), initial [4..8) and final residuals [8..12) of four systems, [12] steps with a solve above its tolerance, [13] the
+// algorithm (0: no branch, 1: conjugate gradients (QGD_IMPL_SOLVER=pcg), 2: Chebyshev iteration), [14] stalled steps.  lastStep: the systems
+// are Ux, Uy, Uz, e of the QGD case's two solves as the last step left them, else the four of the QHD case's one solve as it stands
+static int caseImplicitInfo(CaseCore* c, const char* refusal, bool lastStep, double info[16]) {
+    QGD_TRY
+    if (!c || !info) return fail(QGD_ERR_INVALID, refusal);
+    for (int k = 0; k < 16; ++k) info[k] = 0.0;
+    ImplicitSolver* S = c->implSolver;
+    if (!S) return QGD_OK;
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    implicitSolverSetStream(S, c->stream());
+    int it[4];
+    double r0[4], r1[4], bad = 0, stalled = 0;
+    if (lastStep) implicitSolverInfo(S, it, r0, r1, &bad, &stalled);
+    else {
+        double allDone = 0;
+        implicitSolveStatus4(S, &allDone, it, r0, r1);
+        bad = implicitSolverUnconverged(S, &stalled);
+    }
+    for (int k = 0; k < 4; ++k) { info[k] = it[k]; info[4 + k] = r0[k]; info[8 + k] = r1[k]; }
+    info[12] = bad; info[13] = implicitSolverChebyshev(S) ? 2.0 : 1.0; info[14] = stalled;
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_qhd_case_implicit_control(qgd_qhd_case_t c, double control[68], int set) {
+    return caseImplicitControl(c, "qgd_qhd_case_implicit_control: an implicitDiffusion case is needed", control, set);
+}
+int qgd_qhd_case_implicit_control_ptr(qgd_qhd_case_t c, void** devicePtr) {
+    return caseImplicitControlPtr(c, "qgd_qhd_case_implicit_control_ptr: an implicitDiffusion case is needed", devicePtr);
+}
+int qgd_qhd_case_implicit_info(qgd_qhd_case_t c, double info[16]) { return caseImplicitInfo(c, "bad argument", false, info); }
+int qgd_qhd_case_implicit_solve_status(qgd_qhd_case_t c, double status[2]) {
+    return caseImplicitSolveStatus(c, "qgd_qhd_case_implicit_solve_status: an implicitDiffusion case is needed", 4, status);
 }
 int qgd_qhd_case_solve_status(qgd_qhd_case_t c, double status[4]) {
     QGD_TRY
@@ -3269,14 +3314,7 @@ int qgd_qhd_case_solve_status(qgd_qhd_case_t c, double status[4]) {
     return QGD_OK;
     QGD_CATCH
 }
-int qgd_qhd_case_sync(qgd_qhd_case_t c) {
-    QGD_TRY
-    if (!c) return fail(QGD_ERR_INVALID, "null case");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    HIP_CHECK(hipStreamSynchronize(c->dev->stream));
-    return QGD_OK;
-    QGD_CATCH
-}
+int qgd_qhd_case_sync(qgd_qhd_case_t c) { return caseSync(c); }
 // what the phase in flight waits for before qgd_qhd_case_step_phase(c, 9): see include/qgd_amd.h
 int qgd_qhd_case_pending(qgd_qhd_case_t c, int32_t* action, void** devicePtr, int64_t* count) {
     if (!c || !action) return fail(QGD_ERR_INVALID, "bad argument");
@@ -3323,26 +3361,15 @@ static HaloBuffers& haloBuffers(qgd_qhd_case_s* c) {
 }
 int qgd_qhd_case_halo_count(qgd_qhd_case_t c, int slot, int kind, int64_t* sendCount, int64_t* recvCount) {
     if (!c || slot < 0 || kind < 0 || kind > 4 || !sendCount || !recvCount) return fail(QGD_ERR_INVALID, "bad argument");
-    *sendCount = *recvCount = 0;
-    if (slot >= (int)c->dev->halo.size()) return QGD_OK;
-    const HaloMessage m = haloMessage(c, kind);
-    *sendCount = (int64_t)m.sendCount(c->dev->halo[slot]);
-    *recvCount = (int64_t)m.recvCount(c->dev->halo[slot]);
-    return QGD_OK;
+    return caseHaloCount(c, slot, haloMessage(c, kind), sendCount, recvCount);
 }
 int qgd_qhd_case_halo_pack(qgd_qhd_case_t c, int slot, int kind, double* sendBufDevice) {
-    QGD_TRY
     if (!c || slot < 0 || kind < 0 || kind > 4) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return caseHaloMove(c, slot, kind, sendBufDevice, true, c->dev->stream);
-    QGD_CATCH
+    return caseHaloMovePublic(c, slot, haloMessage(c, kind), sendBufDevice, true, c->stream());
 }
 int qgd_qhd_case_halo_unpack(qgd_qhd_case_t c, int slot, int kind, const double* recvBufDevice) {
-    QGD_TRY
     if (!c || slot < 0 || kind < 0 || kind > 4) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    return caseHaloMove(c, slot, kind, const_cast<double*>(recvBufDevice), false, c->dev->stream);
-    QGD_CATCH
+    return caseHaloMovePublic(c, slot, haloMessage(c, kind), recvBufDevice, false, c->stream());
 }
 int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int64_t outDoubles) {
     QGD_TRY
@@ -3411,22 +3438,14 @@ int qgd_qhd_case_fused_info(qgd_qhd_case_t c, int64_t info[4]) {
 }
 
 // ---- scalarTransportQHDFoam case resident on the device (qgd_scalar.hip) -------------------------------------------------
-struct qgd_scalar_case_s {
-    qgd_device_s* dev = nullptr;
+struct qgd_scalar_case_s : CaseCore {   // (implSolver: the T equation's one system)
     qgd_scalar_options opt{};
-    int stencil = ST_GVP3;
-    bool usesPoints = true, fieldsSet = false;
-    std::vector<PatchBCDev> bc;
-    PatchBCDev* bcDev = nullptr;
-    DeviceArena arena;
     ScalarView view{};
     double *work = nullptr, *red = nullptr;
-    ImplicitSolver* solver = nullptr;
     // the two extrema the time-step control reads are constants of the run (U, tauQGDf and the mesh do not change): reduced once on the
     // device at set_fields, the rule itself is then host arithmetic on them and no step waits for the device
     double maxUh = 0, minTau = 0;
-    double dt = 0, dtDiag = 0, CoNum = 0, time = 0;   // dtDiag: the deltaT view.diag was built with
-    int64_t steps = 0;
+    double dt = 0, dtDiag = 0, CoNum = 0;   // dtDiag: the deltaT view.diag was built with
 };
 
 int qgd_scalar_options_default(qgd_scalar_options* o) {
@@ -3458,15 +3477,13 @@ int qgd_scalar_case_create(qgd_device_t d, const qgd_scalar_options* opt, qgd_sc
         return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: fluxSchemeT must be QGD_FLUX_LINEAR or QGD_FLUX_UPWIND");
     if (opt->adjustTimeStep && (!(opt->maxCo > 0) || !(opt->maxDeltaT > 0) || !(opt->cTau > 0)))
         return fail(QGD_ERR_INVALID, "qgd_scalar_case_create: adjustTimeStep needs maxCo, maxDeltaT, cTau > 0");
-    if (!d->caseRefusal.empty()) return fail(d->caseRefusalCode, "qgd_scalar_case_create: " + d->caseRefusal);
     int st = 0;
-    int rc = deviceStencil(d, opt->stencil, &st);
+    const int rc = caseCreatePreamble("qgd_scalar_case_create", d, opt->stencil, &st);
     if (rc) return rc;
-    HIP_CHECK(hipSetDevice(d->deviceId));
     qgd_scalar_case_s* c = new qgd_scalar_case_s();
     try {
-        c->dev = d; c->opt = *opt; c->stencil = st;
-        c->usesPoints = (st == ST_GVP3 || st == ST_GVP2);
+        caseCoreInit(c, d, st);
+        c->opt = *opt;
         const MeshView& v = d->view;
         DeviceArena& a = c->arena;
         ScalarView& q = c->view;
@@ -3481,12 +3498,10 @@ int qgd_scalar_case_create(qgd_device_t d, const qgd_scalar_options* opt, qgd_sc
         q.Hi = (opt->mu / opt->Pr) / opt->rho0;
         q.upwindT = opt->fluxSchemeT == QGD_FLUX_UPWIND ? 1 : 0;
         q.tauModel = opt->tauModel; q.Tau = opt->Tau; q.aQGD = opt->aQGD; q.UQHD = opt->UQHD; q.T0 = opt->T0; q.Gr = opt->Gr; q.nu = opt->mu / opt->rho0;
-        if (opt->implicitDiffusion) c->solver = implicitSolverCreate(d->stream, v, 0, v.nC);
-        c->bc.resize(d->patches.size());
-        for (size_t i = 0; i < d->patches.size(); ++i) initPatchBC(c->bc[i], d->patches[i]);
-        c->bcDev = a.alloc<PatchBCDev>(std::max<size_t>(1, c->bc.size()));
-    } catch (...) { if (c->solver) implicitSolverFree(c->solver); c->arena.release(); delete c; throw; }
-    d->liveCases++;
+        if (opt->implicitDiffusion) c->implSolver = implicitSolverCreate(d->stream, v, 0, v.nC);
+        casePatchTable(c);
+    } catch (...) { caseAbandon(c, 0); throw; }
+    caseCount(c);
     *out = c;
     return QGD_OK;
     QGD_CATCH
@@ -3494,27 +3509,12 @@ int qgd_scalar_case_create(qgd_device_t d, const qgd_scalar_options* opt, qgd_sc
 int qgd_scalar_case_free(qgd_scalar_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
-    (void)hipStreamSynchronize(c->dev->stream);
-    if (c->solver) implicitSolverFree(c->solver);
-    c->arena.release();
-    c->dev->liveCases--;
-    delete c;
-    return QGD_OK;
+    (void)hipStreamSynchronize(c->stream());   // (with or without a solver: no kernel of the last step still reads the arena)
+    return caseAbandon(c, QGD_OK);
 }
 int qgd_scalar_case_set_bc(qgd_scalar_case_t c, int32_t patch, int32_t bcU, const double* valueU, int32_t bcT, double valueT) {
     QGD_TRY
-    if (!c) return fail(QGD_ERR_INVALID, "null case");
-    if (patch < 0 || patch >= (int32_t)c->bc.size()) return fail(QGD_ERR_INVALID, "qgd_scalar_case_set_bc: patch out of range");
-    auto okU = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_SLIP || k == QGD_BC_NONE; };
-    auto okT = [](int k) { return k == QGD_BC_ZEROGRADIENT || k == QGD_BC_FIXEDVALUE || k == QGD_BC_NONE; };
-    if (!okU(bcU) || !okT(bcT)) return fail(QGD_ERR_INVALID, "qgd_scalar_case_set_bc: unsupported boundary-condition kind");
-    PatchBCDev& b = c->bc[patch];
-    int32_t bcP = QGD_BC_ZEROGRADIENT;
-    constraintKinds(b.ptype, bcU, bcT, bcP);   // a constraint patch keeps its own field type whatever the caller asks for
-    b.bcU = bcU; b.bcT = bcT; b.vT = valueT;
-    if (valueU) for (int k = 0; k < 3; ++k) b.vU[k] = valueU[k];
-    c->fieldsSet = false;
-    return QGD_OK;
+    return casePatchEntry(c, "qgd_scalar_case_set_bc", patch, bcU, valueU, bcT, valueT, 0, QGD_BC_ZEROGRADIENT, 0.0);
     QGD_CATCH
 }
 int qgd_scalar_case_set_fields(qgd_scalar_case_t c, const double* U, const double* T) {
@@ -3537,7 +3537,7 @@ int qgd_scalar_case_set_fields(qgd_scalar_case_t c, const double* U, const doubl
     HIP_CHECK(hipStreamSynchronize(d->stream));
     c->maxUh = std::max(red[0], 0.0); c->minTau = red[1];
     c->dt = c->opt.deltaT; c->dtDiag = 0; c->CoNum = c->dt * c->maxUh; c->time = 0; c->steps = 0;
-    if (c->solver) implicitStatsReset(c->solver);
+    if (c->implSolver) implicitStatsReset(c->implSolver);
     c->fieldsSet = true;
     return QGD_OK;
     QGD_CATCH
@@ -3562,13 +3562,13 @@ int qgd_scalar_case_step(qgd_scalar_case_t c, int32_t nSteps) {
         if (!o.implicitDiffusion) continue;                                 // .C L113: there is no else -- T stays as it is
         (void)hipGetLastError();
         if (c->dt != c->dtDiag) { launchScalarDiag(d->stream, m, c->view, c->dt); c->dtDiag = c->dt; }
-        implicitStepMark(c->solver, true);
+        implicitStepMark(c->implSolver, true);
         launchScalarAssemble(d->stream, c->stencil, c->usesPoints, m, c->view, c->bcDev, c->dt, true);
         HIP_CHECK(hipGetLastError());
-        implicitSolveSetup(c->solver, 1, 1, c->view.a, c->view.diag, c->view.rhs, c->view.T, o.implicitTol, o.implicitMaxIter);
-        implicitSolveRun(c->solver, nullptr);
-        implicitSolveEnd(c->solver, 1);
-        implicitStepMark(c->solver, false);
+        implicitSolveSetup(c->implSolver, 1, 1, c->view.a, c->view.diag, c->view.rhs, c->view.T, o.implicitTol, o.implicitMaxIter);
+        implicitSolveRun(c->implSolver, nullptr);
+        implicitSolveEnd(c->implSolver, 1);
+        implicitStepMark(c->implSolver, false);
         launchScalarPatchValues(d->stream, m, c->view, c->bcDev);            // solve() ends in correctBoundaryConditions()
         HIP_CHECK(hipGetLastError());
     }
@@ -3617,25 +3617,18 @@ int qgd_scalar_case_info(qgd_scalar_case_t c, double info[12]) {
     for (int k = 0; k < 12; ++k) info[k] = 0.0;
     info[0] = c->time; info[1] = c->dt > 0 ? c->dt : c->opt.deltaT; info[2] = c->CoNum; info[3] = (double)c->steps;
     info[10] = c->maxUh; info[11] = c->minTau;
-    if (c->solver && c->fieldsSet) {
+    if (c->implSolver && c->fieldsSet) {
         HIP_CHECK(hipSetDevice(c->dev->deviceId));
         int it[4] = {0, 0, 0, 0};
         double r0[4] = {0, 0, 0, 0}, r1[4] = {0, 0, 0, 0}, un = 0, stalled = 0;
-        implicitSolverInfo(c->solver, it, r0, r1, &un, &stalled);   // the case's solve is kept in the second block (implicitSolveEnd(S, 1))
+        implicitSolverInfo(c->implSolver, it, r0, r1, &un, &stalled);   // the case's solve is kept in the second block (implicitSolveEnd(S, 1))
         info[4] = it[3]; info[5] = r0[3]; info[6] = r1[3]; info[7] = un; info[8] = stalled;
-        info[9] = implicitSolverChebyshev(c->solver) ? 2.0 : 1.0;
+        info[9] = implicitSolverChebyshev(c->implSolver) ? 2.0 : 1.0;
     }
     return QGD_OK;
     QGD_CATCH
 }
-int qgd_scalar_case_sync(qgd_scalar_case_t c) {
-    QGD_TRY
-    if (!c) return fail(QGD_ERR_INVALID, "null case");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    HIP_CHECK(hipStreamSynchronize(c->dev->stream));
-    return QGD_OK;
-    QGD_CATCH
-}
+int qgd_scalar_case_sync(qgd_scalar_case_t c) { return caseSync(c); }
 
 int qgd_comm_unique_id(void* id128) {
     QGD_TRY
@@ -3685,6 +3678,15 @@ int qgd_comm_info(qgd_comm_t c, int32_t info[3]) {
     QGD_CATCH
 }
 
+// the all-reduces of a solve across the ranks (SolveHooks::allreduce, ::allreduceBuf) over RCCL on `st`; none on one rank
+static void rcclAllReduceHooks(SolveHooks& hooks, qgd_comm_s* comm, hipStream_t st) {
+    if (!comm || comm->nRanks <= 1) return;
+    hooks.allreduce = [comm, st](double* ptr, int n) { RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, ncclSum, comm->comm, st)); };
+    // the Chebyshev solves' spectral bound: MAX over the ranks (op 3; 2 = SUM)
+    hooks.allreduceBuf = [comm, st](double* ptr, int64_t n, int op) {
+        RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, op == 3 ? ncclMax : ncclSum, comm->comm, st));
+    };
+}
 int qgd_case_halo_exchange(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, int nSlots) {
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
@@ -3729,13 +3731,7 @@ int qgd_case_step_sharded(qgd_case_t c, qgd_comm_t comm, const int32_t* peers, i
         // gradients, the new velocity and the search directions travel as grouped send/recv pairs, then the state message as usual
         SolveHooks hooks;
         hipStream_t st = c->stream();
-        if (comm->nRanks > 1) {
-            hooks.allreduce = [&](double* ptr, int n) { RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, ncclSum, comm->comm, st)); };
-            // the Chebyshev solves' spectral bound: MAX over the ranks (op 3; 2 = SUM)
-            hooks.allreduceBuf = [&](double* ptr, int64_t n, int op) {
-                RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, op == 3 ? ncclMax : ncclSum, comm->comm, st));
-            };
-        }
+        rcclAllReduceHooks(hooks, comm, st);
         auto halo = [&](int kind) { exchangeOn(c, comm, peers, nSlots, st, kind); };
         hooks.haloDirection = [&]() { halo(3); };
         hooks.haloGuess = [&]() { halo(4); };
@@ -3796,14 +3792,9 @@ int qgd_qhd_case_step_sharded(qgd_qhd_case_t c, qgd_comm_t comm, const int32_t* 
     HIP_CHECK(hipSetDevice(d->deviceId));
     if (sharded) checkHaloPeers(comm, peers, std::min<int>(nSlots, (int)d->halo.size()));
     SolveHooks hooks;
-    if (comm && comm->nRanks > 1)
-        hooks.allreduce = [&](double* ptr, int n) { RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, ncclSum, comm->comm, d->stream)); };
+    rcclAllReduceHooks(hooks, comm, d->stream);
     if (sharded) hooks.haloDirection = [&]() { exchangeOn(c, comm, peers, nSlots, 2); };
     if (sharded) hooks.haloMg = [&]() { exchangeOn(c, comm, peers, nSlots, 3); };
-    if (comm && comm->nRanks > 1)
-        hooks.allreduceBuf = [&](double* ptr, int64_t n, int op) {
-            RCCL_CHECK(rcclRef().allReduce(ptr, ptr, (size_t)n, ncclFloat64, op == 3 ? ncclMax : ncclSum, comm->comm, d->stream));
-        };
     std::function<void(int)> haloState;
     if (sharded) haloState = [&](int kind) { exchangeOn(c, comm, peers, nSlots, kind); };
     for (int i = 0; i < nSteps; ++i) qhdStepWith(c, &hooks, haloState);
@@ -3930,22 +3921,7 @@ int qgd_case_fused_info(qgd_case_t c, int64_t info[8]) {
     return QGD_OK;
 }
 
-int qgd_case_implicit_info(qgd_case_t c, double info[16]) {
-    QGD_TRY
-    if (!c || !info) return fail(QGD_ERR_INVALID, "null argument");
-    for (int k = 0; k < 16; ++k) info[k] = 0.0;
-    info[13] = c->opt.implicitDiffusion ? 1.0 : 0.0;
-    if (!c->implSolver) return QGD_OK;
-    info[13] = implicitSolverChebyshev(c->implSolver) ? 2.0 : 1.0;   // 1: conjugate gradients (QGD_IMPL_SOLVER=pcg), 2: Chebyshev iteration
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    implicitSolverSetStream(c->implSolver, c->stream());
-    int it[4]; double r0[4], r1[4], bad = 0, stalled = 0;
-    implicitSolverInfo(c->implSolver, it, r0, r1, &bad, &stalled);
-    for (int k = 0; k < 4; ++k) { info[k] = it[k]; info[4 + k] = r0[k]; info[8 + k] = r1[k]; }
-    info[12] = bad; info[14] = stalled;
-    return QGD_OK;
-    QGD_CATCH
-}
+int qgd_case_implicit_info(qgd_case_t c, double info[16]) { return caseImplicitInfo(c, "null argument", true, info); }
 int qgd_case_implicit_apply_time(qgd_case_t c, int reps, double info[2]) {
     QGD_TRY
     if (!c || !info || reps <= 0) return fail(QGD_ERR_INVALID, "bad argument");
@@ -3960,36 +3936,11 @@ int qgd_case_implicit_apply_time(qgd_case_t c, int reps, double info[2]) {
     return QGD_OK;
     QGD_CATCH
 }
-// control block of the solve in flight: 68 doubles, slot-major (control[slot * 4 + component]); a sharded run SUM-reduces
-// control[0..12), [12..16), [16..20), [20..24), [24..32) after solver phases 0, 1, 2, 3, 4.  status: {all components done,
-// right-hand sides of the solve in flight}
-int qgd_case_implicit_control(qgd_case_t c, double control[68], int set) {
-    QGD_TRY
-    if (!c || !control || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    hipStream_t st = c->stream();
-    if (set) HIP_CHECK(hipMemcpyAsync(implicitSolverCtl(c->implSolver), control, 68 * sizeof(double), hipMemcpyHostToDevice, st));
-    else HIP_CHECK(hipMemcpyAsync(control, implicitSolverCtl(c->implSolver), 68 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return QGD_OK;
-    QGD_CATCH
-}
-int qgd_case_implicit_control_ptr(qgd_case_t c, void** devicePtr) {
-    if (!c || !devicePtr || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
-    *devicePtr = implicitSolverCtl(c->implSolver);
-    return QGD_OK;
-}
-int qgd_case_implicit_solve_status(qgd_case_t c, double status[2]) {
-    QGD_TRY
-    if (!c || !status || !c->implSolver) return fail(QGD_ERR_INVALID, "bad argument");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    implicitSolverSetStream(c->implSolver, c->stream());
-    int it[3]; double r0[3], r1[3];
-    implicitSolveStatus(c->implSolver, &status[0], it, r0, r1);
-    status[1] = implicitSolverRhs(c->implSolver);
-    return QGD_OK;
-    QGD_CATCH
-}
+// the control block of the solve in flight: a sharded run SUM-reduces control[0..12), [12..16), [16..20), [20..24), [24..32) after solver
+// phases 0, 1, 2, 3, 4
+int qgd_case_implicit_control(qgd_case_t c, double control[68], int set) { return caseImplicitControl(c, "bad argument", control, set); }
+int qgd_case_implicit_control_ptr(qgd_case_t c, void** devicePtr) { return caseImplicitControlPtr(c, "bad argument", devicePtr); }
+int qgd_case_implicit_solve_status(qgd_case_t c, double status[2]) { return caseImplicitSolveStatus(c, "bad argument", 3, status); }
 
 int qgd_struct_sizes(int64_t sizes[4]) {
     if (!sizes) return fail(QGD_ERR_INVALID, "null argument");
@@ -4110,34 +4061,28 @@ static int monitorBuild(const std::string& who, qgd_device_s* d, const qgd_monit
     *out = mo;
     return QGD_OK;
 }
-// what the two create entries share: `who` names the entry, `setFields` the call it asks for first; `monitors` is the case's own list
-static int monitorCreate(const char* who, const char* setFields, qgd_device_s* d, bool fieldsSet, std::vector<qgd_monitor_s*>& monitors,
-                         const qgd_monitor_spec* spec, const MonitorShape& shape, qgd_monitor_s** out) {
-    if (!fieldsSet) return fail(QGD_ERR_INVALID, std::string(who) + ": call " + setFields + " first (a monitor samples the state the case holds)");
+// what the two create entries share: `who` names the entry, `setFields` the call it asks for first, `qhd` the kind of the case
+static int monitorCreate(const char* who, const char* setFields, CaseCore* c, bool qhd, const qgd_monitor_spec* spec, const MonitorShape& shape,
+                         qgd_monitor_s** out) {
+    QGD_TRY
+    if (!c || !spec || !out) return fail(QGD_ERR_INVALID, std::string(who) + ": null argument");
+    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, std::string(who) + ": call " + setFields + " first (a monitor samples the state the case holds)");
     qgd_monitor_s* mo = nullptr;
-    const int rc = monitorBuild(who, d, spec, shape, &mo);
+    const int rc = monitorBuild(who, c->dev, spec, shape, &mo);
     if (rc) return rc;
+    mo->c = c; mo->qhd = qhd;
     g_monitors.push_back(mo);
-    monitors.push_back(mo);
+    c->monitors.push_back(mo);
     *out = mo;
     return QGD_OK;
+    QGD_CATCH
 }
 int qgd_monitor_create(qgd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
-    QGD_TRY
-    if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_monitor_create: null argument");
-    const int rc = monitorCreate("qgd_monitor_create", "qgd_case_set_fields", c->dev, c->fieldsSet, c->monitors, spec, kFlowMonitorShape, out);
-    if (rc == QGD_OK) (*out)->c = c;
-    return rc;
-    QGD_CATCH
+    return monitorCreate("qgd_monitor_create", "qgd_case_set_fields", c, false, spec, kFlowMonitorShape, out);
 }
 // the monitor of a QHD case (qgd_qhd_monitor.hip): the same handle, served by the entries below
 int qgd_qhd_monitor_create(qgd_qhd_case_t c, const qgd_monitor_spec* spec, qgd_monitor_t* out) {
-    QGD_TRY
-    if (!c || !spec || !out) return fail(QGD_ERR_INVALID, "qgd_qhd_monitor_create: null argument");
-    const int rc = monitorCreate("qgd_qhd_monitor_create", "qgd_qhd_case_set_fields", c->dev, c->fieldsSet, c->monitors, spec, kQhdMonitorShape, out);
-    if (rc == QGD_OK) (*out)->qc = c;
-    return rc;
-    QGD_CATCH
+    return monitorCreate("qgd_qhd_monitor_create", "qgd_qhd_case_set_fields", c, true, spec, kQhdMonitorShape, out);
 }
 int qgd_monitor_layout(qgd_monitor_t m, int64_t offsets[QGD_MONITOR_SECTIONS], int64_t* nDoubles, int32_t* gridCap) {
     if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_layout: not an open monitor (a monitor is freed with its case)");
@@ -4150,37 +4095,34 @@ int qgd_monitor_sample(qgd_monitor_t m, int32_t slot) {
     QGD_TRY
     if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: not an open monitor (a monitor is freed with its case)");
     if (slot < 0 || slot >= QGD_MONITOR_SLOTS) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: slot must be 0.." + std::to_string(QGD_MONITOR_SLOTS - 1));
-    if (m->qc) {   // a QHD case: three launches and the copy on the device's stream
-        qgd_qhd_case_s* qc = m->qc;
-        if (!qc->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: the case's boundary conditions changed: call qgd_qhd_case_set_fields first");
-        HIP_CHECK(hipSetDevice(qc->dev->deviceId));
+    CaseCore* core = m->c;
+    if (!core->fieldsSet)
+        return fail(QGD_ERR_INVALID, m->qhd ? "qgd_monitor_sample: the case's boundary conditions changed: call qgd_qhd_case_set_fields first"
+                                            : "qgd_monitor_sample: the case's boundary conditions or coefficients changed: call qgd_case_set_fields first");
+    HIP_CHECK(hipSetDevice(core->dev->deviceId));
+    hipStream_t st = core->stream();
+    (void)hipGetLastError();
+    if (m->qhd) {   // a QHD case: three launches
+        qgd_qhd_case_s* qc = static_cast<qgd_qhd_case_s*>(core);
         const int fluxState = qc->steps == 0 ? 0 : (qc->view.implicit ? 2 : 1);
-        hipStream_t st = qc->dev->stream;
-        (void)hipGetLastError();
         launchQhdMonitorSample(st, m->view, qc->dev->view, qc->view, fluxState, m->result);   // (the view as it stands now: the fused advance swaps c4)
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(m->host + (size_t)slot * (size_t)m->nDoubles, m->result, sizeof(double) * (size_t)m->nDoubles, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipEventRecord(m->ev[slot], st));
-        m->sampled[slot] = true; m->time[slot] = qc->time; m->step[slot] = qc->steps;
-        return QGD_OK;
-    }
-    qgd_case_s* c = m->c;
-    if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_monitor_sample: the case's boundary conditions or coefficients changed: call qgd_case_set_fields first");
-    HIP_CHECK(hipSetDevice(c->dev->deviceId));
-    const int fluxState = !c->fluxAssembled ? 0 : (c->opt.implicitDiffusion ? 2 : 1);
-    hipStream_t st = c->stream();
-    (void)hipGetLastError();
-    launchMonitorSample(st, m->view, c->dev->view, c->view, c->gas, fluxState, m->result);   // (the view as it stands now: the fused step swaps A / B)
-    HIP_CHECK(hipGetLastError());
-    const size_t slotDoubles = (size_t)(m->nDoubles + m->spDoubles);
-    if (m->spDoubles) {   // the species block: three more launches, behind the flow block in the same device buffer, so one copy takes both
-        const int spState = !c->spFluxesValid ? 0 : (c->opt.implicitDiffusion ? 2 : 1);
-        launchMonitorSpeciesSample(st, m->view, m->spView, c->dev->view, c->view, c->sp, c->spImpl.aF, spState, m->result + m->nDoubles);
+    } else {
+        qgd_case_s* c = static_cast<qgd_case_s*>(core);
+        const int fluxState = !c->fluxAssembled ? 0 : (c->opt.implicitDiffusion ? 2 : 1);
+        launchMonitorSample(st, m->view, c->dev->view, c->view, c->gas, fluxState, m->result);   // (the view as it stands now: the fused step swaps A / B)
         HIP_CHECK(hipGetLastError());
+        if (m->spDoubles) {   // the species block: three more launches, behind the flow block in the same device buffer, so one copy takes both
+            const int spState = !c->spFluxesValid ? 0 : (c->opt.implicitDiffusion ? 2 : 1);
+            launchMonitorSpeciesSample(st, m->view, m->spView, c->dev->view, c->view, c->sp, c->spImpl.aF, spState, m->result + m->nDoubles);
+            HIP_CHECK(hipGetLastError());
+        }
     }
+    // the copy into the slot follows on the same stream (a QHD monitor has no species block: spDoubles == 0)
+    const size_t slotDoubles = (size_t)(m->nDoubles + m->spDoubles);
     HIP_CHECK(hipMemcpyAsync(m->host + (size_t)slot * slotDoubles, m->result, sizeof(double) * slotDoubles, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipEventRecord(m->ev[slot], st));
-    m->sampled[slot] = true; m->time[slot] = c->time; m->step[slot] = c->steps;
+    m->sampled[slot] = true; m->time[slot] = core->time; m->step[slot] = core->steps;
     return QGD_OK;
     QGD_CATCH
 }
@@ -4190,11 +4132,12 @@ int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, do
     if (slot < 0 || slot >= QGD_MONITOR_SLOTS) return fail(QGD_ERR_INVALID, "qgd_monitor_read: slot must be 0.." + std::to_string(QGD_MONITOR_SLOTS - 1));
     if (!out || cap < m->nDoubles) return fail(QGD_ERR_INVALID, "qgd_monitor_read: output too small (qgd_monitor_layout gives the doubles of a result block)");
     if (!m->sampled[slot]) return fail(QGD_ERR_INVALID, "qgd_monitor_read: slot " + std::to_string(slot) + " was never sampled");
-    HIP_CHECK(hipSetDevice(monitorDevice(m)->deviceId));
+    HIP_CHECK(hipSetDevice(m->c->dev->deviceId));
     HIP_CHECK(hipEventSynchronize(m->ev[slot]));
     const double* src = m->host + (size_t)slot * (size_t)(m->nDoubles + m->spDoubles);
     std::copy(src, src + m->nDoubles, out);
-    if (time) *time = (m->c && m->c->opt.adjustTimeStep) ? src[7] : m->time[slot];   // (a QHD case steps at a fixed deltaT; its header[7] holds flags)
+    const bool adjusts = !m->qhd && static_cast<qgd_case_s*>(m->c)->opt.adjustTimeStep;
+    if (time) *time = adjusts ? src[7] : m->time[slot];   // (a QHD case steps at a fixed deltaT; its header[7] holds flags)
     if (step) *step = m->step[slot];
     return QGD_OK;
     QGD_CATCH
@@ -4203,8 +4146,8 @@ int qgd_monitor_read(qgd_monitor_t m, int32_t slot, double* out, int64_t cap, do
 int qgd_monitor_enable_species(qgd_monitor_t m) {
     QGD_TRY
     if (!monitorLive(m)) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: not an open monitor (a monitor is freed with its case)");
-    if (m->qc) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: the monitor of a QHD case has no species block (QHDFoam and SRFQHDFoam carry no species)");
-    qgd_case_s* c = m->c;
+    if (m->qhd) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: the monitor of a QHD case has no species block (QHDFoam and SRFQHDFoam carry no species)");
+    qgd_case_s* c = static_cast<qgd_case_s*>(m->c);
     if (!c->sp.nS) return fail(QGD_ERR_INVALID, "qgd_monitor_enable_species: the case carries no species (qgd_case_set_species)");
     if (m->spDoubles) return QGD_OK;
     for (bool s : m->sampled)
@@ -4256,9 +4199,9 @@ int qgd_monitor_species_read(qgd_monitor_t m, int32_t slot, double* out, int64_t
 }
 int qgd_monitor_free(qgd_monitor_t m) {
     if (!monitorLive(m)) return QGD_OK;   // null, or freed with its case
-    (void)hipSetDevice(monitorDevice(m)->deviceId);
-    (void)hipStreamSynchronize(monitorStream(m));
-    std::vector<qgd_monitor_s*>& open = monitorsOfCase(m);
+    (void)hipSetDevice(m->c->dev->deviceId);
+    (void)hipStreamSynchronize(m->c->stream());
+    std::vector<qgd_monitor_s*>& open = m->c->monitors;
     open.erase(std::remove(open.begin(), open.end(), m), open.end());
     monitorDestroy(m);
     return QGD_OK;

@@ -110,24 +110,43 @@ def test_cases_and_their_device_may_die_in_any_order():
     launch check).  The device frees the cases still open on it before itself; both close() are idempotent."""
     import ctypes
     import gc
-    from qgdsolver_amd import qhdfoam
+    from qgdsolver_amd import qhdfoam, scalarfoam
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipGetLastError()
     mesh = q.PolyMesh.box(4, 3, 2)
+    n = mesh.nCells
     opt = q.default_options(deltaT=1e-3, mu=1e-3, implicitDiffusion=1)
     qopt = qhdfoam.qhd_options(stencil="GaussVolPoint", tauModel="HbyUQHD", aQGD=0.5, UQHD=1.0, rho0=1.0, mu=1e-2, Pr=0.71, beta=3e-3,
                                g=(0.0, -9.81, 0.0), deltaT=1e-3, pTol=1e-10, pMaxIter=200, pRefCell=0, pRefValue=0.0)
+    sopt = scalarfoam.scalar_options(deltaT=1e-3, mu=1e-2)
+
+    def open_all(dev):
+        """a case of every kind on the device, and an open, sampled monitor on each kind that has one"""
+        case, qcase, scase = q.QGDFoamCase(dev, opt), qhdfoam.QHDFoamCase(dev, qopt), scalarfoam.ScalarTransportQHDCase(dev, sopt)
+        case.set_fields(np.zeros((n, 3)), np.ones(n), np.ones(n))
+        qcase.set_fields(np.zeros((n, 3)), np.ones(n), np.zeros(n))
+        scase.set_fields(np.zeros((n, 3)), np.ones(n))
+        monitors = [case.monitor(probes=[0], patches=[0]), qcase.monitor(probes=[0], patches=[0])]
+        for m in monitors:
+            m.sample()
+        return [case, qcase, scase], monitors
+
     dev = q.Device(mesh)
-    case, qcase = q.QGDFoamCase(dev, opt), qhdfoam.QHDFoamCase(dev, qopt)
+    cases, monitors = open_all(dev)
     dev.close()                                    # the device first
-    assert case._h is None and qcase._h is None    # ... has freed its cases
-    case.close(); qcase.close()
+    assert all(c._h is None for c in cases)        # ... has freed its cases, and they their monitors
+    for m in monitors:
+        assert L.lib.qgd_monitor_layout(m._h, None, None, None) != L.QGD_OK and b"not an open monitor" in L.lib.qgd_last_error()
+        m.close()
+    for c in cases:
+        c.close()
     assert hip.hipGetLastError() == 0
-    for _ in range(3):                             # one garbage cycle holding both: the collector picks the order
+    for _ in range(3):                             # one garbage cycle holding all of them: the collector picks the order
         dev = q.Device(mesh)
-        cyc = [dev, q.QGDFoamCase(dev, opt), qhdfoam.QHDFoamCase(dev, qopt)]
+        cases, monitors = open_all(dev)
+        cyc = [dev] + cases + monitors
         cyc.append(cyc)
-        del dev, cyc
+        del dev, cases, monitors, cyc
         gc.collect()
         assert hip.hipGetLastError() == 0
     dev = q.Device(mesh)
