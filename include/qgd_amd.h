@@ -296,7 +296,9 @@ int qgd_device_face_tiles(qgd_device_t d, int64_t info[4]);
  * local topology (per-face list positions, per-cell face entries, per-vertex cell positions: blocks that are alike share one, so on a
  * structured mesh those tables stay in L2 instead of being streamed per block per step), [3] = LDS bytes per workgroup, [4] = bytes of a
  * block's own lists (labels, weights, counts), [5] = bytes of one template, [6] = host milliseconds the builder took, [7] = the lattice brick
- * the blocks were cut from, bx | by << 8 | bz << 16 (0: count-based runs of the Morton order). */
+ * the blocks were cut from, bx | by << 8 | bz << 16 (0: count-based runs of the Morton order); bit 24 of [7] = the vertex interpolation
+ * weights are kept as 16-bit offsets from one reference bit pattern (a mesh whose weights all lie within 65 535 patterns of each other, e.g.
+ * a uniform hexahedral region; QGD_FUSED_PACKED_W=0: never) -- [4] counts 2 bytes per weight then, not 8. */
 int qgd_device_fused_blocks(qgd_device_t d, int64_t info[8]);
 
 /* qgdInterpolate / linearInterpolate [QGDInterpolate_8H_source.html L38-67]: face = w*(phi_O - phi_N) + phi_N, patch faces

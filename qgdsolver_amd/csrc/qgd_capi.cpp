@@ -934,7 +934,7 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
             const int fusedMode = fusedChoice >= 0 ? fusedChoice : envChoice("QGD_FUSED", 1, kFusedModes, 3);
             if (fusedMode != 0) {
                 stage("face tiles (build + upload)");
-                FusedBlocks fb = buildFusedBlocks(s);
+                FusedBlocks fb = buildFusedBlocks(s, false);   // (a mesh whose vertex weights pack keeps the 16-bit table alone)
                 stage("cell blocks of the fused step (build)");
                 // LDS per workgroup: RecA of every staged cell, RecB of the own + across-a-face cells, then vertex records + all coordinates,
                 // later overwritten by the fluxes (FusedBlocks::maxLds); then the parked face entries of the own cells
@@ -955,13 +955,15 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                     fb.capV <= kFusedCapV && fb.capF <= kFusedCapF && fb.capPE <= 255 && lds <= ldsLimit) {
                     v.fuBlocks = fb.nBlocks; v.fuLayerBlocks = fb.nLayerBlocks; v.fuCapC = fb.capC; v.fuCapV = fb.capV; v.fuCapF = fb.capF;
                     v.fuCapE = fb.capE; v.fuLds = (int32_t)lds; v.fuLdsCell = (int32_t)(ldsPark / 8);
-                    v.fuCapPE = fb.capPE; v.fuMaxTot = fb.maxTot; v.fuMaxAll = fb.maxAll; v.fuMaxV = fb.maxV; v.fuMaxF = fb.maxF;
+                    v.fuCapPE = fb.capPE; v.fuMaxTot = (uint16_t)fb.maxTot; v.fuMaxAll = (uint16_t)fb.maxAll; v.fuMaxV = (uint16_t)fb.maxV; v.fuMaxF = (uint16_t)fb.maxF;   // (all within the caps checked above)
                     d->fusedFacesComputed = fb.facesComputed; d->fusedCellsStaged = fb.cellsStaged; d->fusedCellsStagedFull = fb.cellsStagedFull;
                     d->fusedVertsStaged = fb.vertsStaged;
-                    v.fuHdr2 = reinterpret_cast<const int4*>(up(fb.hdr2)); v.fuVCount = up(fb.vCount); v.fuVPos = up(fb.vPos); v.fuVW = up(fb.vW);
+                    v.fuHdr2 = reinterpret_cast<const int4*>(up(fb.hdr2)); v.fuVCount = up(fb.vCount); v.fuVPos = up(fb.vPos);
+                    // the vertex weights: 16-bit offsets from one pattern where the mesh's weights pack (FusedBlocks::vW16), the doubles otherwise
+                    if (fb.packedW) { v.fuVW = nullptr; v.fuVW16 = up(fb.vW16); v.fuVWRef = fb.wRef; }
+                    else { v.fuVW = up(fb.vW); v.fuVW16 = nullptr; v.fuVWRef = 0; }
                     v.fuHdr = reinterpret_cast<const int4*>(up(fb.hdr)); v.fuCells = up(fb.cells); v.fuVerts = up(fb.verts);
                     v.fuFaceLabel = up(fb.faceLabel); v.fuFacePos = up(fb.facePos); v.fuNEntry = up(fb.nEntry); v.fuEntry = up(fb.entry);
-                    v.fuTemplates = fb.nTemplates;
                     {   // the implicitDiffusion branch's layout of the same blocks (qgd_kernels.hip fusedFaceCellKernel<..., IMPL>)
                         const int64_t parkI = ((int64_t)fb.maxLdsImpl + 15) / 16 * 16, ldsI = (parkI + 6 * 128 * 4 + 255) / 256 * 256;
                         v.fuLdsImpl = ldsI <= ldsLimit ? (int32_t)ldsI : 0;   // (on a box: the explicit step's figure, three blocks per CU)
@@ -969,10 +971,10 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                     }
                     d->fusedInfo[0] = fb.nBlocks; d->fusedInfo[1] = fb.nLayerBlocks; d->fusedInfo[2] = fb.nTemplates; d->fusedInfo[3] = lds;
                     // bytes a block streams per step out of its own lists / of its template's
-                    d->fusedInfo[4] = 32 + 4 * (int64_t)fb.capC + 4 * (int64_t)fb.capV + 4 * (int64_t)fb.capF + fb.capV + 128 + 8 * (int64_t)fb.capPE * fb.capV;
+                    d->fusedInfo[4] = 32 + 4 * (int64_t)fb.capC + 4 * (int64_t)fb.capV + 4 * (int64_t)fb.capF + fb.capV + 128 + (fb.packedW ? 2 : 8) * (int64_t)fb.capPE * fb.capV;
                     d->fusedInfo[5] = 12 * (int64_t)fb.capF + 4 * (int64_t)fb.capE * 128 + 2 * (int64_t)fb.capPE * fb.capV;
                     d->fusedInfo[6] = (int64_t)(fb.buildSeconds * 1e3);
-                    d->fusedInfo[7] = fb.brick[0] | fb.brick[1] << 8 | fb.brick[2] << 16;
+                    d->fusedInfo[7] = fb.brick[0] | fb.brick[1] << 8 | fb.brick[2] << 16 | (fb.packedW ? 1 << 24 : 0);
                 }
             }
         }

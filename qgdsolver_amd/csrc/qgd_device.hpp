@@ -72,12 +72,31 @@ struct MeshView {
     int32_t fuBlocks, fuLayerBlocks, fuCapC, fuCapV, fuCapF, fuCapE, fuLds, fuLdsCell;   // fuLayerBlocks: a shard's boundary-layer blocks come first;   // fuLdsCell: where the per-cell park of the kernel starts, in doubles
     const int4* fuHdr; const int32_t* fuCells; const int32_t* fuVerts; const int32_t* fuFaceLabel; const uint8_t* fuNEntry;
     // a block's local topology sits in its template (fuHdr2[blk].y): 3 position words per face, the own cells' face entries, the vertices' cell positions
-    const uint32_t* fuFacePos; const int32_t* fuEntry; int32_t fuTemplates;
+    const uint32_t* fuFacePos; const int32_t* fuEntry;
+    // (The maxima over the blocks -- staged cells incl. / without the extra ones here, vertices and faces below -- are host information: a block
+    // lays its LDS out by its own counts.  16 bits each (they are under the kernel's caps, qgd_fused_caps.hpp), and placed so that every member
+    // a kernel reads sits where it sat before the packed weights' two members came: no kernel's argument loads move.)
+    uint16_t fuMaxTot, fuMaxAll;
     int32_t fuXcdRun;        // QGD_FU_XCD_RUN (default 64): consecutive blocks dealt to one XCD before the next XCD's run (the face tiles' xcdRun is 16)
     int32_t fuLdsImpl, fuLdsCellImpl;   // the same two figures as fuLds / fuLdsCell for the implicitDiffusion branch's layout (+ 72 B of fvc::grad(U) per own / across-a-face cell, eight flux planes)
-    int32_t fuCapPE, fuMaxTot, fuMaxAll, fuMaxV, fuMaxF;   // cells per vertex (stride); staged cells incl. / without the extra ones, vertices, faces: maxima over the blocks (information; a block lays its LDS out by its own counts)
+    int32_t fuCapPE;         // cells per vertex (stride)
+    uint16_t fuMaxV, fuMaxF;
+    // a mesh whose weights pack (qgd_setup.hpp FusedBlocks::vW16): the pattern its weights are offsets from, and eight 16-bit offsets per
+    // vertex, vertex-major; fuVW is null then, and fuVW16 is null where fuVW holds the table (fuVertexWeight below reads whichever is there)
+    int64_t fuVWRef; const int16_t* fuVW16;
     const int4* fuHdr2; const uint8_t* fuVCount; const uint16_t* fuVPos; const double* fuVW;   // the vertex values are formed inside the block
 };
+#if defined(__HIPCC__)
+// bits(w) = reference + offset: integer arithmetic on the pattern, the stored double comes back exactly
+__device__ __forceinline__ double fuWeightFromOffset(const int64_t ref, const int off) {
+    return __builtin_bit_cast(double, ref + (int64_t)off);
+}
+// weight e of vertex lv of block blk, from whichever table the view holds
+__device__ __forceinline__ double fuVertexWeight(const MeshView& m, const int blk, const int lv, const int e) {
+    if (m.fuVW16) return fuWeightFromOffset(m.fuVWRef, (int)m.fuVW16[((size_t)blk * m.fuCapV + lv) * 8 + e]);
+    return m.fuVW[((size_t)blk * m.fuCapPE + e) * m.fuCapV + lv];
+}
+#endif
 
 // Per-patch boundary-condition table (device copy, <= 64 patches)
 struct PatchBCDev {

@@ -1115,7 +1115,14 @@ __device__ __forceinline__ v2d fuRowMaxMin(v2d r) {
 // tauQGDf before the first cell may advance, so the block stops after its ordered sums: it leaves max Cof / min tauQGDf of its faces in its
 // slot of blkFace (slot fuBlkFace + block, behind the face kernels' and the patch kernel's; faceReduceKernel folds them all, deltaTKernel follows) and the five net flux sums of each own
 // cell in cellSum; cellFinishKernel advances the cells from there.  Vertex values and face fluxes still never reach device memory.
-template <bool SGEO, bool UPW = false, bool IMPL = false, bool ADJ = false>
+// PACKW = the vertex weights as 16-bit offsets (MeshView::fuVW16; qgd_setup.hpp FusedBlocks::vW16): on a mesh whose weights all lie within
+// 65 535 bit patterns of each other -- every uniform hexahedral region, where each is 1/8 give or take rounding -- a vertex's eight weights are
+// ONE 16-byte load of the front-loaded group instead of eight 8-byte ones (17 memory instructions in the group, not 24; 16 B per vertex formed,
+// not 64), and the doubles are formed where they are used, in (1b): sign-extend, add to the reference pattern, take the sum as a double --
+// the stored double exactly, so the states are the same bits.  A compile-time flag, because the group must issue the same number of memory
+// instructions on every path (the counted wait); the launchers choose it from the view.  PACKW = 0 is the kernel as it was, instruction for
+// instruction.  capPE is 8 with PACKW: no vertex has a ninth cell, the walk beyond the registers cannot happen.
+template <bool SGEO, bool UPW = false, bool IMPL = false, bool ADJ = false, int PACKW = 0>
 // (IMPL with `Gauss upwind` fluxes needs a few registers more than three waves per SIMD leave: that instantiation is compiled for two -- no scratch)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((IMPL && UPW) ? 2 : 3, (IMPL && UPW) ? 2 : 3)))
 void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, const int firstBlock, const ImplView iv,
@@ -1195,7 +1202,8 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // (0b) THE FRONT-LOADED GROUP, in the same round behind the lists: what needs the header but no label -- the block's local topology out
     // of its TEMPLATE (hdr2.y; qgd_setup.hpp FusedBlocks: the interior bricks of a structured region share a few hundred templates, which
     // stay in L2): the positions of this thread's two faces' cells and vertices in the staged lists, its cell's six face entries, its
-    // vertex's eight cell positions -- and the vertex's eight weights.  The lists are latency: they leave the return path idle, and these
+    // vertex's eight cell positions -- and the vertex's eight weights (PACKW: their eight 16-bit offsets, one load).  The lists are latency:
+    // they leave the return path idle, and these
     // bytes fill it instead of competing with the records one round trip later.  The header is waited for HERE (lgkmcnt), behind the lists.
     // The group stays in flight across the wait that ends the round, so the number of memory instructions between the last list load and
     // that wait must be the same on every path: no branch in here.  A lane outside its mask (lf < nFc, tid < 128, tid < nUv) keeps its
@@ -1205,7 +1213,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     const int nOwn = hdr.x, nUc = hdr.y, nUv = hdr.z, nFc = hdr.w;
     const bool vertLane = tid < nUv;
     const size_t tpl = (size_t)hdr2.y;
-    constexpr int kFrontLoads = KF + KE + 2 * KP;
+    constexpr int kFrontLoads = KF + KE + KP + (PACKW ? 1 : KP);
     constexpr int kRsrcWord3 = 0x00020000;          // raw buffer, 32-bit data format
     constexpr int kBeyond = 0x40000000;             // an offset no table reaches (a descriptor spans one block's or one template's part)
     struct Pos3 { uint32_t c, va, vb; };
@@ -1214,17 +1222,21 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // addresses -- with a scalar template id the compiler would otherwise hold three scalar bases to the end, and spill other scalars for them)
     const int32_t* ent = m.fuEntry + tpl * m.fuCapE * 128 + (tid & 127);
     const uint16_t* vPos = m.fuVPos + tpl * capPE * capV + vt;
-    const double* vW = m.fuVW + (size_t)blk * capPE * capV + vt;
-    fuPin(ent); fuPin(vPos); fuPin(vW);
+    const double* vW = PACKW ? nullptr : m.fuVW + (size_t)blk * capPE * capV + vt;
+    fuPin(ent); fuPin(vPos);
+    if constexpr (!PACKW) fuPin(vW);
     Pos3 fp[KF];
     int e6[KE];
     int pcPos[KP];
     double pcW[KP];
+    int wOff[4] = {0, 0, 0, 0};   // PACKW: the vertex's eight weights as loaded, 16-bit offsets from m.fuVWRef (the doubles are formed in (1b))
     {
         const __amdgpu_buffer_rsrc_t rFacePos = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(m.fuFacePos + tpl * capF * 3), 0, capF * 12, kRsrcWord3);
         const __amdgpu_buffer_rsrc_t rEntry = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(m.fuEntry + tpl * m.fuCapE * 128), 0, m.fuCapE * 128 * 4, kRsrcWord3);
         const __amdgpu_buffer_rsrc_t rVPos = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(m.fuVPos + tpl * capPE * capV), 0, capPE * capV * 2, kRsrcWord3);
-        const __amdgpu_buffer_rsrc_t rVW = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(m.fuVW + (size_t)blk * capPE * capV), 0, capPE * capV * 8, kRsrcWord3);
+        // (PACKW: the descriptor of the block's part of the 16-bit table, 16 B per vertex -- capPE is 8 there)
+        const __amdgpu_buffer_rsrc_t rVW = PACKW ? __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t*>(m.fuVW16 + (size_t)blk * capV * 8), 0, capV * 16, kRsrcWord3)
+                                                 : __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(m.fuVW + (size_t)blk * capPE * capV), 0, capPE * capV * 8, kRsrcWord3);
 #pragma unroll
         for (int j = 0; j < KF; ++j) {
             const int lf = tid + j * NT;
@@ -1237,9 +1249,14 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
 #pragma unroll
         for (int i = 0; i < KP; ++i)
             pcPos[i] = (int)__builtin_amdgcn_raw_buffer_load_b16(rVPos, vertLane ? (min(i, capPE - 1) * capV + vt) * 2 : kBeyond, 0, 0);
+        if constexpr (PACKW) {
+            const i32x4 o = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rVW, vertLane ? vt * 16 : kBeyond, 0, 0));
+            wOff[0] = o[0]; wOff[1] = o[1]; wOff[2] = o[2]; wOff[3] = o[3];
+        } else {
 #pragma unroll
-        for (int i = 0; i < KP; ++i)
-            pcW[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rVW, vertLane ? (min(i, capPE - 1) * capV + vt) * 8 : kBeyond, 0, 0));
+            for (int i = 0; i < KP; ++i)
+                pcW[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rVW, vertLane ? (min(i, capPE - 1) * capV + vt) * 8 : kBeyond, 0, 0));
+        }
     }
     // The round ends HERE for the lists, at once (the loads above went out back to back and return in issue order): the memory counter may
     // stay at the front-loaded group, which nothing needs before the records are staged.  Left to itself the compiler waits label by label.
@@ -1247,9 +1264,10 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // wait behind the lists, no wait inside round 1 -- the two-word read of fuHdr2 and fuTimes3Plus answer register-allocation accidents of
     // one compiler version, and only the disassembly shows them.  Redo the ISA check of DESIGN.md section 5 after every ROCm change; a wait
     // that comes back costs speed, not correctness.)
-    static_assert(kFrontLoads == 24, "the wait below is written for vmcnt(24)");
+    static_assert(kFrontLoads == (PACKW ? 17 : 24), "the wait below is written for vmcnt(24), vmcnt(17) with packed weights");
     __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0x4F78);   // vmcnt(24): low four bits 8, high two bits 1; expcnt and lgkmcnt left alone
+    // vmcnt(kFrontLoads): its low four bits in bits 3:0, its high two in bits 15:14; expcnt and lgkmcnt left alone (0x4F78 for 24, 0x4F71 for 17)
+    __builtin_amdgcn_s_waitcnt(0x0F70 | (kFrontLoads & 15) | ((kFrontLoads >> 4) << 14));
     __builtin_amdgcn_sched_barrier(0);
     // (1) one round trip later, what needs a label: the records, piece by piece; the faces' streams; the cell's own scalars; a patch
     // point's record.  No wait for a front-loaded value stands between the first of these loads and the staging stores.
@@ -1347,11 +1365,20 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     fuPin(nEraw);
 #pragma unroll
     for (int i = 0; i < KP; ++i) fuPin(pcPos[i]);
+    if constexpr (PACKW) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) fuPin(wOff[q]);
+    }
 #pragma unroll
     for (int j = 0; j < KF; ++j) { fuPin(fk[j]); fuPin(fp[j].c); fuPin(fp[j].va); fuPin(fp[j].vb); }
     // (1b) the vertex values [volPointInterpolation: inverse-distance weights over pointCells, in their order -- pointInterpRecKernel's
     // arithmetic, out of the staged cell records]
     if (tid < nUv) {
+        if constexpr (PACKW) {
+            // the weights out of their offsets: sign-extend the half word, add it to the reference pattern, take the sum as a double
+#pragma unroll
+            for (int i = 0; i < KP; ++i) pcW[i] = fuWeightFromOffset(m.fuVWRef, (wOff[i >> 1] << (16 - 16 * (i & 1))) >> 16);
+        }
         if (__ballot(nPc != KP) == 0) {
             // a wavefront of interior vertices of hexahedra: eight cells each, no predicates
             RecA acc = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -1367,7 +1394,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             for (int i = 0; i < nPc; ++i) {
                 int pos = 0;
                 double w = 0.0;
-                if (i < KP) {
+                if (PACKW || i < KP) {   // (packed weights: capPE == 8, no vertex has a ninth cell)
 #pragma unroll
                     for (int q = 0; q < KP; ++q) { pos = (i == q) ? pcPos[q] : pos; w = (i == q) ? pcW[q] : w; }
                 } else {
@@ -2323,15 +2350,26 @@ static FusedXcdOrder fusedXcdOrder(int nBlocks, int run) {
     const int span = run << 3;
     return {(nBlocks / span) * span, shift};
 }
+// one launch of fusedFaceCellKernel<SGEO, UPW, IMPL, ADJ, PACKW>: SGEO, UPW and PACKW (the view holds the vertex weights as 16-bit offsets,
+// MeshView::fuVW16) are chosen here, IMPL and ADJ by the caller
+#define QGD_FUSED_LAUNCH4(SG, UP, IM, AD, n, lds, ...)                                                                          \
+    do {                                                                                                                        \
+        if (m.fuVW16) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 1><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
+        else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD><<<n, 256, lds, L.stream>>>(__VA_ARGS__)));            \
+    } while (0)
+#define QGD_FUSED_LAUNCH(IM, AD, n, lds, ...)                                          \
+    do {                                                                               \
+        if (m.sGeo && upw) QGD_FUSED_LAUNCH4(true, true, IM, AD, n, lds, __VA_ARGS__);  \
+        else if (upw) QGD_FUSED_LAUNCH4(false, true, IM, AD, n, lds, __VA_ARGS__);      \
+        else if (m.sGeo) QGD_FUSED_LAUNCH4(true, false, IM, AD, n, lds, __VA_ARGS__);   \
+        else QGD_FUSED_LAUNCH4(false, false, IM, AD, n, lds, __VA_ARGS__);              \
+    } while (0)
 void launchFusedFaceCell(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, int firstBlock, int nBlocks) {
     if (nBlocks <= 0) return;
     const FusedXcdOrder x = fusedXcdOrder(nBlocks, m.fuXcdRun);
     const bool upw = g.upwindU || g.upwindH;   // a `Gauss upwind` entry for div(phiJm,U) or div(phiJm,H)
     const ImplView none{};
-    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
-    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
-    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
-    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false><<<nBlocks, 256, m.fuLds, L.stream>>>(m, c, g, firstBlock, none, nullptr, x.full, x.shift)));
+    QGD_FUSED_LAUNCH(false, false, nBlocks, m.fuLds, m, c, g, firstBlock, none, nullptr, x.full, x.shift);
 }
 // Courant-number control: all blocks up to their flux sums (+ the Courant partials), then -- after deltaTKernel -- the cells
 void launchFusedAdjust(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g) {
@@ -2340,10 +2378,7 @@ void launchFusedAdjust(const Launcher& L, const MeshView& m, const CaseView& c, 
     const ImplView none{};
     const int n = m.fuBlocks;
     const FusedXcdOrder x = fusedXcdOrder(n, m.fuXcdRun);
-    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
-    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
-    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, false, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
-    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, false, false, true><<<n, 256, m.fuLds, L.stream>>>(m, c, g, 0, none, nullptr, x.full, x.shift)));
+    QGD_FUSED_LAUNCH(false, true, n, m.fuLds, m, c, g, 0, none, nullptr, x.full, x.shift);
 }
 void launchCellFinish(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, int mode, const int32_t* list, int nList) {
     const int n = (mode == 1) ? nList : m.nC;
@@ -2355,14 +2390,16 @@ void launchCellFinish(const Launcher& L, const MeshView& m, const CaseView& c, c
 // the implicitDiffusion branch's block-fused assembly of the U systems (fusedFaceCellKernel<..., IMPL = true>): more dynamic LDS than the
 // 64 KB a launch gets by default, so the kernels' limit is raised first; false when the device refuses (the caller keeps the separate kernels)
 template <bool SGEO, bool UPW>
-static bool fusedImplLimit(int lds) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+static bool fusedImplLimit(int lds, bool packed) {
+    const void* k = packed ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 1>) : reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true>);
+    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
 }
 bool fusedImplUPrepare(const MeshView& m, const GasModel& g) {
     if (m.fuBlocks <= 0 || m.fuLdsImpl <= 0) return false;
     const bool upw = g.upwindU || g.upwindH;
-    const bool ok = m.sGeo ? (upw ? fusedImplLimit<true, true>(m.fuLdsImpl) : fusedImplLimit<true, false>(m.fuLdsImpl))
-                           : (upw ? fusedImplLimit<false, true>(m.fuLdsImpl) : fusedImplLimit<false, false>(m.fuLdsImpl));
+    const bool pk = m.fuVW16 != nullptr;
+    const bool ok = m.sGeo ? (upw ? fusedImplLimit<true, true>(m.fuLdsImpl, pk) : fusedImplLimit<true, false>(m.fuLdsImpl, pk))
+                           : (upw ? fusedImplLimit<false, true>(m.fuLdsImpl, pk) : fusedImplLimit<false, false>(m.fuLdsImpl, pk));
     if (!ok) (void)hipGetLastError();
     return ok;
 }
@@ -2370,11 +2407,10 @@ void launchFusedImplU(const Launcher& L, const MeshView& m, const CaseView& c, c
     const bool upw = g.upwindU || g.upwindH;
     const int n = m.fuBlocks;
     const FusedXcdOrder x = fusedXcdOrder(n, m.fuXcdRun);
-    if (m.sGeo && upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, true, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
-    else if (upw) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, true, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
-    else if (m.sGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<true, false, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
-    else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<false, false, true><<<n, 256, m.fuLdsImpl, L.stream>>>(m, c, g, 0, iv, bc, x.full, x.shift)));
+    QGD_FUSED_LAUNCH(true, false, n, m.fuLdsImpl, m, c, g, 0, iv, bc, x.full, x.shift);
 }
+#undef QGD_FUSED_LAUNCH
+#undef QGD_FUSED_LAUNCH4
 void launchCellUpdate(const Launcher& L, const MeshView& m, const CaseView& c, const GasModel& g, int mode,
                       const int32_t* list, int nList) {
     const int n = (mode == 1) ? nList : m.nC;

@@ -559,10 +559,10 @@ void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict
     const int vt = min(tid, capV - 1);
     const int myVert = tVerts[vt];
     const int nPc = (int)m.fuVCount[(size_t)blk * capV + vt];
-    const double* __restrict__ vW = m.fuVW + (size_t)blk * capPE * capV + vt;
+    // (the weights from whichever table the view holds: the doubles, or the 16-bit offsets of a mesh whose weights pack -- fuVertexWeight)
     double pcW[KP];
 #pragma unroll
-    for (int i = 0; i < KP; ++i) pcW[i] = vW[(size_t)min(i, capPE - 1) * capV];
+    for (int i = 0; i < KP; ++i) pcW[i] = fuVertexWeight(m, blk, vt, min(i, capPE - 1));
     // (1) one round trip later: the records piece by piece, the faces' streams, the block's local topology out of its template
     const size_t tpl = (size_t)hdr2.y;
     struct Pos3 { uint32_t c, va, vb; };
@@ -653,7 +653,7 @@ void qhdFusedAdvanceKernel(const MeshView m, const QhdView q, double* __restrict
                     for (int u = 0; u < KP; ++u) { pos = (i == u) ? pcPos[u] : pos; w = (i == u) ? pcW[u] : w; }
                 } else {
                     pos = (int)vPos[(size_t)i * capV];
-                    w = vW[(size_t)i * capV];
+                    w = fuVertexWeight(m, blk, vt, i);
                 }
                 acc += w * sp[pos];
             }

@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 #include <unordered_map>
 
@@ -758,7 +759,47 @@ struct OneBlock {
 };
 }  // namespace
 
-FusedBlocks buildFusedBlocks(const StaticData& s) {
+bool packFusedWeights(FusedBlocks& B) {
+    B.packedW = 0; B.wRef = 0;
+    RawVec<int16_t>().swap(B.vW16);
+    if (B.capPE != 8 || B.nBlocks <= 0) return false;
+    const int64_t nV = (int64_t)B.nBlocks * B.capV;
+    const size_t capV = (size_t)B.capV;
+    auto bitsOf = [&](int64_t v, int e) {
+        int64_t b;
+        std::memcpy(&b, &B.vW[((size_t)(v / B.capV) * 8 + e) * capV + (size_t)(v % B.capV)], 8);
+        return b;
+    };
+    // the spread of the patterns over every weight in use (min and max are exact: the same whatever the threads)
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+#pragma omp parallel for schedule(static) reduction(min : lo) reduction(max : hi)
+    for (int64_t v = 0; v < nV; ++v)
+        for (int e = 0; e < (int)B.vCount[v]; ++e) { const int64_t b = bitsOf(v, e); lo = std::min(lo, b); hi = std::max(hi, b); }
+    if (lo > hi || lo < 0 || hi - lo > 65535) return false;   // no weight at all; a negative weight (its pattern is no neighbour of a positive one's)
+    // the midpoint, rounded up: offsets lo - ref >= -32768 and hi - ref <= 32767 for every spread up to 65 535
+    const int64_t ref = lo + (hi - lo + 1) / 2;
+    B.vW16.resize((size_t)nV * 8);
+    int64_t bad = 0;
+#pragma omp parallel for schedule(static) reduction(+ : bad)
+    for (int64_t v = 0; v < nV; ++v)
+        for (int e = 0; e < 8; ++e) {
+            int16_t off = 0;
+            if (e < (int)B.vCount[v]) {
+                const int64_t b = bitsOf(v, e);
+                off = (int16_t)(b - ref);
+                const double w = fusedWeightFromOffset(ref, off);
+                int64_t back;
+                std::memcpy(&back, &w, 8);
+                bad += back != b;
+            }
+            B.vW16[(size_t)v * 8 + e] = off;
+        }
+    if (bad != 0) { RawVec<int16_t>().swap(B.vW16); return false; }   // (cannot happen inside the spread; the decode is the proof, not the rule)
+    B.wRef = ref; B.packedW = 1;
+    return true;
+}
+
+FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
     FusedBlocks B;
     const auto tStart = std::chrono::steady_clock::now();
     const int64_t nC = s.nC, nIF = s.nIF;
@@ -1258,6 +1299,10 @@ FusedBlocks buildFusedBlocks(const StaticData& s) {
         }
         B.nTemplates = (int32_t)nT;
         B.templateMismatches = (int32_t)mismatched.size();
+    }
+    {
+        const char* e = std::getenv("QGD_FUSED_PACKED_W");
+        if (!(e && std::atoi(e) == 0) && packFusedWeights(B) && !keepFullWeights) RawVec<double>().swap(B.vW);
     }
     B.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
     return B;

@@ -9,6 +9,7 @@
 //    contiguous 16-B aligned chunk)
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <type_traits>
 #include <utility>
@@ -172,6 +173,14 @@ struct FusedBlocks {
     RawVec<uint8_t> vCount;   // capV per block
     RawVec<uint16_t> vPos;    // capPE x capV per template
     RawVec<double> vW;        // capPE x capV per block
+    // PACKED WEIGHTS (packFusedWeights below; QGD_FUSED_PACKED_W=0: never).  On a uniform hexahedral region every weight is 1/8 give or take
+    // rounding, so the bit patterns of ALL weights of the mesh lie within a few thousand of each other: where capPE == 8 and their spread
+    // is <= 65 535, a weight is kept as the signed 16-bit offset of its pattern from wRef (the midpoint pattern) -- 16 B per vertex
+    // instead of 64, and bits(w) = wRef + offset gives the double back exactly.  Vertex-major: a vertex's eight offsets are one aligned
+    // 16-B piece.  Entries beyond a vertex's count are 0.  Graded, jittered and unstructured meshes do not qualify and keep vW alone.
+    int32_t packedW = 0;      // 1: vW16 / wRef hold every weight of vW
+    int64_t wRef = 0;
+    RawVec<int16_t> vW16;     // 8 x capV per block: vW16[(blk * capV + lv) * 8 + e]
     RawVec<uint8_t> nEntry;   // 128 per block: face entries of each own cell
     RawVec<int32_t> entry;    // capE x 128 per template, entry-major: (local face << 1) | (1: the cell is the neighbour, minus), or ~label of a boundary face
     int32_t brick[3] = {0, 0, 0};  // the lattice brick the blocks were cut from (8 x 4 x 4 unless another shape fills the blocks better; 0: count-based runs)
@@ -181,6 +190,17 @@ struct FusedBlocks {
 };
 // LDS a block's records may take so that three blocks (+ 3 KB of parked face entries each) share a CU's 160 KB: what an 8x4x4 brick needs
 constexpr int32_t kFusedLdsTarget = 48 * 360 + 32 * 288 + 72 * 225 + 24 * 288;
-FusedBlocks buildFusedBlocks(const StaticData& s);
+// keepFullWeights = false: vW is dropped once vW16 holds it (the device path: 8 x 8 B per vertex formed that nothing reads again)
+FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights = true);
+// The packing rule on a block table whose nBlocks, capV, capPE, vCount and vW are filled: fills vW16 / wRef and sets packedW where the
+// weights qualify (every entry decoded once and compared with vW bit for bit), leaves all three empty / 0 where they do not.  The
+// result does not depend on the number of threads.  Returns packedW.
+bool packFusedWeights(FusedBlocks& B);
+inline double fusedWeightFromOffset(int64_t ref, int16_t off) {
+    const int64_t bits = ref + (int64_t)off;
+    double w;
+    std::memcpy(&w, &bits, 8);
+    return w;
+}
 
 }  // namespace qgd

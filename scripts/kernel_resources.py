@@ -103,8 +103,9 @@ def kernel_disassembly(lib, mnemonics):
                     ins, _, enc = line.strip().partition("//")
                     if ins.strip() == "...":   # objdump's mark for zero bytes behind the last instruction (alignment of the next symbol)
                         continue
-                    # (the address in front of the encoding goes: a kernel may move inside its code object)
-                    cur.append(ins.split()[0] if mnemonics else ins.strip() + " |" + enc.partition(":")[2])
+                    # (the address in front of the encoding goes: a kernel may move inside its code object; so does the kernel's own name in
+                    # the note behind a branch, `<name+0x78>` -> `<+0x78>`: with --gained-parameter the name differs, the target does not)
+                    cur.append(ins.split()[0] if mnemonics else ins.strip() + " |" + re.sub(r"<[^<>+\s]+(\+0x[0-9a-f]+)?>\s*$", r"<\1>", enc.partition(":")[2]))
     return kernels
 
 
