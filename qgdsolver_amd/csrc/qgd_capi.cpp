@@ -900,8 +900,8 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
             if (t.fb != 0 && lds <= 65536 && 4 * (int64_t)t.spill.size() <= nTiles) {
                 v.tileLds = (int32_t)lds;
                 v.tileMaxC = t.maxCells; v.tileMaxV = t.maxVerts;
-                v.qhdTiles = envOnOff("QGD_QHD_TILES", 1);
-                v.implTiles = envOnOff("QGD_IMPL_TILES", 1);
+                v.qhdTiles = (uint16_t)envOnOff("QGD_QHD_TILES", 1);
+                v.implTiles = (uint16_t)envOnOff("QGD_IMPL_TILES", 1);
                 if (v.fblock == 128 && envOnOff("QGD_FTILE_FIXED", 1) != 0 &&
                     (int64_t)nTiles * std::max(t.maxCells, t.maxVerts) < (int64_t)INT32_MAX) {
                     // the lists once more at a fixed stride (built and uploaded one after the other: the host peak stays at one table)
@@ -962,6 +962,16 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                     // the vertex weights: 16-bit offsets from one pattern where the mesh's weights pack (FusedBlocks::vW16), the doubles otherwise
                     if (fb.packedW) { v.fuVW = nullptr; v.fuVW16 = up(fb.vW16); v.fuVWRef = fb.wRef; }
                     else { v.fuVW = up(fb.vW); v.fuVW16 = nullptr; v.fuVWRef = 0; }
+                    // the per-face streams w / hQGDf / kind, block-major as 16-bit offsets + a byte where they pack too (FusedBlocks::fW16)
+                    v.fuFace = nullptr;
+                    if (fb.packedF) {
+                        FusedFaceView ff{};
+                        ff.fuFW16 = up(fb.fW16); ff.fuFKC = up(fb.fKC); ff.fuFWRef = fb.fwRef;
+                        for (int q = 0; q < 4; ++q) ff.fuFHRef[q] = fb.fhRef[q];
+                        std::vector<int64_t> raw(sizeof(FusedFaceView) / 8);   // (uploaded as plain words)
+                        std::memcpy(raw.data(), &ff, sizeof ff);
+                        v.fuFace = reinterpret_cast<const FusedFaceView*>(up(raw));
+                    }
                     v.fuHdr = reinterpret_cast<const int4*>(up(fb.hdr)); v.fuCells = up(fb.cells); v.fuVerts = up(fb.verts);
                     v.fuFaceLabel = up(fb.faceLabel); v.fuFacePos = up(fb.facePos); v.fuNEntry = up(fb.nEntry); v.fuEntry = up(fb.entry);
                     {   // the implicitDiffusion branch's layout of the same blocks (qgd_kernels.hip fusedFaceCellKernel<..., IMPL>)
@@ -971,10 +981,11 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                     }
                     d->fusedInfo[0] = fb.nBlocks; d->fusedInfo[1] = fb.nLayerBlocks; d->fusedInfo[2] = fb.nTemplates; d->fusedInfo[3] = lds;
                     // bytes a block streams per step out of its own lists / of its template's
-                    d->fusedInfo[4] = 32 + 4 * (int64_t)fb.capC + 4 * (int64_t)fb.capV + 4 * (int64_t)fb.capF + fb.capV + 128 + (fb.packedW ? 2 : 8) * (int64_t)fb.capPE * fb.capV;
+                    d->fusedInfo[4] = 32 + 4 * (int64_t)fb.capC + 4 * (int64_t)fb.capV + 4 * (int64_t)fb.capF + fb.capV + 128 + (fb.packedW ? 2 : 8) * (int64_t)fb.capPE * fb.capV +
+                                      (fb.packedF ? 5 * (int64_t)fb.capF : 0);
                     d->fusedInfo[5] = 12 * (int64_t)fb.capF + 4 * (int64_t)fb.capE * 128 + 2 * (int64_t)fb.capPE * fb.capV;
                     d->fusedInfo[6] = (int64_t)(fb.buildSeconds * 1e3);
-                    d->fusedInfo[7] = fb.brick[0] | fb.brick[1] << 8 | fb.brick[2] << 16 | (fb.packedW ? 1 << 24 : 0);
+                    d->fusedInfo[7] = fb.brick[0] | fb.brick[1] << 8 | fb.brick[2] << 16 | (fb.packedW ? 1 << 24 : 0) | (fb.packedF ? 1 << 25 : 0);
                 }
             }
         }

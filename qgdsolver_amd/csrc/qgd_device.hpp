@@ -15,6 +15,14 @@ struct alignas(16) RecB { double H, c, muQGD, aOc; };        // 32 B: derived pe
 
 enum StencilKind : int { ST_REDUCED = 0, ST_LSQ = 1, ST_GVP3 = 2, ST_GVP2 = 3 };
 
+// The per-face streams of the fused step, block-major (device memory; MeshView::fuFace): per face slot of a block (slot i of block b at
+// b * fuCapF + i, the order of fuFaceLabel) one word -- the 16-bit offsets of w (low half, from fuFWRef) and of hQGDf (high half, from
+// fuFHRef[class]) -- and one byte, kind | class << 2.  Read through the scalar path with the block's header.
+struct FusedFaceView {
+    const uint32_t* fuFW16; const uint8_t* fuFKC; int64_t fuFWRef; int64_t fuFHRef[4]; int64_t pad;
+};
+static_assert(sizeof(FusedFaceView) == 64, "read as one 64-byte scalar load");
+
 // Static mesh data on the device; every face array is indexed by global face label.
 struct MeshView {
     int32_t nP, nF, nIF, nC, nBF;
@@ -63,9 +71,14 @@ struct MeshView {
     // QGD_FTILE_FIXED (default 1; 128-face tiles, 3 waves per SIMD): the same lists at a fixed stride of tileMaxC /
     // tileMaxV labels per tile (padded with the tile's last label; all zero for the tiles of tileSpill, which carry tileFlag = 1)
     const int32_t* tileCellsFix; const int32_t* tileVertsFix; const uint8_t* tileFlag;
-    int32_t qhdTiles;        // QGD_QHD_TILES (default 1): QHD's two face passes use the tiles too (qgd_qhd.hip qhdFace{1,2}TileKernel)
-    int32_t implTiles;       // QGD_IMPL_TILES (default 1): so does the face kernel of QGDFoam's implicit branch (qgd_implicit.hip implFaceTileKernel)
+    // a mesh whose per-face streams pack too (FusedFaceView above; qgd_setup.hpp FusedBlocks::fW16): the device copy of their view, null
+    // where the fused kernel gathers m.w / m.hf / m.fkind by label.  ONE pointer, and here: the view must not grow and no member a kernel
+    // reads may move (every kernel's argument loads would), so it took the place of the two host-only switches below, which now share the
+    // four bytes that were padding behind sGeo.
+    const FusedFaceView* fuFace;
     int32_t sGeo;            // 1: the 3-D GaussVolPoint kernels rebuild Sf of quadrilateral faces from the vertices (no Sf stream)
+    uint16_t qhdTiles;       // QGD_QHD_TILES (default 1): QHD's two face passes use the tiles too (qgd_qhd.hip qhdFace{1,2}TileKernel)
+    uint16_t implTiles;      // QGD_IMPL_TILES (default 1): so does the face kernel of QGDFoam's implicit branch (qgd_implicit.hip implFaceTileKernel)
     const double* V; const double* hQGD; const uint8_t* ghost;
     const int32_t* bPatch; const double* hQGDb;
     // cell blocks of the fused face + cell kernel (qgd_setup.hpp FusedBlocks); fuBlocks == 0: not built

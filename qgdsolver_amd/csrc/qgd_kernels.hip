@@ -1122,6 +1122,13 @@ __device__ __forceinline__ v2d fuRowMaxMin(v2d r) {
 // the stored double exactly, so the states are the same bits.  A compile-time flag, because the group must issue the same number of memory
 // instructions on every path (the counted wait); the launchers choose it from the view.  PACKW = 0 is the kernel as it was, instruction for
 // instruction.  capPE is 8 with PACKW: no vertex has a ninth cell, the walk beyond the registers cannot happen.
+// PACKW = 2: the per-face streams too (MeshView::fuFace -> FusedFaceView; FusedBlocks::fW16).  w, hQGDf and the kind of a block's face slots lie
+// block-major in slot order, one word (two 16-bit offsets) and one byte (kind | class << 2) per slot: they need no label, so they join the
+// front-loaded group (two 4-byte and two 1-byte loads per thread, vmcnt(21)) and the three gathers per face of round 1 -- 17 B per face by
+// label -- are gone.  The doubles are formed in the face loop, as the weights are in (1b): reference + offset, the stored double exactly.
+// Their view (two table pointers, five reference patterns) is device memory behind ONE pointer of MeshView, which must not grow: 64 uniform
+// bytes, asked for through the scalar path with the header and waited for with it.  PACKW = 1 is the kernel as it was, instruction for
+// instruction.
 template <bool SGEO, bool UPW = false, bool IMPL = false, bool ADJ = false, int PACKW = 0>
 // (IMPL with `Gauss upwind` fluxes needs a few registers more than three waves per SIMD leave: that instantiation is compiled for two -- no scratch)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((IMPL && UPW) ? 2 : 3, (IMPL && UPW) ? 2 : 3)))
@@ -1157,6 +1164,12 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     __builtin_amdgcn_sched_barrier(0);
     const i32x4 hdr = *(HdrPtr)(uintptr_t)(m.fuHdr + blk);
     const i32x2 hdr2 = *(Hdr2Ptr)(uintptr_t)(m.fuHdr2 + blk);
+    // (PACKW == 2: the face streams' view with them -- the same for every block, so it stays in the scalar cache)
+    // (a volatile read: it is asked for HERE, with the header, and not where its first use is -- in the middle of the front-loaded group)
+    typedef long long i64x8 __attribute__((ext_vector_type(8)));
+    typedef const volatile i64x8 __attribute__((address_space(4)))* FaceViewPtr;
+    i64x8 fv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (PACKW == 2) fv = *(FaceViewPtr)(uintptr_t)m.fuFace;
     __builtin_amdgcn_sched_barrier(0);
     // (0a) THE LISTS: everything whose address depends on no loaded value -- the piece labels out of the lists (padded to their strides with
     // their last entry, so no count is needed to read them), the labels of this thread's two faces, its vertex and its cell.
@@ -1167,6 +1180,8 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // used under that mask only; it passes an empty asm first where the compiler would otherwise move integer arithmetic on it into a
     // masked block, behind a wait for the load (fuPin).
     const int wv0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+    // (PACKW == 2 && SGEO && !IMPL uses the label only where a face is no quadrilateral, the mesh has polygons or a shard counts faces under
+    // ADJ; reading it lazily there instead of here was measured and is no gain at 64 M cells: profiles/ab_fused_packed_faces.txt)
     int fl[KF];
 #pragma unroll
     for (int j = 0; j < KF; ++j) fl[j] = tFaceLabel[min(tid + j * NT, capF - 1)];
@@ -1213,7 +1228,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     const int nOwn = hdr.x, nUc = hdr.y, nUv = hdr.z, nFc = hdr.w;
     const bool vertLane = tid < nUv;
     const size_t tpl = (size_t)hdr2.y;
-    constexpr int kFrontLoads = KF + KE + KP + (PACKW ? 1 : KP);
+    constexpr int kFrontLoads = KF + KE + KP + (PACKW ? 1 : KP) + (PACKW == 2 ? 2 * KF : 0);
     constexpr int kRsrcWord3 = 0x00020000;          // raw buffer, 32-bit data format
     constexpr int kBeyond = 0x40000000;             // an offset no table reaches (a descriptor spans one block's or one template's part)
     struct Pos3 { uint32_t c, va, vb; };
@@ -1230,6 +1245,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     int pcPos[KP];
     double pcW[KP];
     int wOff[4] = {0, 0, 0, 0};   // PACKW: the vertex's eight weights as loaded, 16-bit offsets from m.fuVWRef (the doubles are formed in (1b))
+    int fOff[KF] = {0, 0}, fKc[KF] = {0, 0};   // PACKW == 2: this thread's face slots as loaded -- the offsets of w | hQGDf << 16, and kind | class << 2
     {
         const __amdgpu_buffer_rsrc_t rFacePos = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(m.fuFacePos + tpl * capF * 3), 0, capF * 12, kRsrcWord3);
         const __amdgpu_buffer_rsrc_t rEntry = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(m.fuEntry + tpl * m.fuCapE * 128), 0, m.fuCapE * 128 * 4, kRsrcWord3);
@@ -1257,6 +1273,21 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             for (int i = 0; i < KP; ++i)
                 pcW[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rVW, vertLane ? (min(i, capPE - 1) * capV + vt) * 8 : kBeyond, 0, 0));
         }
+        if constexpr (PACKW == 2) {
+            // the block's part of the face-slot tables: capF words, capF bytes
+            const __amdgpu_buffer_rsrc_t rFW = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint32_t*>((uintptr_t)fv[0]) + (size_t)blk * capF, 0, capF * 4, kRsrcWord3);
+            const __amdgpu_buffer_rsrc_t rFK = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t*>((uintptr_t)fv[1]) + (size_t)blk * capF, 0, capF, kRsrcWord3);
+#pragma unroll
+            for (int j = 0; j < KF; ++j) {
+                const int lf = tid + j * NT;
+                fOff[j] = (int)__builtin_amdgcn_raw_buffer_load_b32(rFW, lf < nFc ? lf * 4 : kBeyond, 0, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < KF; ++j) {
+                const int lf = tid + j * NT;
+                fKc[j] = (int)__builtin_amdgcn_raw_buffer_load_b8(rFK, lf < nFc ? lf : kBeyond, 0, 0);
+            }
+        }
     }
     // The round ends HERE for the lists, at once (the loads above went out back to back and return in issue order): the memory counter may
     // stay at the front-loaded group, which nothing needs before the records are staged.  Left to itself the compiler waits label by label.
@@ -1264,9 +1295,9 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // wait behind the lists, no wait inside round 1 -- the two-word read of fuHdr2 and fuTimes3Plus answer register-allocation accidents of
     // one compiler version, and only the disassembly shows them.  Redo the ISA check of DESIGN.md section 5 after every ROCm change; a wait
     // that comes back costs speed, not correctness.)
-    static_assert(kFrontLoads == (PACKW ? 17 : 24), "the wait below is written for vmcnt(24), vmcnt(17) with packed weights");
+    static_assert(kFrontLoads == (PACKW == 2 ? 21 : PACKW ? 17 : 24), "the wait below is written for vmcnt(24), vmcnt(17) with packed weights, vmcnt(21) with packed face streams too");
     __builtin_amdgcn_sched_barrier(0);
-    // vmcnt(kFrontLoads): its low four bits in bits 3:0, its high two in bits 15:14; expcnt and lgkmcnt left alone (0x4F78 for 24, 0x4F71 for 17)
+    // vmcnt(kFrontLoads): its low four bits in bits 3:0, its high two in bits 15:14; expcnt and lgkmcnt left alone (0x4F78 for 24, 0x4F71 for 17, 0x4F75 for 21)
     __builtin_amdgcn_s_waitcnt(0x0F70 | (kFrontLoads & 15) | ((kFrontLoads >> 4) << 14));
     __builtin_amdgcn_sched_barrier(0);
     // (1) one round trip later, what needs a label: the records, piece by piece; the faces' streams; the cell's own scalars; a patch
@@ -1308,8 +1339,10 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     int fk[KF];
 #pragma unroll
     for (int j = 0; j < KF; ++j) {
-        if (wv0 + j * NT < nFc) {
-            if (tid + j * NT < nFc) { fw[j] = ldStream(m.w + fl[j]); fh[j] = ldStream(m.hf + fl[j]); fk[j] = m.fkind[fl[j]]; }
+        if constexpr (PACKW != 2) {   // (PACKW == 2: they came with the front-loaded group, block-major)
+            if (wv0 + j * NT < nFc) {
+                if (tid + j * NT < nFc) { fw[j] = ldStream(m.w + fl[j]); fh[j] = ldStream(m.hf + fl[j]); fk[j] = m.fkind[fl[j]]; }
+            }
         }
     }
     fuPin(ci);
@@ -1370,7 +1403,11 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         for (int q = 0; q < 4; ++q) fuPin(wOff[q]);
     }
 #pragma unroll
-    for (int j = 0; j < KF; ++j) { fuPin(fk[j]); fuPin(fp[j].c); fuPin(fp[j].va); fuPin(fp[j].vb); }
+    for (int j = 0; j < KF; ++j) {
+        if constexpr (PACKW == 2) { fuPin(fOff[j]); fuPin(fKc[j]); }
+        else fuPin(fk[j]);
+        fuPin(fp[j].c); fuPin(fp[j].va); fuPin(fp[j].vb);
+    }
     // (1b) the vertex values [volPointInterpolation: inverse-distance weights over pointCells, in their order -- pointInterpRecKernel's
     // arithmetic, out of the staged cell records]
     if (tid < nUv) {
@@ -1421,6 +1458,15 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     for (int j = 0; j < KF; ++j) {
         const int lf = tid + j * NT;
         if (lf < nFc) {
+            if constexpr (PACKW == 2) {
+                // w, hQGDf and the kind out of the slot's word and byte: sign-extend the half word, add it to the reference pattern (w's, or
+                // the one of hQGDf's class), take the sum as a double
+                const int cls = fKc[j] >> 2;
+                const int64_t hRef = cls == 0 ? fv[3] : cls == 1 ? fv[4] : cls == 2 ? fv[5] : fv[6];   // (FusedFaceView: fuFHRef[class]; fuFWRef)
+                fw[j] = fuWeightFromOffset(fv[2], (fOff[j] << 16) >> 16);
+                fh[j] = fuWeightFromOffset(hRef, fOff[j] >> 16);
+                fk[j] = fKc[j] & 3;
+            }
             const int f = fl[j], kind = fk[j];
             const unsigned lc = fp[j].c, lva = fp[j].va, lvb = fp[j].vb;
             const int lo = (int)(lc & 0xffffu), ln = (int)(lc >> 16);
@@ -2351,10 +2397,11 @@ static FusedXcdOrder fusedXcdOrder(int nBlocks, int run) {
     return {(nBlocks / span) * span, shift};
 }
 // one launch of fusedFaceCellKernel<SGEO, UPW, IMPL, ADJ, PACKW>: SGEO, UPW and PACKW (the view holds the vertex weights as 16-bit offsets,
-// MeshView::fuVW16) are chosen here, IMPL and ADJ by the caller
+// MeshView::fuVW16: 1; the per-face streams too, fuFace: 2) are chosen here, IMPL and ADJ by the caller
 #define QGD_FUSED_LAUNCH4(SG, UP, IM, AD, n, lds, ...)                                                                          \
     do {                                                                                                                        \
-        if (m.fuVW16) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 1><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
+        if (m.fuFace) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 2><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
+        else if (m.fuVW16) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 1><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
         else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD><<<n, 256, lds, L.stream>>>(__VA_ARGS__)));            \
     } while (0)
 #define QGD_FUSED_LAUNCH(IM, AD, n, lds, ...)                                          \
@@ -2390,14 +2437,15 @@ void launchCellFinish(const Launcher& L, const MeshView& m, const CaseView& c, c
 // the implicitDiffusion branch's block-fused assembly of the U systems (fusedFaceCellKernel<..., IMPL = true>): more dynamic LDS than the
 // 64 KB a launch gets by default, so the kernels' limit is raised first; false when the device refuses (the caller keeps the separate kernels)
 template <bool SGEO, bool UPW>
-static bool fusedImplLimit(int lds, bool packed) {
-    const void* k = packed ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 1>) : reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true>);
+static bool fusedImplLimit(int lds, int packed) {
+    const void* k = packed == 2 ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 2>)
+                  : packed == 1 ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 1>) : reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true>);
     return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
 }
 bool fusedImplUPrepare(const MeshView& m, const GasModel& g) {
     if (m.fuBlocks <= 0 || m.fuLdsImpl <= 0) return false;
     const bool upw = g.upwindU || g.upwindH;
-    const bool pk = m.fuVW16 != nullptr;
+    const int pk = m.fuFace ? 2 : m.fuVW16 ? 1 : 0;   // the level the launch will pick
     const bool ok = m.sGeo ? (upw ? fusedImplLimit<true, true>(m.fuLdsImpl, pk) : fusedImplLimit<true, false>(m.fuLdsImpl, pk))
                            : (upw ? fusedImplLimit<false, true>(m.fuLdsImpl, pk) : fusedImplLimit<false, false>(m.fuLdsImpl, pk));
     if (!ok) (void)hipGetLastError();

@@ -799,6 +799,96 @@ bool packFusedWeights(FusedBlocks& B) {
     return true;
 }
 
+bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
+    B.packedF = 0; B.nHfClasses = 0; B.fwRef = 0;
+    for (int q = 0; q < 4; ++q) B.fhRef[q] = 0;
+    RawVec<uint32_t>().swap(B.fW16);
+    RawVec<uint8_t>().swap(B.fKC);
+    if (B.packedW != 1 || B.nBlocks <= 0 || B.capF <= 0) return false;
+    const int64_t nB = B.nBlocks;
+    const size_t capF = (size_t)B.capF;
+    auto bitsOf = [](const double& v) { int64_t b; std::memcpy(&b, &v, 8); return b; };
+    // the spreads over every computed face slot (min and max are exact: the same whatever the threads)
+    int64_t wLo = INT64_MAX, wHi = INT64_MIN, hLo = INT64_MAX, hHi = INT64_MIN;
+#pragma omp parallel for schedule(static) reduction(min : wLo, hLo) reduction(max : wHi, hHi)
+    for (int64_t b = 0; b < nB; ++b)
+        for (int32_t i = 0; i < B.hdr[4 * b + 3]; ++i) {
+            const int32_t f = B.faceLabel[(size_t)b * capF + i];
+            const int64_t bw = bitsOf(s.w[f]), bh = bitsOf(s.hf[f]);
+            wLo = std::min(wLo, bw); wHi = std::max(wHi, bw); hLo = std::min(hLo, bh); hHi = std::max(hHi, bh);
+        }
+    if (wLo > wHi || wLo < 0 || hLo < 0 || wHi - wLo > 65535) return false;   // no face at all; a negative value; w too wide
+    // the classes of hf: the sorted patterns cut greedily -- class c starts at the smallest pattern beyond the 65 536 of class c - 1
+    int64_t start[4] = {hLo, 0, 0, 0}, top[4] = {hHi, 0, 0, 0};
+    int nCl = 1;
+    while (hHi - start[nCl - 1] > 65535) {
+        if (nCl == 4) return false;
+        const int64_t bound = start[nCl - 1] + 65535;
+        int64_t next = INT64_MAX;
+#pragma omp parallel for schedule(static) reduction(min : next)
+        for (int64_t b = 0; b < nB; ++b)
+            for (int32_t i = 0; i < B.hdr[4 * b + 3]; ++i) {
+                const int64_t bh = bitsOf(s.hf[B.faceLabel[(size_t)b * capF + i]]);
+                if (bh > bound) next = std::min(next, bh);
+            }
+        start[nCl++] = next;
+    }
+    auto classOf = [&](int64_t bh) { int c = 0; while (c + 1 < nCl && bh >= start[c + 1]) ++c; return c; };
+    if (nCl > 1) {   // (one class: its top is the maximum found above)
+        for (int q = 0; q < 4; ++q) top[q] = INT64_MIN;
+#pragma omp parallel
+        {
+            int64_t mine[4] = {INT64_MIN, INT64_MIN, INT64_MIN, INT64_MIN};
+#pragma omp for schedule(static) nowait
+            for (int64_t b = 0; b < nB; ++b)
+                for (int32_t i = 0; i < B.hdr[4 * b + 3]; ++i) {
+                    const int64_t bh = bitsOf(s.hf[B.faceLabel[(size_t)b * capF + i]]);
+                    const int cl = classOf(bh);
+                    mine[cl] = std::max(mine[cl], bh);
+                }
+#pragma omp critical(qgdPackFaceTop)
+            for (int q = 0; q < 4; ++q) top[q] = std::max(top[q], mine[q]);
+        }
+    }
+    // the midpoints, rounded up: every offset lies in [-32768, 32767] for a spread up to 65 535
+    const int64_t wRef = wLo + (wHi - wLo + 1) / 2;
+    int64_t hRef[4] = {0, 0, 0, 0};
+    for (int q = 0; q < nCl; ++q) hRef[q] = start[q] + (top[q] - start[q] + 1) / 2;
+    B.fW16.resize((size_t)nB * capF);
+    B.fKC.resize((size_t)nB * capF);
+    int64_t bad = 0;
+#pragma omp parallel for schedule(static) reduction(+ : bad)
+    for (int64_t b = 0; b < nB; ++b) {
+        const int32_t nF = B.hdr[4 * b + 3];
+        for (int32_t i = 0; i < B.capF; ++i) {
+            uint32_t word = 0;
+            uint8_t kc = 0;
+            if (i < nF) {
+                const int32_t f = B.faceLabel[(size_t)b * capF + i];
+                const int64_t bw = bitsOf(s.w[f]), bh = bitsOf(s.hf[f]);
+                const int cl = classOf(bh);
+                const uint8_t kind = s.fkind[f];
+                word = (uint32_t)(uint16_t)(int16_t)(bw - wRef) | (uint32_t)(uint16_t)(int16_t)(bh - hRef[cl]) << 16;
+                kc = (uint8_t)((kind & 3) | cl << 2);
+                // the decode, as the kernel does it
+                const double w = fusedWeightFromOffset(wRef, (int16_t)(word & 0xffffu)), h = fusedWeightFromOffset(hRef[kc >> 2], (int16_t)(word >> 16));
+                bad += bitsOf(w) != bw || bitsOf(h) != bh || (kc & 3) != kind;
+            }
+            B.fW16[(size_t)b * capF + i] = word;
+            B.fKC[(size_t)b * capF + i] = kc;
+        }
+    }
+    if (bad != 0) {   // (cannot happen inside the spreads; the decode is the proof, not the rule)
+        RawVec<uint32_t>().swap(B.fW16);
+        RawVec<uint8_t>().swap(B.fKC);
+        return false;
+    }
+    B.fwRef = wRef; B.nHfClasses = nCl;
+    for (int q = 0; q < 4; ++q) B.fhRef[q] = hRef[q];
+    B.packedF = 1;
+    return true;
+}
+
 FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
     FusedBlocks B;
     const auto tStart = std::chrono::steady_clock::now();
@@ -1303,6 +1393,8 @@ FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
     {
         const char* e = std::getenv("QGD_FUSED_PACKED_W");
         if (!(e && std::atoi(e) == 0) && packFusedWeights(B) && !keepFullWeights) RawVec<double>().swap(B.vW);
+        const char* ef = std::getenv("QGD_FUSED_PACKED_F");   // (the face streams pack only where the weights did)
+        if (!(ef && std::atoi(ef) == 0)) packFusedFaceStreams(B, s);
     }
     B.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
     return B;

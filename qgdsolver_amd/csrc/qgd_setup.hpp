@@ -181,6 +181,19 @@ struct FusedBlocks {
     int32_t packedW = 0;      // 1: vW16 / wRef hold every weight of vW
     int64_t wRef = 0;
     RawVec<int16_t> vW16;     // 8 x capV per block: vW16[(blk * capV + lv) * 8 + e]
+    // PACKED FACE STREAMS (packFusedFaceStreams below; QGD_FUSED_PACKED_F=0: never; only where packedW == 1).  The linear weight w, hQGDf and
+    // the kind of a block's face slots are static, so they can lie block-major in the kernel's face-slot order (slot i of block b at
+    // b * capF + i, the order of faceLabel) and be read in the list round, without the label.  On a uniform mesh w is 1/2 give or take
+    // rounding and hQGDf has one value per axis spacing: where, over every computed face slot, the patterns of w lie within 65 535 of each
+    // other and those of hf fall into at most four classes that each do, a slot is one 32-bit word -- low half int16(bits(w) - fwRef), high
+    // half int16(bits(hf) - fhRef[class]) -- and one byte, kind | class << 2: 5 B per face instead of 17 B gathered by label.  Padding
+    // slots are zero.  The classes are cut greedily from the sorted patterns (class c starts at the smallest pattern beyond class c - 1's
+    // 65 536), so they do not depend on the thread count; the references are the midpoint patterns, rounded up.
+    int32_t packedF = 0;      // 1: fW16 / fKC / fwRef / fhRef hold w, hf and fkind of every computed face slot
+    int32_t nHfClasses = 0;
+    int64_t fwRef = 0, fhRef[4] = {0, 0, 0, 0};
+    RawVec<uint32_t> fW16;    // capF per block
+    RawVec<uint8_t> fKC;      // capF per block
     RawVec<uint8_t> nEntry;   // 128 per block: face entries of each own cell
     RawVec<int32_t> entry;    // capE x 128 per template, entry-major: (local face << 1) | (1: the cell is the neighbour, minus), or ~label of a boundary face
     int32_t brick[3] = {0, 0, 0};  // the lattice brick the blocks were cut from (8 x 4 x 4 unless another shape fills the blocks better; 0: count-based runs)
@@ -196,6 +209,10 @@ FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights = true);
 // weights qualify (every entry decoded once and compared with vW bit for bit), leaves all three empty / 0 where they do not.  The
 // result does not depend on the number of threads.  Returns packedW.
 bool packFusedWeights(FusedBlocks& B);
+// The same for the per-face streams, on a block table whose nBlocks, capF, hdr, faceLabel and packedW are filled: fills fW16 / fKC / fwRef /
+// fhRef and sets packedF where s.w and s.hf of the computed face slots qualify (every slot decoded once and compared with s.w, s.hf and
+// s.fkind of its face), leaves them empty / 0 where they do not or where packedW != 1.  Returns packedF.
+bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s);
 inline double fusedWeightFromOffset(int64_t ref, int16_t off) {
     const int64_t bits = ref + (int64_t)off;
     double w;

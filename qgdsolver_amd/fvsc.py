@@ -77,7 +77,8 @@ class Device:
         b = int(a[7])
         return dict(blocks=int(a[0]), layerBlocks=int(a[1]), templates=int(a[2]), ldsBytes=int(a[3]), blockListBytes=int(a[4]),
                     templateBytes=int(a[5]), buildSeconds=a[6] / 1e3, brick=(b & 255, (b >> 8) & 255, (b >> 16) & 255),
-                    packedWeights=bool((b >> 24) & 1))   # the vertex weights are 16-bit offsets from one pattern (QGD_FUSED_PACKED_W)
+                    packedWeights=bool((b >> 24) & 1),   # the vertex weights are 16-bit offsets from one pattern (QGD_FUSED_PACKED_W)
+                    packedFaces=bool((b >> 25) & 1))     # w, hQGDf and kind of the face slots block-major, 5 B per slot (QGD_FUSED_PACKED_F)
 
     def face_tiles(self):
         """how the internal faces go through the 3-D GaussVolPoint flux kernel (qgd_device_face_tiles)"""
