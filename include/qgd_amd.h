@@ -300,7 +300,9 @@ int qgd_device_face_tiles(qgd_device_t d, int64_t info[4]);
  * weights are kept as 16-bit offsets from one reference bit pattern (a mesh whose weights all lie within 65 535 patterns of each other, e.g.
  * a uniform hexahedral region; QGD_FUSED_PACKED_W=0: never) -- [4] counts 2 bytes per weight then, not 8; bit 25 of [7] = the per-face streams w, hQGDf and kind of a
  * block's face slots lie block-major too, as two 16-bit offsets and one byte per slot (only with bit 24; QGD_FUSED_PACKED_F=0: never) --
- * [4] counts those 5 bytes per face slot then. */
+ * [4] counts those 5 bytes per face slot then.  What the packed tables hold, for tests and reports (0 where they were not built): bits 26..28
+ * of [7] = the classes of hQGDf (1..4), bits 29..44 = the largest |offset| among the vertex-weight offsets (0..32768), bits 45..60 = the
+ * largest |offset| among the face words, over w and hQGDf (0..32768). */
 int qgd_device_fused_blocks(qgd_device_t d, int64_t info[8]);
 
 /* qgdInterpolate / linearInterpolate [QGDInterpolate_8H_source.html L38-67]: face = w*(phi_O - phi_N) + phi_N, patch faces

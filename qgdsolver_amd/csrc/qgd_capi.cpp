@@ -985,7 +985,9 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                                       (fb.packedF ? 5 * (int64_t)fb.capF : 0);
                     d->fusedInfo[5] = 12 * (int64_t)fb.capF + 4 * (int64_t)fb.capE * 128 + 2 * (int64_t)fb.capPE * fb.capV;
                     d->fusedInfo[6] = (int64_t)(fb.buildSeconds * 1e3);
-                    d->fusedInfo[7] = fb.brick[0] | fb.brick[1] << 8 | fb.brick[2] << 16 | (fb.packedW ? 1 << 24 : 0) | (fb.packedF ? 1 << 25 : 0);
+                    // (the figures above bit 25 say what the packed tables hold, for tests and reports: nothing reads them to decide anything)
+                    d->fusedInfo[7] = fb.brick[0] | fb.brick[1] << 8 | fb.brick[2] << 16 | (fb.packedW ? 1 << 24 : 0) | (fb.packedF ? 1 << 25 : 0) |
+                                      (int64_t)(fb.nHfClasses & 7) << 26 | (int64_t)(fb.maxWeightOffset & 0xffff) << 29 | (int64_t)(fb.maxFaceOffset & 0xffff) << 45;
                 }
             }
         }

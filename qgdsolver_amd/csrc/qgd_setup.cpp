@@ -760,7 +760,7 @@ struct OneBlock {
 }  // namespace
 
 bool packFusedWeights(FusedBlocks& B) {
-    B.packedW = 0; B.wRef = 0;
+    B.packedW = 0; B.wRef = 0; B.maxWeightOffset = 0;
     RawVec<int16_t>().swap(B.vW16);
     if (B.capPE != 8 || B.nBlocks <= 0) return false;
     const int64_t nV = (int64_t)B.nBlocks * B.capV;
@@ -780,13 +780,15 @@ bool packFusedWeights(FusedBlocks& B) {
     const int64_t ref = lo + (hi - lo + 1) / 2;
     B.vW16.resize((size_t)nV * 8);
     int64_t bad = 0;
-#pragma omp parallel for schedule(static) reduction(+ : bad)
+    int32_t maxOff = 0;
+#pragma omp parallel for schedule(static) reduction(+ : bad) reduction(max : maxOff)
     for (int64_t v = 0; v < nV; ++v)
         for (int e = 0; e < 8; ++e) {
             int16_t off = 0;
             if (e < (int)B.vCount[v]) {
                 const int64_t b = bitsOf(v, e);
                 off = (int16_t)(b - ref);
+                maxOff = std::max(maxOff, std::abs((int32_t)off));
                 const double w = fusedWeightFromOffset(ref, off);
                 int64_t back;
                 std::memcpy(&back, &w, 8);
@@ -795,12 +797,12 @@ bool packFusedWeights(FusedBlocks& B) {
             B.vW16[(size_t)v * 8 + e] = off;
         }
     if (bad != 0) { RawVec<int16_t>().swap(B.vW16); return false; }   // (cannot happen inside the spread; the decode is the proof, not the rule)
-    B.wRef = ref; B.packedW = 1;
+    B.wRef = ref; B.packedW = 1; B.maxWeightOffset = maxOff;
     return true;
 }
 
 bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
-    B.packedF = 0; B.nHfClasses = 0; B.fwRef = 0;
+    B.packedF = 0; B.nHfClasses = 0; B.fwRef = 0; B.maxFaceOffset = 0;
     for (int q = 0; q < 4; ++q) B.fhRef[q] = 0;
     RawVec<uint32_t>().swap(B.fW16);
     RawVec<uint8_t>().swap(B.fKC);
@@ -857,7 +859,8 @@ bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
     B.fW16.resize((size_t)nB * capF);
     B.fKC.resize((size_t)nB * capF);
     int64_t bad = 0;
-#pragma omp parallel for schedule(static) reduction(+ : bad)
+    int32_t maxOff = 0;
+#pragma omp parallel for schedule(static) reduction(+ : bad) reduction(max : maxOff)
     for (int64_t b = 0; b < nB; ++b) {
         const int32_t nF = B.hdr[4 * b + 3];
         for (int32_t i = 0; i < B.capF; ++i) {
@@ -870,6 +873,7 @@ bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
                 const uint8_t kind = s.fkind[f];
                 word = (uint32_t)(uint16_t)(int16_t)(bw - wRef) | (uint32_t)(uint16_t)(int16_t)(bh - hRef[cl]) << 16;
                 kc = (uint8_t)((kind & 3) | cl << 2);
+                maxOff = std::max(maxOff, std::max(std::abs((int32_t)(int16_t)(word & 0xffffu)), std::abs((int32_t)(int16_t)(word >> 16))));
                 // the decode, as the kernel does it
                 const double w = fusedWeightFromOffset(wRef, (int16_t)(word & 0xffffu)), h = fusedWeightFromOffset(hRef[kc >> 2], (int16_t)(word >> 16));
                 bad += bitsOf(w) != bw || bitsOf(h) != bh || (kc & 3) != kind;
@@ -883,7 +887,7 @@ bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
         RawVec<uint8_t>().swap(B.fKC);
         return false;
     }
-    B.fwRef = wRef; B.nHfClasses = nCl;
+    B.fwRef = wRef; B.nHfClasses = nCl; B.maxFaceOffset = maxOff;
     for (int q = 0; q < 4; ++q) B.fhRef[q] = hRef[q];
     B.packedF = 1;
     return true;

@@ -177,8 +177,11 @@ struct FusedBlocks {
     // rounding, so the bit patterns of ALL weights of the mesh lie within a few thousand of each other: where capPE == 8 and their spread
     // is <= 65 535, a weight is kept as the signed 16-bit offset of its pattern from wRef (the midpoint pattern) -- 16 B per vertex
     // instead of 64, and bits(w) = wRef + offset gives the double back exactly.  Vertex-major: a vertex's eight offsets are one aligned
-    // 16-B piece.  Entries beyond a vertex's count are 0.  Graded, jittered and unstructured meshes do not qualify and keep vW alone.
+    // 16-B piece.  Entries beyond a vertex's count are 0.  What excludes a mesh is the spread alone: graded and unstructured meshes and a
+    // jitter of the points beyond roughly 3e-12 of the cell size exceed it and keep vW alone; a smaller jitter moves the patterns by
+    // thousands and still packs, with offsets that use all 16 bits (tests/packed_wide_recipes.py).
     int32_t packedW = 0;      // 1: vW16 / wRef hold every weight of vW
+    int32_t maxWeightOffset = 0;   // the largest |offset| in vW16 (0 .. 32768; reporting only)
     int64_t wRef = 0;
     RawVec<int16_t> vW16;     // 8 x capV per block: vW16[(blk * capV + lv) * 8 + e]
     // PACKED FACE STREAMS (packFusedFaceStreams below; QGD_FUSED_PACKED_F=0: never; only where packedW == 1).  The linear weight w, hQGDf and
@@ -191,6 +194,7 @@ struct FusedBlocks {
     // 65 536), so they do not depend on the thread count; the references are the midpoint patterns, rounded up.
     int32_t packedF = 0;      // 1: fW16 / fKC / fwRef / fhRef hold w, hf and fkind of every computed face slot
     int32_t nHfClasses = 0;
+    int32_t maxFaceOffset = 0;     // the largest |offset| in fW16, over both halves of every word (0 .. 32768; reporting only)
     int64_t fwRef = 0, fhRef[4] = {0, 0, 0, 0};
     RawVec<uint32_t> fW16;    // capF per block
     RawVec<uint8_t> fKC;      // capF per block

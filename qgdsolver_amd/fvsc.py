@@ -78,7 +78,10 @@ class Device:
         return dict(blocks=int(a[0]), layerBlocks=int(a[1]), templates=int(a[2]), ldsBytes=int(a[3]), blockListBytes=int(a[4]),
                     templateBytes=int(a[5]), buildSeconds=a[6] / 1e3, brick=(b & 255, (b >> 8) & 255, (b >> 16) & 255),
                     packedWeights=bool((b >> 24) & 1),   # the vertex weights are 16-bit offsets from one pattern (QGD_FUSED_PACKED_W)
-                    packedFaces=bool((b >> 25) & 1))     # w, hQGDf and kind of the face slots block-major, 5 B per slot (QGD_FUSED_PACKED_F)
+                    packedFaces=bool((b >> 25) & 1),     # w, hQGDf and kind of the face slots block-major, 5 B per slot (QGD_FUSED_PACKED_F)
+                    # what the packed tables hold (0 where they were not built): classes of hQGDf, the largest |offset| of a vertex weight
+                    # and of a face word (w and hQGDf), each 0 .. 32768
+                    hfClasses=(b >> 26) & 7, maxWeightOffset=(b >> 29) & 0xffff, maxFaceOffset=(b >> 45) & 0xffff)
 
     def face_tiles(self):
         """how the internal faces go through the 3-D GaussVolPoint flux kernel (qgd_device_face_tiles)"""
