@@ -936,25 +936,17 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                 stage("face tiles (build + upload)");
                 FusedBlocks fb = buildFusedBlocks(s, false);   // (a mesh whose vertex weights pack keeps the 16-bit table alone)
                 stage("cell blocks of the fused step (build)");
-                // LDS per workgroup: RecA of every staged cell, RecB of the own + across-a-face cells, then vertex records + all coordinates,
-                // later overwritten by the fluxes (FusedBlocks::maxLds); then the parked face entries of the own cells
-                const int64_t ldsRec = fb.maxLds;   // the block that needs most; every block lays its records out by its own counts
-                const int64_t ldsPark = (ldsRec + 15) / 16 * 16;
-                const int64_t lds = (ldsPark + 6 * 128 * 4 + 255) / 256 * 256;
-                // (a mesh whose blocks come out small -- under 88 cells on average: every block costs a workgroup two face passes whatever it
-                // holds -- is better off with the three kernels: 5.0 against 4.4 ms per step on the 16 M-cell mesh of config 5 with 67-cell blocks)
                 int64_t owned = 0;
                 for (int64_t ci = 0; ci < s.nC; ++ci) owned += (s.ghost.empty() || s.ghost[ci] != 1) ? 1 : 0;
-                // what one workgroup may ask for without raising the kernel's dynamic-LDS attribute: the device's own figure (64 KB on gfx950;
-                // blocks of <= 32 cells are exempt from the builder's three-per-CU budget, so one fat polyhedral block could exceed it -- such
-                // a mesh keeps the three kernels instead of failing in its first step)
+                // what one workgroup may ask for without raising the kernel's dynamic-LDS attribute: the device's own figure (64 KB on gfx950)
                 hipDeviceProp_t prop;
                 HIP_CHECK(hipGetDeviceProperties(&prop, deviceId));
                 const int64_t ldsLimit = std::min<int64_t>((int64_t)prop.sharedMemPerBlock, 64 * 1024);
-                if (fb.nBlocks > 0 && (fusedMode == 2 || (int64_t)fb.nBlocks * 88 <= owned + 87) && fb.maxAll <= kFusedCapC && fb.maxTot <= kFusedCapTot &&
-                    fb.capV <= kFusedCapV && fb.capF <= kFusedCapF && fb.capPE <= 255 && lds <= ldsLimit) {
+                const FusedLaunchPlan plan = planFusedLaunch(fb, owned, ldsLimit, fusedMode == 2);   // (the rule and the LDS sizes: qgd_setup.hpp)
+                if (plan.use) {
                     v.fuBlocks = fb.nBlocks; v.fuLayerBlocks = fb.nLayerBlocks; v.fuCapC = fb.capC; v.fuCapV = fb.capV; v.fuCapF = fb.capF;
-                    v.fuCapE = fb.capE; v.fuLds = (int32_t)lds; v.fuLdsCell = (int32_t)(ldsPark / 8);
+                    v.fuCapE = fb.capE; v.fuLds = plan.lds; v.fuLdsCell = plan.ldsCell;
+                    v.fuLdsImpl = plan.ldsImpl; v.fuLdsCellImpl = plan.ldsCellImpl;   // (the implicitDiffusion branch's layout of the same blocks)
                     v.fuCapPE = fb.capPE; v.fuMaxTot = (uint16_t)fb.maxTot; v.fuMaxAll = (uint16_t)fb.maxAll; v.fuMaxV = (uint16_t)fb.maxV; v.fuMaxF = (uint16_t)fb.maxF;   // (all within the caps checked above)
                     d->fusedFacesComputed = fb.facesComputed; d->fusedCellsStaged = fb.cellsStaged; d->fusedCellsStagedFull = fb.cellsStagedFull;
                     d->fusedVertsStaged = fb.vertsStaged;
@@ -974,12 +966,7 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                     }
                     v.fuHdr = reinterpret_cast<const int4*>(up(fb.hdr)); v.fuCells = up(fb.cells); v.fuVerts = up(fb.verts);
                     v.fuFaceLabel = up(fb.faceLabel); v.fuFacePos = up(fb.facePos); v.fuNEntry = up(fb.nEntry); v.fuEntry = up(fb.entry);
-                    {   // the implicitDiffusion branch's layout of the same blocks (qgd_kernels.hip fusedFaceCellKernel<..., IMPL>)
-                        const int64_t parkI = ((int64_t)fb.maxLdsImpl + 15) / 16 * 16, ldsI = (parkI + 6 * 128 * 4 + 255) / 256 * 256;
-                        v.fuLdsImpl = ldsI <= ldsLimit ? (int32_t)ldsI : 0;   // (on a box: the explicit step's figure, three blocks per CU)
-                        v.fuLdsCellImpl = (int32_t)(parkI / 8);
-                    }
-                    d->fusedInfo[0] = fb.nBlocks; d->fusedInfo[1] = fb.nLayerBlocks; d->fusedInfo[2] = fb.nTemplates; d->fusedInfo[3] = lds;
+                    d->fusedInfo[0] = fb.nBlocks; d->fusedInfo[1] = fb.nLayerBlocks; d->fusedInfo[2] = fb.nTemplates; d->fusedInfo[3] = plan.lds;
                     // bytes a block streams per step out of its own lists / of its template's
                     d->fusedInfo[4] = 32 + 4 * (int64_t)fb.capC + 4 * (int64_t)fb.capV + 4 * (int64_t)fb.capF + fb.capV + 128 + (fb.packedW ? 2 : 8) * (int64_t)fb.capPE * fb.capV +
                                       (fb.packedF ? 5 * (int64_t)fb.capF : 0);

@@ -702,6 +702,7 @@ FaceTiles buildFaceTiles(const StaticData& s, int32_t fb) {
 }
 
 // ---- cell blocks of the fused face + cell kernel (qgd_setup.hpp FusedBlocks) ---------------------------------------------------------
+// buildFusedBlocks, at the end of this section, is the list of the stages; each stage is a function or a small struct above it.
 namespace {
 inline uint64_t spread21(uint64_t x) {   // 21 bits -> every third bit
     x &= 0x1fffffull;
@@ -712,6 +713,7 @@ inline uint64_t spread21(uint64_t x) {   // 21 bits -> every third bit
     x = (x | x << 2) & 0x1249249249249249ull;
     return x;
 }
+inline int64_t bitsOf(double v) { int64_t b; std::memcpy(&b, &v, 8); return b; }
 // label -> position among the few hundred labels of one block: open addressing on a stamped table (no allocation, no clearing per block)
 struct SmallMap {
     static constexpr uint32_t N = 4096;
@@ -729,9 +731,12 @@ struct SmallMap {
     void put(int32_t k, int32_t v) { const uint32_t h = slot(k); stamp[h] = gen; key[h] = k; val[h] = v; }
     int32_t at(int32_t k) const { return val[slot(k)]; }
 };
+using Hash = std::array<uint64_t, 2>;
+using Range = std::pair<int64_t, int64_t>;                       // [first, second) of the sorted cells
+using SortedCells = std::vector<std::pair<uint64_t, int32_t>>;   // the owned cells as {key, label}, ascending
 struct OneBlock {
     std::vector<int32_t> cells, verts, face, entry;   // entry: row-major here (own cell x capE), transposed at the end
-    std::vector<int32_t> faces, others, vs;           // scratch of tryBlock (kept between blocks: no allocation per block)
+    std::vector<int32_t> faces, others, vs;           // scratch of BlockMaker::make (kept between blocks: no allocation per block)
     std::vector<uint8_t> vCount;                      // per staged vertex
     std::vector<uint16_t> vPos;                       // row-major here (vertex x maxPE)
     std::vector<double> vW;
@@ -740,7 +745,7 @@ struct OneBlock {
     int32_t nOwn = 0, maxE = 0;
     // 128-bit fingerprint of the block's local topology (counts, per-face positions, face entries, per-vertex cell positions): what two
     // blocks must share to share a template
-    std::array<uint64_t, 2> topoHash() const {
+    Hash topoHash() const {
         uint64_t h1 = 0x9e3779b97f4a7c15ull, h2 = 0xc2b2ae3d27d4eb4full;
         auto mix = [&](uint64_t x) {
             h1 = (h1 ^ x) * 0x100000001b3ull; h1 ^= h1 >> 29;
@@ -757,6 +762,74 @@ struct OneBlock {
 #endif
     }
 };
+
+// ---- packing: what packFusedWeights and packFusedFaceStreams share ----
+// The spread of a set of bit patterns (min and max are exact: the same whatever the threads) and the pattern its members are offsets from.
+struct PatternSpan {
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    void take(int64_t b) { lo = std::min(lo, b); hi = std::max(hi, b); }
+    void merge(const PatternSpan& o) { lo = std::min(lo, o.lo); hi = std::max(hi, o.hi); }
+    // some value at all; no negative one (its pattern is no neighbour of a positive one's); every offset fits 16 bits
+    bool packs() const { return lo <= hi && lo >= 0 && hi - lo <= 65535; }
+    // the midpoint, rounded up: offsets lo - ref >= -32768 and hi - ref <= 32767 for every spread up to 65 535
+    int64_t ref() const { return lo + (hi - lo + 1) / 2; }
+};
+#pragma omp declare reduction(merge : PatternSpan : omp_out.merge(omp_in))
+// A pattern as its 16-bit offset from ref, decoded once as the kernel does it and compared: the decode is the proof, not the rule (bad
+// stays 0 inside a spread that packs).
+struct OffsetCheck {
+    int64_t bad = 0;
+    int32_t maxOff = 0;
+    int16_t encode(int64_t bits, int64_t ref) {
+        const int16_t off = (int16_t)(bits - ref);
+        maxOff = std::max(maxOff, std::abs((int32_t)off));
+        bad += bitsOf(fusedWeightFromOffset(ref, off)) != bits;
+        return off;
+    }
+    void merge(const OffsetCheck& o) { bad += o.bad; maxOff = std::max(maxOff, o.maxOff); }
+};
+#pragma omp declare reduction(merge : OffsetCheck : omp_out.merge(omp_in))
+// The distinct patterns of a stream gathered in one walk: a bit per pattern in the aligned windows of 65 536 patterns they touch.  Four
+// classes of 65 536 patterns touch at most eight windows, so a ninth says that the stream does not pack and ends the gathering.  A set of
+// bits: the same whatever the threads and the order of merging.
+struct PatternSet {
+    static constexpr int kWindows = 8;
+    static constexpr size_t kWords = 65536 / 64;
+    int n = 0;
+    bool over = false;
+    int64_t window[kWindows] = {};
+    std::vector<uint64_t> bits;   // kWords per window
+    int slotOf(int64_t w) {       // -1: a ninth window
+        for (int q = 0; q < n; ++q) if (window[q] == w) return q;
+        if (n == kWindows) { over = true; return -1; }
+        window[n] = w;
+        bits.resize((size_t)(n + 1) * kWords, 0);
+        return n++;
+    }
+    void take(int64_t b) {
+        const int q = over ? -1 : slotOf(b >> 16);
+        if (q >= 0) bits[(size_t)q * kWords + (size_t)((b & 0xffff) >> 6)] |= 1ull << (b & 63);
+    }
+    void merge(const PatternSet& o) {
+        over = over || o.over;
+        for (int p = 0; p < o.n && !over; ++p) {
+            const int q = slotOf(o.window[p]);
+            for (size_t k = 0; q >= 0 && k < kWords; ++k) bits[(size_t)q * kWords + k] |= o.bits[(size_t)p * kWords + k];
+        }
+    }
+    std::vector<int64_t> ascending() const {
+        int order[kWindows];
+        for (int q = 0; q < n; ++q) order[q] = q;
+        std::sort(order, order + n, [&](int a, int b) { return window[a] < window[b]; });
+        std::vector<int64_t> out;
+        for (int i = 0; i < n; ++i)
+            for (size_t k = 0; k < kWords; ++k)
+                for (uint64_t word = bits[(size_t)order[i] * kWords + k]; word != 0; word &= word - 1)
+                    out.push_back(window[order[i]] * 65536 + (int64_t)(k * 64) + __builtin_ctzll(word));
+        return out;
+    }
+};
+#pragma omp declare reduction(merge : PatternSet : omp_out.merge(omp_in))
 }  // namespace
 
 bool packFusedWeights(FusedBlocks& B) {
@@ -765,39 +838,20 @@ bool packFusedWeights(FusedBlocks& B) {
     if (B.capPE != 8 || B.nBlocks <= 0) return false;
     const int64_t nV = (int64_t)B.nBlocks * B.capV;
     const size_t capV = (size_t)B.capV;
-    auto bitsOf = [&](int64_t v, int e) {
-        int64_t b;
-        std::memcpy(&b, &B.vW[((size_t)(v / B.capV) * 8 + e) * capV + (size_t)(v % B.capV)], 8);
-        return b;
-    };
-    // the spread of the patterns over every weight in use (min and max are exact: the same whatever the threads)
-    int64_t lo = INT64_MAX, hi = INT64_MIN;
-#pragma omp parallel for schedule(static) reduction(min : lo) reduction(max : hi)
+    auto pattern = [&](int64_t v, int e) { return bitsOf(B.vW[((size_t)(v / B.capV) * 8 + e) * capV + (size_t)(v % B.capV)]); };
+    PatternSpan span;   // over every weight in use
+#pragma omp parallel for schedule(static) reduction(merge : span)
     for (int64_t v = 0; v < nV; ++v)
-        for (int e = 0; e < (int)B.vCount[v]; ++e) { const int64_t b = bitsOf(v, e); lo = std::min(lo, b); hi = std::max(hi, b); }
-    if (lo > hi || lo < 0 || hi - lo > 65535) return false;   // no weight at all; a negative weight (its pattern is no neighbour of a positive one's)
-    // the midpoint, rounded up: offsets lo - ref >= -32768 and hi - ref <= 32767 for every spread up to 65 535
-    const int64_t ref = lo + (hi - lo + 1) / 2;
+        for (int e = 0; e < (int)B.vCount[v]; ++e) span.take(pattern(v, e));
+    if (!span.packs()) return false;
+    const int64_t ref = span.ref();
     B.vW16.resize((size_t)nV * 8);
-    int64_t bad = 0;
-    int32_t maxOff = 0;
-#pragma omp parallel for schedule(static) reduction(+ : bad) reduction(max : maxOff)
+    OffsetCheck check;
+#pragma omp parallel for schedule(static) reduction(merge : check)
     for (int64_t v = 0; v < nV; ++v)
-        for (int e = 0; e < 8; ++e) {
-            int16_t off = 0;
-            if (e < (int)B.vCount[v]) {
-                const int64_t b = bitsOf(v, e);
-                off = (int16_t)(b - ref);
-                maxOff = std::max(maxOff, std::abs((int32_t)off));
-                const double w = fusedWeightFromOffset(ref, off);
-                int64_t back;
-                std::memcpy(&back, &w, 8);
-                bad += back != b;
-            }
-            B.vW16[(size_t)v * 8 + e] = off;
-        }
-    if (bad != 0) { RawVec<int16_t>().swap(B.vW16); return false; }   // (cannot happen inside the spread; the decode is the proof, not the rule)
-    B.wRef = ref; B.packedW = 1; B.maxWeightOffset = maxOff;
+        for (int e = 0; e < 8; ++e) B.vW16[(size_t)v * 8 + e] = e < (int)B.vCount[v] ? check.encode(pattern(v, e), ref) : (int16_t)0;
+    if (check.bad != 0) { RawVec<int16_t>().swap(B.vW16); return false; }
+    B.wRef = ref; B.packedW = 1; B.maxWeightOffset = check.maxOff;
     return true;
 }
 
@@ -809,58 +863,36 @@ bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
     if (B.packedW != 1 || B.nBlocks <= 0 || B.capF <= 0) return false;
     const int64_t nB = B.nBlocks;
     const size_t capF = (size_t)B.capF;
-    auto bitsOf = [](const double& v) { int64_t b; std::memcpy(&b, &v, 8); return b; };
-    // the spreads over every computed face slot (min and max are exact: the same whatever the threads)
-    int64_t wLo = INT64_MAX, wHi = INT64_MIN, hLo = INT64_MAX, hHi = INT64_MIN;
-#pragma omp parallel for schedule(static) reduction(min : wLo, hLo) reduction(max : wHi, hHi)
+    // one walk over every computed face slot: the spread of w and the distinct patterns of hf
+    PatternSpan wSpan;
+    PatternSet hSet;
+#pragma omp parallel for schedule(static) reduction(merge : wSpan) reduction(merge : hSet)
     for (int64_t b = 0; b < nB; ++b)
         for (int32_t i = 0; i < B.hdr[4 * b + 3]; ++i) {
             const int32_t f = B.faceLabel[(size_t)b * capF + i];
-            const int64_t bw = bitsOf(s.w[f]), bh = bitsOf(s.hf[f]);
-            wLo = std::min(wLo, bw); wHi = std::max(wHi, bw); hLo = std::min(hLo, bh); hHi = std::max(hHi, bh);
+            wSpan.take(bitsOf(s.w[f]));
+            hSet.take(bitsOf(s.hf[f]));
         }
-    if (wLo > wHi || wLo < 0 || hLo < 0 || wHi - wLo > 65535) return false;   // no face at all; a negative value; w too wide
+    if (!wSpan.packs() || hSet.over) return false;   // no face at all; a negative value; w too wide; hf in more than four classes
     // the classes of hf: the sorted patterns cut greedily -- class c starts at the smallest pattern beyond the 65 536 of class c - 1
-    int64_t start[4] = {hLo, 0, 0, 0}, top[4] = {hHi, 0, 0, 0};
-    int nCl = 1;
-    while (hHi - start[nCl - 1] > 65535) {
-        if (nCl == 4) return false;
-        const int64_t bound = start[nCl - 1] + 65535;
-        int64_t next = INT64_MAX;
-#pragma omp parallel for schedule(static) reduction(min : next)
-        for (int64_t b = 0; b < nB; ++b)
-            for (int32_t i = 0; i < B.hdr[4 * b + 3]; ++i) {
-                const int64_t bh = bitsOf(s.hf[B.faceLabel[(size_t)b * capF + i]]);
-                if (bh > bound) next = std::min(next, bh);
-            }
-        start[nCl++] = next;
-    }
-    auto classOf = [&](int64_t bh) { int c = 0; while (c + 1 < nCl && bh >= start[c + 1]) ++c; return c; };
-    if (nCl > 1) {   // (one class: its top is the maximum found above)
-        for (int q = 0; q < 4; ++q) top[q] = INT64_MIN;
-#pragma omp parallel
-        {
-            int64_t mine[4] = {INT64_MIN, INT64_MIN, INT64_MIN, INT64_MIN};
-#pragma omp for schedule(static) nowait
-            for (int64_t b = 0; b < nB; ++b)
-                for (int32_t i = 0; i < B.hdr[4 * b + 3]; ++i) {
-                    const int64_t bh = bitsOf(s.hf[B.faceLabel[(size_t)b * capF + i]]);
-                    const int cl = classOf(bh);
-                    mine[cl] = std::max(mine[cl], bh);
-                }
-#pragma omp critical(qgdPackFaceTop)
-            for (int q = 0; q < 4; ++q) top[q] = std::max(top[q], mine[q]);
+    PatternSpan cls[4];
+    int nCl = 0;
+    for (const int64_t p : hSet.ascending()) {
+        if (p < 0) return false;
+        if (nCl == 0 || p - cls[nCl - 1].lo > 65535) {
+            if (nCl == 4) return false;
+            ++nCl;
         }
+        cls[nCl - 1].take(p);
     }
-    // the midpoints, rounded up: every offset lies in [-32768, 32767] for a spread up to 65 535
-    const int64_t wRef = wLo + (wHi - wLo + 1) / 2;
+    auto classOf = [&](int64_t bh) { int c = 0; while (c + 1 < nCl && bh >= cls[c + 1].lo) ++c; return c; };
+    const int64_t wRef = wSpan.ref();
     int64_t hRef[4] = {0, 0, 0, 0};
-    for (int q = 0; q < nCl; ++q) hRef[q] = start[q] + (top[q] - start[q] + 1) / 2;
+    for (int q = 0; q < nCl; ++q) hRef[q] = cls[q].ref();
     B.fW16.resize((size_t)nB * capF);
     B.fKC.resize((size_t)nB * capF);
-    int64_t bad = 0;
-    int32_t maxOff = 0;
-#pragma omp parallel for schedule(static) reduction(+ : bad) reduction(max : maxOff)
+    OffsetCheck check;
+#pragma omp parallel for schedule(static) reduction(merge : check)
     for (int64_t b = 0; b < nB; ++b) {
         const int32_t nF = B.hdr[4 * b + 3];
         for (int32_t i = 0; i < B.capF; ++i) {
@@ -868,158 +900,200 @@ bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
             uint8_t kc = 0;
             if (i < nF) {
                 const int32_t f = B.faceLabel[(size_t)b * capF + i];
-                const int64_t bw = bitsOf(s.w[f]), bh = bitsOf(s.hf[f]);
+                const int64_t bh = bitsOf(s.hf[f]);
                 const int cl = classOf(bh);
-                const uint8_t kind = s.fkind[f];
-                word = (uint32_t)(uint16_t)(int16_t)(bw - wRef) | (uint32_t)(uint16_t)(int16_t)(bh - hRef[cl]) << 16;
-                kc = (uint8_t)((kind & 3) | cl << 2);
-                maxOff = std::max(maxOff, std::max(std::abs((int32_t)(int16_t)(word & 0xffffu)), std::abs((int32_t)(int16_t)(word >> 16))));
-                // the decode, as the kernel does it
-                const double w = fusedWeightFromOffset(wRef, (int16_t)(word & 0xffffu)), h = fusedWeightFromOffset(hRef[kc >> 2], (int16_t)(word >> 16));
-                bad += bitsOf(w) != bw || bitsOf(h) != bh || (kc & 3) != kind;
+                kc = (uint8_t)((s.fkind[f] & 3) | cl << 2);
+                // (hf decoded through the class the byte names, as the kernel does it)
+                word = (uint32_t)(uint16_t)check.encode(bitsOf(s.w[f]), wRef) | (uint32_t)(uint16_t)check.encode(bh, hRef[kc >> 2]) << 16;
+                check.bad += (kc & 3) != s.fkind[f];
             }
             B.fW16[(size_t)b * capF + i] = word;
             B.fKC[(size_t)b * capF + i] = kc;
         }
     }
-    if (bad != 0) {   // (cannot happen inside the spreads; the decode is the proof, not the rule)
+    if (check.bad != 0) {
         RawVec<uint32_t>().swap(B.fW16);
         RawVec<uint8_t>().swap(B.fKC);
         return false;
     }
-    B.fwRef = wRef; B.nHfClasses = nCl; B.maxFaceOffset = maxOff;
+    B.fwRef = wRef; B.nHfClasses = nCl; B.maxFaceOffset = check.maxOff;
     for (int q = 0; q < 4; ++q) B.fhRef[q] = hRef[q];
     B.packedF = 1;
     return true;
 }
 
-FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
-    FusedBlocks B;
-    const auto tStart = std::chrono::steady_clock::now();
-    const int64_t nC = s.nC, nIF = s.nIF;
-    if (nC == 0 || nIF == 0 || s.nGeomD != 3) return B;
-    if (3 * (int64_t)s.nC > INT32_MAX || 3 * (int64_t)s.nP > INT32_MAX) return B;
-    // lattice spacing per axis: the mean distance of the two cell centres across the faces that look along that axis (dx, dy, dz on a box,
-    // whatever its cells' aspect ratio); the mean cell size where an axis has no such faces
-    double vol = 0.0;
-    for (int64_t c = 0; c < nC; ++c) vol += s.V[c];
-    double h[3] = {std::cbrt(vol / (double)nC), 0.0, 0.0};
-    h[1] = h[2] = h[0];
-    {
-        double sum[3] = {0, 0, 0};
-        int64_t cnt[3] = {0, 0, 0};
-        for (int64_t f = 0; f < nIF; ++f) {
-            const double a[3] = {std::fabs(s.Sf[0][f]), std::fabs(s.Sf[1][f]), std::fabs(s.Sf[2][f])};
-            const int d = a[0] >= a[1] ? (a[0] >= a[2] ? 0 : 2) : (a[1] >= a[2] ? 1 : 2);
-            sum[d] += std::fabs(s.Cc[3 * (size_t)s.nei[f] + d] - s.Cc[3 * (size_t)s.own[f] + d]);
-            ++cnt[d];
-        }
-        for (int d = 0; d < 3; ++d) if (cnt[d] > 0 && sum[d] > 0.0) h[d] = sum[d] / (double)cnt[d];
-    }
-    // a shard: its ghost cells belong to no block (the halo exchange writes them).  The lattice is anchored at the OWNED cells -- a ghost
-    // plane in front of them must not shift every brick off the shard's own planes (round 5 took the minimum over all cells: a slab between
-    // two cuts started at lattice index 1 and averaged 106 cells per block instead of 128).
-    std::vector<int32_t> ownedCells;
-    ownedCells.reserve((size_t)nC);
-    for (int64_t c = 0; c < nC; ++c) {
-        const int role = s.ghost.empty() ? 0 : s.ghost[c];
-        if (role == 1) continue;
-        ownedCells.push_back((int32_t)c);
-    }
-    const int64_t nOwned = (int64_t)ownedCells.size();
-    if (nOwned == 0) return B;
-    double lo[3] = {1e300, 1e300, 1e300};
-    for (int64_t i = 0; i < nOwned; ++i)
-        for (int d = 0; d < 3; ++d) lo[d] = std::min(lo[d], s.Cc[3 * (size_t)ownedCells[i] + d]);
-    auto latticeOf = [&](int32_t c, int d) {
+namespace {
+// ---- the builder's switches, read once ----
+struct BuilderOptions {
+    int64_t brick[3] = {0, 0, 0};   // QGD_FUSED_BRICK=bx,by,bz forces a brick (probes); 0: the builder chooses
+    bool templates = true;          // QGD_FUSED_TEMPLATES=0: one template per block
+    bool packWeights = true;        // QGD_FUSED_PACKED_W=0: the vertex weights stay doubles
+    bool packFaces = true;          // QGD_FUSED_PACKED_F=0: the face streams stay where they are (they pack only where the weights did)
+};
+// the counts of a full brick inside a lattice: own cells, + across a face, + around its edges and corners, vertices, internal faces
+struct BrickCounts { int64_t own, nAll, tot, nV, nF; };
+constexpr BrickCounts brickCounts(int64_t bx, int64_t by, int64_t bz) {
+    const int64_t own = bx * by * bz, surf = bx * by + by * bz + bx * bz;
+    return {own, own + 2 * surf, own + 2 * surf + 4 * (bx + by + bz) + 8, (bx + 1) * (by + 1) * (bz + 1), 3 * own + surf};
+}
+// a brick whose full block fits the caps and the LDS budget of three blocks per CU
+constexpr bool brickFits(int64_t bx, int64_t by, int64_t bz) {
+    const BrickCounts n = brickCounts(bx, by, bz);
+    return n.own <= kFusedCells && n.nAll <= kFusedCapC && n.tot <= kFusedCapTot && n.nV <= kFusedCapV && n.nF <= kFusedCapF &&
+           fusedBlockLds((int32_t)n.tot, (int32_t)n.nAll, (int32_t)n.nV, (int32_t)n.nF) <= kFusedLdsTarget;
+}
+static_assert(brickCounts(8, 4, 4).tot == 360 && brickCounts(8, 4, 4).nAll == 288 && brickCounts(8, 4, 4).nV == 225 && brickCounts(8, 4, 4).nF == 464 &&
+              brickFits(8, 4, 4), "kFusedLdsTarget is what an 8 x 4 x 4 brick needs");
+bool switchedOff(const char* name) { const char* e = std::getenv(name); return e && std::atoi(e) == 0; }
+BuilderOptions readBuilderOptions() {
+    BuilderOptions opt;
+    int b[3] = {0, 0, 0};
+    const char* e = std::getenv("QGD_FUSED_BRICK");
+    if (e && std::sscanf(e, "%d,%d,%d", &b[0], &b[1], &b[2]) == 3 && b[0] >= 1 && b[0] <= 16 && b[1] >= 1 && b[1] <= 16 && b[2] >= 1 && b[2] <= 16 &&
+        brickFits(b[0], b[1], b[2]))   // (a forced brick that does not fit is ignored)
+        for (int d = 0; d < 3; ++d) opt.brick[d] = b[d];
+    opt.templates = !switchedOff("QGD_FUSED_TEMPLATES");
+    opt.packWeights = !switchedOff("QGD_FUSED_PACKED_W");
+    opt.packFaces = !switchedOff("QGD_FUSED_PACKED_F");
+    return opt;
+}
+
+// ---- the lattice of the owned cells and the bricks it is cut into ----
+// Plain data: what places a cell in its brick, for the stages below and for whoever addresses a brick's records by arithmetic later.
+struct BrickLattice {
+    double h[3] = {0, 0, 0};         // spacing per axis
+    double lo[3] = {0, 0, 0};        // origin: the least centre coordinate of the owned cells
+    int64_t n[3] = {1, 1, 1};        // extents in lattice cells
+    int64_t brick[3] = {8, 4, 4};    // a brick is AT MOST this many lattice cells per axis
+    int lbits[3] = {0, 0, 0};        // bits of the position inside a brick, per axis
+    int lshift = 0;                  // ... of all three: a cell's key above them is its brick's Morton code
+    std::vector<int32_t> segOf[3];   // per axis: the segment (brick coordinate) of a lattice index
+    std::vector<int32_t> segLo[3];   // per axis: the lattice index at which each segment starts (+ the end)
+    int64_t indexOf(const StaticData& s, int32_t c, int d) const {
         return (int64_t)std::min(2097151.0, std::max(0.0, std::floor((s.Cc[3 * (size_t)c + d] - lo[d]) / h[d] + 0.25)));
-    };
-    // Bricks of AT MOST 8 x 4 x 4 lattice cells whose extents divide the owned lattice evenly: an axis of n lattice cells is cut into
-    // ceil(n / b) segments of floor / ceil(n / segments) cells (400 -> 50 x 8; a 50-plane slab -> 13 segments of 3 or 4 planes: 123 cells per
-    // brick instead of twelve full layers and a flat two-plane rest).  Key = Morton code of the brick coordinates above the position inside
-    // the brick, so that bricks which are neighbours in space are neighbours in the launch order, as before.
-    int64_t nLat[3] = {1, 1, 1};
-    for (int64_t i = 0; i < nOwned; ++i)
-        for (int d = 0; d < 3; ++d) nLat[d] = std::max(nLat[d], latticeOf(ownedCells[i], d) + 1);
-    // The brick is 8 x 4 x 4 unless another shape fills its blocks markedly better on this lattice (a 50^3 box: 7 x 13 x 13 bricks of 106 cells,
-    // or 10^3 cubes of 5^3 = 125): among the shapes of at most 128 cells whose full brick fits the LDS budget of three blocks per CU, the one
-    // with the most cells per brick wins if it beats 8 x 4 x 4 by more than 5 %.  QGD_FUSED_BRICK=bx,by,bz forces one (probes).
-    int64_t kBrick[3] = {8, 4, 4};
-    {
-        auto fits = [](int64_t bx, int64_t by, int64_t bz) {
-            const int64_t own = bx * by * bz, surf = bx * by + by * bz + bx * bz;
-            const int64_t nAll = own + 2 * surf, tot = nAll + 4 * (bx + by + bz) + 8, nV = (bx + 1) * (by + 1) * (bz + 1), nF = 3 * own + surf;
-            return own <= kFusedCells && nAll <= kFusedCapC && tot <= kFusedCapTot && nV <= kFusedCapV && nF <= kFusedCapF &&
-                   48 * tot + 32 * nAll + std::max(72 * nV + 24 * nAll, 40 * nF) <= (int64_t)kFusedLdsTarget;
-        };
-        auto meanCells = [&](int64_t bx, int64_t by, int64_t bz) {
-            const int64_t b[3] = {bx, by, bz};
-            double m = 1.0;
-            for (int d = 0; d < 3; ++d) m *= (double)nLat[d] / (double)((nLat[d] + b[d] - 1) / b[d]);
-            return m;
-        };
-        int forced[3] = {0, 0, 0};
-        const char* e = std::getenv("QGD_FUSED_BRICK");
-        if (e && std::sscanf(e, "%d,%d,%d", &forced[0], &forced[1], &forced[2]) == 3 && forced[0] >= 1 && forced[0] <= 16 && forced[1] >= 1 &&
-            forced[1] <= 16 && forced[2] >= 1 && forced[2] <= 16 && fits(forced[0], forced[1], forced[2])) {
-            for (int d = 0; d < 3; ++d) kBrick[d] = forced[d];
-        } else {
-            double best = meanCells(8, 4, 4) * 1.05;
-            for (int64_t bx = 3; bx <= 8; ++bx)
-                for (int64_t by = 3; by <= 8; ++by)
-                    for (int64_t bz = 3; bz <= 8; ++bz) {
-                        if (!fits(bx, by, bz)) continue;
-                        const double m = meanCells(bx, by, bz);
-                        if (m > best) { best = m; kBrick[0] = bx; kBrick[1] = by; kBrick[2] = bz; }
-                    }
-        }
     }
-    int lbits[3];   // bits of the position inside a brick, per axis
-    for (int d = 0; d < 3; ++d) { lbits[d] = 0; while ((1ll << lbits[d]) < kBrick[d]) ++lbits[d]; }
-    const int lshift = lbits[0] + lbits[1] + lbits[2];
-    std::vector<int32_t> segOf[3], segLo[3];
-    for (int d = 0; d < 3; ++d) {
-        const int64_t n = nLat[d], ns = (n + kBrick[d] - 1) / kBrick[d];
-        segOf[d].resize((size_t)n); segLo[d].resize((size_t)ns + 1);
-        for (int64_t i = 0; i <= ns; ++i) segLo[d][(size_t)i] = (int32_t)(i * n / ns);
-        for (int64_t i = 0; i < ns; ++i)
-            for (int32_t q = segLo[d][(size_t)i]; q < segLo[d][(size_t)i + 1]; ++q) segOf[d][(size_t)q] = (int32_t)i;
-    }
-    std::vector<std::pair<uint64_t, int32_t>> key((size_t)nOwned);
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < nOwned; ++i) {
-        const int32_t c = ownedCells[i];
+    // Morton code of the brick coordinates above the position inside the brick, so that bricks which are neighbours in space are
+    // neighbours in the launch order
+    uint64_t keyOf(const StaticData& s, int32_t c) const {
         uint64_t b[3], l[3];
         for (int d = 0; d < 3; ++d) {
-            const int64_t q = latticeOf(c, d);
+            const int64_t q = indexOf(s, c, d);
             b[d] = (uint64_t)segOf[d][(size_t)q];
             l[d] = (uint64_t)(q - segLo[d][b[d]]);
         }
-        key[i] = {(spread21(b[0]) | spread21(b[1]) << 1 | spread21(b[2]) << 2) << lshift | l[0] | l[1] << lbits[0] | l[2] << (lbits[0] + lbits[1]), c};
+        return (spread21(b[0]) | spread21(b[1]) << 1 | spread21(b[2]) << 2) << lshift | l[0] | l[1] << lbits[0] | l[2] << (lbits[0] + lbits[1]);
     }
-    std::vector<int32_t>().swap(ownedCells);
-    // (sorted in runs, then merged: keeps the host peak at one copy and uses the cores)
-    {
-        const int nRuns = 16;
-        std::vector<int64_t> cut(nRuns + 1);
-        for (int r = 0; r <= nRuns; ++r) cut[r] = nOwned * r / nRuns;
-#pragma omp parallel for schedule(dynamic, 1)
-        for (int r = 0; r < nRuns; ++r) std::sort(key.begin() + cut[r], key.begin() + cut[r + 1]);
-        for (int width = 1; width < nRuns; width *= 2) {
-#pragma omp parallel for schedule(dynamic, 1)
-            for (int r = 0; r < nRuns; r += 2 * width)
-                if (r + width < nRuns)
-                    std::inplace_merge(key.begin() + cut[r], key.begin() + cut[r + width], key.begin() + cut[std::min(nRuns, r + 2 * width)]);
-        }
+};
+// a shard: its ghost cells belong to no block (the halo exchange writes them)
+std::vector<int32_t> ownedCellsOf(const StaticData& s) {
+    std::vector<int32_t> owned;
+    owned.reserve((size_t)s.nC);
+    for (int64_t c = 0; c < s.nC; ++c)
+        if (s.ghost.empty() || s.ghost[c] != 1) owned.push_back((int32_t)c);
+    return owned;
+}
+BrickLattice measureLattice(const StaticData& s, const std::vector<int32_t>& owned) {
+    BrickLattice L;
+    // lattice spacing per axis: the mean distance of the two cell centres across the faces that look along that axis (dx, dy, dz on a box,
+    // whatever its cells' aspect ratio); the mean cell size where an axis has no such faces
+    double vol = 0.0;
+    for (int64_t c = 0; c < s.nC; ++c) vol += s.V[c];
+    L.h[0] = L.h[1] = L.h[2] = std::cbrt(vol / (double)s.nC);
+    double sum[3] = {0, 0, 0};
+    int64_t cnt[3] = {0, 0, 0};
+    for (int64_t f = 0; f < s.nIF; ++f) {
+        const double a[3] = {std::fabs(s.Sf[0][f]), std::fabs(s.Sf[1][f]), std::fabs(s.Sf[2][f])};
+        const int d = a[0] >= a[1] ? (a[0] >= a[2] ? 0 : 2) : (a[1] >= a[2] ? 1 : 2);
+        sum[d] += std::fabs(s.Cc[3 * (size_t)s.nei[f] + d] - s.Cc[3 * (size_t)s.own[f] + d]);
+        ++cnt[d];
     }
-    auto entriesOf = [&](int32_t c, int32_t* out) {   // ascending face label, ~f when the cell is the neighbour
+    for (int d = 0; d < 3; ++d) if (cnt[d] > 0 && sum[d] > 0.0) L.h[d] = sum[d] / (double)cnt[d];
+    // The lattice is anchored at the OWNED cells -- a ghost plane in front of them must not shift every brick off the shard's own planes
+    // (round 5 took the minimum over all cells: a slab between two cuts started at lattice index 1 and averaged 106 cells per block instead
+    // of 128).
+    for (int d = 0; d < 3; ++d) L.lo[d] = 1e300;
+    for (const int32_t c : owned)
+        for (int d = 0; d < 3; ++d) L.lo[d] = std::min(L.lo[d], s.Cc[3 * (size_t)c + d]);
+    for (const int32_t c : owned)
+        for (int d = 0; d < 3; ++d) L.n[d] = std::max(L.n[d], L.indexOf(s, c, d) + 1);
+    return L;
+}
+// The brick is 8 x 4 x 4 unless another shape fills its blocks markedly better on this lattice (a 50^3 box: 7 x 13 x 13 bricks of 106 cells,
+// or 10^3 cubes of 5^3 = 125): among the shapes of at most 128 cells whose full brick fits the LDS budget of three blocks per CU, the one
+// with the most cells per brick wins if it beats 8 x 4 x 4 by more than 5 %.
+void chooseBrick(BrickLattice& L, const BuilderOptions& opt) {
+    if (opt.brick[0] > 0) {
+        for (int d = 0; d < 3; ++d) L.brick[d] = opt.brick[d];
+        return;
+    }
+    auto meanCells = [&](int64_t bx, int64_t by, int64_t bz) {
+        const int64_t b[3] = {bx, by, bz};
+        double m = 1.0;
+        for (int d = 0; d < 3; ++d) m *= (double)L.n[d] / (double)((L.n[d] + b[d] - 1) / b[d]);
+        return m;
+    };
+    double best = meanCells(8, 4, 4) * 1.05;
+    for (int64_t bx = 3; bx <= 8; ++bx)
+        for (int64_t by = 3; by <= 8; ++by)
+            for (int64_t bz = 3; bz <= 8; ++bz) {
+                if (!brickFits(bx, by, bz)) continue;
+                const double m = meanCells(bx, by, bz);
+                if (m > best) { best = m; L.brick[0] = bx; L.brick[1] = by; L.brick[2] = bz; }
+            }
+}
+// Bricks of AT MOST brick[] lattice cells whose extents divide the owned lattice evenly: an axis of n lattice cells is cut into
+// ceil(n / b) segments of floor / ceil(n / segments) cells (400 -> 50 x 8; a 50-plane slab -> 13 segments of 3 or 4 planes: 123 cells per
+// brick instead of twelve full layers and a flat two-plane rest).
+void cutSegments(BrickLattice& L) {
+    for (int d = 0; d < 3; ++d) {
+        while ((1ll << L.lbits[d]) < L.brick[d]) ++L.lbits[d];
+        const int64_t n = L.n[d], ns = (n + L.brick[d] - 1) / L.brick[d];
+        L.segOf[d].resize((size_t)n); L.segLo[d].resize((size_t)ns + 1);
+        for (int64_t i = 0; i <= ns; ++i) L.segLo[d][(size_t)i] = (int32_t)(i * n / ns);
+        for (int64_t i = 0; i < ns; ++i)
+            for (int32_t q = L.segLo[d][(size_t)i]; q < L.segLo[d][(size_t)i + 1]; ++q) L.segOf[d][(size_t)q] = (int32_t)i;
+    }
+    L.lshift = L.lbits[0] + L.lbits[1] + L.lbits[2];
+}
+// the owned cells in the order of their keys (sorted in runs, then merged: keeps the host peak at one copy and uses the cores)
+SortedCells sortCells(const StaticData& s, const BrickLattice& L, std::vector<int32_t>&& owned) {
+    const int64_t nOwned = (int64_t)owned.size();
+    SortedCells key((size_t)nOwned);
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < nOwned; ++i) key[i] = {L.keyOf(s, owned[i]), owned[i]};
+    std::vector<int32_t>().swap(owned);
+    const int nRuns = 16;
+    std::vector<int64_t> cut(nRuns + 1);
+    for (int r = 0; r <= nRuns; ++r) cut[r] = nOwned * r / nRuns;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int r = 0; r < nRuns; ++r) std::sort(key.begin() + cut[r], key.begin() + cut[r + 1]);
+    for (int width = 1; width < nRuns; width *= 2) {
+#pragma omp parallel for schedule(dynamic, 1)
+        for (int r = 0; r < nRuns; r += 2 * width)
+            if (r + width < nRuns)
+                std::inplace_merge(key.begin() + cut[r], key.begin() + cut[r + width], key.begin() + cut[std::min(nRuns, r + 2 * width)]);
+    }
+    return key;
+}
+
+// ---- one range of the sorted cells -> one block ----
+// Owns its workspace (three label -> position maps and the block): one per thread, no allocation per block.
+struct BlockMaker {
+    const StaticData& s;
+    const SortedCells& key;
+    std::vector<SmallMap> maps = std::vector<SmallMap>(3);   // positions of the block's cells, vertices, faces
+    OneBlock o;
+    BlockMaker(const StaticData& s_, const SortedCells& key_) : s(s_), key(key_) {}
+    int entriesOf(int32_t c, int32_t* out) const {   // ascending face label, ~f when the cell is the neighbour
         const int n = s.cfCount[c];
         const size_t base = (size_t)s.cfSlice[c >> 6] * 64 + (c & 63);
         for (int i = 0; i < n; ++i) out[i] = s.cfItem[base + (size_t)i * 64];
         return n;
-    };
-    // one range of the sorted cells -> one block, or false when it does not fit the caps
-    auto tryBlock = [&](int64_t b0, int64_t b1, OneBlock& o, SmallMap& posC, SmallMap& posV, SmallMap& posF) {
+    }
+    // fills o from cells [b0, b1); false when they do not fit the caps
+    bool make(int64_t b0, int64_t b1) {
+        SmallMap &posC = maps[0], &posV = maps[1], &posF = maps[2];
+        const int64_t nIF = s.nIF;
         o.cells.clear(); o.verts.clear(); o.face.clear(); o.entry.clear(); o.nEntry.clear(); o.maxE = 0;
         o.nOwn = (int32_t)(b1 - b0);
         std::vector<int32_t>& faces = o.faces;
@@ -1077,13 +1151,10 @@ FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
                 o.vW[lv * o.maxPE + i] = s.pcW[base + (size_t)i * 64];
             }
         }
-        // what the block needs of the kernel's LDS (fusedFaceCellKernel: RecA of every staged cell, RecB of the own + across-a-face ones, then
-        // vertex records + coordinates + centres, which the fluxes overwrite): a block over the budget that lets three blocks share a CU is
-        // cut like one over the caps, unless it is small already
-        o.lds = 48 * (int32_t)o.cells.size() + 32 * o.nAll + std::max(72 * (int32_t)vs.size() + 24 * o.nAll, 40 * (int32_t)faces.size());
-        // (the implicitDiffusion branch's assembly reuses the vertex region for four flux planes, then the gradients of the own + across-a-face
-        // cells, then four planes again: qgd_kernels.hip fusedFaceCellKernel<..., IMPL>)
-        o.ldsImpl = 48 * (int32_t)o.cells.size() + 32 * o.nAll + std::max({72 * (int32_t)vs.size() + 24 * o.nAll, 32 * (int32_t)faces.size(), 72 * o.nAll});
+        // what the block needs of the kernel's LDS (qgd_setup.hpp fusedBlockLds): a block over the budget that lets three blocks share a CU
+        // is cut like one over the caps, unless it is small already
+        o.lds = fusedBlockLds((int32_t)o.cells.size(), o.nAll, (int32_t)vs.size(), (int32_t)faces.size());
+        o.ldsImpl = fusedBlockLdsImpl((int32_t)o.cells.size(), o.nAll, (int32_t)vs.size(), (int32_t)faces.size());
         if (o.lds > kFusedLdsTarget && o.nOwn > 32) return false;
         o.face.resize(4 * faces.size());
         for (size_t lf = 0; lf < faces.size(); ++lf) {
@@ -1107,203 +1178,225 @@ FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
             }
         }
         return true;
-    };
-    // ranges of the sorted cells.  A range that does not fit the caps
-    // is halved -- and a mesh whose 128-cell ranges mostly do not fit (cells with more than six faces: triangles, polyhedra) would end up with
-    // 64-cell blocks whose second face pass runs nearly empty; so the ranges get shorter in steps until few of them need the cut.
-    // First choice: the lattice BRICKS themselves -- the cells whose Morton keys share everything above the position inside the brick (8x4x4 lattice
-    // cells) --, whatever the mesh's extents and wherever a shard's ghost planes sit; bricks of one 16x8x8 parent that are short of cells (the
-    // rim of the mesh, a shard's one-plane boundary layer) are joined up to 128 cells, a brick with more is cut evenly.  Runs of a fixed
-    // count instead (second choice, lengths 112 ... 64) drift across the bricks as soon as one brick is short.
-    std::vector<int64_t> rangeStart;   // nRanges + 1 positions in the sorted cells
-    int64_t nRanges = 0;
-    auto brickRanges = [&]() {
-        rangeStart.clear();
-        auto part = [&](int64_t p0, int64_t p1) {   // [p0, p1) of the sorted cells, all of one role
-            int64_t curStart = -1, curEnd = -1;
-            uint64_t curParent = 0;
-            auto flush = [&]() { if (curStart >= 0) rangeStart.push_back(curStart); curStart = -1; };
-            int64_t i = p0;
-            while (i < p1) {
-                const uint64_t brick = key[i].first >> lshift;
-                int64_t j = i + 1;
-                while (j < p1 && (key[j].first >> lshift) == brick) ++j;
-                const int64_t sz = j - i;
-                if (sz > kFusedCells) {
-                    flush();
-                    const int64_t k = (sz + kFusedCells - 1) / kFusedCells;
-                    for (int64_t q = 0; q < k; ++q) rangeStart.push_back(i + sz * q / k);
-                } else if (curStart >= 0 && curEnd == i && (curEnd - curStart) + sz <= kFusedCells && (brick >> 3) == curParent) {
-                    curEnd = j;
-                } else {
-                    flush();
-                    curStart = i; curEnd = j; curParent = brick >> 3;
-                }
-                i = j;
-            }
+    }
+};
+
+// ---- candidate ranges of the sorted cells, and pass 1: where each is cut ----
+// A range that does not fit the caps is halved (cutRanges) -- and a mesh whose 128-cell ranges mostly do not fit (cells with more than six faces: triangles, polyhedra) would end up with
+// 64-cell blocks whose second face pass runs nearly empty; so the ranges get shorter in steps until few of them need the cut.
+// First choice: the lattice BRICKS themselves -- the cells whose Morton keys share everything above the position inside the brick (8x4x4 lattice
+// cells) --, whatever the mesh's extents and wherever a shard's ghost planes sit; bricks of one 16x8x8 parent that are short of cells (the
+// rim of the mesh, a shard's one-plane boundary layer) are joined up to 128 cells, a brick with more is cut evenly.  Runs of a fixed
+// count instead (second choice, lengths 112 ... 64) drift across the bricks as soon as one brick is short.
+// Both return the ranges' starts and, last, the end of the cells.
+std::vector<int64_t> brickRanges(const SortedCells& key, int lshift) {
+    const int64_t nOwned = (int64_t)key.size();
+    std::vector<int64_t> start;
+    int64_t curStart = -1, curEnd = -1;   // the bricks joined so far
+    uint64_t curParent = 0;
+    auto flush = [&]() { if (curStart >= 0) start.push_back(curStart); curStart = -1; };
+    for (int64_t i = 0, j; i < nOwned; i = j) {
+        const uint64_t brick = key[i].first >> lshift;
+        j = i + 1;
+        while (j < nOwned && (key[j].first >> lshift) == brick) ++j;
+        const int64_t sz = j - i;
+        if (sz > kFusedCells) {
             flush();
-        };
-        part(0, nOwned);
-        nRanges = (int64_t)rangeStart.size();
-        rangeStart.push_back(nOwned);
-    };
-    auto runRanges = [&](int64_t len) {
-        rangeStart.clear();
-        for (int64_t p = 0; p < nOwned; p += len) rangeStart.push_back(p);
-        nRanges = (int64_t)rangeStart.size();
-        rangeStart.push_back(nOwned);
-    };
-    auto rangeOf = [&](int64_t r) {
-        return std::pair<int64_t, int64_t>{rangeStart[r], rangeStart[r + 1]};
-    };
-    // Pass 1: where each range is cut (nearly always: not at all) and what the largest block needs.  Pass 2 builds every block again,
-    // straight into the padded tables: twice the arithmetic instead of half a million small vectors kept between the passes.
-    std::vector<int32_t> nOf;
-    std::vector<std::vector<std::pair<int64_t, int64_t>>> cuts;   // only for the ranges that were cut
-    using Hash = std::array<uint64_t, 2>;
-    std::vector<Hash> hashOne;                  // the topology fingerprint of a range that is one block
-    std::vector<std::vector<Hash>> hashCuts;    // ... of the blocks of a range that was cut
-    bool failed = false;
-    int64_t facesDone = 0, cellsTot = 0, cellsAll = 0, vertsTot = 0;
+            const int64_t k = (sz + kFusedCells - 1) / kFusedCells;
+            for (int64_t q = 0; q < k; ++q) start.push_back(i + sz * q / k);
+        } else if (curStart >= 0 && curEnd == i && (curEnd - curStart) + sz <= kFusedCells && (brick >> 3) == curParent) {
+            curEnd = j;
+        } else {
+            flush();
+            curStart = i; curEnd = j; curParent = brick >> 3;
+        }
+    }
+    flush();
+    start.push_back(nOwned);
+    return start;
+}
+std::vector<int64_t> runRanges(int64_t nOwned, int64_t len) {
+    std::vector<int64_t> start;
+    for (int64_t p = 0; p < nOwned; p += len) start.push_back(p);
+    start.push_back(nOwned);
+    return start;
+}
+// What a cutting measures: sums and maxima over its blocks.  Every member is an integer sum or maximum, so the order in which the threads'
+// instances merge does not matter.
+struct CutStats {
+    int64_t blocks = 0, faces = 0, cellsTot = 0, cellsAll = 0, verts = 0;
     int32_t maxC = 0, maxV = 0, maxF = 0, maxE = 1, maxAll = 0, maxPE = 1, maxLds = 0, maxLdsImpl = 0;
-    // keep the first way of cutting ranges whose blocks average 104 cells or more, else the one with the largest average
-    struct Kept { std::vector<int64_t> rangeStart; std::vector<int32_t> nOf; std::vector<std::vector<std::pair<int64_t, int64_t>>> cuts;
-                  std::vector<Hash> hashOne; std::vector<std::vector<Hash>> hashCuts; bool bricks = false;
-                  int64_t nRanges = 0, facesDone = 0, cellsTot = 0, cellsAll = 0, vertsTot = 0, blocks = 0;
-                  int32_t maxC = 0, maxV = 0, maxF = 0, maxE = 1, maxAll = 0, maxPE = 1, maxLds = 0, maxLdsImpl = 0; } best;
-    for (const int64_t len : {(int64_t)0, (int64_t)112, (int64_t)96, (int64_t)80, (int64_t)64}) {
-        if (len == 0) brickRanges(); else runRanges(len);
-        nOf.assign((size_t)nRanges, 1);
-        cuts.assign((size_t)nRanges, {});
-        hashOne.assign((size_t)nRanges, Hash{0, 0});
-        hashCuts.assign((size_t)nRanges, {});
-        failed = false;
-        facesDone = cellsTot = cellsAll = vertsTot = 0;
-        maxC = maxV = maxF = maxAll = maxLds = maxLdsImpl = 0; maxE = maxPE = 1;
-#pragma omp parallel reduction(+ : facesDone, cellsTot, cellsAll, vertsTot) reduction(max : maxC, maxV, maxF, maxE, maxAll, maxPE, maxLds, maxLdsImpl)
-        {
-            std::vector<SmallMap> maps(3);
-            OneBlock o;
+    void take(const OneBlock& o) {
+        CutStats one;
+        one.blocks = 1;
+        one.faces = one.maxF = (int32_t)o.face.size() / 4;
+        one.cellsTot = one.maxC = (int32_t)o.cells.size();
+        one.cellsAll = one.maxAll = o.nAll;
+        one.verts = one.maxV = (int32_t)o.verts.size();
+        one.maxE = o.maxE; one.maxPE = o.maxPE; one.maxLds = o.lds; one.maxLdsImpl = o.ldsImpl;
+        merge(one);
+    }
+    void merge(const CutStats& c) {
+        blocks += c.blocks; faces += c.faces; cellsTot += c.cellsTot; cellsAll += c.cellsAll; verts += c.verts;
+        maxC = std::max(maxC, c.maxC); maxV = std::max(maxV, c.maxV); maxF = std::max(maxF, c.maxF); maxE = std::max(maxE, c.maxE);
+        maxAll = std::max(maxAll, c.maxAll); maxPE = std::max(maxPE, c.maxPE); maxLds = std::max(maxLds, c.maxLds);
+        maxLdsImpl = std::max(maxLdsImpl, c.maxLdsImpl);
+    }
+};
+#pragma omp declare reduction(merge : CutStats : omp_out.merge(omp_in))
+// One way of cutting the cells into blocks: the ranges, into how many blocks each was cut (nearly always: one), and the blocks' fingerprints.
+struct Cutting {
+    bool bricks = false;                     // the ranges are the lattice bricks
+    std::vector<int64_t> rangeStart;         // nRanges + 1 positions in the sorted cells
+    std::vector<int32_t> nOf;                // blocks per range
+    std::vector<std::vector<Range>> cuts;    // only for the ranges that were cut
+    std::vector<Hash> hashOne;               // the topology fingerprint of a range that is one block
+    std::vector<std::vector<Hash>> hashCuts; // ... of the blocks of a range that was cut
+    CutStats stats;
+    int64_t nRanges() const { return (int64_t)rangeStart.size() - 1; }
+};
+// Pass 1 over the ranges of c: where each is cut and what the largest block needs.  Pass 2 (fillTables) builds every block again, straight
+// into the padded tables: twice the arithmetic instead of half a million small vectors kept between the passes.
+// false: one cell with more faces / vertices than a block holds.
+bool cutRanges(const StaticData& s, const SortedCells& key, Cutting& c) {
+    const int64_t nRanges = c.nRanges();
+    c.nOf.assign((size_t)nRanges, 1);
+    c.cuts.assign((size_t)nRanges, {});
+    c.hashOne.assign((size_t)nRanges, Hash{0, 0});
+    c.hashCuts.assign((size_t)nRanges, {});
+    bool failed = false;
+    CutStats stats;
+#pragma omp parallel reduction(merge : stats)
+    {
+        BlockMaker maker(s, key);
 #pragma omp for schedule(dynamic, 64)
-            for (int64_t r = 0; r < nRanges; ++r) {
-                bool stop;
+        for (int64_t r = 0; r < nRanges; ++r) {
+            bool stop;
 #pragma omp atomic read
-                stop = failed;
-                if (stop) continue;
-                std::vector<std::pair<int64_t, int64_t>> work{rangeOf(r)}, done;
-                std::vector<Hash> doneHash;
-                while (!work.empty()) {
-                    const auto [b0, b1] = work.back();
-                    work.pop_back();
-                    if (tryBlock(b0, b1, o, maps[0], maps[1], maps[2])) {
-                        done.push_back({b0, b1});
-                        doneHash.push_back(o.topoHash());
-                        maxC = std::max<int32_t>(maxC, (int32_t)o.cells.size());
-                        maxV = std::max<int32_t>(maxV, (int32_t)o.verts.size());
-                        maxF = std::max<int32_t>(maxF, (int32_t)o.face.size() / 4);
-                        maxE = std::max(maxE, o.maxE);
-                        maxAll = std::max(maxAll, o.nAll);
-                        maxPE = std::max(maxPE, o.maxPE);
-                        maxLds = std::max(maxLds, o.lds);
-                        maxLdsImpl = std::max(maxLdsImpl, o.ldsImpl);
-                        facesDone += (int64_t)o.face.size() / 4;
-                        cellsTot += (int64_t)o.cells.size(); cellsAll += o.nAll; vertsTot += (int64_t)o.verts.size();
-                        continue;
-                    }
-                    if (b1 - b0 == 1) {   // one cell with more faces / vertices than a block holds
-#pragma omp atomic write
-                        failed = true;
-                        break;
-                    }
-                    const int64_t mid = (b0 + b1) / 2;
-                    work.push_back({mid, b1});
-                    work.push_back({b0, mid});
+            stop = failed;
+            if (stop) continue;
+            std::vector<Range> work{{c.rangeStart[r], c.rangeStart[r + 1]}}, done;
+            std::vector<Hash> doneHash;
+            while (!work.empty()) {
+                const auto [b0, b1] = work.back();
+                work.pop_back();
+                if (maker.make(b0, b1)) {
+                    done.push_back({b0, b1});
+                    doneHash.push_back(maker.o.topoHash());
+                    stats.take(maker.o);
+                    continue;
                 }
-                nOf[r] = (int32_t)done.size();
-                if (done.size() != 1) { cuts[r] = std::move(done); hashCuts[r] = std::move(doneHash); }
-                else hashOne[r] = doneHash[0];
+                if (b1 - b0 == 1) {
+#pragma omp atomic write
+                    failed = true;
+                    break;
+                }
+                const int64_t mid = (b0 + b1) / 2;
+                work.push_back({mid, b1});
+                work.push_back({b0, mid});
             }
+            c.nOf[r] = (int32_t)done.size();
+            if (done.size() != 1) { c.cuts[r] = std::move(done); c.hashCuts[r] = std::move(doneHash); }
+            else c.hashOne[r] = doneHash[0];
         }
-        if (failed) break;
-        int64_t blocks = 0;
-        for (int64_t r = 0; r < nRanges; ++r) blocks += nOf[r];
-        if (best.blocks == 0 || blocks < best.blocks) {
-            best.bricks = (len == 0);
-            best.rangeStart = rangeStart; best.nOf = nOf; best.cuts = cuts; best.nRanges = nRanges;
-            best.hashOne = hashOne; best.hashCuts = hashCuts;
-            best.facesDone = facesDone; best.cellsTot = cellsTot; best.cellsAll = cellsAll; best.vertsTot = vertsTot; best.blocks = blocks;
-            best.maxC = maxC; best.maxV = maxV; best.maxF = maxF; best.maxE = maxE; best.maxAll = maxAll; best.maxPE = maxPE; best.maxLds = maxLds; best.maxLdsImpl = maxLdsImpl;
-        }
+    }
+    c.stats = stats;
+    return !failed;
+}
+// Keeps the first way of cutting whose blocks average 104 cells or more, else the one with the fewest blocks (the first of equals).
+bool bestCutting(const StaticData& s, const SortedCells& key, int lshift, Cutting& best) {
+    const int64_t nOwned = (int64_t)key.size();
+    for (const int64_t len : {(int64_t)0, (int64_t)112, (int64_t)96, (int64_t)80, (int64_t)64}) {
+        Cutting c;
+        c.bricks = len == 0;
+        c.rangeStart = c.bricks ? brickRanges(key, lshift) : runRanges(nOwned, len);
+        if (!cutRanges(s, key, c)) return false;
+        const int64_t blocks = c.stats.blocks;
+        if (best.stats.blocks == 0 || blocks < best.stats.blocks) best = std::move(c);
         if (blocks * 104 <= nOwned) break;
     }
-    if (!failed) {
-        rangeStart.swap(best.rangeStart); nOf.swap(best.nOf); cuts.swap(best.cuts); nRanges = best.nRanges;
-        hashOne.swap(best.hashOne); hashCuts.swap(best.hashCuts);
-        facesDone = best.facesDone; cellsTot = best.cellsTot; cellsAll = best.cellsAll; vertsTot = best.vertsTot;
-        maxC = best.maxC; maxV = best.maxV; maxF = best.maxF; maxE = best.maxE; maxAll = best.maxAll; maxPE = best.maxPE; maxLds = best.maxLds; maxLdsImpl = best.maxLdsImpl;
+    return true;
+}
+
+// ---- the blocks in launch order, their templates, the tables ----
+struct BlockOrder {
+    std::vector<Range> blk;       // every block's range of the sorted cells, in range order
+    std::vector<Hash> hash;       // ... its fingerprint
+    std::vector<int64_t> first;   // ... its launch position
+    int64_t nLayer = 0;
+    int64_t nBlocks() const { return (int64_t)blk.size(); }
+};
+// A shard: the blocks that hold a cell a neighbour waits for (role 2) come first, so that the step can advance them before the others and
+// overlap the exchange with the rest (qgd_capi.cpp stepAdvance).  They are whole bricks like every other block -- round 5 gave the
+// one-plane boundary layer blocks of its own, flat 8 x 8 x 1 ones of 64 cells that staged three records per cell.
+BlockOrder layerBlocksFirst(const StaticData& s, const SortedCells& key, const Cutting& c) {
+    BlockOrder o;
+    for (int64_t r = 0; r < c.nRanges(); ++r) {
+        if (c.nOf[r] == 1) { o.blk.push_back({c.rangeStart[r], c.rangeStart[r + 1]}); o.hash.push_back(c.hashOne[r]); }
+        else { o.blk.insert(o.blk.end(), c.cuts[r].begin(), c.cuts[r].end()); o.hash.insert(o.hash.end(), c.hashCuts[r].begin(), c.hashCuts[r].end()); }
     }
-    if (failed) return B;
-    // a shard: the blocks that hold a cell a neighbour waits for (role 2) come first, so that the step can advance them before the others and
-    // overlap the exchange with the rest (qgd_capi.cpp stepAdvance).  They are whole bricks like every other block -- round 5 gave the
-    // one-plane boundary layer blocks of its own, flat 8 x 8 x 1 ones of 64 cells that staged three records per cell.
-    std::vector<std::pair<int64_t, int64_t>> blk;   // every block's range of the sorted cells, in range order
-    std::vector<Hash> blkHash;
-    for (int64_t r = 0; r < nRanges; ++r) {
-        if (nOf[r] == 1) { blk.push_back(rangeOf(r)); blkHash.push_back(hashOne[r]); }
-        else { blk.insert(blk.end(), cuts[r].begin(), cuts[r].end()); blkHash.insert(blkHash.end(), hashCuts[r].begin(), hashCuts[r].end()); }
-    }
-    const int64_t nBlocks = (int64_t)blk.size();
+    const int64_t nBlocks = o.nBlocks();
     std::vector<uint8_t> layerBlock((size_t)nBlocks, 0);
     if (!s.ghost.empty()) {
 #pragma omp parallel for schedule(static)
         for (int64_t b = 0; b < nBlocks; ++b)
-            for (int64_t i = blk[b].first; i < blk[b].second; ++i) if (s.ghost[key[i].second] == 2) { layerBlock[b] = 1; break; }
+            for (int64_t i = o.blk[b].first; i < o.blk[b].second; ++i) if (s.ghost[key[i].second] == 2) { layerBlock[b] = 1; break; }
     }
-    std::vector<int64_t> first((size_t)nBlocks, 0);   // where block b of the range order goes
-    int64_t nLayerBlocks = 0;
-    {
-        int64_t pos = 0;
-        for (int pass = 1; pass >= 0; --pass) {
-            for (int64_t b = 0; b < nBlocks; ++b) if (layerBlock[b] == pass) first[b] = pos++;
-            if (pass == 1) nLayerBlocks = pos;
-        }
+    o.first.assign((size_t)nBlocks, 0);
+    int64_t pos = 0;
+    for (int pass = 1; pass >= 0; --pass) {
+        for (int64_t b = 0; b < nBlocks; ++b) if (layerBlock[b] == pass) o.first[b] = pos++;
+        if (pass == 1) o.nLayer = pos;
     }
-    B.maxC = maxC; B.maxV = maxV; B.maxF = maxF;
+    return o;
+}
+// Templates: the distinct topology fingerprints in ascending order (deterministic); a block's template = its fingerprint's rank; the
+// template's tables are written by the first block (in launch order) that has it, and every other block compares its own with them.
+struct TemplatePlan {
+    bool shared = false;           // any two blocks alike (and templates allowed); else one template per block
+    int64_t n = 0;
+    std::vector<int32_t> of;       // by launch position
+    std::vector<int64_t> writer;   // range-order index of the block that writes template t (shared only)
+};
+TemplatePlan assignTemplates(const BlockOrder& o, bool allowed) {
+    const int64_t nBlocks = o.nBlocks();
+    TemplatePlan t;
+    t.of.assign((size_t)nBlocks, 0);
+    std::vector<Hash> uniq(o.hash);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    t.shared = allowed && (int64_t)uniq.size() < nBlocks;
+    t.n = t.shared ? (int64_t)uniq.size() : nBlocks;
+    if (!t.shared) {
+        for (int64_t b = 0; b < nBlocks; ++b) t.of[b] = (int32_t)b;
+        return t;
+    }
+    t.writer.assign((size_t)t.n, -1);
+    std::vector<int64_t> writerPos((size_t)t.n, INT64_MAX);
+    for (int64_t ib = 0; ib < nBlocks; ++ib) {
+        const int64_t k = std::lower_bound(uniq.begin(), uniq.end(), o.hash[ib]) - uniq.begin();
+        t.of[(size_t)o.first[ib]] = (int32_t)k;
+        if (o.first[ib] < writerPos[k]) { writerPos[k] = o.first[ib]; t.writer[k] = ib; }
+    }
+    return t;
+}
+void setCaps(FusedBlocks& B, const CutStats& st) {
+    B.maxC = st.maxC; B.maxV = st.maxV; B.maxF = st.maxF;
     B.capC = (B.maxC + 7) / 8 * 8; B.capV = (B.maxV + 7) / 8 * 8; B.capF = (B.maxF + 7) / 8 * 8;
-    B.capE = maxE;
-    B.capPE = maxPE; B.maxTot = maxC; B.maxAll = maxAll; B.maxLds = maxLds; B.maxLdsImpl = maxLdsImpl;
-    // templates: the distinct topology fingerprints in ascending order (deterministic); a block's template = its fingerprint's rank; the
-    // template's tables are written by the first block (in launch order) that has it, and every other block compares its own with them.  QGD_FUSED_TEMPLATES=0: one template per block.
-    std::vector<int32_t> tplOf((size_t)nBlocks, 0);      // by launch position
-    std::vector<int64_t> tplWriter;                       // range-order index of the block that writes template t
-    int64_t nTemplates = nBlocks;
-    bool templated = false;
-    {
-        std::vector<Hash> uniq(blkHash);
-        std::sort(uniq.begin(), uniq.end());
-        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-        const char* e = std::getenv("QGD_FUSED_TEMPLATES");
-        templated = !(e && std::atoi(e) == 0) && (int64_t)uniq.size() < nBlocks;   // any two blocks alike
-        if (templated) {
-            nTemplates = (int64_t)uniq.size();
-            tplWriter.assign((size_t)nTemplates, -1);
-            std::vector<int64_t> writerPos((size_t)nTemplates, INT64_MAX);
-            for (int64_t ib = 0; ib < nBlocks; ++ib) {
-                const int64_t t = std::lower_bound(uniq.begin(), uniq.end(), blkHash[ib]) - uniq.begin();
-                tplOf[(size_t)first[ib]] = (int32_t)t;
-                if (first[ib] < writerPos[t]) { writerPos[t] = first[ib]; tplWriter[t] = ib; }
-            }
-        } else {
-            for (int64_t b = 0; b < nBlocks; ++b) tplOf[b] = (int32_t)b;
-        }
-    }
-    if (std::max(nBlocks * (int64_t)std::max({B.capC, B.capV * B.capPE, B.capF}), nTemplates * (int64_t)std::max({B.capV * B.capPE, 3 * B.capF, B.capE * kFusedCells})) >
-        (int64_t)INT32_MAX) return B;
-    B.nBlocks = (int32_t)nBlocks;
-    B.nLayerBlocks = (int32_t)nLayerBlocks;
-    B.nTemplates = (int32_t)nTemplates; B.templated = templated ? 1 : 0;
-    for (int d = 0; d < 3; ++d) B.brick[d] = best.bricks ? (int32_t)kBrick[d] : 0;
-    B.facesComputed = facesDone; B.cellsStaged = cellsTot; B.cellsStagedFull = cellsAll; B.vertsStaged = vertsTot;
+    B.capE = st.maxE;
+    B.capPE = st.maxPE; B.maxTot = st.maxC; B.maxAll = st.maxAll; B.maxLds = st.maxLds; B.maxLdsImpl = st.maxLdsImpl;
+    B.facesComputed = st.faces; B.cellsStaged = st.cellsTot; B.cellsStagedFull = st.cellsAll; B.vertsStaged = st.verts;
+}
+// false: a table would pass 2^31 entries (the kernels index them with 32-bit integers)
+bool resizeTemplateTables(FusedBlocks& B, int64_t nTemplates) {
+    if (nTemplates * (int64_t)std::max({B.capV * B.capPE, 3 * B.capF, B.capE * kFusedCells}) > (int64_t)INT32_MAX) return false;
+    B.vPos.resize((size_t)nTemplates * B.capPE * B.capV);
+    B.facePos.resize((size_t)nTemplates * B.capF * 3);
+    B.entry.resize((size_t)nTemplates * B.capE * kFusedCells);
+    return true;
+}
+bool allocateTables(FusedBlocks& B, int64_t nBlocks, int64_t nTemplates) {
+    if (nBlocks * (int64_t)std::max({B.capC, B.capV * B.capPE, B.capF}) > (int64_t)INT32_MAX || !resizeTemplateTables(B, nTemplates)) return false;
     B.hdr.resize(4 * (size_t)nBlocks);
     B.hdr2.resize(4 * (size_t)nBlocks);
     B.vCount.resize((size_t)nBlocks * B.capV);
@@ -1312,96 +1405,135 @@ FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
     B.verts.resize((size_t)nBlocks * B.capV);
     B.faceLabel.resize((size_t)nBlocks * B.capF);
     B.nEntry.resize((size_t)nBlocks * kFusedCells);
-    B.vPos.resize((size_t)nTemplates * B.capPE * B.capV);
-    B.facePos.resize((size_t)nTemplates * B.capF * 3);
-    B.entry.resize((size_t)nTemplates * B.capE * kFusedCells);
-    // a template's tables as block `o` wants them, at template slot t: written (the template's writer), or compared with what is there
-    // (every other block of the template: equal fingerprints are no proof of equal topologies)
-    auto templateTables = [&](const OneBlock& o, size_t t, bool write) {
-        const int32_t nV = (int32_t)o.verts.size(), nF = (int32_t)o.face.size() / 4;
-        bool same = true;
-        auto put = [&](auto& slot, auto v) { if (write) slot = v; else same = same && slot == v; };
-        for (int32_t i = 0; i < B.capV; ++i) {
-            const int32_t n = i < nV ? o.vCount[i] : 0;
-            for (int32_t e = 0; e < B.capPE; ++e) put(B.vPos[(t * B.capPE + e) * B.capV + i], e < n ? o.vPos[(size_t)i * o.maxPE + e] : (uint16_t)0);
-        }
-        for (int32_t i = 0; i < B.capF; ++i)
-            for (int q = 0; q < 3; ++q) put(B.facePos[(t * B.capF + i) * 3 + q], nF ? (uint32_t)o.face[4 * (size_t)std::min(i, nF - 1) + 1 + q] : 0u);
-        for (int32_t j = 0; j < kFusedCells; ++j) {
-            const int32_t nE = j < o.nOwn ? o.nEntry[j] : 0;
-            for (int32_t e = 0; e < B.capE; ++e) put(B.entry[(t * B.capE + e) * kFusedCells + j], e < nE ? o.entry[(size_t)j * o.maxE + e] : 0);
-        }
-        return same;
-    };
-    // the counts a block reads its template's tables with: the block's own against those of the template's writer (at launch position w)
-    auto sameCounts = [&](size_t b, size_t w) {
-        for (int q = 0; q < 4; ++q) if (B.hdr[4 * b + q] != B.hdr[4 * w + q]) return false;
-        if (B.hdr2[4 * b] != B.hdr2[4 * w]) return false;
-        return std::equal(&B.nEntry[b * kFusedCells], &B.nEntry[b * kFusedCells] + kFusedCells, &B.nEntry[w * kFusedCells]) &&
-               std::equal(&B.vCount[b * B.capV], &B.vCount[b * B.capV] + B.capV, &B.vCount[w * B.capV]);
-    };
-    // Pass 2 in two sweeps when blocks share templates: the writers first, then the others, which find their template's tables complete and
-    // compare their own with them once.  A block whose tables differ (two topologies, one fingerprint) gets a template of its own below.
+    return true;
+}
+// a block's own lists at launch position b, padded to their strides
+void writeBlockLists(FusedBlocks& B, size_t b, size_t t, const OneBlock& o) {
+    const int32_t nTot = (int32_t)o.cells.size(), nV = (int32_t)o.verts.size(), nF = (int32_t)o.face.size() / 4;
+    B.hdr[4 * b] = o.nOwn; B.hdr[4 * b + 1] = o.nAll; B.hdr[4 * b + 2] = nV; B.hdr[4 * b + 3] = nF;
+    B.hdr2[4 * b] = nTot; B.hdr2[4 * b + 1] = (int32_t)t; B.hdr2[4 * b + 2] = B.hdr2[4 * b + 3] = 0;
+    for (int32_t i = 0; i < B.capC; ++i) B.cells[b * B.capC + i] = o.cells[std::min(i, nTot - 1)];
+    for (int32_t i = 0; i < B.capV; ++i) {
+        const int32_t n = i < nV ? o.vCount[i] : 0;
+        B.vCount[b * B.capV + i] = (uint8_t)n;
+        for (int32_t e = 0; e < B.capPE; ++e) B.vW[(b * B.capPE + e) * B.capV + i] = e < n ? o.vW[(size_t)i * o.maxPE + e] : 0.0;
+    }
+    for (int32_t i = 0; i < B.capV; ++i) B.verts[b * B.capV + i] = nV ? o.verts[std::min(i, nV - 1)] : 0;
+    for (int32_t i = 0; i < B.capF; ++i) B.faceLabel[b * B.capF + i] = nF ? o.face[4 * (size_t)std::min(i, nF - 1)] : 0;
+    for (int32_t j = 0; j < kFusedCells; ++j) B.nEntry[b * kFusedCells + j] = (uint8_t)(j < o.nOwn ? o.nEntry[j] : 0);
+}
+// a template's tables as block `o` wants them, at template slot t: written (the template's writer), or compared with what is there
+// (every other block of the template: equal fingerprints are no proof of equal topologies)
+bool templateTables(FusedBlocks& B, const OneBlock& o, size_t t, bool write) {
+    const int32_t nV = (int32_t)o.verts.size(), nF = (int32_t)o.face.size() / 4;
+    bool same = true;
+    auto put = [&](auto& slot, auto v) { if (write) slot = v; else same = same && slot == v; };
+    for (int32_t i = 0; i < B.capV; ++i) {
+        const int32_t n = i < nV ? o.vCount[i] : 0;
+        for (int32_t e = 0; e < B.capPE; ++e) put(B.vPos[(t * B.capPE + e) * B.capV + i], e < n ? o.vPos[(size_t)i * o.maxPE + e] : (uint16_t)0);
+    }
+    for (int32_t i = 0; i < B.capF; ++i)
+        for (int q = 0; q < 3; ++q) put(B.facePos[(t * B.capF + i) * 3 + q], nF ? (uint32_t)o.face[4 * (size_t)std::min(i, nF - 1) + 1 + q] : 0u);
+    for (int32_t j = 0; j < kFusedCells; ++j) {
+        const int32_t nE = j < o.nOwn ? o.nEntry[j] : 0;
+        for (int32_t e = 0; e < B.capE; ++e) put(B.entry[(t * B.capE + e) * kFusedCells + j], e < nE ? o.entry[(size_t)j * o.maxE + e] : 0);
+    }
+    return same;
+}
+// the counts a block reads its template's tables with: the block's own against those of the template's writer (at launch position w)
+bool sameCounts(const FusedBlocks& B, size_t b, size_t w) {
+    for (int q = 0; q < 4; ++q) if (B.hdr[4 * b + q] != B.hdr[4 * w + q]) return false;
+    if (B.hdr2[4 * b] != B.hdr2[4 * w]) return false;
+    return std::equal(&B.nEntry[b * kFusedCells], &B.nEntry[b * kFusedCells] + kFusedCells, &B.nEntry[w * kFusedCells]) &&
+           std::equal(&B.vCount[b * B.capV], &B.vCount[b * B.capV] + B.capV, &B.vCount[w * B.capV]);
+}
+// Pass 2, in two sweeps when blocks share templates: the writers first, then the others, which find their template's tables complete and
+// compare their own with them once.  Returns the blocks (range order) whose tables differ: two topologies, one fingerprint.
+std::vector<int64_t> fillTables(FusedBlocks& B, const StaticData& s, const SortedCells& key, const BlockOrder& order, const TemplatePlan& tpl) {
     std::vector<int64_t> mismatched;
-    for (int sweep = 0; sweep < (templated ? 2 : 1); ++sweep) {
+    const int64_t nBlocks = order.nBlocks();
+    for (int sweep = 0; sweep < (tpl.shared ? 2 : 1); ++sweep) {
 #pragma omp parallel
         {
-            std::vector<SmallMap> maps(3);
-            OneBlock o;
+            BlockMaker maker(s, key);
 #pragma omp for schedule(dynamic, 64)
             for (int64_t ib = 0; ib < nBlocks; ++ib) {
-                const size_t b = (size_t)first[ib];
-                const size_t t = (size_t)tplOf[b];
-                const bool writer = !templated || tplWriter[t] == ib;
+                const size_t b = (size_t)order.first[ib];
+                const size_t t = (size_t)tpl.of[b];
+                const bool writer = !tpl.shared || tpl.writer[t] == ib;
                 if (writer != (sweep == 0)) continue;
-                const auto [b0, b1] = blk[ib];
-                tryBlock(b0, b1, o, maps[0], maps[1], maps[2]);
-                const int32_t nTot = (int32_t)o.cells.size(), nV = (int32_t)o.verts.size(), nF = (int32_t)o.face.size() / 4;
-                B.hdr[4 * b] = o.nOwn; B.hdr[4 * b + 1] = o.nAll; B.hdr[4 * b + 2] = nV; B.hdr[4 * b + 3] = nF;
-                B.hdr2[4 * b] = nTot; B.hdr2[4 * b + 1] = (int32_t)t; B.hdr2[4 * b + 2] = B.hdr2[4 * b + 3] = 0;
-                for (int32_t i = 0; i < B.capC; ++i) B.cells[b * B.capC + i] = o.cells[std::min(i, nTot - 1)];
-                for (int32_t i = 0; i < B.capV; ++i) {
-                    const int32_t n = i < nV ? o.vCount[i] : 0;
-                    B.vCount[b * B.capV + i] = (uint8_t)n;
-                    for (int32_t e = 0; e < B.capPE; ++e) B.vW[(b * B.capPE + e) * B.capV + i] = e < n ? o.vW[(size_t)i * o.maxPE + e] : 0.0;
-                }
-                for (int32_t i = 0; i < B.capV; ++i) B.verts[b * B.capV + i] = nV ? o.verts[std::min(i, nV - 1)] : 0;
-                for (int32_t i = 0; i < B.capF; ++i) B.faceLabel[b * B.capF + i] = nF ? o.face[4 * (size_t)std::min(i, nF - 1)] : 0;
-                for (int32_t j = 0; j < kFusedCells; ++j) B.nEntry[b * kFusedCells + j] = (uint8_t)(j < o.nOwn ? o.nEntry[j] : 0);
-                if (writer) { templateTables(o, t, true); continue; }
-                if (sameCounts(b, (size_t)first[tplWriter[t]]) && templateTables(o, t, false)) continue;
+                maker.make(order.blk[ib].first, order.blk[ib].second);
+                writeBlockLists(B, b, t, maker.o);
+                if (writer) { templateTables(B, maker.o, t, true); continue; }
+                if (sameCounts(B, b, (size_t)order.first[tpl.writer[t]]) && templateTables(B, maker.o, t, false)) continue;
 #pragma omp critical(qgdTemplateMismatch)
                 mismatched.push_back(ib);
             }
         }
     }
-    if (!mismatched.empty()) {
-        std::sort(mismatched.begin(), mismatched.end(), [&](int64_t a, int64_t b) { return first[a] < first[b]; });   // (deterministic template ids)
-        const int64_t nT = nTemplates + (int64_t)mismatched.size();
-        if (nT * (int64_t)std::max({B.capV * B.capPE, 3 * B.capF, B.capE * kFusedCells}) > (int64_t)INT32_MAX) return FusedBlocks{};
-        B.vPos.resize((size_t)nT * B.capPE * B.capV);
-        B.facePos.resize((size_t)nT * B.capF * 3);
-        B.entry.resize((size_t)nT * B.capE * kFusedCells);
-        std::vector<SmallMap> maps(3);
-        OneBlock o;
-        for (size_t k = 0; k < mismatched.size(); ++k) {
-            const int64_t ib = mismatched[k];
-            const size_t t = (size_t)nTemplates + k;
-            tryBlock(blk[ib].first, blk[ib].second, o, maps[0], maps[1], maps[2]);
-            templateTables(o, t, true);
-            B.hdr2[4 * (size_t)first[ib] + 1] = (int32_t)t;
-        }
-        B.nTemplates = (int32_t)nT;
-        B.templateMismatches = (int32_t)mismatched.size();
+    return mismatched;
+}
+// the mismatched blocks get templates of their own behind the others; false: the template tables would pass 2^31 entries
+bool ownTemplates(FusedBlocks& B, const StaticData& s, const SortedCells& key, const BlockOrder& order, std::vector<int64_t> mismatched) {
+    std::sort(mismatched.begin(), mismatched.end(), [&](int64_t a, int64_t b) { return order.first[a] < order.first[b]; });   // (deterministic template ids)
+    const int64_t nShared = B.nTemplates;
+    if (!resizeTemplateTables(B, nShared + (int64_t)mismatched.size())) return false;
+    BlockMaker maker(s, key);
+    for (size_t k = 0; k < mismatched.size(); ++k) {
+        const int64_t ib = mismatched[k];
+        maker.make(order.blk[ib].first, order.blk[ib].second);
+        templateTables(B, maker.o, (size_t)nShared + k, true);
+        B.hdr2[4 * (size_t)order.first[ib] + 1] = (int32_t)((size_t)nShared + k);
     }
-    {
-        const char* e = std::getenv("QGD_FUSED_PACKED_W");
-        if (!(e && std::atoi(e) == 0) && packFusedWeights(B) && !keepFullWeights) RawVec<double>().swap(B.vW);
-        const char* ef = std::getenv("QGD_FUSED_PACKED_F");   // (the face streams pack only where the weights did)
-        if (!(ef && std::atoi(ef) == 0)) packFusedFaceStreams(B, s);
-    }
+    B.nTemplates = (int32_t)(nShared + (int64_t)mismatched.size());
+    B.templateMismatches = (int32_t)mismatched.size();
+    return true;
+}
+}  // namespace
+
+FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
+    FusedBlocks B;
+    const auto tStart = std::chrono::steady_clock::now();
+    if (s.nC == 0 || s.nIF == 0 || s.nGeomD != 3) return B;
+    if (3 * (int64_t)s.nC > INT32_MAX || 3 * (int64_t)s.nP > INT32_MAX) return B;
+    const BuilderOptions opt = readBuilderOptions();
+    std::vector<int32_t> owned = ownedCellsOf(s);
+    if (owned.empty()) return B;
+    BrickLattice lattice = measureLattice(s, owned);
+    chooseBrick(lattice, opt);
+    cutSegments(lattice);
+    const SortedCells key = sortCells(s, lattice, std::move(owned));
+    Cutting cut;
+    if (!bestCutting(s, key, lattice.lshift, cut)) return B;
+    const BlockOrder order = layerBlocksFirst(s, key, cut);
+    const TemplatePlan tpl = assignTemplates(order, opt.templates);
+    setCaps(B, cut.stats);
+    if (!allocateTables(B, order.nBlocks(), tpl.n)) return B;
+    B.nBlocks = (int32_t)order.nBlocks();
+    B.nLayerBlocks = (int32_t)order.nLayer;
+    B.nTemplates = (int32_t)tpl.n; B.templated = tpl.shared ? 1 : 0;
+    for (int d = 0; d < 3; ++d) B.brick[d] = cut.bricks ? (int32_t)lattice.brick[d] : 0;
+    const std::vector<int64_t> mismatched = fillTables(B, s, key, order, tpl);
+    if (!mismatched.empty() && !ownTemplates(B, s, key, order, mismatched)) return FusedBlocks{};
+    if (opt.packWeights && packFusedWeights(B) && !keepFullWeights) RawVec<double>().swap(B.vW);
+    if (opt.packFaces) packFusedFaceStreams(B, s);
     B.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
     return B;
+}
+
+FusedLaunchPlan planFusedLaunch(const FusedBlocks& B, int64_t nOwned, int64_t ldsLimit, bool anyBlocks) {
+    FusedLaunchPlan p;
+    auto launchLds = [](int64_t records, int32_t& lds, int32_t& ldsCell) {
+        const int64_t park = (records + 15) / 16 * 16;   // the parked face entries: 6 x 128 words behind the records
+        lds = (int32_t)((park + 6 * 128 * 4 + 255) / 256 * 256);
+        ldsCell = (int32_t)(park / 8);
+    };
+    launchLds(B.maxLds, p.lds, p.ldsCell);
+    launchLds(B.maxLdsImpl, p.ldsImpl, p.ldsCellImpl);
+    if (p.ldsImpl > ldsLimit) p.ldsImpl = 0;   // (on a box: the explicit step's figure, three blocks per CU)
+    p.use = B.nBlocks > 0 && (anyBlocks || (int64_t)B.nBlocks * 88 <= nOwned + 87) && B.maxAll <= kFusedCapC && B.maxTot <= kFusedCapTot &&
+            B.capV <= kFusedCapV && B.capF <= kFusedCapF && B.capPE <= 255 && p.lds <= ldsLimit;
+    return p;
 }
 
 }  // namespace qgd

@@ -8,6 +8,7 @@
 //  * gathered per-cell / per-vertex data is AoS records (one record = one
 //    contiguous 16-B aligned chunk)
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -205,8 +206,21 @@ struct FusedBlocks {
     int64_t facesComputed = 0;     // over all blocks (a face between two blocks is computed by both)
     int64_t cellsStaged = 0, cellsStagedFull = 0, vertsStaged = 0;   // over all blocks: cell records staged (RecA), of which with RecB + centre; vertices formed
 };
+// LDS bytes of one block's records, from its counts of staged cells, own + across-a-face cells, vertices and faces (fusedFaceCellKernel lays
+// each block out by its own counts at run time): RecA of every staged cell, RecB of the own + across-a-face ones, then vertex records +
+// coordinates + centres, which the fluxes overwrite
+constexpr int32_t fusedBlockLds(int32_t nTot, int32_t nAll, int32_t nV, int32_t nF) {
+    return 48 * nTot + 32 * nAll + std::max(72 * nV + 24 * nAll, 40 * nF);
+}
+// ... in the layout of the implicitDiffusion branch's assembly, which reuses the vertex region for four flux planes, then the gradients of the
+// own + across-a-face cells, then four planes again (qgd_kernels.hip fusedFaceCellKernel<..., IMPL>)
+constexpr int32_t fusedBlockLdsImpl(int32_t nTot, int32_t nAll, int32_t nV, int32_t nF) {
+    return 48 * nTot + 32 * nAll + std::max({72 * nV + 24 * nAll, 32 * nF, 72 * nAll});
+}
 // LDS a block's records may take so that three blocks (+ 3 KB of parked face entries each) share a CU's 160 KB: what an 8x4x4 brick needs
-constexpr int32_t kFusedLdsTarget = 48 * 360 + 32 * 288 + 72 * 225 + 24 * 288;
+// (360 staged cells, 288 of them own or across a face, 225 vertices, 464 faces)
+constexpr int32_t kFusedLdsTarget = fusedBlockLds(360, 288, 225, 464);
+static_assert(kFusedLdsTarget == 48 * 360 + 32 * 288 + 72 * 225 + 24 * 288, "the LDS budget of three blocks per CU");
 // keepFullWeights = false: vW is dropped once vW16 holds it (the device path: 8 x 8 B per vertex formed that nothing reads again)
 FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights = true);
 // The packing rule on a block table whose nBlocks, capV, capPE, vCount and vW are filled: fills vW16 / wRef and sets packedW where the
@@ -217,6 +231,19 @@ bool packFusedWeights(FusedBlocks& B);
 // fhRef and sets packedF where s.w and s.hf of the computed face slots qualify (every slot decoded once and compared with s.w, s.hf and
 // s.fkind of its face), leaves them empty / 0 where they do not or where packedW != 1.  Returns packedF.
 bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s);
+// Whether the device uses a block table, and the dynamic LDS of its launches: the records of the block that needs most (maxLds / maxLdsImpl),
+// rounded to 16 B, then the parked face entries of the own cells, rounded to 256 B; ldsCell = where the parked entries start, in 8-B units.
+// The tables are refused when they are empty; when the blocks come out small -- under 88 cells on average: every block costs a workgroup
+// two face passes whatever it holds, and such a mesh is better off with the three kernels (5.0 against 4.4 ms per step on a 16 M-cell mesh
+// with 67-cell blocks) -- unless the caller takes any blocks (anyBlocks: tests, probes); when a count exceeds what the kernels' 16-bit
+// positions and budgets hold; and when the explicit layout needs more than ldsLimit, what one workgroup may ask for (blocks of <= 32
+// cells are exempt from the builder's three-per-CU budget, so one fat polyhedral block could exceed it: such a mesh keeps the three
+// kernels instead of failing in its first step).  ldsImpl is 0 where the implicitDiffusion layout alone exceeds the limit.
+struct FusedLaunchPlan {
+    bool use = false;
+    int32_t lds = 0, ldsCell = 0, ldsImpl = 0, ldsCellImpl = 0;
+};
+FusedLaunchPlan planFusedLaunch(const FusedBlocks& B, int64_t nOwned, int64_t ldsLimit, bool anyBlocks);
 inline double fusedWeightFromOffset(int64_t ref, int16_t off) {
     const int64_t bits = ref + (int64_t)off;
     double w;

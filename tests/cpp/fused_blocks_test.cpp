@@ -12,6 +12,9 @@
 //     the count is zero and the template counts are what they were before the comparison existed.  Compiled a second time with
 //     -DQGD_TEST_TOPOHASH_BITS=1 -- a fingerprint of one bit: unlike blocks are certain to share one -- the count must be positive, and
 //     every block's tables, read through its template, must still be what the mesh dictates (the entry-by-entry checks above);
+//   * the launch plan (planFusedLaunch): the device takes the brick meshes' tables as they are and the thin meshes' only when told to take
+//     any blocks, with the dynamic LDS this program rounds from its own maxima; refuses every table one byte below its need and with any
+//     cap exceeded, whoever asks;
 //   * thin meshes, whose blocks are small, have more blocks than 64-face tiles of internal faces -- the premise of
 //     tests/test_courant_small_blocks_gpu.py: under Courant-number control a block needs a partial slot that is neither a face tile's
 //     nor the patch kernel's.
@@ -45,7 +48,8 @@ static int fails = 0;
 static int mismatchesSeen = 0;
 
 // wantTemplates: the template count of the full fingerprint, as it was before the builder compared tables (-1: not pinned)
-static FusedBlocks checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, int maxTemplates = -1, int wantTemplates = -1) {
+// wantUse: 1 = the device takes these tables as they are (the brick meshes), 0 = only when told to take any blocks (the thin meshes), -1: not pinned
+static FusedBlocks checkMesh(const char* tag, HostMesh& m, double minMeanCells = 0.0, int maxTemplates = -1, int wantTemplates = -1, int wantUse = -1) {
     if (m.magSf.empty()) m.computeGeometry();
     m.computeDerived();
     const StaticData s = buildStaticData(m);
@@ -72,7 +76,7 @@ static FusedBlocks checkMesh(const char* tag, HostMesh& m, double minMeanCells =
     CHECK(B.templateMismatches == 0, "%s: %d template mismatches with the full fingerprint", tag, B.templateMismatches);
     CHECK(wantTemplates < 0 || B.nTemplates == wantTemplates, "%s: %d templates, %d before the tables were compared", tag, B.nTemplates, wantTemplates);
 #endif
-    int32_t maxTot = 0, maxAll = 0, maxV = 0, maxF = 0, maxLds = 0;
+    int32_t maxTot = 0, maxAll = 0, maxV = 0, maxF = 0, maxLds = 0, maxLdsImpl = 0;
     int64_t faces = 0;
     for (int32_t b = 0; b < B.nBlocks; ++b) {
         const int32_t nOwn = B.hdr[4 * b], nAll = B.hdr[4 * b + 1], nV = B.hdr[4 * b + 2], nF = B.hdr[4 * b + 3], nTot = B.hdr2[4 * b];
@@ -82,6 +86,7 @@ static FusedBlocks checkMesh(const char* tag, HostMesh& m, double minMeanCells =
         faces += nF;
         const int32_t lds = 48 * nTot + 32 * nAll + std::max(72 * nV + 24 * nAll, 40 * nF);   // the kernel's layout of this block's records
         maxLds = std::max(maxLds, lds);
+        maxLdsImpl = std::max(maxLdsImpl, 48 * nTot + 32 * nAll + std::max({72 * nV + 24 * nAll, 32 * nF, 72 * nAll}));   // ... of the implicitDiffusion branch
         CHECK(lds <= kFusedLdsTarget || nOwn <= 32, "block %d needs %d B of LDS with %d own cells", b, lds, nOwn);
         const int32_t* cells = &B.cells[(size_t)b * B.capC];
         const int32_t* verts = &B.verts[(size_t)b * B.capV];
@@ -172,6 +177,36 @@ static FusedBlocks checkMesh(const char* tag, HostMesh& m, double minMeanCells =
           maxF, B.maxTot, B.maxAll, B.maxV, B.maxF);
     CHECK(maxLds == B.maxLds, "%s: LDS %d vs %d", tag, maxLds, B.maxLds);
     CHECK(faces == B.facesComputed && faces >= 0, "%s: faces computed", tag);
+    {   // the launch plan (planFusedLaunch): whether the device takes the tables, and the dynamic LDS of its launches
+        int64_t owned = 0;
+        for (int32_t c = 0; c < s.nC; ++c) owned += (s.ghost.empty() || s.ghost[c] != 1) ? 1 : 0;
+        // this program's own rounding: the records of the largest block to 16 B, 6 x 128 words of parked face entries behind them, to 256 B
+        const int32_t park = (maxLds + 15) / 16 * 16, need = (park + 6 * 128 * 4 + 255) / 256 * 256;
+        const int64_t limit = 64 * 1024;
+        const FusedLaunchPlan plain = planFusedLaunch(B, owned, limit, false), any = planFusedLaunch(B, owned, limit, true);
+        std::printf("    launch plan: %d B of LDS, %s\n", any.lds, plain.use ? "used" : any.use ? "used only when any blocks are" : "refused");
+        CHECK(need <= limit, "%s: %d B of LDS", tag, need);
+        CHECK(any.use && any.lds == need && any.ldsCell == park / 8, "%s: plan %d %d %d, %d %d wanted", tag, (int)any.use, any.lds, any.ldsCell, need, park / 8);
+        CHECK(plain.lds == any.lds && plain.ldsCell == any.ldsCell && plain.ldsImpl == any.ldsImpl && plain.ldsCellImpl == any.ldsCellImpl, "%s: the mode changes the sizes", tag);
+        const int32_t parkI = (maxLdsImpl + 15) / 16 * 16, needI = (parkI + 6 * 128 * 4 + 255) / 256 * 256;
+        CHECK(maxLdsImpl == B.maxLdsImpl && any.ldsImpl == (needI <= limit ? needI : 0) && any.ldsCellImpl == parkI / 8, "%s: implicit layout %d %d %d, %d %d wanted", tag,
+              B.maxLdsImpl, any.ldsImpl, any.ldsCellImpl, needI, parkI / 8);
+        CHECK(wantUse < 0 || plain.use == (wantUse == 1), "%s: plan says %d without being told to take any blocks", tag, (int)plain.use);
+        // one byte below the need: refused, whoever asks
+        CHECK(!planFusedLaunch(B, owned, need - 1, false).use && !planFusedLaunch(B, owned, need - 1, true).use, "%s: used with %d B of LDS allowed", tag, need - 1);
+        CHECK(planFusedLaunch(B, owned, need, true).use, "%s: refused with exactly %d B allowed", tag, need);
+        // a cap exceeded: refused in both modes
+        auto refused = [&](const FusedBlocks& X) { return !planFusedLaunch(X, owned, limit, false).use && !planFusedLaunch(X, owned, limit, true).use; };
+        FusedBlocks X = B;
+        CHECK(!refused(X), "%s: the copy is refused", tag);
+        X.maxAll = kFusedCapC + 1; CHECK(refused(X), "%s: maxAll over its cap", tag); X.maxAll = B.maxAll;
+        X.maxTot = kFusedCapTot + 1; CHECK(refused(X), "%s: maxTot over its cap", tag); X.maxTot = B.maxTot;
+        X.capV = kFusedCapV + 8; CHECK(refused(X), "%s: capV over its cap", tag); X.capV = B.capV;
+        X.capF = kFusedCapF + 8; CHECK(refused(X), "%s: capF over its cap", tag); X.capF = B.capF;
+        X.capPE = 256; CHECK(refused(X), "%s: capPE over 255", tag); X.capPE = B.capPE;
+        X.nBlocks = 0; CHECK(refused(X), "%s: no blocks", tag); X.nBlocks = B.nBlocks;
+        CHECK(!refused(X), "%s: the restored copy is refused", tag);
+    }
     return B;
 }
 
@@ -186,7 +221,7 @@ static FusedBlocks checkMesh(const char* tag, HostMesh& m, double minMeanCells =
 // that was just over; the two meet at f > 1 only, where faces share vertices and the blocks grow again.  The chains below have
 // 19 blocks against 16 + 17 slots.)
 static void checkSmallBlocks(const char* tag, HostMesh& m, bool inletOverwritten) {
-    const FusedBlocks B = checkMesh(tag, m);
+    const FusedBlocks B = checkMesh(tag, m, 0.0, -1, -1, 0);
     const int32_t nIF = m.nInternalFaces, nBF = m.nFaces - m.nInternalFaces;
     const int32_t faceBlocks = (nIF + 63) / 64, bfaceBlocks = (nBF + 255) / 256;
     std::printf("    %d blocks, %d face tiles, %d patch workgroups\n", B.nBlocks, faceBlocks, bfaceBlocks);
@@ -262,8 +297,8 @@ int main(int argc, char** argv) {
     if (argc > 1) return checkFiles(argc, argv);
     const double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
     const int32_t pt[6] = {0, 0, 0, 0, 0, 0};
-    { HostMesh m = makeBox(16, 8, 8, 0, 8, lo, hi, pt); checkMesh("box 16x8x8 (bricks)", m, 0.0, -1, 8); }
-    { HostMesh m = makeBox(13, 7, 5, 0, 5, lo, hi, pt); checkMesh("box 13x7x5 (ragged)", m, 0.0, -1, 5); }
+    { HostMesh m = makeBox(16, 8, 8, 0, 8, lo, hi, pt); checkMesh("box 16x8x8 (bricks)", m, 0.0, -1, 8, 1); }
+    { HostMesh m = makeBox(13, 7, 5, 0, 5, lo, hi, pt); checkMesh("box 13x7x5 (ragged)", m, 0.0, -1, 5, 1); }
     { HostMesh m = makeBox(3, 2, 2, 0, 2, lo, hi, pt); checkMesh("box 3x2x2", m, 0.0, -1, 1); }
     {
         HostMesh m = makeBox(11, 9, 7, 0, 7, lo, hi, pt);
@@ -275,8 +310,8 @@ int main(int argc, char** argv) {
     { HostMesh m = makeBox(12, 6, 12, 3, 9, lo, hi, pt); checkMesh("slab 3..9 of a 12x6x12 box (two cuts)", m, 0.0, -1, 3); }
     // what a cut must not cost: a 50-plane slab between two cuts keeps brick-shaped blocks -- 13 brick layers of 3 or 4
     // planes, 123 cells per block -- and the blocks of the planes a neighbour waits for are whole bricks, not flat one-plane ones
-    { HostMesh m = makeBox(80, 80, 150, 49, 101, lo, hi, pt); checkMesh("planes 50..100 of an 80x80x150 box (50 owned planes between two ghost planes)", m, 120.0, 2600 - 8 * 18 * 11 + 40, 730); }   // the 8 x 18 x 11 bricks without a patch face or a ghost plane share a handful of templates
-    { HostMesh m = makeBox(50, 50, 50, 0, 50, lo, hi, pt); checkMesh("box 50x50x50 (extents 8x4x4 bricks do not divide: 5x5x5 ones)", m, 120.0, 1000 - 8 * 8 * 8 + 1, 489); }   // 512 interior cubes, ONE template
+    { HostMesh m = makeBox(80, 80, 150, 49, 101, lo, hi, pt); checkMesh("planes 50..100 of an 80x80x150 box (50 owned planes between two ghost planes)", m, 120.0, 2600 - 8 * 18 * 11 + 40, 730, 1); }   // the 8 x 18 x 11 bricks without a patch face or a ghost plane share a handful of templates
+    { HostMesh m = makeBox(50, 50, 50, 0, 50, lo, hi, pt); checkMesh("box 50x50x50 (extents 8x4x4 bricks do not divide: 5x5x5 ones)", m, 120.0, 1000 - 8 * 8 * 8 + 1, 489, 1); }   // 512 interior cubes, ONE template
     {   // a jittered, Morton-renumbered mesh: no two blocks list their cells alike -> one template per block, the kernel's untemplated path
         HostMesh m = makeBox(24, 16, 16, 0, 16, lo, hi, pt);
         jitterPoints(m, 0.15, 7);
