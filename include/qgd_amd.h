@@ -302,7 +302,11 @@ int qgd_device_face_tiles(qgd_device_t d, int64_t info[4]);
  * block's face slots lie block-major too, as two 16-bit offsets and one byte per slot (only with bit 24; QGD_FUSED_PACKED_F=0: never) --
  * [4] counts those 5 bytes per face slot then.  What the packed tables hold, for tests and reports (0 where they were not built): bits 26..28
  * of [7] = the classes of hQGDf (1..4), bits 29..44 = the largest |offset| among the vertex-weight offsets (0..32768), bits 45..60 = the
- * largest |offset| among the face words, over w and hQGDf (0..32768). */
+ * largest |offset| among the face words, over w and hQGDf (0..32768).  Bit 61 of [7] = the geometry the blocks stage -- cell centres, vertex
+ * coordinates, V and hQGD of the own cells -- lies block-major too, as 16-bit dictionary codes and offsets (only with bit 25;
+ * QGD_FUSED_PACKED_G=0: never); [4] counts those 5 376 bytes per block then.  [6] holds the milliseconds in its low 32 bits; above them, for
+ * tests and reports: bits 32..36 = the largest dictionary of a block's axis (1..16), bits 40..51 = the largest 12-bit offset among the
+ * codes (0..4095). */
 int qgd_device_fused_blocks(qgd_device_t d, int64_t info[8]);
 
 /* qgdInterpolate / linearInterpolate [QGDInterpolate_8H_source.html L38-67]: face = w*(phi_O - phi_N) + phi_N, patch faces

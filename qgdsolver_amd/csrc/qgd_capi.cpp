@@ -960,8 +960,15 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                         FusedFaceView ff{};
                         ff.fuFW16 = up(fb.fW16); ff.fuFKC = up(fb.fKC); ff.fuFWRef = fb.fwRef;
                         for (int q = 0; q < 4; ++q) ff.fuFHRef[q] = fb.fhRef[q];
-                        std::vector<int64_t> raw(sizeof(FusedFaceView) / 8);   // (uploaded as plain words)
+                        // (the geometry's view directly behind it, where that packs too: FusedBlocks::gCode)
+                        FusedGeoView fg{};
+                        if (fb.packedG) {
+                            fg.fuGCode = up(fb.gCode); fg.fuGOwn = up(fb.gOwn); fg.fuGDict = up(fb.gDict); fg.fuGVRef = fb.gvRef; fg.fuGHRef = fb.ghRef;
+                            v.fuGeo = 1;
+                        }
+                        std::vector<int64_t> raw((sizeof(FusedFaceView) + sizeof(FusedGeoView)) / 8);   // (uploaded as plain words)
                         std::memcpy(raw.data(), &ff, sizeof ff);
+                        std::memcpy(raw.data() + sizeof ff / 8, &fg, sizeof fg);
                         v.fuFace = reinterpret_cast<const FusedFaceView*>(up(raw));
                     }
                     v.fuHdr = reinterpret_cast<const int4*>(up(fb.hdr)); v.fuCells = up(fb.cells); v.fuVerts = up(fb.verts);
@@ -969,12 +976,14 @@ static int deviceCreate(qgd_mesh_t mh, int deviceId, int fusedChoice, qgd_device
                     d->fusedInfo[0] = fb.nBlocks; d->fusedInfo[1] = fb.nLayerBlocks; d->fusedInfo[2] = fb.nTemplates; d->fusedInfo[3] = plan.lds;
                     // bytes a block streams per step out of its own lists / of its template's
                     d->fusedInfo[4] = 32 + 4 * (int64_t)fb.capC + 4 * (int64_t)fb.capV + 4 * (int64_t)fb.capF + fb.capV + 128 + (fb.packedW ? 2 : 8) * (int64_t)fb.capPE * fb.capV +
-                                      (fb.packedF ? 5 * (int64_t)fb.capF : 0);
+                                      (fb.packedF ? 5 * (int64_t)fb.capF : 0) + (fb.packedG ? 256 * 16 + 128 * 4 + 96 * 8 : 0);
                     d->fusedInfo[5] = 12 * (int64_t)fb.capF + 4 * (int64_t)fb.capE * 128 + 2 * (int64_t)fb.capPE * fb.capV;
-                    d->fusedInfo[6] = (int64_t)(fb.buildSeconds * 1e3);
+                    // (above the milliseconds' 32 bits: the largest geometry dictionary and the largest 12-bit offset, for tests and reports)
+                    d->fusedInfo[6] = std::min<int64_t>((int64_t)(fb.buildSeconds * 1e3), 0xffffffffLL) | (int64_t)(fb.maxGeoDict & 31) << 32 | (int64_t)(fb.maxGeoOffset & 4095) << 40;
                     // (the figures above bit 25 say what the packed tables hold, for tests and reports: nothing reads them to decide anything)
                     d->fusedInfo[7] = fb.brick[0] | fb.brick[1] << 8 | fb.brick[2] << 16 | (fb.packedW ? 1 << 24 : 0) | (fb.packedF ? 1 << 25 : 0) |
-                                      (int64_t)(fb.nHfClasses & 7) << 26 | (int64_t)(fb.maxWeightOffset & 0xffff) << 29 | (int64_t)(fb.maxFaceOffset & 0xffff) << 45;
+                                      (int64_t)(fb.nHfClasses & 7) << 26 | (int64_t)(fb.maxWeightOffset & 0xffff) << 29 | (int64_t)(fb.maxFaceOffset & 0xffff) << 45 |
+                                      (int64_t)(fb.packedG ? 1 : 0) << 61;
                 }
             }
         }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <functional>
 
@@ -22,6 +23,13 @@ struct FusedFaceView {
     const uint32_t* fuFW16; const uint8_t* fuFKC; int64_t fuFWRef; int64_t fuFHRef[4]; int64_t pad;
 };
 static_assert(sizeof(FusedFaceView) == 64, "read as one 64-byte scalar load");
+// The packed geometry of the fused step (qgd_setup.hpp FusedBlocks::gCode), where a mesh has it: a second 64-byte view directly BEHIND the
+// FusedFaceView in the same allocation (MeshView::fuFace + 1; MeshView::fuGeo says that it is there).  Per block 256 x 16 B of coordinate
+// codes, 128 words of the own cells' V | hQGD offsets, 96 dictionary patterns.
+struct FusedGeoView {
+    const uint16_t* fuGCode; const uint32_t* fuGOwn; const int64_t* fuGDict; int64_t fuGVRef, fuGHRef; int64_t pad[3];
+};
+static_assert(sizeof(FusedGeoView) == 64, "read as one 64-byte scalar load");
 
 // Static mesh data on the device; every face array is indexed by global face label.
 struct MeshView {
@@ -32,6 +40,9 @@ struct MeshView {
     int32_t fblock;          // face tile of the 3-D GaussVolPoint kernel: 64, 128 or 256 faces per workgroup
     int32_t hasOther;        // 1: some internal face has more than four vertices (FK_OTHER)
     int32_t xcdRun;          // tiles per XCD run of the workgroup->tile map (0: one contiguous eighth per XCD)
+    // host information, in the four bytes that were padding in front of the first pointer (the view does not grow, no member moves): 1 = a
+    // FusedGeoView stands behind *fuFace and the launchers take fusedFaceCellKernel<..., PACKW = 3>.  No kernel reads it.
+    int32_t fuGeo;
     const int32_t* own;      // nF
     const int32_t* nei;      // nIF
     const int4* verts;       // nF
@@ -99,6 +110,7 @@ struct MeshView {
     int64_t fuVWRef; const int16_t* fuVW16;
     const int4* fuHdr2; const uint8_t* fuVCount; const uint16_t* fuVPos; const double* fuVW;   // the vertex values are formed inside the block
 };
+static_assert(offsetof(MeshView, fuGeo) == 60 && offsetof(MeshView, own) == 64, "fuGeo fills padding: no member behind it moves");
 #if defined(__HIPCC__)
 // bits(w) = reference + offset: integer arithmetic on the pattern, the stored double comes back exactly
 __device__ __forceinline__ double fuWeightFromOffset(const int64_t ref, const int off) {

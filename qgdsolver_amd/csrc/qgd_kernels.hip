@@ -1048,6 +1048,12 @@ void cellUpdateKernel(const MeshView m, const CaseView c, const GasModel gm, con
 // masked block, where it would put a wait for the load between the loads of a round (no instruction is emitted)
 template <class T> __device__ __forceinline__ void fuPin(T& v) { asm volatile("" : "+v"(v)); }
 
+// the static LDS of a block's geometry dictionaries (fusedFaceCellKernel<..., PACKW = 3> alone names it, so that arm alone pays for it)
+template <int N> __device__ __forceinline__ long long* fuGeoDictLds() {
+    __shared__ long long dict[N];
+    return dict;
+}
+
 // 3 l + o as a shift and a three-operand add.  Written as a product the compiler takes the 64-bit multiply-add, whose addend is a register
 // pair with an unused upper half: whatever register that half lands on is waited for, and between the rounds of the fused kernel it lands
 // on a load still in flight.
@@ -1129,6 +1135,14 @@ __device__ __forceinline__ v2d fuRowMaxMin(v2d r) {
 // Their view (two table pointers, five reference patterns) is device memory behind ONE pointer of MeshView, which must not grow: 64 uniform
 // bytes, asked for through the scalar path with the header and waited for with it.  PACKW = 1 is the kernel as it was, instruction for
 // instruction.
+// PACKW = 3: the geometry too (MeshView::fuGeo; FusedGeoView behind the FusedFaceView; FusedBlocks::gCode / gOwn / gDict).  The centres of the
+// own + across-a-face cells, the vertex coordinates and V / hQGD of the own cells lie block-major as 16-bit codes in the kernel's own LDS slot
+// order: 16 B per thread (its four centre slots, its three vertex slots), one word per own cell, 96 dictionary patterns per block -- three
+// loads of the front-loaded group (vmcnt(24)) in place of the nine gathers by label of round 1 (m.Cc, m.X, m.V, m.hQGD) and of the three
+// loads of vertex labels in the list round.  The dictionaries go to 768 B of static LDS with the staging stores; the doubles of sC and sX
+// are formed between the two barriers of (1b), on all threads: dictionary[axis][code >> 12] + (code & 4095), a 64-bit integer sum taken as
+// a double -- the stored double exactly; V and hQGD in front of the staging barrier, reference + half word.  PACKW = 2 is the kernel as it
+// was, instruction for instruction.
 template <bool SGEO, bool UPW = false, bool IMPL = false, bool ADJ = false, int PACKW = 0>
 // (IMPL with `Gauss upwind` fluxes needs a few registers more than three waves per SIMD leave: that instantiation is compiled for two -- no scratch)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((IMPL && UPW) ? 2 : 3, (IMPL && UPW) ? 2 : 3)))
@@ -1169,7 +1183,10 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     typedef long long i64x8 __attribute__((ext_vector_type(8)));
     typedef const volatile i64x8 __attribute__((address_space(4)))* FaceViewPtr;
     i64x8 fv = {0, 0, 0, 0, 0, 0, 0, 0};
-    if constexpr (PACKW == 2) fv = *(FaceViewPtr)(uintptr_t)m.fuFace;
+    if constexpr (PACKW >= 2) fv = *(FaceViewPtr)(uintptr_t)m.fuFace;
+    // (PACKW == 3: the geometry's view, the 64 bytes behind it -- FusedGeoView: codes, own-cell words, dictionaries, the patterns of V and hQGD)
+    i64x8 gv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (PACKW == 3) gv = *(FaceViewPtr)((uintptr_t)m.fuFace + 64);
     __builtin_amdgcn_sched_barrier(0);
     // (0a) THE LISTS: everything whose address depends on no loaded value -- the piece labels out of the lists (padded to their strides with
     // their last entry, so no count is needed to read them), the labels of this thread's two faces, its vertex and its cell.
@@ -1199,8 +1216,10 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     }
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
-        const int q = tid + k * NT, r = (q * 43691) >> 17;
-        idV[k] = tVerts[min(r, capV - 1)];
+        if constexpr (PACKW != 3) {   // (PACKW == 3 gathers no coordinate by label: the list round is three loads shorter)
+            const int q = tid + k * NT, r = (q * 43691) >> 17;
+            idV[k] = tVerts[min(r, capV - 1)];
+        }
     }
     // this thread's vertex (thread v forms vertex v of the block's list; threads beyond the block's vertices repeat its last one)
     const int vt = min(tid, capV - 1);
@@ -1228,7 +1247,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     const int nOwn = hdr.x, nUc = hdr.y, nUv = hdr.z, nFc = hdr.w;
     const bool vertLane = tid < nUv;
     const size_t tpl = (size_t)hdr2.y;
-    constexpr int kFrontLoads = KF + KE + KP + (PACKW ? 1 : KP) + (PACKW == 2 ? 2 * KF : 0);
+    constexpr int kFrontLoads = KF + KE + KP + (PACKW ? 1 : KP) + (PACKW >= 2 ? 2 * KF : 0) + (PACKW == 3 ? 3 : 0);
     constexpr int kRsrcWord3 = 0x00020000;          // raw buffer, 32-bit data format
     constexpr int kBeyond = 0x40000000;             // an offset no table reaches (a descriptor spans one block's or one template's part)
     struct Pos3 { uint32_t c, va, vb; };
@@ -1245,7 +1264,12 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     int pcPos[KP];
     double pcW[KP];
     int wOff[4] = {0, 0, 0, 0};   // PACKW: the vertex's eight weights as loaded, 16-bit offsets from m.fuVWRef (the doubles are formed in (1b))
-    int fOff[KF] = {0, 0}, fKc[KF] = {0, 0};   // PACKW == 2: this thread's face slots as loaded -- the offsets of w | hQGDf << 16, and kind | class << 2
+    int fOff[KF] = {0, 0}, fKc[KF] = {0, 0};   // PACKW >= 2: this thread's face slots as loaded -- the offsets of w | hQGDf << 16, and kind | class << 2
+    // PACKW == 3: the geometry as loaded -- the codes of this thread's centre slots (two half words each in gC[0], gC[1]) and vertex slots
+    // (gC[2], the low half of gC[3]), the offsets of its own cell's V | hQGD << 16, and lane t's pattern of the block's dictionaries
+    constexpr int kGeoDict = 96;   // 2 sets x 3 axes x 16 entries
+    int gC[4] = {0, 0, 0, 0}, gW = 0;
+    long long gD = 0;
     {
         const __amdgpu_buffer_rsrc_t rFacePos = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(m.fuFacePos + tpl * capF * 3), 0, capF * 12, kRsrcWord3);
         const __amdgpu_buffer_rsrc_t rEntry = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(m.fuEntry + tpl * m.fuCapE * 128), 0, m.fuCapE * 128 * 4, kRsrcWord3);
@@ -1273,7 +1297,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
             for (int i = 0; i < KP; ++i)
                 pcW[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rVW, vertLane ? (min(i, capPE - 1) * capV + vt) * 8 : kBeyond, 0, 0));
         }
-        if constexpr (PACKW == 2) {
+        if constexpr (PACKW >= 2) {
             // the block's part of the face-slot tables: capF words, capF bytes
             const __amdgpu_buffer_rsrc_t rFW = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint32_t*>((uintptr_t)fv[0]) + (size_t)blk * capF, 0, capF * 4, kRsrcWord3);
             const __amdgpu_buffer_rsrc_t rFK = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t*>((uintptr_t)fv[1]) + (size_t)blk * capF, 0, capF, kRsrcWord3);
@@ -1288,6 +1312,17 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
                 fKc[j] = (int)__builtin_amdgcn_raw_buffer_load_b8(rFK, lf < nFc ? lf : kBeyond, 0, 0);
             }
         }
+        if constexpr (PACKW == 3) {
+            // the block's part of the geometry tables: 16 B of codes per thread (its four centre slots, its three vertex slots), a word per
+            // own cell, 96 dictionary patterns -- a lane that stages no slot, owns no cell, holds no pattern fetches nothing
+            const __amdgpu_buffer_rsrc_t rGC = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint16_t*>((uintptr_t)gv[0]) + (size_t)blk * (NT * 8), 0, NT * 16, kRsrcWord3);
+            const __amdgpu_buffer_rsrc_t rGO = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint32_t*>((uintptr_t)gv[1]) + (size_t)blk * 128, 0, 128 * 4, kRsrcWord3);
+            const __amdgpu_buffer_rsrc_t rGD = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<int64_t*>((uintptr_t)gv[2]) + (size_t)blk * kGeoDict, 0, kGeoDict * 8, kRsrcWord3);
+            const i32x4 o = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rGC, (tid < 3 * nUc || tid < 3 * nUv) ? tid * 16 : kBeyond, 0, 0));
+            gC[0] = o[0]; gC[1] = o[1]; gC[2] = o[2]; gC[3] = o[3];
+            gW = (int)__builtin_amdgcn_raw_buffer_load_b32(rGO, tid < 128 ? tid * 4 : kBeyond, 0, 0);
+            gD = __builtin_bit_cast(long long, __builtin_amdgcn_raw_buffer_load_b64(rGD, tid < kGeoDict ? tid * 8 : kBeyond, 0, 0));
+        }
     }
     // The round ends HERE for the lists, at once (the loads above went out back to back and return in issue order): the memory counter may
     // stay at the front-loaded group, which nothing needs before the records are staged.  Left to itself the compiler waits label by label.
@@ -1295,7 +1330,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     // wait behind the lists, no wait inside round 1 -- the two-word read of fuHdr2 and fuTimes3Plus answer register-allocation accidents of
     // one compiler version, and only the disassembly shows them.  Redo the ISA check of DESIGN.md section 5 after every ROCm change; a wait
     // that comes back costs speed, not correctness.)
-    static_assert(kFrontLoads == (PACKW == 2 ? 21 : PACKW ? 17 : 24), "the wait below is written for vmcnt(24), vmcnt(17) with packed weights, vmcnt(21) with packed face streams too");
+    static_assert(kFrontLoads == (PACKW == 3 ? 24 : PACKW == 2 ? 21 : PACKW ? 17 : 24), "the wait below is written for vmcnt(24), vmcnt(17) with packed weights, vmcnt(21) with packed face streams too, vmcnt(24) with packed geometry too");
     __builtin_amdgcn_sched_barrier(0);
     // vmcnt(kFrontLoads): its low four bits in bits 3:0, its high two in bits 15:14; expcnt and lgkmcnt left alone (0x4F78 for 24, 0x4F71 for 17, 0x4F75 for 21)
     __builtin_amdgcn_s_waitcnt(0x0F70 | (kFrontLoads & 15) | ((kFrontLoads >> 4) << 14));
@@ -1307,7 +1342,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
 #pragma unroll
     for (int k = 0; k < KB2; ++k) idB[k] = idB[k] * 2 + ((tid + k * NT) & 1);
 #pragma unroll
-    for (int k = 0; k < KV; ++k) { const int q = tid + k * NT, r = (q * 43691) >> 17; idV[k] = fuTimes3Plus(idV[k], q - 3 * r); }
+    for (int k = 0; k < KV; ++k) { if constexpr (PACKW != 3) { const int q = tid + k * NT, r = (q * 43691) >> 17; idV[k] = fuTimes3Plus(idV[k], q - 3 * r); } }
     const v2d* __restrict__ gA = reinterpret_cast<const v2d*>(c.A);
     const v2d* __restrict__ gB = reinterpret_cast<const v2d*>(c.B);
     const v2d* __restrict__ gP = reinterpret_cast<const v2d*>(c.P);
@@ -1325,7 +1360,9 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     }
 #pragma unroll
     for (int k = 0; k < KCC; ++k) {
-        if (wv0 + k * NT < 3 * nUc) { if (tid + k * NT < 3 * nUc) dC[k] = m.Cc[idC[k]]; }
+        if constexpr (PACKW != 3) {   // (PACKW == 3: the centres, the coordinates, V and hQGD came with the front-loaded group, as codes)
+            if (wv0 + k * NT < 3 * nUc) { if (tid + k * NT < 3 * nUc) dC[k] = m.Cc[idC[k]]; }
+        }
     }
 #pragma unroll
     for (int k = 0; k < KB2; ++k) {
@@ -1333,13 +1370,15 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     }
 #pragma unroll
     for (int k = 0; k < KV; ++k) {
-        if (wv0 + k * NT < 3 * nUv) { if (tid + k * NT < 3 * nUv) dX[k] = m.X[idV[k]]; }
+        if constexpr (PACKW != 3) {
+            if (wv0 + k * NT < 3 * nUv) { if (tid + k * NT < 3 * nUv) dX[k] = m.X[idV[k]]; }
+        }
     }
     double fw[KF], fh[KF];
     int fk[KF];
 #pragma unroll
     for (int j = 0; j < KF; ++j) {
-        if constexpr (PACKW != 2) {   // (PACKW == 2: they came with the front-loaded group, block-major)
+        if constexpr (PACKW < 2) {   // (PACKW >= 2: they came with the front-loaded group, block-major)
             if (wv0 + j * NT < nFc) {
                 if (tid + j * NT < nFc) { fw[j] = ldStream(m.w + fl[j]); fh[j] = ldStream(m.hf + fl[j]); fk[j] = m.fkind[fl[j]]; }
             }
@@ -1348,7 +1387,8 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     fuPin(ci);
     double rEold, Vc, hq, dt0;
     if (cellLane) {
-        rEold = c.rE[ci]; Vc = m.V[ci]; hq = m.hQGD[ci];
+        rEold = c.rE[ci];
+        if constexpr (PACKW != 3) { Vc = m.V[ci]; hq = m.hQGD[ci]; }
         if constexpr (!IMPL && !ADJ) dt0 = c.dt[0];
     }
     v2d dPt[3];
@@ -1381,11 +1421,18 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
         if (tid == 0) sMon[0] = mon;   // (behind the stores of dA, which was asked for later: no wait of its own)
     }
 #pragma unroll
-    for (int k = 0; k < KCC; ++k) { const int q = tid + k * NT; if (q < 3 * nUc) sC[q] = dC[k]; }
+    for (int k = 0; k < KCC; ++k) { if constexpr (PACKW != 3) { const int q = tid + k * NT; if (q < 3 * nUc) sC[q] = dC[k]; } }
 #pragma unroll
     for (int k = 0; k < KB2; ++k) { const int q = tid + k * NT; if (q < 2 * nUc) sB[q] = dB[k]; }
 #pragma unroll
-    for (int k = 0; k < KV; ++k) { const int q = tid + k * NT; if (q < 3 * nUv) sX[q] = dX[k]; }
+    for (int k = 0; k < KV; ++k) { if constexpr (PACKW != 3) { const int q = tid + k * NT; if (q < 3 * nUv) sX[q] = dX[k]; } }
+    if constexpr (PACKW == 3) {
+        // the block's dictionaries to LDS (sC and sX are written from them in (1b), behind the barrier); V and hQGD of the own cell out of
+        // its word: sign-extend the half word, add it to the mesh's reference pattern, take the sum as a double
+        fuPin(gD); fuPin(gW);
+        if (tid < kGeoDict) fuGeoDictLds<kGeoDict>()[tid] = gD;
+        if (cellLane) { Vc = fuWeightFromOffset(gv[3], (gW << 16) >> 16); hq = fuWeightFromOffset(gv[4], gW >> 16); }
+    }
     // deltaT / V of the own cell, the head of the update's dependent chain of divisions: both operands are here, so it is formed in front
     // of the barrier and not behind the last one (advanceCell's operands and operation: the same bits)
     double dtV = 0.0;
@@ -1404,9 +1451,27 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     }
 #pragma unroll
     for (int j = 0; j < KF; ++j) {
-        if constexpr (PACKW == 2) { fuPin(fOff[j]); fuPin(fKc[j]); }
+        if constexpr (PACKW >= 2) { fuPin(fOff[j]); fuPin(fKc[j]); }
         else fuPin(fk[j]);
         fuPin(fp[j].c); fuPin(fp[j].va); fuPin(fp[j].vb);
+    }
+    if constexpr (PACKW == 3) {
+        // the centres and the coordinates out of their codes, into the LDS places the staging stores fill on the other arms (the faces read
+        // them behind the next barrier): slot q = 3 * list position + axis is dictionary[axis][code >> 12] + (code & 4095), a 64-bit
+        // integer sum taken as a double -- the stored double exactly
+        const long long* const gDict = fuGeoDictLds<kGeoDict>();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) fuPin(gC[q]);
+#pragma unroll
+        for (int k = 0; k < KCC; ++k) {
+            const int q = tid + k * NT, a = q - 3 * ((q * 43691) >> 17), code = (gC[k >> 1] >> (16 * (k & 1))) & 0xffff;
+            if (q < 3 * nUc) sC[q] = __builtin_bit_cast(double, gDict[a * 16 + (code >> 12)] + (long long)(code & 4095));
+        }
+#pragma unroll
+        for (int k = 0; k < KV; ++k) {
+            const int q = tid + k * NT, a = q - 3 * ((q * 43691) >> 17), code = (gC[2 + (k >> 1)] >> (16 * (k & 1))) & 0xffff;
+            if (q < 3 * nUv) sX[q] = __builtin_bit_cast(double, gDict[48 + a * 16 + (code >> 12)] + (long long)(code & 4095));
+        }
     }
     // (1b) the vertex values [volPointInterpolation: inverse-distance weights over pointCells, in their order -- pointInterpRecKernel's
     // arithmetic, out of the staged cell records]
@@ -1458,7 +1523,7 @@ void fusedFaceCellKernel(const MeshView m, const CaseView c, const GasModel gm, 
     for (int j = 0; j < KF; ++j) {
         const int lf = tid + j * NT;
         if (lf < nFc) {
-            if constexpr (PACKW == 2) {
+            if constexpr (PACKW >= 2) {
                 // w, hQGDf and the kind out of the slot's word and byte: sign-extend the half word, add it to the reference pattern (w's, or
                 // the one of hQGDf's class), take the sum as a double
                 const int cls = fKc[j] >> 2;
@@ -2397,10 +2462,11 @@ static FusedXcdOrder fusedXcdOrder(int nBlocks, int run) {
     return {(nBlocks / span) * span, shift};
 }
 // one launch of fusedFaceCellKernel<SGEO, UPW, IMPL, ADJ, PACKW>: SGEO, UPW and PACKW (the view holds the vertex weights as 16-bit offsets,
-// MeshView::fuVW16: 1; the per-face streams too, fuFace: 2) are chosen here, IMPL and ADJ by the caller
+// MeshView::fuVW16: 1; the per-face streams too, fuFace: 2; the geometry too, fuGeo: 3) are chosen here, IMPL and ADJ by the caller
 #define QGD_FUSED_LAUNCH4(SG, UP, IM, AD, n, lds, ...)                                                                          \
     do {                                                                                                                        \
-        if (m.fuFace) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 2><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
+        if (m.fuFace && m.fuGeo) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 3><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
+        else if (m.fuFace) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 2><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
         else if (m.fuVW16) QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD, 1><<<n, 256, lds, L.stream>>>(__VA_ARGS__))); \
         else QGD_TIMED(L, QGD_K_FACE, (fusedFaceCellKernel<SG, UP, IM, AD><<<n, 256, lds, L.stream>>>(__VA_ARGS__)));            \
     } while (0)
@@ -2438,14 +2504,15 @@ void launchCellFinish(const Launcher& L, const MeshView& m, const CaseView& c, c
 // 64 KB a launch gets by default, so the kernels' limit is raised first; false when the device refuses (the caller keeps the separate kernels)
 template <bool SGEO, bool UPW>
 static bool fusedImplLimit(int lds, int packed) {
-    const void* k = packed == 2 ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 2>)
+    const void* k = packed == 3 ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 3>)
+                  : packed == 2 ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 2>)
                   : packed == 1 ? reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true, false, 1>) : reinterpret_cast<const void*>(&fusedFaceCellKernel<SGEO, UPW, true>);
     return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
 }
 bool fusedImplUPrepare(const MeshView& m, const GasModel& g) {
     if (m.fuBlocks <= 0 || m.fuLdsImpl <= 0) return false;
     const bool upw = g.upwindU || g.upwindH;
-    const int pk = m.fuFace ? 2 : m.fuVW16 ? 1 : 0;   // the level the launch will pick
+    const int pk = m.fuFace ? (m.fuGeo ? 3 : 2) : m.fuVW16 ? 1 : 0;   // the level the launch will pick
     const bool ok = m.sGeo ? (upw ? fusedImplLimit<true, true>(m.fuLdsImpl, pk) : fusedImplLimit<true, false>(m.fuLdsImpl, pk))
                            : (upw ? fusedImplLimit<false, true>(m.fuLdsImpl, pk) : fusedImplLimit<false, false>(m.fuLdsImpl, pk));
     if (!ok) (void)hipGetLastError();

@@ -922,6 +922,90 @@ bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s) {
     return true;
 }
 
+bool packFusedGeometry(FusedBlocks& B, const StaticData& s) {
+    auto drop = [&] {
+        B.packedG = 0; B.maxGeoDict = 0; B.maxGeoOffset = 0; B.gvRef = 0; B.ghRef = 0;
+        RawVec<uint16_t>().swap(B.gCode);
+        RawVec<uint32_t>().swap(B.gOwn);
+        RawVec<int64_t>().swap(B.gDict);
+        return false;
+    };
+    drop();
+    if (B.packedF != 1 || B.nBlocks <= 0 || B.capC <= 0 || B.capV <= 0) return false;
+    const int64_t nB = B.nBlocks;
+    const size_t capC = (size_t)B.capC, capV = (size_t)B.capV;
+    // V and hQGD of every own cell: one span each over the mesh
+    PatternSpan vSpan, hSpan;
+#pragma omp parallel for schedule(static) reduction(merge : vSpan) reduction(merge : hSpan)
+    for (int64_t b = 0; b < nB; ++b)
+        for (int32_t j = 0; j < B.hdr[4 * b]; ++j) {
+            const int32_t ci = B.cells[(size_t)b * capC + j];
+            vSpan.take(bitsOf(s.V[ci]));
+            hSpan.take(bitsOf(s.hQGD[ci]));
+        }
+    if (!vSpan.packs() || !hSpan.packs()) return false;
+    const int64_t vRef = vSpan.ref(), hRef = hSpan.ref();
+    B.gCode.resize((size_t)nB * 256 * 8);
+    B.gOwn.resize((size_t)nB * 128);
+    B.gDict.resize((size_t)nB * 96);
+    OffsetCheck check;          // the own cells' words
+    int64_t bad = 0;            // blocks that do not fit, codes that do not decode
+    int32_t maxDict = 0, maxOff = 0;
+#pragma omp parallel for schedule(static) reduction(merge : check) reduction(+ : bad) reduction(max : maxDict) reduction(max : maxOff)
+    for (int64_t b = 0; b < nB; ++b) {
+        uint16_t* code = &B.gCode[(size_t)b * 256 * 8];
+        uint32_t* own = &B.gOwn[(size_t)b * 128];
+        int64_t* dict = &B.gDict[(size_t)b * 96];
+        std::fill(code, code + 256 * 8, (uint16_t)0);
+        std::fill(own, own + 128, 0u);
+        std::fill(dict, dict + 96, (int64_t)0);
+        const int32_t nOwn = B.hdr[4 * b], nUc = B.hdr[4 * b + 1], nUv = B.hdr[4 * b + 2];
+        // (what the kernel's piece loads cover: four centre slots and three vertex slots per thread, one word per own-cell lane)
+        if (nOwn > 128 || 3 * nUc > 4 * 256 || 3 * nUv > 3 * 256) { ++bad; continue; }
+        for (int32_t j = 0; j < nOwn; ++j) {
+            const int32_t ci = B.cells[(size_t)b * capC + j];
+            own[j] = (uint32_t)(uint16_t)check.encode(bitsOf(s.V[ci]), vRef) | (uint32_t)(uint16_t)check.encode(bitsOf(s.hQGD[ci]), hRef) << 16;
+        }
+        std::vector<int64_t> sorted;
+        for (int set = 0; set < 2; ++set) {
+            const int32_t n = set == 0 ? nUc : nUv;
+            const int32_t* label = set == 0 ? &B.cells[(size_t)b * capC] : &B.verts[(size_t)b * capV];
+            const double* src = set == 0 ? s.Cc.data() : s.X.data();
+            for (int a = 0; a < 3; ++a) {
+                // the axis' dictionary: the sorted patterns cut greedily -- entry e starts at the smallest pattern beyond the 4 096 of entry e - 1
+                sorted.clear();
+                for (int32_t r = 0; r < n; ++r) sorted.push_back(bitsOf(src[3 * (size_t)label[r] + a]));
+                std::sort(sorted.begin(), sorted.end());
+                int64_t* d = dict + set * 48 + a * 16;
+                int nE = 0;
+                bool over = false;
+                for (const int64_t p : sorted) {
+                    if (nE != 0 && (uint64_t)p - (uint64_t)d[nE - 1] <= 4095) continue;
+                    if (nE == 16) { over = true; break; }
+                    d[nE++] = p;
+                }
+                if (over) { ++bad; continue; }
+                maxDict = std::max(maxDict, (int32_t)nE);
+                for (int32_t r = 0; r < n; ++r) {
+                    const int64_t p = bitsOf(src[3 * (size_t)label[r] + a]);
+                    const int e = (int)(std::upper_bound(d, d + nE, p) - d) - 1;
+                    const int64_t off = p - d[e];
+                    const uint16_t c = (uint16_t)(e << 12 | (int)(off & 4095));
+                    const int32_t q = 3 * r + a;
+                    code[(size_t)(q & 255) * 8 + set * 4 + (q >> 8)] = c;
+                    maxOff = std::max(maxOff, (int32_t)(c & 4095));
+                    // (decoded once as the kernel does it: the decode is the proof)
+                    bad += bitsOf(fusedCoordFromCode(d, c)) != p;
+                }
+            }
+        }
+    }
+    if (bad != 0 || check.bad != 0) return drop();
+    B.gvRef = vRef; B.ghRef = hRef; B.maxGeoDict = maxDict; B.maxGeoOffset = maxOff;
+    B.packedG = 1;
+    return true;
+}
+
 namespace {
 // ---- the builder's switches, read once ----
 struct BuilderOptions {
@@ -929,6 +1013,7 @@ struct BuilderOptions {
     bool templates = true;          // QGD_FUSED_TEMPLATES=0: one template per block
     bool packWeights = true;        // QGD_FUSED_PACKED_W=0: the vertex weights stay doubles
     bool packFaces = true;          // QGD_FUSED_PACKED_F=0: the face streams stay where they are (they pack only where the weights did)
+    bool packGeometry = true;       // QGD_FUSED_PACKED_G=0: centres, coordinates, V and hQGD stay where they are (they pack only where the face streams did)
 };
 // the counts of a full brick inside a lattice: own cells, + across a face, + around its edges and corners, vertices, internal faces
 struct BrickCounts { int64_t own, nAll, tot, nV, nF; };
@@ -955,6 +1040,7 @@ BuilderOptions readBuilderOptions() {
     opt.templates = !switchedOff("QGD_FUSED_TEMPLATES");
     opt.packWeights = !switchedOff("QGD_FUSED_PACKED_W");
     opt.packFaces = !switchedOff("QGD_FUSED_PACKED_F");
+    opt.packGeometry = !switchedOff("QGD_FUSED_PACKED_G");
     return opt;
 }
 
@@ -1517,6 +1603,7 @@ FusedBlocks buildFusedBlocks(const StaticData& s, bool keepFullWeights) {
     if (!mismatched.empty() && !ownTemplates(B, s, key, order, mismatched)) return FusedBlocks{};
     if (opt.packWeights && packFusedWeights(B) && !keepFullWeights) RawVec<double>().swap(B.vW);
     if (opt.packFaces) packFusedFaceStreams(B, s);
+    if (opt.packGeometry) packFusedGeometry(B, s);
     B.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tStart).count();
     return B;
 }

@@ -199,6 +199,22 @@ struct FusedBlocks {
     int64_t fwRef = 0, fhRef[4] = {0, 0, 0, 0};
     RawVec<uint32_t> fW16;    // capF per block
     RawVec<uint8_t> fKC;      // capF per block
+    // PACKED GEOMETRY (packFusedGeometry below; QGD_FUSED_PACKED_G=0: never; only where packedF == 1).  The centres of a block's own +
+    // across-a-face cells, the coordinates of its vertices and V / hQGD of its own cells are static too, and on a mesh whose blocks see few
+    // distinct coordinates per axis they carry little information.  Per block and per axis a dictionary of at most 16 reference patterns --
+    // one set for the centres, one for the vertices, cut greedily from the block's sorted patterns (entry e starts at the smallest pattern
+    // beyond the 4 096 of entry e - 1) -- and per coordinate one 16-bit code, entry << 12 | pattern - dictionary[entry]: bits = entry +
+    // offset gives the double back exactly.  The codes lie in the kernel's own LDS slot order (slot q = 3 * list position + axis): thread t
+    // of the 256 stages the centre slots t + 256 k (k < 4) and the vertex slots t + 256 k (k < 3), and its eight half words -- four centre
+    // codes, three vertex codes, one spare -- are one aligned 16-B piece.  V and hQGD of own cell j are the two signed 16-bit offsets of one
+    // word (low half from gvRef, high half from ghRef, the midpoint patterns of the mesh).  Slots beyond a block's counts are zero.
+    int32_t packedG = 0;      // 1: gCode / gOwn / gDict / gvRef / ghRef hold Cc, X, V and hQGD of everything the blocks stage
+    int32_t maxGeoDict = 0;   // the largest dictionary met, over blocks, sets and axes (1 .. 16; reporting only)
+    int32_t maxGeoOffset = 0; // the largest 12-bit offset in gCode (0 .. 4095; reporting only)
+    int64_t gvRef = 0, ghRef = 0;
+    RawVec<uint16_t> gCode;   // 8 x 256 per block: gCode[(blk * 256 + t) * 8 + k] centre slot t + 256 k, [.. + 4 + k] vertex slot t + 256 k
+    RawVec<uint32_t> gOwn;    // 128 per block
+    RawVec<int64_t> gDict;    // 96 per block: [set * 48 + axis * 16 + entry], set 0 = centres, 1 = vertices; unused entries 0
     RawVec<uint8_t> nEntry;   // 128 per block: face entries of each own cell
     RawVec<int32_t> entry;    // capE x 128 per template, entry-major: (local face << 1) | (1: the cell is the neighbour, minus), or ~label of a boundary face
     int32_t brick[3] = {0, 0, 0};  // the lattice brick the blocks were cut from (8 x 4 x 4 unless another shape fills the blocks better; 0: count-based runs)
@@ -231,6 +247,18 @@ bool packFusedWeights(FusedBlocks& B);
 // fhRef and sets packedF where s.w and s.hf of the computed face slots qualify (every slot decoded once and compared with s.w, s.hf and
 // s.fkind of its face), leaves them empty / 0 where they do not or where packedW != 1.  Returns packedF.
 bool packFusedFaceStreams(FusedBlocks& B, const StaticData& s);
+// The same for the geometry, on a block table whose nBlocks, capC, capV, hdr, cells, verts and packedF are filled: fills gCode / gOwn / gDict /
+// gvRef / ghRef and sets packedG where no block needs a 17th dictionary entry on an axis, every block's slots fit the kernel's piece loads
+// and V and hQGD of the own cells each span at most 65 535 patterns (every entry decoded once and compared with s.Cc, s.X, s.V and s.hQGD),
+// leaves them empty / 0 where not or where packedF != 1.  Returns packedG.
+bool packFusedGeometry(FusedBlocks& B, const StaticData& s);
+// a geometry code decoded as the kernel does it: dictionary entry + 12-bit offset, taken as a double
+inline double fusedCoordFromCode(const int64_t* dictAxis, uint16_t code) {
+    const int64_t bits = dictAxis[code >> 12] + (int64_t)(code & 4095);
+    double x;
+    std::memcpy(&x, &bits, 8);
+    return x;
+}
 // Whether the device uses a block table, and the dynamic LDS of its launches: the records of the block that needs most (maxLds / maxLdsImpl),
 // rounded to 16 B, then the parked face entries of the own cells, rounded to 256 B; ldsCell = where the parked entries start, in 8-B units.
 // The tables are refused when they are empty; when the blocks come out small -- under 88 cells on average: every block costs a workgroup

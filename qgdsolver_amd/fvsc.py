@@ -76,12 +76,15 @@ class Device:
         L.check(L.lib.qgd_device_fused_blocks(self._h, a), "qgd_device_fused_blocks")
         b = int(a[7])
         return dict(blocks=int(a[0]), layerBlocks=int(a[1]), templates=int(a[2]), ldsBytes=int(a[3]), blockListBytes=int(a[4]),
-                    templateBytes=int(a[5]), buildSeconds=a[6] / 1e3, brick=(b & 255, (b >> 8) & 255, (b >> 16) & 255),
+                    templateBytes=int(a[5]), buildSeconds=(int(a[6]) & 0xffffffff) / 1e3, brick=(b & 255, (b >> 8) & 255, (b >> 16) & 255),
                     packedWeights=bool((b >> 24) & 1),   # the vertex weights are 16-bit offsets from one pattern (QGD_FUSED_PACKED_W)
                     packedFaces=bool((b >> 25) & 1),     # w, hQGDf and kind of the face slots block-major, 5 B per slot (QGD_FUSED_PACKED_F)
                     # what the packed tables hold (0 where they were not built): classes of hQGDf, the largest |offset| of a vertex weight
                     # and of a face word (w and hQGDf), each 0 .. 32768
-                    hfClasses=(b >> 26) & 7, maxWeightOffset=(b >> 29) & 0xffff, maxFaceOffset=(b >> 45) & 0xffff)
+                    hfClasses=(b >> 26) & 7, maxWeightOffset=(b >> 29) & 0xffff, maxFaceOffset=(b >> 45) & 0xffff,
+                    # centres, vertex coordinates, V and hQGD block-major as dictionary codes / 16-bit offsets (QGD_FUSED_PACKED_G), the
+                    # largest dictionary of a block's axis (1 .. 16) and the largest 12-bit offset among the codes
+                    packedGeometry=bool((b >> 61) & 1), maxGeoDict=(int(a[6]) >> 32) & 31, maxGeoOffset=(int(a[6]) >> 40) & 4095)
 
     def face_tiles(self):
         """how the internal faces go through the 3-D GaussVolPoint flux kernel (qgd_device_face_tiles)"""

@@ -335,7 +335,8 @@ class QGDFoamCase:
         return dict(fused=int(a[0]) == 1, fusedImplicit=int(a[0]) == 2, fusedAdjust=int(a[0]) == 3, blocks=int(a[1]), facesComputed=int(a[2]), ldsBytes=int(a[3]), cellsStaged=int(a[4]),
                     cellsStagedFull=int(a[5]), verticesFormed=int(a[6]), layerBlocks=int(a[7]),
                     packedWeights=bool(a[1]) and self.dev.fused_blocks()["packedWeights"],
-                    packedFaces=bool(a[1]) and self.dev.fused_blocks()["packedFaces"])
+                    packedFaces=bool(a[1]) and self.dev.fused_blocks()["packedFaces"],
+                    packedGeometry=bool(a[1]) and self.dev.fused_blocks()["packedGeometry"])
 
     def implicit_info(self):
         """the four linear solves of the implicitDiffusion branch in the last step (qgd_case_implicit_info)"""

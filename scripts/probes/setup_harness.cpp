@@ -109,6 +109,9 @@ static void digestMesh(const std::string& spec) {
     digest("hdr", B.hdr); digest("hdr2", B.hdr2); digest("cells", B.cells); digest("verts", B.verts); digest("faceLabel", B.faceLabel);
     digest("facePos", B.facePos); digest("vCount", B.vCount); digest("vPos", B.vPos); digest("vW", B.vW); digest("vW16", B.vW16);
     digest("fW16", B.fW16); digest("fKC", B.fKC); digest("nEntry", B.nEntry); digest("entry", B.entry);
+    std::printf("  packedG %d maxGeoDict %d maxGeoOffset %d gvRef %016llx ghRef %016llx\n", B.packedG, B.maxGeoDict, B.maxGeoOffset, (unsigned long long)B.gvRef,
+                (unsigned long long)B.ghRef);
+    digest("gCode", B.gCode); digest("gOwn", B.gOwn); digest("gDict", B.gDict);
 }
 
 int main(int argc, char** argv) {
