@@ -259,8 +259,11 @@ static HostMesh readPrimitives(const char* path) {
 }
 
 static int checkFiles(int argc, char** argv) {
-    for (int a = 1; a + 3 < argc; a += 4) {
+    // per mesh: file, vertex stride capPE, least number of blocks, shards (0: the whole mesh), least and largest number of face entries of an own cell
+    CHECK((argc - 1) % 6 == 0, "%d arguments: six per mesh", argc - 1);
+    for (int a = 1; a + 5 < argc; a += 6) {
         const int wantPE = std::atoi(argv[a + 1]), minBlocks = std::atoi(argv[a + 2]), shardOf = std::atoi(argv[a + 3]);
+        const int wantMinE = std::atoi(argv[a + 4]), wantMaxE = std::atoi(argv[a + 5]);
         HostMesh m = readPrimitives(argv[a]);
         std::string tag = argv[a];
         if (shardOf > 0) {
@@ -286,7 +289,7 @@ static int checkFiles(int argc, char** argv) {
                 minE = std::min(minE, (int32_t)nE); maxE = std::max(maxE, (int32_t)nE);
             }
         std::printf("    face entries per own cell: %d .. %d (stride %d)\n", minE, maxE, B.capE);
-        CHECK(minE >= 4 && minE <= 5 && maxE <= 6, "%s: face entries per cell %d .. %d", tag.c_str(), minE, maxE);
+        CHECK(minE == wantMinE && maxE == wantMaxE, "%s: face entries per cell %d .. %d, %d .. %d wanted", tag.c_str(), minE, maxE, wantMinE, wantMaxE);
     }
     if (fails) { std::printf("%d checks failed\n", fails); return 1; }
     std::printf("ok\n");

@@ -5,8 +5,8 @@ blocks than 64-face tiles (the premise of tests/test_courant_small_blocks_gpu.py
 tables: a second build truncates the topology fingerprint to one bit (QGD_TEST_TOPOHASH_BITS, a macro the library's own build never
 defines), so that unlike blocks are certain to meet in one template unless the builder compares their tables.  Handed primitives files, the
 program runs the same checks on them: the tetrahedral / prismatic / mixed meshes of tests/unstructured.py, whose vertices have up to 24 cells
-(the vertex stride capPE is 24 / 12, not the 8 of every hexahedral mesh) and whose cells have 4 or 5 face entries, and a Morton-ordered shard
-of the 1728 tetrahedra."""
+(the vertex stride capPE is 24 / 12, not the 8 of every hexahedral mesh) and whose cells have 4 or 5 face entries, a Morton-ordered shard
+of the 1728 tetrahedra, and the 2:1 refined boxes ref533 / ref866, whose cells have 6 to 24 face entries (stride capE 24)."""
 import os
 import subprocess
 
@@ -52,11 +52,27 @@ def test_block_tables_of_tetrahedra_prisms_and_mixed_cells(tmp_path):
     tetrahedra, 12 on prisms and on the mix), the 1728 tetrahedra make many blocks, no block differs from its template, and the middle one of
     three Morton-ordered shards of the 1728 tetrahedra (more ghost cells than owned ones) passes the same checks"""
     args = []
-    for kind, cap_pe, min_blocks, shard_of in (("tet433", 24, 2, 0), ("tet866", 24, 2, 0), ("prism543", 12, 1, 0), ("mix643", 12, 1, 0),
-                                               ("tet866", 24, 2, 3)):
+    for kind, cap_pe, min_blocks, shard_of, least, most in (("tet433", 24, 2, 0, 4, 4), ("tet866", 24, 2, 0, 4, 4), ("prism543", 12, 1, 0, 5, 5),
+                                                            ("mix643", 12, 1, 0, 5, 6), ("tet866", 24, 2, 3, 4, 4)):
         path = str(tmp_path / f"{kind}.txt")
         unstructured.write_primitives(path, unstructured.primitives(kind))
-        args += [path, str(cap_pe), str(min_blocks), str(shard_of)]
+        args += [path, str(cap_pe), str(min_blocks), str(shard_of), str(least), str(most)]
     out = build_and_run(tmp_path, "fused_blocks_test_files", args=args)
     print(out)
     assert out.count(" cells, ") == 5 and "ghost cells for" in out
+
+
+def test_block_tables_of_refined_cells(tmp_path):
+    """the same checks on one level of 2:1 refinement: a coarse hexahedron between refined ones has 24 face entries beside the 6 of its
+    neighbours' children in one block, so the entry stride capE is 24 (6 on every other mesh here); the vertices stay within eight cells.
+    ref533, ref866 and the middle one of three Morton-ordered shards of ref866; no block differs from its template"""
+    args = []
+    for kind, min_blocks, shard_of in (("ref533", 1, 0), ("ref866", 2, 0), ("ref866", 2, 3)):
+        path = str(tmp_path / f"{kind}.txt")
+        unstructured.write_primitives(path, unstructured.refined_primitives(kind))
+        args += [path, "8", str(min_blocks), str(shard_of), "6", "24"]
+    out = build_and_run(tmp_path, "fused_blocks_test_files", args=args)
+    print(out)
+    assert out.count(" cells, ") == 3 and "ghost cells for" in out
+    assert out.count("face entries per own cell: 6 .. 24 (stride 24)") == 3
+    assert out.count(" 0 blocks matched a template by fingerprint and not by their tables") == 3

@@ -18,7 +18,8 @@ and every arm asserts that `packedGeometry` is what it expects and that the fuse
     QGD_FUSED_TEMPLATES=0        the template offset grows with the block; the geometry tables are per block either way
     IMPL on box(9,5,5)           to 1e-13 relative and with equal iteration counts, as tests/test_implicit_diffusion.py compares the assembly
     graded box                   20x8x8, the last cell twice as long as the first along x: V spans far more than 65 535 patterns -- not packed
-    c5_mesh(16, 8**3, poly), prism543   bit-identical whichever way the rule decides; the decision is printed
+    c5_mesh(16, 8**3, poly), prism543, ref533   bit-identical whichever way the rule decides; the decision is printed (ref533: one level of
+                                 2:1 refinement, cells of 6 to 24 face entries -- the template tail beyond the six entries kept in LDS)
     the wide recipes             tests/packed_geometry_recipes.py: codes that use the high offset bits and several dictionary entries
 """
 import contextlib
@@ -183,6 +184,14 @@ def test_uniform_prisms_whichever_way_the_rule_decides():
     b = blocks_of(mesh)
     print(f"prism543: the rule decides packed geometry {b['packedGeometry']}, faces {b['packedFaces']}, weights {b['packedWeights']}")
     ib = three_arms(mesh, "plain", "prism543", None)
+    assert ib["packedGeometry"] is b["packedGeometry"], (ib, b)
+
+
+def test_refined_cells_whichever_way_the_rule_decides():
+    mesh = make_mesh("ref533")
+    b = blocks_of(mesh)
+    print(f"ref533: the rule decides packed geometry {b['packedGeometry']}, faces {b['packedFaces']}, weights {b['packedWeights']}")
+    ib = three_arms(mesh, "plain", "ref533", None)
     assert ib["packedGeometry"] is b["packedGeometry"], (ib, b)
 
 

@@ -86,7 +86,9 @@ GPU_CASES = [("box654_jitter", "GaussVolPoint", mixed_bcs), ("box654_tri", "Gaus
 # tetrahedra and prisms (tests/unstructured.py): vertices of 24 / 12 cells -- the vertex walk of the IMPL instantiation beyond its eight register
 # slots -- and matrix rows of four and five off-diagonal entries under the Chebyshev iteration's eight-at-a-time row walk
 UNSTRUCTURED_CASES = [("tet433", "GaussVolPoint", mixed_bcs), ("prism543", "GaussVolPoint", mixed_bcs), ("tet866", "GaussVolPoint", mixed_bcs)]
-DELTA_T = {"tet433": 2e-4, "prism543": 2e-4, "tet866": 2e-4}
+# one level of 2:1 refinement: matrix rows of 6 to 24 off-diagonal entries in one slice of the ELL matrix, three passes of the cell kernels' walks
+UNSTRUCTURED_CASES += [("ref533", "GaussVolPoint", mixed_bcs)]
+DELTA_T = {"tet433": 2e-4, "prism543": 2e-4, "tet866": 2e-4, "ref533": 2e-4}
 
 
 def _implicit_arms(kind, stencil):
@@ -102,7 +104,7 @@ IMPLICIT_ARMS = [c + (a,) for c in GPU_CASES + UNSTRUCTURED_CASES for a in _impl
 
 
 def test_the_implicit_matrix_covers_the_block_fused_assembly():
-    assert [c[0] for c in IMPLICIT_ARMS if c[3] == "fused"] == ["box654_jitter", "box654_tri", "tet433", "prism543", "tet866"]
+    assert [c[0] for c in IMPLICIT_ARMS if c[3] == "fused"] == ["box654_jitter", "box654_tri", "tet433", "prism543", "tet866", "ref533"]
     assert sum(1 for c in IMPLICIT_ARMS if c[3] == "kernels") == len(GPU_CASES) + len(UNSTRUCTURED_CASES)
 
 

@@ -56,6 +56,7 @@ MESHES = {
     "polyhedra": lambda: c5_mesh(16, 8 ** 3, poly=True),
     "plain": lambda: q.PolyMesh.box(20, 14, 9),                                                      # 2520 -> 630 -> 157
     "tetrahedra": lambda: make_mesh("tet866"),                                                       # 1728 rows of <= 4 entries: 1728 -> 313 -> 22
+    "refined": lambda: make_mesh("ref533"),                                                          # 143 rows of 6 to 24 entries beside each other
 }
 # tag: (mesh, knobs, all-Neumann pressure without a reference cell)
 ROWS = {
@@ -83,8 +84,13 @@ ROWS = {
     # a graph no box of hexahedra has: four neighbours per cell at most, aggregates grown over 24 cells per vertex (tests/unstructured.py)
     "tetrahedra": ("tetrahedra", DEEP, False),
     "double tetrahedra": ("tetrahedra", dict(DEEP, QGD_MG_F32="0"), False),
+    # one level of 2:1 refinement (tests/unstructured.py): a coarse cell between refined ones has 24 neighbours, its children's cells six -- the
+    # row walks of the level-0 sweeps take three passes of eight on some lanes of a wavefront and one on the others
+    "refined": ("refined", DEEP, False),
+    "double refined": ("refined", dict(DEEP, QGD_MG_F32="0"), False),
 }
-FEW_LEVELS = {"singular": 1, "singular ragged": 1, "singular wide": 2, "singular polyhedra": 2, "double singular polyhedra": 2}
+FEW_LEVELS = {"singular": 1, "singular ragged": 1, "singular wide": 2, "singular polyhedra": 2, "double singular polyhedra": 2,
+              "refined": 2, "double refined": 2}           # 143 rows: one coarsening reaches the dense last level
 SWEEP_LOOP = {"singular ragged": "ell", "singular polyhedra": "csr", "double singular polyhedra": "csr"}     # else mgCoarseKernel
 DEFAULT_ROWS = ("hex", "hex ragged", "2d", "chain", "polyhedra")
 MG_KNOBS = ("QGD_MG_DIST", "QGD_MG_DENSE_MAX", "QGD_MG_PT_ELL_MIN", "QGD_MG_F32", "QGD_MG_CHEB", "QGD_MG_NU", "QGD_MG_NU0", "QGD_MG_SA", "QGD_MG_PASSES",

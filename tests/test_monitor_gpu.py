@@ -168,6 +168,7 @@ def test_one_nan_cell_is_counted_named_and_kept_out_of_the_extrema():
 # ---- 3. balance ------------------------------------------------------------------------------------------------------------------------
 BALANCE = [pytest.param(arm, adjust, None, id=f"{arm}-{adjust}") for arm, adjust in (("fused", 0), ("kernels", 0), ("kernels", 1), ("fusedAdjust", 1))]
 BALANCE += [pytest.param(arm, 0, kind, id=f"{arm}-0-{kind}") for kind in ("tet433", "prism543", "mix643") for arm in ("fused", "kernels")]
+BALANCE += [pytest.param(arm, 0, "ref533", id=f"{arm}-0-ref533") for arm in ("fused", "kernels")]      # 2:1 refined: cells of 6 to 24 faces
 
 
 @pytest.mark.parametrize("arm,adjust,kind", BALANCE)
@@ -230,7 +231,7 @@ def check_patches(s, case, mesh, patches, faces_of=None, what=""):
             sum_ok(s["patchPressureForce"][row, k], pb[f - nif] * Sf[f, k], tag + f" p Sf {k}")
 
 
-@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly", "box257_257_1", "tet433", "prism543", "mix643"])
+@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly", "box257_257_1", "tet433", "prism543", "mix643", "ref533"])
 def test_patch_totals_against_the_face_fields(kind):
     dims = {"box111": (1, 1, 1), "box20_17_3": (20, 17, 3), "box257_257_1": (257, 257, 1)}
     mesh = q.PolyMesh.box(*dims[kind]) if kind in dims else make_mesh(kind)

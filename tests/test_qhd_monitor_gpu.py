@@ -174,7 +174,7 @@ def test_layout_and_grid_cap():
 
 
 # ---- 2. against numpy on case.field() ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", ["box111", "box5_3_17", "box488", "box257_1_1", "box654_poly", "tet433", "prism543", "mix643", "box64_64_65"])
+@pytest.mark.parametrize("kind", ["box111", "box5_3_17", "box488", "box257_1_1", "box654_poly", "tet433", "prism543", "mix643", "box64_64_65", "ref533"])
 def test_integrals_extrema_and_probes_against_numpy(kind):
     dims = {"box111": (1, 1, 1), "box5_3_17": (5, 3, 17), "box488": (4, 8, 8), "box257_1_1": (257, 1, 1), "box64_64_65": (64, 64, 65)}
     mesh = make_mesh(kind) if kind not in dims else q.PolyMesh.box(*dims[kind])
@@ -276,7 +276,7 @@ def check_patches(s, case, mesh, patches, faces_of=None, what=""):
     return terms
 
 
-@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly", "box257_257_1", "tet433"])
+@pytest.mark.parametrize("kind", ["box111", "box20_17_3", "box654_poly", "box257_257_1", "tet433", "ref533"])
 def test_patch_totals_against_the_face_fields(kind):
     dims = {"box111": (1, 1, 1), "box20_17_3": (20, 17, 3), "box257_257_1": (257, 257, 1)}
     mesh = q.PolyMesh.box(*dims[kind]) if kind in dims else make_mesh(kind)

@@ -222,7 +222,8 @@ PARITY = [("line1d", "reduced", 1e-2, False), ("line1d", "GaussVolPoint", 1e-2, 
           ("plane2d_jitter", "GaussVolPoint", 1e-2, False), ("plane2d_jitter", "leastSquares", 1e-2, False),
           ("box654_jitter", "GaussVolPoint", 1e-2, False), ("box654_jitter", "reduced", 1e-2, False),
           ("box654_jitter", "GaussVolPoint", 0.0, False), ("plane2d_jitter", "GaussVolPoint", 1e-2, True),
-          ("tet433", "GaussVolPoint", 1e-2, False), ("mix643", "reduced", 1e-2, False), ("prism543", "GaussVolPoint", 1e-2, True)]
+          ("tet433", "GaussVolPoint", 1e-2, False), ("mix643", "reduced", 1e-2, False), ("prism543", "GaussVolPoint", 1e-2, True),
+          ("ref533", "GaussVolPoint", 1e-2, False), ("ref533", "reduced", 1e-2, True)]
 
 
 @pytest.mark.gpu

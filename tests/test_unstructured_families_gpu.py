@@ -15,7 +15,11 @@ it prints are collected for this file's one line per family, mesh and arm (pytes
 
 Bars: species 1e-12 (test_species_case_gpu), species implicit 1e-10 (test_species_implicit_case_gpu), sensor 1e-12 cSc1 and the muQGD
 identity 1e-14, states 1e-10 (test_var_sc_model_gpu), QHDFoam implicit 1e-9 with solves below 1e-13 (test_qhd_implicit), QHD shards 1e-8
-(test_qhd_sharded), implicit shards 1e-10 (test_implicit_sharded), symmetry and cyclic 1e-10 against the oracle, conservation 1e-13."""
+(test_qhd_sharded), implicit shards 1e-10 (test_implicit_sharded), symmetry and cyclic 1e-10 against the oracle, conservation 1e-13.
+
+The 2:1 refined boxes (unstructured.REFINED) have rows here too -- species, the varScModel7 sensor, QHDFoam with implicitDiffusion true, the
+range cuts of the iterative branches: what they bring is the other end of the per-cell walks, cells of 9 to 24 faces beside cells of 6
+(tests/test_refined_cells_gpu.py has the table of loops and rows)."""
 import functools
 import re
 
@@ -43,7 +47,7 @@ from test_partition import mixed_bcs
 from test_qhd_case import cavity_bcs, initial, options as qhd_options
 from test_qhd_implicit import TIGHT, run_oracle as run_qhd_oracle
 from test_species_case import flow_fields, smooth_composition
-from test_unstructured_gpu import EXPLICIT, VALENCE
+from test_unstructured_gpu import EXPLICIT, MOST_FACES, VALENCE
 from test_unstructured_meshes import PERIODIC_KINDS, PERIODIC_OPT, conservation_defect, periodic_fields, periodic_mesh
 from util import assert_path, make_mesh, oracle_mesh_of, param_rows, rel_err
 
@@ -58,7 +62,13 @@ def report(family, tag, worst, bar):
 
 def mesh_property(kind):
     """what makes the mesh worth running: vertices of 24 / 12 cells, cells of 4 / 5 / 5 + 6 faces, and on mix643 both face counts within
-    one slice of 64 cells -- prisms and hexahedra share the wavefronts of every one-lane-per-cell walk"""
+    one slice of 64 cells -- prisms and hexahedra share the wavefronts of every one-lane-per-cell walk.  The refined kinds: cells of 24
+    faces (three full passes of a loop that takes eight faces per pass), and at least three face counts within one slice of 64 cells"""
+    if kind in unstructured.REFINED:
+        per_cell = unstructured.faces_per_cell(unstructured.refined_primitives(kind))
+        assert int(per_cell.max()) == MOST_FACES[kind] == 24 and int(per_cell.min()) == 6
+        assert any(len(set(per_cell[i:i + 64])) >= 3 for i in range(0, per_cell.size, 64))
+        return
     prim = unstructured.primitives(kind)
     assert int(unstructured.point_valence(prim).max()) == VALENCE[kind] > 8
     per_cell = unstructured.faces_per_cell(prim)
@@ -106,7 +116,7 @@ def hexahedral_body(capsys, test_fn, *args):
 
 
 # ---- 1. species, explicit ----------------------------------------------------------------------------------------------------------------
-SPECIES_ROWS = [("tet433", "GaussVolPoint"), ("mix643", "GaussVolPoint"), ("prism543", "reduced")]
+SPECIES_ROWS = [("tet433", "GaussVolPoint"), ("mix643", "GaussVolPoint"), ("prism543", "reduced"), ("ref533", "GaussVolPoint")]
 SPECIES_OPT = dict(deltaT=1e-3, mu=1e-3)
 
 
@@ -120,10 +130,10 @@ def test_species_explicit_match_the_replay(kind, scheme, adjust, capsys):
     report("species explicit", (kind, scheme, "adjust", adjust, "kernels"), worst, sp.TOL)
 
 
-def test_species_batch_edge_on_tetrahedra():
-    """test_species_case_gpu.test_batch_edges with batchWidth + 1 transported species on tet433: the second register batch holds one species
-    and walks the same rows of 24"""
-    mesh_property("tet433")
+def species_batch_edge(kind):
+    """test_species_case_gpu.test_batch_edges with batchWidth + 1 transported species: the second register batch holds one species and walks
+    the same rows"""
+    mesh_property(kind)
     probe_dev = q.Device(q.PolyMesh.box(2, 2, 2), fused_tables=False)
     probe = q.QGDFoamCase(probe_dev, q.default_options())
     W = probe.species_info()["batchWidth"]
@@ -133,7 +143,7 @@ def test_species_batch_edge_on_tetrahedra():
     Sc = [0.5 + 0.25 * i for i in range(n_active + 1)]
     inlet = [0.4 / n_active] * (n_active + 1)
     inlet[inert] = 0.6
-    mesh, dev, gc, oc, rep = sp.build("tet433", "GaussVolPoint", None, flow_fields, SPECIES_OPT, sp.many_species(n_active, inert), inert, Sc, inlet, keep=True)
+    mesh, dev, gc, oc, rep = sp.build(kind, "GaussVolPoint", None, flow_fields, SPECIES_OPT, sp.many_species(n_active, inert), inert, Sc, inlet, keep=True)
     assert gc.species_info()["nSpecies"] == n_active + 1
     gc.step(1)
     rep.step(1)
@@ -145,8 +155,13 @@ def test_species_batch_edge_on_tetrahedra():
     worst.update({f"Y {i}": rel_err(gc.species_field(i, "Y"), rep.Y[i]) for i in range(rep.n)})
     assert min(float(y.min()) for y in rep.Y) > 0.0
     assert_path(gc, "kernels", "batch edge")
-    report("species explicit", ("tet433", "GaussVolPoint", f"{n_active} transported species", "kernels"), worst, sp.TOL)
+    report("species explicit", (kind, "GaussVolPoint", f"{n_active} transported species", "kernels"), worst, sp.TOL)
     gc.close(); dev.close()
+
+
+def test_species_batch_edge_on_tetrahedra():
+    """... on tet433: point rows of 24 cells"""
+    species_batch_edge("tet433")
 
 
 SPECIES_SHARDS = ("tet433", "GaussVolPoint", 3, 6)          # mesh, stencil, world, species (five transported: two register batches)
@@ -266,7 +281,7 @@ def test_species_implicit_match_the_replay(kind):
 
 
 # ---- 3. varScModel7 ---------------------------------------------------------------------------------------------------------------------------
-SENSOR_KINDS = ["tet433", "prism543", "mix643"]
+SENSOR_KINDS = ["tet433", "prism543", "mix643", "ref533"]
 SENSOR_PARAMS = param_rows(tv.test_sensor_matches_the_restatement_after_set_fields, "params")
 VAR_SC_RUNS = [(kind, arm) for kind in ("tet433", "mix643") for arm in ("fused", "kernels", "fusedAdjust", "implicitDiffusion")]
 
@@ -275,7 +290,7 @@ VAR_SC_RUNS = [(kind, arm) for kind in ("tet433", "mix643") for arm in ("fused",
 @pytest.mark.parametrize("kind", SENSOR_KINDS)
 def test_var_sc_sensor_matches_the_restatement(kind, params, capsys):
     """test_var_sc_model_gpu.test_sensor_matches_the_restatement_after_set_fields: varSc7Kernel, one lane per cell, eight face slots per pass
-    masked by cfCount = 4 / 5 / 6 and sumP / cnt with cnt = 4 or 5 (1e-12 cSc1; muQGD = p ScQGD tauQGD to 1e-14; sc_range() the extrema)"""
+    masked by cfCount = 4 / 5 / 6 and sumP / cnt with cnt = 4 or 5 -- on ref533 up to three passes, cnt up to 24 -- (1e-12 cSc1; muQGD = p ScQGD tauQGD to 1e-14; sc_range() the extrema)"""
     assert len(SENSOR_PARAMS) == 3
     mesh_property(kind)
     worst = hexahedral_body(capsys, tv.test_sensor_matches_the_restatement_after_set_fields, kind, "GaussVolPoint", params)
@@ -301,7 +316,7 @@ def test_var_sc_every_step_takes_the_restatement_of_its_pressures(kind, arm, cap
 
 
 # ---- 6. QHDFoam, implicitDiffusion true: the reference's default ----------------------------------------------------------------------------------
-QHD_IMPLICIT_ROWS = ["tet433", "mix643"]
+QHD_IMPLICIT_ROWS = ["tet433", "mix643", "ref533"]
 QHD_FIELDS = ("U", "T", "p", "phi", "U.boundary", "T.boundary", "p.boundary")
 
 
@@ -341,7 +356,7 @@ def test_qhd_implicit_branch_matches_oracle(kind):
 
 
 # ---- 7. shards of the iterative branches ----------------------------------------------------------------------------------------------------------
-SHARD_CUTS = [("tet433", 3), ("tet866", 2)]
+SHARD_CUTS = [("tet433", 3), ("tet866", 2), ("ref866", 2)]
 
 
 @pytest.mark.parametrize("kind,world", SHARD_CUTS)

@@ -4,7 +4,11 @@ tetrahedra per cube, 12 on two prisms per cube) and cells of four and five faces
 
 assemble() is the one polyhedra-to-polyMesh step: cells come as lists of vertex loops, faces are de-duplicated by their vertex set, oriented
 owner -> neighbour (outwards on the boundary) and put into OpenFOAM's order -- internal faces sorted by (owner, neighbour), owner < neighbour,
-then the boundary faces grouped by the six sides of the box (xMin, xMax, yMin, yMax, zMin, zMax: the patch order of PolyMesh.box)."""
+then the boundary faces grouped by the six sides of the box (xMin, xMax, yMin, yMax, zMin, zMax: the patch order of PolyMesh.box).
+
+REFINED / refined_primitives(): boxes of hexahedra with one level of 2:1 refinement, as refineMesh (hexRef8) leaves them -- a coarse cube between
+refined ones has 24 faces, an unsplit face next to a split edge 5 to 8 points of which three are collinear, a hanging vertex 5 or 6 cells.
+They go through the same assemble().  Not built here: more than one level, refined boxes whose opposite sides match (for cyclic patches)."""
 import functools
 import itertools
 
@@ -138,6 +142,127 @@ def primitives(kind, jitter=0.1):
         raise AssertionError(("an unmatched face inside the box", loop))
 
     return assemble(pts, lattice_cells(nx, ny, nz, shape_of), side_of)
+
+
+# ---- one level of 2:1 refinement, the way hexRef8 leaves a mesh ---------------------------------------------------------------------------
+# kind: (lattice, refined(i, j, k), quadtree).  The checkerboards enclose coarse cubes on every side: 24 faces (18 / 21 / 15 / 9 next to the
+# box and to the unrefined part), beside the 6 of their refined neighbours' children in the same 64 cells
+REFINED = {
+    "ref533": ((5, 3, 3), lambda i, j, k: i < 3 and (i + j + k) % 2 == 0, False),
+    "ref866": ((8, 6, 6), lambda i, j, k: i < 5 and (i + j + k) % 2 == 0, False),
+    "ref2d87": ((8, 7, 1), lambda i, j, k: i < 5 and (i + j) % 2 == 0, True),          # z empty, height 0.1: 2 x 2 x 1 children
+}
+REFINED_HEIGHT_2D = 0.1
+
+
+def refined_cells(nx, ny, nz, refined, quadtree=False):
+    """cells (lists of vertex loops) of the lattice with the cubes refined(i, j, k) names cut into 2 x 2 x 2 (quadtree: 2 x 2 x 1) hexahedra,
+    over points named by their doubled integer coordinates: (2 i, 2 j, 2 k) is a lattice point, an odd coordinate lies half way.  Cubes with
+    i fastest, the children of a cube (x fastest) in its place.  An unrefined cube lists the four (quadtree: two) quadrilaterals of a side whose
+    neighbour is refined, and on every other side one loop with the mid-edge point of each edge that a cube around that edge refines: the
+    hanging nodes"""
+    n = (nx, ny, nz)
+    halves = (2, 2, 1 if quadtree else 2)                                 # pieces per axis of a refined cube
+
+    def is_refined(c):
+        return all(0 <= c[a] < n[a] for a in range(3)) and bool(refined(*c))
+
+    def edge_is_split(p, q):
+        """p, q: lattice points (cube coordinates) one step apart along `axis`; the up to four cubes around the edge"""
+        axis = next(a for a in range(3) if p[a] != q[a])
+        if halves[axis] == 1:
+            return False
+        others = [a for a in range(3) if a != axis]
+        for da, db in itertools.product((-1, 0), repeat=2):
+            c = list(p)
+            c[others[0]] += da
+            c[others[1]] += db
+            if is_refined(c):
+                return True
+        return False
+
+    def hexahedron(lo, size):
+        """lo: doubled coordinates of the low corner; size: doubled extent per axis"""
+        corner = [tuple(lo[a] + size[a] * ((l >> a) & 1) for a in range(3)) for l in range(8)]
+        return [[corner[l] for l in loop] for loop in _HEX_FACES]
+
+    cells = []
+    for k, j, i in itertools.product(range(nz), range(ny), range(nx)):
+        cube = (i, j, k)
+        if is_refined(cube):
+            size = tuple(2 // h for h in halves)
+            for dz, dy, dx in itertools.product(range(halves[2]), range(halves[1]), range(halves[0])):
+                cells.append(hexahedron((2 * i + dx * size[0], 2 * j + dy * size[1], 2 * k + dz * size[2]), size))
+            continue
+        corner = [(i + (l & 1), j + ((l >> 1) & 1), k + (l >> 2)) for l in range(8)]
+        loops = []
+        for side, quad in enumerate(_HEX_FACES):
+            axis, beyond = side // 2, list(cube)
+            beyond[axis] += 1 if side % 2 else -1
+            if is_refined(beyond):                                        # the children's faces, as the neighbour lists them
+                u, v = [a for a in range(3) if a != axis]
+                plane = 2 * corner[quad[0]][axis]
+                for dv, du in itertools.product(range(halves[v]), range(halves[u])):
+                    su, sv = 2 // halves[u], 2 // halves[v]
+                    loop = []
+                    for a, b in ((0, 0), (1, 0), (1, 1), (0, 1)):
+                        key = [0, 0, 0]
+                        key[axis], key[u], key[v] = plane, 2 * cube[u] + (du + a) * su, 2 * cube[v] + (dv + b) * sv
+                        loop.append(tuple(key))
+                    loops.append(loop)
+                continue
+            loop = []
+            for s in range(4):
+                p, q = corner[quad[s]], corner[quad[(s + 1) % 4]]
+                loop.append(tuple(2 * x for x in p))
+                if edge_is_split(min(p, q), max(p, q)):
+                    loop.append(tuple(x + y for x, y in zip(p, q)))
+            loops.append(loop)
+        cells.append(loops)
+    return cells
+
+
+@functools.lru_cache(maxsize=None)
+def refined_primitives(kind, jitter=0.1):
+    """the named refined box as arrays (primitives()), with "midEdges": rows (hanging node, end, end) of point labels.  Only the lattice points
+    inside the box are jittered (quadtree: in the plane, alike on both z planes); a mid-edge, mid-face or mid-cell point is the mean of the
+    2, 4 or 8 lattice points around it, so a hanging node lies on the edge it hangs on"""
+    (nx, ny, nz), refined, quadtree = REFINED[kind]
+    seed = sum(map(ord, kind))
+    if quadtree:
+        assert nz == 1
+        plane, ij = lattice_points(nx, ny, 1, 0.0)
+        plane, ij = plane[: (nx + 1) * (ny + 1)], ij[: (nx + 1) * (ny + 1)]
+        inside = np.all((ij[:, :2] > 0) & (ij[:, :2] < (nx, ny)), axis=1)
+        move = np.random.default_rng(seed).uniform(-1.0, 1.0, (plane.shape[0], 2)) * (jitter / np.array([nx, ny]))
+        plane[inside, :2] += move[inside]
+        pts = np.concatenate([plane, plane + (0.0, 0.0, REFINED_HEIGHT_2D)])
+    else:
+        pts, _ = lattice_points(nx, ny, nz, jitter, seed=seed)
+    lattice = pts.reshape(nz + 1, ny + 1, nx + 1, 3)
+    cells = refined_cells(nx, ny, nz, refined, quadtree)
+    keys = sorted({key for loops in cells for loop in loops for key in loop}, key=lambda key: key[::-1])
+    label = {key: l for l, key in enumerate(keys)}
+    points = np.empty((len(keys), 3))
+    for key, l in label.items():
+        around = [lattice[c, b, a] for a, b, c in itertools.product(*[(x // 2,) if x % 2 == 0 else (x // 2, x // 2 + 1) for x in key])]
+        points[l] = sum(around[1:], around[0]) / len(around)
+    doubled, top = np.array(keys), 2 * np.array([nx, ny, nz])
+
+    def side_of(loop):
+        x = doubled[loop]
+        for axis in range(3):
+            if np.all(x[:, axis] == 0):
+                return 2 * axis
+            if np.all(x[:, axis] == top[axis]):
+                return 2 * axis + 1
+        raise AssertionError(("an unmatched face inside the box", loop))
+
+    prim = assemble(points, [[[label[key] for key in loop] for loop in loops] for loops in cells], side_of)
+    mids = [(key, axis) for key in keys for axis in range(3) if [x % 2 for x in key] == [int(a == axis) for a in range(3)]]
+    ends = [[tuple(x + s * (a == axis) for a, x in enumerate(key)) for s in (-1, 1)] for key, axis in mids]
+    prim["midEdges"] = np.array([[label[key], label[lo], label[hi]] for (key, _), (lo, hi) in zip(mids, ends)], dtype=np.int32).reshape(-1, 3)
+    return prim
 
 
 def point_valence(prim):

@@ -17,10 +17,10 @@ def rel_err(a, b):
 
 
 def make_mesh(kind, patch_types=None):
-    """Named test meshes.  Returns a PolyMesh.  patch_types (the unstructured kinds only): the types of the six sides instead of generic
-    patches, put on a copy of the cached primitives, which stay as they are"""
+    """Named test meshes.  Returns a PolyMesh.  patch_types (the unstructured and the refined kinds only): the types of the six sides instead
+    of generic patches, put on a copy of the cached primitives, which stay as they are"""
     G, E = L.PATCH_GENERIC, L.PATCH_EMPTY
-    if patch_types is not None and kind not in unstructured.KINDS:
+    if patch_types is not None and kind not in unstructured.KINDS and kind not in unstructured.REFINED:
         raise KeyError((kind, "patch_types belongs to the unstructured kinds"))
     if kind == "box654":
         return q.PolyMesh.box(6, 5, 4)
@@ -42,8 +42,12 @@ def make_mesh(kind, patch_types=None):
         return q.PolyMesh.forward_step(30, 10, 6, 2, lx=3.0, ly=1.0, lz=0.1)
     if kind == "box_sym":  # symmetryPlane on yMin: constraint patch for leastSquares / GaussVolPoint rules
         return q.PolyMesh.box(6, 5, 1, hi=(1.0, 1.0, 0.1), patch_types=[G, G, L.PATCH_SYMMETRYPLANE, G, E, E])
-    if kind in unstructured.KINDS:  # tetrahedra / prisms / prisms + hexahedra: point valence 24 / 12 / 12, cells of 4 / 5 / 5 + 6 faces
-        a = unstructured.primitives(kind)
+    if kind in unstructured.KINDS or kind in unstructured.REFINED:
+        # tetrahedra / prisms / prisms + hexahedra: point valence 24 / 12 / 12, cells of 4 / 5 / 5 + 6 faces; one level of 2:1 refinement:
+        # cells of 6 to 24 faces, faces with hanging nodes (the quadtree ref2d87: zMin and zMax empty unless patch_types says otherwise)
+        a = unstructured.primitives(kind) if kind in unstructured.KINDS else unstructured.refined_primitives(kind)
+        if patch_types is None and kind in unstructured.REFINED and unstructured.REFINED[kind][2]:
+            patch_types = [G, G, G, G, E, E]
         if patch_types is not None:
             a = dict(a, patchType=np.array(patch_types, dtype=np.int32))
             assert a["patchType"].shape == (6,)
