@@ -461,9 +461,9 @@ int qgd_qhd_case_set_bc(qgd_qhd_case_t c, int32_t patch, int32_t bcU, const doub
                         int32_t bcP, double valueP);
 int qgd_qhd_case_set_fields(qgd_qhd_case_t c, const double* U, const double* T, const double* p);
 int qgd_qhd_case_step(qgd_qhd_case_t c, int32_t nSteps);
-/* "U","T","p" (+ ".boundary"), face fields "phi","phiu","phiwo","tauQGDf", "faceTerms" (4 nF, after a step: see the QHD run monitor) */
+/* "U","T","p" (+ ".boundary"), face fields "phi","phiu","phiwo","tauQGDf","hQGDf", "faceTerms" (4 nF, after a step: see the QHD run monitor) */
 int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int64_t outDoubles);
-/* info[0]=time, [1]=deltaT, [2..4]= iterations / initial / final normalised residual of the last pressure solve,
+/* info[0]=time, [1]=deltaT in force, [2..4]= iterations / initial / final normalised residual of the last pressure solve,
  * [5]=steps, [6]=multigrid levels, [7]=milliseconds of the last pressure solve */
 int qgd_qhd_case_info(qgd_qhd_case_t c, double info[8]);
 /* QGD_QHD_FUSED=1 (off by default: at 8 M cells the one launch takes what the three kernels take, profiles/r06_ab_qhd_fused_advance.txt):
@@ -505,6 +505,37 @@ int qgd_qhd_case_srf_info(qgd_qhd_case_t c, double info[8]);
  * These three entries were added without a change of QGD_ABI_VERSION (it stays 9: no struct grew, no existing entry changed its
  * meaning). */
 int qgd_qhd_case_set_bc_values(qgd_qhd_case_t c, int32_t patch, const double* U, int64_t nFaces);
+
+/* ---- adjustTimeStep of QHDFoam and SRFQHDFoam ---------------------------------------------------------------------------------
+ * QHDFoam.C L104-106 / SRFQHDFoam.C L114-116: readTimeControls.H, QHDCourantNo.H, setDeltaT-QGDQHD.H between updateFluxes.H and
+ * runTime++.  With the control on, every qgd_qhd_case_step reduces on the device, after the fluxes of the step,
+ *   M = max_f |phiu_f| / (|Sf_f| hQGDf_f)    [QHDCourantNo.H L44-48: Cof = deltaT |Uf & Sf/|Sf|| / hQGDf; phiu = Sf & Uf]
+ * over every face that carries a field (internal and patch faces, not those of empty patches), and the host applies
+ *   CoNum = deltaT M;  f = maxCo/(CoNum + SMALL);  deltaTFact = min(min(f, 1 + 0.1 f), 1.2)           [setDeltaT-QGDQHD.H L41-50]
+ *   deltaT = min(deltaTFact deltaT, min(maxDeltaT, cTau min_f tauQGDf))                                 [L52-61]
+ * (SMALL = 1e-15; min tauQGDf over the same faces, reduced once per qgd_qhd_case_set_fields: thermo is not corrected in the loop).
+ * The pressure equation does not hold deltaT; the U and T equations of the step use the new one (Euler ddt; under implicitDiffusion
+ * the diagonals V/deltaT + ... are rebuilt when deltaT differs from the one they were built with).  The pair is read at the one wait
+ * a step has anyway (before the pressure solve): no further wait.  The start values of the solves (QGD_QHD_PEXTRAP,
+ * QGD_IMPL_XEXTRAP) take the Lagrange weights of the actual step lengths, by value, whenever the steps behind them are unequal
+ * (QGD_QHD_LAGRANGE=0: the equal-step weights whatever the steps); with equal steps the kernels and weights are those of a fixed deltaT,
+ * bit for bit.  They move iteration counts only.  The face weights (8 B per face) and min tauQGDf are formed when the controls or
+ * qgd_qhd_case_time_info are first asked for after qgd_qhd_case_set_fields: a case that never asks holds and launches nothing for them.
+ *
+ * qgd_qhd_case_set_time_control: any time between steps (readTimeControls.H is re-read on every pass), acts from the next step, and
+ * survives qgd_qhd_case_set_fields (which returns deltaT to the options').  adjustTimeStep = 0 restores the options' fixed deltaT.
+ * QGD_ERR_INVALID: maxCo, maxDeltaT or cTau non-finite or not positive (the listing's defaults: 1, GREAT, 0.75).
+ * QGD_ERR_NOT_IMPLEMENTED: a sharded device (the maximum would need a MAX all-reduce point in the phase table).  With the control on,
+ * qgd_qhd_case_step_phase and qgd_qhd_case_step_sharded return QGD_ERR_NOT_IMPLEMENTED: qgd_qhd_case_step alone serves it.
+ *
+ * qgd_qhd_case_time_info: info = {time, the deltaT in force (that of the last step, or after adjustTimeStep = 0 the options' again), CoNum the last step's control saw (deltaT before it x M), M of the last
+ * step, min tauQGDf, adjustTimeStep, steps, 0}.  With the control off CoNum and M are still reported (reduced when asked for, from the
+ * fluxes of the last step: a step of a case without the control launches nothing for it); both are 0 before the first step.
+ * qgd_qhd_case_info[1] and the QHD run monitor's deltaT report the deltaT in force; time accumulates the adjusted steps;
+ * qgd_qhd_case_get_field answers "hQGDf" (nF).  Added without a change of QGD_ABI_VERSION (it stays 9: no struct grew, no existing
+ * entry changed its meaning). */
+int qgd_qhd_case_set_time_control(qgd_qhd_case_t c, int32_t adjustTimeStep, double maxCo, double maxDeltaT, double cTau);
+int qgd_qhd_case_time_info(qgd_qhd_case_t c, double info[8]);
 
 /* ---- the QHD case on a cell-range shard (qgd_mesh_box slabs, qgd_mesh_shard) ------------------------------------------------
  * What the reference does through processor patches inside fvm::laplacian / PCG / fvc::grad under MPI

@@ -141,6 +141,8 @@ SIGNATURES = {
     "qgd_qhd_case_set_srf": (C.c_int, [handle, c_double_p, C.c_int32]),
     "qgd_qhd_case_srf_info": (C.c_int, [handle, c_double_p]),
     "qgd_qhd_case_set_bc_values": (C.c_int, [handle, C.c_int32, c_double_p, C.c_int64]),
+    "qgd_qhd_case_set_time_control": (C.c_int, [handle, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    "qgd_qhd_case_time_info": (C.c_int, [handle, c_double_p]),
     "qgd_qhd_case_implicit_control": (C.c_int, [handle, c_double_p, C.c_int]),
     "qgd_qhd_case_implicit_control_ptr": (C.c_int, [handle, handle_p]),
     "qgd_qhd_case_implicit_solve_status": (C.c_int, [handle, c_double_p]),

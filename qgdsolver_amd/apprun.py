@@ -127,14 +127,20 @@ def step_chunks(case, advance, t0, chunk, total, precision, report, write_time=N
 
 
 def run_qhd(app, solves, case_dir, n_steps, write, log, assemble, summary):
-    """The run of QHDFoam and SRFQHDFoam.  assemble(t0_name) -> (dev, case, opt, banner lines of its own, write_time(name));
-    summary(case) -> (name, values, text): the closing line of a step's report and the field whose finiteness the run depends on;
-    ``solves`` names the implicit solves in the note on their start values."""
+    """The run of QHDFoam and SRFQHDFoam.  assemble(t0_name) -> (dev, case, opt, banner lines of its own, write_time(name)[, the time
+    controls of foamfile.read_qhd_case_setup: without them the run has a fixed deltaT]); summary(case) -> (name, values, text): the closing line of a step's report and the field
+    whose finiteness the run depends on; ``solves`` names the implicit solves in the note on their start values.
+    adjustTimeStep yes [QHDFoam.C L104-106]: the case sets deltaT every step (QHDFoamCase.set_time_control), every step prints the
+    listing's three lines, the run ends with the first step at or beyond endTime, and writeControl must be timeStep."""
     cd = ff.read_dict(os.path.join(case_dir, "system", "controlDict"))
     t0, t0_name = find_start_time(case_dir, cd)
-    dev, case, opt, banner, write_time = assemble(t0_name)
+    dev, case, opt, banner, write_time, *tc = assemble(t0_name)
     mesh = case.mesh
-    dt, _, chunk, precision, total = run_control(cd, t0, n_steps)
+    tc = tc[0] if tc else {"adjustTimeStep": False}
+    adjust = bool(tc["adjustTimeStep"])
+    dt, end_time, chunk, precision, total = run_control(cd, t0, n_steps, adjust, ADJUST_REFUSAL, run_time=not adjust)
+    if adjust:
+        case.set_time_control(True, tc["maxCo"], tc["maxDeltaT"], tc["cTau"])
     branch = "implicitDiffusion true" if opt["implicitDiffusion"] else "implicitDiffusion false"
     log(f"{app} (qgdsolver_amd, {branch}): {mesh.nCells} cells, fvsc {opt['stencil']}, QGDCoeffs {opt['tauModel']}, deltaT {dt:g}, "
         f"start {t0_name}")
@@ -165,7 +171,16 @@ def run_qhd(app, solves, case_dir, n_steps, write, log, assemble, summary):
         if not np.isfinite(values).all():
             raise FloatingPointError(f"{name} is not finite at time {t:g}")
 
-    written = step_chunks(case, stepping(case.step, functions, t0), t0, chunk, total, precision, report, write_time if write else None)
+    def step_adjusted(n):
+        for _ in range(n):
+            case.step(1)
+            ti = case.time_info()
+            log(f"Courant Number = {ti['CoNum']:.6g}")                                      # QHDCourantNo.H L56
+            log(f"maxDeltaT1 = {min(tc['maxDeltaT'], tc['cTau'] * ti['minTau']):.6g}")       # setDeltaT-QGDQHD.H L46-49
+            log(f"deltaT = {ti['deltaT']:.6g}")                                             # L61
+
+    written = step_chunks(case, stepping(step_adjusted if adjust else case.step, functions, t0), t0, chunk, total, precision, report,
+                          write_time if write else None, end_time)
     if functions is not None:
         functions.finish()
     log("End")

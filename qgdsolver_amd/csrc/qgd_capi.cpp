@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2872,7 +2873,76 @@ struct qgd_qhd_case_s : CaseCore {   // (implSolver: the four systems {Ux, Uy, U
     std::vector<int32_t> bcPRequested;     // p kinds as the caller set them (a box slab's cut plane hides the patch's own kind)
     double lastIter = 0, lastRes0 = 0, lastRes = 0, lastSolveMs = 0;
     double* bValUDev = nullptr;            // qgd_qhd_case_set_bc_values: 3 per boundary face (view.bValU while some patch's valList names U)
+    // adjustTimeStep (qgd_qhd_case_set_time_control) [QHDCourantNo.H L37-57, setDeltaT-QGDQHD.H L41-61]: view.dt is the deltaT in force.
+    // rShf: 1/(|Sf| hQGDf) per face; red: {max |phiu| rShf, min tauQGDf} on the device, redHost its pinned copy, read at the step's one wait
+    bool adjust = false;
+    double maxCo = 1.0, maxDeltaT = 1e300, cTau = 0.75;
+    double *rShf = nullptr, *red = nullptr, *redHost = nullptr;
+    double minTau = 0, maxUh = 0, CoNum = 0;   // of the last step whose maximum was reduced (coSteps == steps: valid for the last step)
+    int64_t coSteps = -1;
+    double dtDiag = 0;                     // implicitDiffusion: the deltaT view.diag4 was built with
+    bool tcReady = false;                  // rShf and minTau stand for the fields of the last qgd_qhd_case_set_fields
+    std::vector<double> dtHist;            // deltaT of the completed steps, newest first (start values under unequal steps)
+    bool lagrange = true;                  // QGD_QHD_LAGRANGE (default 1; 0: the equal-step weights whatever the steps)
 };
+// Lagrange weights of the start value one step of length g0 ahead of the current field, through it and the k fields before it, which lie
+// dtHist[first], dtHist[first + 1], ... apart (a gap from before the first step counts as the oldest known one).  false: the steps are
+// equal -- the binomial weights of the kernels as they were, exactly -- or the case runs with QGD_QHD_LAGRANGE=0
+static bool qhdStartWeights(const qgd_qhd_case_s* c, double g0, size_t first, int k, QhdStartWeights& W) {
+    if (!c->lagrange || k < 1 || c->dtHist.empty()) return false;
+    double s[5] = {0, 0, 0, 0, 0};
+    bool equal = true;
+    for (int j = 1; j <= k; ++j) {
+        const double g = c->dtHist[std::min(first + (size_t)j - 1, c->dtHist.size() - 1)];
+        equal = equal && g == g0;
+        s[j] = s[j - 1] - g;
+    }
+    if (equal) return false;
+    W.k = k;
+    for (int i = 0; i < 5; ++i) {
+        double w = i <= k ? 1.0 : 0.0;
+        for (int j = 0; j <= k && i <= k; ++j) if (j != i) w *= (g0 - s[j]) / (s[i] - s[j]);
+        W.w[i] = w;
+    }
+    return true;
+}
+// rShf and min(tauQGDf) [setDeltaT-QGDQHD.H L52-55], formed when the time controls are first asked for after qgd_qhd_case_set_fields: a
+// case that never asks holds neither the 8 B per face nor launches anything for them
+static void qhdTimeControlReady(qgd_qhd_case_s* c) {
+    if (c->tcReady || !c->fieldsSet) return;
+    qgd_device_s* d = c->dev;
+    const MeshView& m = d->view;
+    HIP_CHECK(hipSetDevice(d->deviceId));
+    if (!c->rShf) { c->rShf = c->arena.alloc<double>(std::max<size_t>((size_t)m.nF, 1)); c->red = c->arena.alloc<double>(2); }
+    if (!c->redHost) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c->redHost), 2 * sizeof(double), hipHostMallocDefault));
+    double red0[2] = {0.0, std::numeric_limits<double>::infinity()};
+    (void)hipGetLastError();
+    HIP_CHECK(hipMemcpyAsync(c->red, red0, sizeof(red0), hipMemcpyHostToDevice, d->stream));
+    launchQhdTimeControlSetup(d->stream, m, c->tauF, c->rShf, c->red);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(red0, c->red, sizeof(red0), hipMemcpyDeviceToHost, d->stream));
+    HIP_CHECK(hipStreamSynchronize(d->stream));
+    c->minTau = red0[1];
+    c->tcReady = true;
+}
+// the step's maximum into redHost[0], stream-ordered: the caller waits for the stream before reading
+static void qhdCourantQueue(qgd_qhd_case_s* c) {
+    hipStream_t s = c->dev->stream;
+    HIP_CHECK(hipMemsetAsync(c->red, 0, sizeof(double), s));
+    launchQhdCourant(s, c->dev->view, c->view, c->rShf, c->red);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(c->redHost, c->red, sizeof(double), hipMemcpyDeviceToHost, s));
+}
+// setDeltaT-QGDQHD.H L41-61 on the maximum just read: the deltaT of the U and T equations of this step
+static void qhdSetDeltaT(qgd_qhd_case_s* c) {
+    double& dt = c->view.dt;
+    c->maxUh = std::max(c->redHost[0], 0.0);
+    c->CoNum = dt * c->maxUh;                                                     // QHDCourantNo.H L44-48
+    c->coSteps = c->steps + 1;
+    const double maxDeltaTFact = c->maxCo / (c->CoNum + 1e-15);
+    const double deltaTFact = std::min(std::min(maxDeltaTFact, 1.0 + 0.1 * maxDeltaTFact), 1.2);
+    dt = std::min(deltaTFact * dt, std::min(c->maxDeltaT, c->cTau * c->minTau));
+}
 
 int qgd_qhd_options_default(qgd_qhd_options* o) {
     if (!o) return fail(QGD_ERR_INVALID, "null argument");
@@ -2915,6 +2985,7 @@ int qgd_qhd_case_create(qgd_device_t d, const qgd_qhd_options* opt, qgd_qhd_case
         q.phiu = a.alloc<double>(nF); q.phiwo = a.alloc<double>(nF); q.phi = a.alloc<double>(nF); q.phitr = a.alloc<double>(nF);
         q.ugu = a.alloc<double>(3 * nF); q.gUc = a.alloc<double>(9 * nC); q.F = a.alloc<double>(4 * nF);
         c->scratch = a.alloc<double>(8);
+        c->lagrange = envOnOff("QGD_QHD_LAGRANGE", 1) != 0;
         q.implicit = opt->implicitDiffusion ? 1 : 0;
         q.upwindU = opt->fluxSchemeU == QGD_FLUX_UPWIND ? 1 : 0;
         q.upwindT = opt->fluxSchemeT == QGD_FLUX_UPWIND ? 1 : 0;
@@ -2953,6 +3024,7 @@ int qgd_qhd_case_free(qgd_qhd_case_t c) {
     if (!c) return QGD_OK;
     (void)hipSetDevice(c->dev->deviceId);
     if (c->solver) pressureSolverFree(c->solver);
+    if (c->redHost) (void)hipHostFree(c->redHost);
     return caseAbandon(c, QGD_OK);
 }
 // QhdView::bValU follows the patches' flags: without a list the kernels read nothing (nullptr) and keep their list-free instantiations
@@ -3049,12 +3121,16 @@ int qgd_qhd_case_set_fields(qgd_qhd_case_t c, const double* U, const double* T, 
     (void)hipGetLastError();
     HIP_CHECK(hipMemsetAsync(c->view.phiwo, 0, sizeof(double) * (size_t)m.nF, d->stream));
     launchQhdInit(d->stream, m, c->view, c->bcDev, dU, dT, dp, c->tauF, c->tbr);
-    if (c->view.implicit) {   // the matrix of the U and T equations: constant in time (thermo is not corrected in the loop, deltaT is fixed)
+    c->view.dt = c->opt.deltaT;   // (an adjusted run before this call may have left another)
+    if (c->view.implicit) {   // the matrix of the U and T equations: constant in time up to V/deltaT on the diagonals (thermo is not corrected in the loop)
         launchQhdImplicitMatrix(d->stream, m, c->view, c->bcDev);
+        c->dtDiag = c->view.dt;
         implicitStatsReset(c->implSolver);
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(d->stream));
+    c->tcReady = false; c->minTau = 0; c->maxUh = 0; c->CoNum = 0; c->coSteps = -1;
+    c->dtHist.clear();
     if (c->solver) { pressureSolverFree(c->solver); c->solver = nullptr; }
     c->solver = pressureSolverCreate(d->stream, m, c->tbr, c->bKind, c->localRefCell, c->opt.precond, d->ownedBegin, d->ownedEnd,
                                      d->cellGlobal.empty() ? nullptr : d->cellGlobal.data(), d->cellGlobalOffset, d->sharded());
@@ -3075,13 +3151,22 @@ static void qhdPhase(qgd_qhd_case_s* c, int phase) {
     switch (phase) {
         case 0:
             launchQhdAssemble(d->stream, c->stencil, c->usesPoints, m, c->view, c->bcDev);
-            if (c->pOrder > 0) { launchQhdExtrapolateP(d->stream, m.nC, c->view.p, c->pHist, c->pPrevHave, c->pOrder); c->pPrevHave = std::min(c->pPrevHave + 1, c->pOrder); }
+            if (c->pOrder > 0) {
+                // p of this solve belongs to the state the last step left: one step of the last deltaT ahead of the p before it
+                QhdStartWeights W;
+                const int k = std::min(c->pPrevHave, c->pOrder);
+                if (!c->dtHist.empty() && qhdStartWeights(c, c->dtHist[0], 1, k, W)) launchQhdExtrapolatePW(d->stream, m.nC, c->view.p, c->pHist, c->pOrder, W);
+                else launchQhdExtrapolateP(d->stream, m.nC, c->view.p, c->pHist, c->pPrevHave, c->pOrder);
+                c->pPrevHave = std::min(c->pPrevHave + 1, c->pOrder);
+            }
             pressureSolveBegin(c->solver, c->view.phiu, c->view.phiwo, c->view.pb, c->view.pgb, c->opt.pTol, c->opt.pRelTol, c->opt.pMaxIter, c->view.p);
             break;
         case 1: case 2: case 3: case 4: case 5: pressureSolvePhase(c->solver, phase); break;
         case 6: launchQhdPostSolve(d->stream, m, c->view, c->bcDev); break;
         case 7:
             pressureSolveFlux(c->solver, c->view.phi);
+            // (adjustTimeStep, or its end: the diagonals follow deltaT -- the dtDiag pattern of the scalar case)
+            if (c->view.implicit && c->view.dt != c->dtDiag) { launchQhdImplicitDiag(d->stream, m, c->view, c->bcDev); c->dtDiag = c->view.dt; }
             if (!c->view.implicit)
             {
                 if (launchQhdAdvance(d->stream, c->stencil, c->usesPoints, m, c->view, c->bcDev, c->needRef, c->localRefCell, c->opt.pRefValue,
@@ -3090,7 +3175,15 @@ static void qhdPhase(qgd_qhd_case_s* c, int phase) {
             } else {
                 // implicitDiffusion: face pass 2 without the laplacians, the right-hand sides; the solve (phases 10..15) and phase 16 follow
                 implicitStepMark(c->implSolver, true);
-                launchQhdImplicitAdvance(d->stream, c->stencil, c->usesPoints, m, c->view, c->bcDev, 0, c->implMask, false, -1, 0.0, nullptr);
+                {
+                    // the start values one step of the NEW deltaT ahead of the current fields; under unequal steps with the weights by value
+                    QhdStartWeights W;
+                    const bool byValue = c->view.xOrder > 0 && qhdStartWeights(c, c->view.dt, 0, std::min(c->view.xHave, c->view.xOrder), W);
+                    QhdView qv = c->view;
+                    if (byValue) qv.xOrder = 0;
+                    launchQhdImplicitAdvance(d->stream, c->stencil, c->usesPoints, m, qv, c->bcDev, 0, c->implMask, false, -1, 0.0, nullptr);
+                    if (byValue) launchQhdStartValuesW(d->stream, m, c->view, W);
+                }
                 if (c->view.xOrder > 0) {   // the right-hand-side kernel put the current fields into the oldest slot: it becomes the newest
                     QhdView& q = c->view;
                     double* t = q.xd[q.xOrder - 1];
@@ -3117,8 +3210,10 @@ static void qhdPhase(qgd_qhd_case_s* c, int phase) {
             break;
         case 8:
             launchQhdFinish(d->stream, m, c->view, c->needRef, pressureSolverCtl(c->solver) + 8);
-            c->time += c->opt.deltaT;
+            c->time += c->view.dt;   // (the options' deltaT, or the one the step's control set)
             c->steps++;
+            c->dtHist.insert(c->dtHist.begin(), c->view.dt);
+            if (c->dtHist.size() > 6) c->dtHist.pop_back();
             break;
         case 9: pressureSolveContinue(c->solver); break;   // after the collective qgd_qhd_case_pending asked for
         default: throw std::invalid_argument("qgd_qhd_case_step_phase: phase must be 0..9 (10..16: implicitDiffusion)");
@@ -3132,8 +3227,11 @@ static void qhdReadStatus(qgd_qhd_case_s* c) {
 }
 // a whole step with the transport behind `hooks` (nullptr: one rank); haloState(kind) exchanges message kind 0 or 1
 static void qhdStepWith(qgd_qhd_case_s* c, const SolveHooks* hooks, const std::function<void(int)>& haloState) {
+    if (c->adjust) qhdTimeControlReady(c);
     qhdPhase(c, 0);
+    if (c->adjust) qhdCourantQueue(c);                 // QHDCourantNo.H: after updateFluxes.H [QHDFoam.C L102-105]
     HIP_CHECK(hipStreamSynchronize(c->dev->stream));   // one wait per step, so that lastSolveMs is the solve alone
+    if (c->adjust) qhdSetDeltaT(c);                    // setDeltaT-QGDQHD.H [L106]; the pressure equation does not hold deltaT, phase 7 does
     const double t0 = nowMs();
     double res[2];
     c->lastIter = pressureSolveRun(c->solver, hooks, res);
@@ -3173,6 +3271,7 @@ int qgd_qhd_case_step_phase(qgd_qhd_case_t c, int phase) {
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_qhd_case_step_phase: call qgd_qhd_case_set_fields first");
     if (phase < 0 || phase > 16) return fail(QGD_ERR_INVALID, "qgd_qhd_case_step_phase: phase must be 0..9 (10..16: implicitDiffusion)");
+    if (c->adjust) return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_qhd_case_step_phase: adjustTimeStep (qgd_qhd_case_set_time_control) is served by qgd_qhd_case_step alone");
     HIP_CHECK(hipSetDevice(c->dev->deviceId));
     qhdPhase(c, phase);
     return QGD_OK;   // stream-ordered: qgd_qhd_case_solve_status / qgd_qhd_case_sync wait
@@ -3400,6 +3499,7 @@ int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int6
     else if (!bnd && s == "phiu") { direct = q.phiu; count = m.nF; }
     else if (!bnd && s == "phiwo") { direct = q.phiwo; count = m.nF; }
     else if (!bnd && s == "tauQGDf") { direct = c->tauF; count = m.nF; }
+    else if (!bnd && s == "hQGDf") { direct = m.hf; count = m.nF; }
     else if (!bnd && s == "faceTerms") {
         // QhdView::F by face label: the four net face terms of the U (3) and T equations, component-major (an internal face keeps its
         // terms at its slot-major position MeshView::fpos, a patch face at its label); under implicitDiffusion the explicit part
@@ -3434,10 +3534,46 @@ int qgd_qhd_case_get_field(qgd_qhd_case_t c, const char* name, double* out, int6
 int qgd_qhd_case_info(qgd_qhd_case_t c, double info[8]) {
     if (!c || !info) return fail(QGD_ERR_INVALID, "null argument");
     int sizes[16];
-    info[0] = c->time; info[1] = c->opt.deltaT; info[2] = c->lastIter; info[3] = c->lastRes0; info[4] = c->lastRes; info[5] = (double)c->steps;
+    info[0] = c->time; info[1] = c->view.dt; info[2] = c->lastIter; info[3] = c->lastRes0; info[4] = c->lastRes; info[5] = (double)c->steps;
     info[6] = c->solver ? (double)pressureSolverLevels(c->solver, sizes, 16) : 0.0;
     info[7] = c->lastSolveMs;
     return QGD_OK;
+}
+
+// readTimeControls.H: the controls of QHDCourantNo.H / setDeltaT-QGDQHD.H, from the next step on
+int qgd_qhd_case_set_time_control(qgd_qhd_case_t c, int32_t adjustTimeStep, double maxCo, double maxDeltaT, double cTau) {
+    QGD_TRY
+    if (!c) return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_time_control: null case");
+    if (c->dev->sharded())
+        return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_qhd_case_set_time_control: a sharded device is not served (the Courant number would need a MAX all-reduce "
+                                             "point in the phase table)");
+    if (!(std::isfinite(maxCo) && maxCo > 0) || !(std::isfinite(maxDeltaT) && maxDeltaT > 0) || !(std::isfinite(cTau) && cTau > 0))
+        return fail(QGD_ERR_INVALID, "qgd_qhd_case_set_time_control: maxCo, maxDeltaT, cTau must be finite and positive");
+    HIP_CHECK(hipSetDevice(c->dev->deviceId));
+    c->adjust = adjustTimeStep != 0;
+    c->maxCo = maxCo; c->maxDeltaT = maxDeltaT; c->cTau = cTau;
+    if (!c->adjust) c->view.dt = c->opt.deltaT;   // (the diagonals of implicitDiffusion follow at the next step: dtDiag)
+    return QGD_OK;
+    QGD_CATCH
+}
+int qgd_qhd_case_time_info(qgd_qhd_case_t c, double info[8]) {
+    QGD_TRY
+    if (!c || !info) return fail(QGD_ERR_INVALID, "qgd_qhd_case_time_info: null argument");
+    if (!c->dev->sharded()) qhdTimeControlReady(c);
+    if (c->fieldsSet && c->steps > 0 && c->coSteps != c->steps && !c->dev->sharded()) {
+        // no control at the last step: its fluxes still stand in phiu (what QHDFoam.C L88-92 prints under a fixed deltaT)
+        HIP_CHECK(hipSetDevice(c->dev->deviceId));
+        qhdCourantQueue(c);
+        HIP_CHECK(hipStreamSynchronize(c->dev->stream));
+        c->maxUh = std::max(c->redHost[0], 0.0);
+        c->CoNum = c->view.dt * c->maxUh;
+        c->coSteps = c->steps;
+    }
+    const bool have = c->coSteps == c->steps && c->steps > 0;
+    info[0] = c->time; info[1] = c->view.dt; info[2] = have ? c->CoNum : 0.0; info[3] = have ? c->maxUh : 0.0; info[4] = c->minTau;
+    info[5] = c->adjust ? 1.0 : 0.0; info[6] = (double)c->steps; info[7] = 0.0;
+    return QGD_OK;
+    QGD_CATCH
 }
 
 int qgd_qhd_case_fused_info(qgd_qhd_case_t c, int64_t info[4]) {
@@ -3797,6 +3933,7 @@ int qgd_qhd_case_step_sharded(qgd_qhd_case_t c, qgd_comm_t comm, const int32_t* 
     QGD_TRY
     if (!c) return fail(QGD_ERR_INVALID, "null case");
     if (!c->fieldsSet) return fail(QGD_ERR_INVALID, "qgd_qhd_case_step_sharded: call qgd_qhd_case_set_fields first");
+    if (c->adjust) return fail(QGD_ERR_NOT_IMPLEMENTED, "qgd_qhd_case_step_sharded: adjustTimeStep (qgd_qhd_case_set_time_control) is served by qgd_qhd_case_step alone");
     qgd_device_s* d = c->dev;
     const bool sharded = !d->halo.empty() && nSlots > 0;
     if (sharded && (!comm || !peers)) return fail(QGD_ERR_INVALID, "qgd_qhd_case_step_sharded: null argument");

@@ -466,7 +466,8 @@ struct QhdView {
     int32_t upwindU, upwindT;                  // qgd_qhd_options::fluxSchemeU / fluxSchemeT == QGD_FLUX_UPWIND
     // implicitDiffusion [QHDUEqn_8H L46-65, QHDTEqn_8H L69-80]: the four systems {Ux, Uy, Uz, T} share the face coefficients
     // aG = |Sf| delta_f (at the faces' slot-major positions) up to gamma = {nu, nu, nu, Hi}; the matrix does not change in time
-    // (thermo is not corrected inside the loop, deltaT is fixed): diag4 is built once, rhs4 / x4 every step (component-major, 4 * nC)
+    // (thermo is not corrected inside the loop) but for V/deltaT on the diagonals: diag4 is built once per deltaT (launchQhdImplicitDiag under
+    // adjustTimeStep), rhs4 / x4 every step (component-major, 4 * nC)
     int32_t implicit;
     double *aG, *diag4, *rhs4, *x4;
     // start values of the four systems (QGD_IMPL_XEXTRAP): the fields {U, T} of the last `xHave` steps before the current one, newest first
@@ -499,6 +500,18 @@ void launchQhdFinish(hipStream_t s, const MeshView& m, const QhdView& q, bool ne
 void launchQhdImplicitMatrix(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc);
 void launchQhdImplicitAdvance(hipStream_t s, int stencil, bool usesPoints, const MeshView& m, const QhdView& q, const PatchBCDev* bc, int part,
                               int validMask, bool needRef, int localRefCell, double refValue, double* shift);
+// start values under unequal steps (adjustTimeStep): Lagrange weights by value -- w[0] for the current field, w[j] for the field j steps
+// back, k fields back count.  launchQhdExtrapolatePW is launchQhdExtrapolateP with them; launchQhdStartValuesW forms the start values of the
+// four systems and moves their history, behind launchQhdImplicitAdvance(part 0) run on a view with xOrder = 0
+struct QhdStartWeights { double w[5]; int k; };
+void launchQhdExtrapolatePW(hipStream_t s, int nC, double* p, double* const hist[4], int order, const QhdStartWeights& W);
+void launchQhdStartValuesW(hipStream_t s, const MeshView& m, const QhdView& q, const QhdStartWeights& W);
+void launchQhdImplicitDiag(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc);   // diag4 for q.dt (adjustTimeStep)
+// adjustTimeStep [QHDCourantNo.H L37-57, setDeltaT-QGDQHD.H L41-61].  rShf (nF) = 1/(|Sf| hQGDf), 0 on the faces of empty patches; red (2
+// doubles, read as 64-bit integers by the atomics) = {max |phiu|/(|Sf| hQGDf), min tauQGDf} over the other faces.  Setup fills rShf and
+// red[1] (preset by the caller to +inf); launchQhdCourant folds into red[0] (preset to 0) from the phiu of the step's face pass 1
+void launchQhdTimeControlSetup(hipStream_t s, const MeshView& m, const double* tauF, double* rShf, double* red);
+void launchQhdCourant(hipStream_t s, const MeshView& m, const QhdView& q, const double* rShf, double* red);
 // halo messages of a sharded QHD case: kind 0 = state {U,T} (4 per cell, 4 per patch face), 1 = p + fvc::grad(U) (10 per cell, 2 per
 // patch face), 2 = the search direction of the pressure solve (1 per cell)
 void launchQhdHalo(hipStream_t s, const QhdView& q, double* direction, int kind, const int32_t* cells, int nCells, const int32_t* bfaces, int nFaces,

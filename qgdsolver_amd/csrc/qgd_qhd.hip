@@ -7,6 +7,7 @@
 //   QHDUEqn.H L36-84           gradPf, Wf, phiUf, fvc::laplacian, fvc::div(nu Sf & lin(T(grad U))), -grad(p)/rho + BdFrc
 //   QHDTEqn.H L65-91           phiTf, phiTauTReg, fvc::laplacian(Hif, T)               face pass 2 + cell update
 //   QHDFoam.C L123-130         reference level of p
+//   QHDFoam.C L104-106         adjustTimeStep: QHDCourantNo.H L37-57 as one face reduction after face pass 1, setDeltaT-QGDQHD.H L41-61 on the host
 //
 // SRFQHDFoam (SRFQHDFoam_8C_source.html L93-147; qgd_qhd_case_set_srf) is the same loop in a single rotating frame: the body force is
 // BdFrc = beta*T*g - 2 (omega ^ U) with U the relative velocity [SRFQHDFoam/updateFields.H L73-74], and QHDTEqn.H is not included, T stays
@@ -1009,7 +1010,54 @@ __global__ __launch_bounds__(QGD_BLOCK) void qhdExtractKernel(const int64_t n, c
     else out[i] = rec4[4 * i + 3];
 }
 
+// ---- adjustTimeStep [QHDCourantNo.H L37-57, setDeltaT-QGDQHD.H L41-61] ------------------------------------------------------------------
+// Cof = deltaT |Unf| / hQGDf with Unf = Uf & Sf/|Sf| = phiu/|Sf| [updateFluxes.H L33]: per face |phiu_f| r_f, r_f = 1/(|Sf| hQGDf) formed once
+// (0 on the faces of empty patches, which carry no field: the weight is the live-face mask as well).  deltaT multiplies the maximum on the host.
+__global__ __launch_bounds__(QGD_BLOCK) void qhdCourantWeightKernel(const MeshView m, double* __restrict__ rShf) {
+    const int f = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (f < m.nF) rShf[f] = m.fkind[f] == 3 ? 0.0 : 1.0 / (m.magSf[f] * m.hf[f]);
+}
+// One extremum over the live faces in one launch: MIN false: max |a_f| r_f (a = phiu); MIN true: min a_f (a = tauQGDf).  A lane walks the faces
+// with the grid's stride, four faces' loads in flight; lanes fold over the wavefront, the waves through LDS, and one lane per workgroup
+// folds into the slot with a 64-bit integer atomic: every value is a non-negative double (or +inf), whose bit patterns order as unsigned
+// integers.  The caller presets the slot (0, or +inf for MIN).  A NaN in a never loses a finite value (fmax / fmin drop it).
+template <bool MIN>
+__global__ __launch_bounds__(QGD_BLOCK) void qhdFaceExtremumKernel(const int nF, const double* __restrict__ a, const double* __restrict__ rShf,
+                                                                  unsigned long long* __restrict__ slot) {
+    __shared__ double sw[QGD_BLOCK / 64];
+    const double none = MIN ? __builtin_inf() : 0.0;
+    const int64_t stride = (int64_t)gridDim.x * QGD_BLOCK;
+    double x = none;
+    for (int64_t f0 = (int64_t)blockIdx.x * QGD_BLOCK + threadIdx.x; f0 < nF; f0 += 4 * stride) {
+        double va[4], vr[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t f = f0 + u * stride;
+            const bool on = f < nF;
+            va[u] = on ? ldStream(a + f) : 0.0;
+            vr[u] = on ? ldStream(rShf + f) : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (MIN) x = fmin(x, vr[u] != 0.0 ? va[u] : none);
+            else x = fmax(x, vr[u] != 0.0 ? fabs(va[u]) * vr[u] : 0.0);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = MIN ? fmin(x, __shfl_down(x, off, 64)) : fmax(x, __shfl_down(x, off, 64));
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 1; i < QGD_BLOCK / 64; ++i) x = MIN ? fmin(x, sw[i]) : fmax(x, sw[i]);
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
+        if (MIN) atomicMin(slot, bits); else atomicMax(slot, bits);
+    }
+}
+
 inline int gridOf(int64_t n) { return (int)((n + QGD_BLOCK - 1) / QGD_BLOCK); }
+// the grid of qhdFaceExtremumKernel: no more workgroups than the device holds at once (256 CUs x 8 of QGD_BLOCK), so at most 2048 atomics
+inline int extremumGrid(int64_t n) { return std::min(gridOf(std::max<int64_t>(n, 1)), 2048); }
 
 // 3-D GaussVolPoint with face tiles of 128 (MeshView::qhdTiles): the staged kernels take the internal faces, the generic ones the
 // tiles beyond the caps and the boundary faces
@@ -1116,6 +1164,58 @@ void launchQhdExtrapolateP(hipStream_t s, int nC, double* p, double* const hist[
     H.have = have; H.order = order;
     qhdExtrapolatePKernel<<<gridOf(nC), QGD_BLOCK, 0, s>>>(nC, p, H);
 }
+// ---- start values while deltaT moves (adjustTimeStep) ---------------------------------------------------------------------------------------
+// The polynomial in time through the current field and the last k ones, evaluated one step ahead, has the binomial weights of
+// qhdExtrapolated only when the steps between them are equal.  With unequal steps the host -- it knows every deltaT -- forms the Lagrange
+// weights and hands them over by value: w[0] for the current field, w[j] for the field j steps back (equal steps give 2, -1 / 3, -3, 1 /
+// ...: the host then launches the kernels above instead, so a run at a fixed deltaT keeps its bits).  Limited like the binomial form.
+__device__ __forceinline__ double qhdExtrapolatedW(const double cur, const double v[4], const QhdStartWeights& W) {
+    double e = (W.w[0] - 1.0) * cur;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (j < W.k) e += W.w[j + 1] * v[j];
+    const double lim = 2.0 * fabs(cur - v[0]);
+    return cur + fmin(fmax(e, -lim), lim);
+}
+// qhdExtrapolatePKernel with the weights by value (W.k = min(have, order) >= 1)
+__global__ __launch_bounds__(QGD_BLOCK) void qhdExtrapolatePWKernel(const int n, double* __restrict__ p, const TimeHistory H, const QhdStartWeights W) {
+    const int i = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double pn = p[i];
+    double v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (j < H.order && H.h[j]) ? H.h[j][i] : 0.0;
+    p[i] = qhdExtrapolatedW(pn, v, W);
+#pragma unroll
+    for (int j = 3; j >= 1; --j) if (j < H.order && H.h[j]) H.h[j][i] = v[j - 1];
+    if (H.order >= 1 && H.h[0]) H.h[0][i] = pn;
+}
+void launchQhdExtrapolatePW(hipStream_t s, int nC, double* p, double* const hist[4], int order, const QhdStartWeights& W) {
+    if (nC <= 0 || order <= 0) return;
+    TimeHistory H;
+    for (int j = 0; j < 4; ++j) H.h[j] = hist[j];
+    H.have = W.k; H.order = order;
+    qhdExtrapolatePWKernel<<<(nC + QGD_BLOCK - 1) / QGD_BLOCK, QGD_BLOCK, 0, s>>>(nC, p, H, W);
+}
+// the start values and the history step of qhdImplicitRhsKernel with the weights by value: launched BEHIND that kernel run on a view whose
+// xOrder is 0 (it then leaves x4 = the current fields and the history alone); q is the case's view (xOrder > 0, W.k = min(xHave, xOrder) >= 1)
+__global__ __launch_bounds__(QGD_BLOCK) void qhdStartValuesWKernel(const int nC, const QhdView q, const QhdStartWeights W) {
+    const int c = blockIdx.x * QGD_BLOCK + threadIdx.x;
+    if (c >= nC) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const size_t j = (size_t)k * nC + c;
+        const double cur = q.c4[(size_t)c * 4 + k];
+        double v[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = t < q.xOrder ? q.xd[t][j] : 0.0;
+        q.x4[j] = qhdExtrapolatedW(cur, v, W);
+        q.xd[q.xOrder - 1][j] = cur;   // the current fields into the oldest slot (the host rotates the pointers)
+    }
+}
+void launchQhdStartValuesW(hipStream_t s, const MeshView& m, const QhdView& q, const QhdStartWeights& W) {
+    if (m.nC <= 0 || q.xOrder <= 0 || W.k < 1) return;
+    qhdStartValuesWKernel<<<(m.nC + QGD_BLOCK - 1) / QGD_BLOCK, QGD_BLOCK, 0, s>>>(m.nC, q, W);
+}
 // after the solve: solve() ends in correctBoundaryConditions() (a shard then sends p and these patch values to its neighbours)
 void launchQhdPostSolve(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
     if (m.nBF) qhdPressureBcKernel<<<gridOf(m.nBF), QGD_BLOCK, 0, s>>>(m, q, bc);
@@ -1161,6 +1261,21 @@ bool launchQhdAdvance(hipStream_t s, int stencil, bool usesPoints, const MeshVie
 void launchQhdImplicitMatrix(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
     qhdImplicitFaceCoefKernel<<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, q);
     qhdImplicitDiagKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc);
+}
+// the diagonals alone, for a deltaT other than the one they were built with (adjustTimeStep): the face coefficients do not hold deltaT
+void launchQhdImplicitDiag(hipStream_t s, const MeshView& m, const QhdView& q, const PatchBCDev* bc) {
+    qhdImplicitDiagKernel<<<gridOf(m.nC), QGD_BLOCK, 0, s>>>(m, q, bc);
+}
+// set-up of the time-step control: the face weights r_f and red[1] = min(tauQGDf) over the live faces [setDeltaT-QGDQHD.H L52-55]
+void launchQhdTimeControlSetup(hipStream_t s, const MeshView& m, const double* tauF, double* rShf, double* red) {
+    if (m.nF <= 0) return;
+    qhdCourantWeightKernel<<<gridOf(m.nF), QGD_BLOCK, 0, s>>>(m, rShf);
+    qhdFaceExtremumKernel<true><<<extremumGrid(m.nF), QGD_BLOCK, 0, s>>>(m.nF, tauF, rShf, reinterpret_cast<unsigned long long*>(red + 1));
+}
+// red[0] = max |phiu_f| / (|Sf| hQGDf) over the live faces [QHDCourantNo.H L44-48 without deltaT]; the caller has zeroed red[0]
+void launchQhdCourant(hipStream_t s, const MeshView& m, const QhdView& q, const double* rShf, double* red) {
+    if (m.nF <= 0) return;
+    qhdFaceExtremumKernel<false><<<extremumGrid(m.nF), QGD_BLOCK, 0, s>>>(m.nF, q.phiu, rShf, reinterpret_cast<unsigned long long*>(red));
 }
 void launchQhdImplicitAdvance(hipStream_t s, int stencil, bool usesPoints, const MeshView& m, const QhdView& q, const PatchBCDev* bc, int part,
                               int validMask, bool needRef, int localRefCell, double refValue, double* shift) {

@@ -1155,11 +1155,14 @@ def read_run_control(cd):
             "writeControl": str(cd.get("writeControl", "timeStep")), "timePrecision": int(cd.get("timePrecision", 6))}
 
 
-def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
+def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None, time_control=False):
     """Read an OpenFOAM QHDFoam case directory [QHDFoam.C L63-72, QHDFoam/createFields.H L32-167].
     (velocity / velocity_bc: the name of the velocity file and the reading of its patch entries, for read_srf_case_setup.)
 
-    Returns (mesh, options dict for ``qhdfoam.qhd_options``, {'U','T','p'} internal arrays, per-patch BC triples).
+    Returns (mesh, options dict for ``qhdfoam.qhd_options``, {'U','T','p'} internal arrays, per-patch BC triples) and, with
+    ``time_control``, a fifth item: {adjustTimeStep, maxCo, maxDeltaT, cTau} of system/controlDict [readTimeControls.H;
+    setDeltaT-QGDQHD.H L45] with the defaults no, 1, GREAT, 0.75 -- for ``QHDFoamCase.set_time_control``.  Without ``time_control`` the
+    caller drives a fixed deltaT, and ``adjustTimeStep yes`` is refused.
     Entries read: constant/polyMesh; constant/thermophysicalProperties -- thermoType (equationOfState rhoConst, transport const),
     mixture.equationOfState.rho, mixture.transport.{mu, Pr, beta} [createFields.H L110-115], QGD{implicitDiffusion (default true,
     QGDThermo.C L70-82), QGDCoeffs constTau | HbyUQHD | T0byGr | H2bynuQHD with the keys of <model>Dict or of QGD itself
@@ -1203,8 +1206,13 @@ def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
     _check_fv_schemes(fs, mesh, need_laplacian=True, need_grad=True, what=fs_path)
     cd = read_dict(os.path.join(case_dir, "system", "controlDict"))
     opt["deltaT"] = float(cd["deltaT"])
-    if _truthy(cd.get("adjustTimeStep", "no")):
-        raise FoamFileError("adjustTimeStep yes: the QHDFoam path runs with the fixed deltaT of controlDict (its matrices are built once)")
+    adjust = _truthy(cd.get("adjustTimeStep", "no"))
+    if adjust and not time_control:
+        raise FoamFileError("adjustTimeStep yes: the QHDFoam path runs with the fixed deltaT of controlDict (its matrices are built once) "
+                            "unless the caller asks for the time controls (time_control=True) and hands them to QHDFoamCase.set_time_control")
+    # runTime.controlDict().lookupOrDefault [readTimeControls.H, L0]: maxCo 1, maxDeltaT GREAT; cTau 0.75 [setDeltaT-QGDQHD.H L45]
+    tc = {"adjustTimeStep": bool(adjust), "maxCo": float(cd.get("maxCo", 1.0)), "maxDeltaT": float(cd.get("maxDeltaT", 1e300)),
+          "cTau": float(cd.get("cTau", 0.75))}
     solvers = _fv_solvers(case_dir)
     for entry in _solver_entries(solvers, ("p",)):      # (the last entry that names p wins, key by key)
         opt["pTol"], opt["pMaxIter"] = _tol_iter(entry)
@@ -1218,7 +1226,8 @@ def read_qhd_case_setup(case_dir, time="0", velocity="U", velocity_bc=None):
     T, bT = read_field(os.path.join(tdir, "T"), mesh)
     p, bP = read_field(os.path.join(tdir, "p"), mesh)
     bcs = _qhd_patch_bcs(mesh, bU, bT, "QHDFoam", velocity, velocity_bc, bP)
-    return mesh, opt, {"U": U, "T": T[:, 0], "p": p[:, 0]}, bcs
+    out = (mesh, opt, {"U": U, "T": T[:, 0], "p": p[:, 0]}, bcs)
+    return out + (tc,) if time_control else out
 
 
 def read_scalar_case_setup(case_dir, time="0"):
@@ -1319,11 +1328,12 @@ def load_qhd_case(case_dir, time="0", device_id=0):
     return assemble_qhd_case(*read_qhd_case_setup(case_dir, time), device_id)
 
 
-def read_srf_case_setup(case_dir, time="0"):
+def read_srf_case_setup(case_dir, time="0", time_control=False):
     """Read an OpenFOAM SRFQHDFoam case directory [SRFQHDFoam.C L70-81, SRFQHDFoam/createFields.H L22-39]: what read_qhd_case_setup reads,
     with the relative velocity ``Urel`` in place of ``U``, and constant/SRFProperties.
 
-    Returns (mesh, options dict, {'U' (= Urel),'T','p'}, per-patch BC triples, srf) with srf = {'omega', 'origin', 'axis', 'rpm'}.
+    Returns (mesh, options dict, {'U' (= Urel),'T','p'}, per-patch BC triples, srf) with srf = {'omega', 'origin', 'axis', 'rpm'} and,
+    with ``time_control``, the time controls of read_qhd_case_setup as a sixth item (without it ``adjustTimeStep yes`` is refused).
     SRFProperties: ``SRFModel rpm; origin (x y z); axis (x y z); rpmCoeffs { rpm N; }`` and omega = axis/|axis| * rpm * 2 pi / 60.
     ASSUMPTION (L0): a restatement of OpenFOAM v2312's SRF::SRFModel (origin, axis normalised on reading) and SRF::rpm
     (omega = axis * rpm * twoPi / 60); their sources are not among the reference's listings.
@@ -1387,8 +1397,8 @@ def read_srf_case_setup(case_dir, time="0"):
         i = names.index(what.split(".", 1)[1])
         return ("fixedValue", iv[None, :] - np.cross(omega, Cf[start[i]: start[i] + size[i]] - origin))
 
-    mesh, opt, fields, bcs = read_qhd_case_setup(case_dir, time, velocity="Urel", velocity_bc=urel_bc)
-    return mesh, opt, fields, bcs, dict(omega=omega, origin=origin, axis=axis / np.linalg.norm(axis), rpm=rpm)
+    mesh, opt, fields, bcs, *tc = read_qhd_case_setup(case_dir, time, velocity="Urel", velocity_bc=urel_bc, time_control=time_control)
+    return (mesh, opt, fields, bcs, dict(omega=omega, origin=origin, axis=axis / np.linalg.norm(axis), rpm=rpm)) + tuple(tc)
 
 
 def apply_qhd_bcs(case, bcs):

@@ -148,6 +148,7 @@ def pEqn(dev, phiu, phiwo, taubyrhof, p, patch_kinds, pb=None, gradb=None, toler
 
 
 # ---- QHDFoam case resident on the device ------------------------------------------------------------------------------
+GREAT = 1e300   # the default of maxDeltaT [createTimeControls.H, L0], as foamfile reads it for the other solvers
 TAU_MODELS = {"constTau": 0, "HbyUQHD": 1, "T0byGr": 2, "H2bynuQHD": 3}
 _BC = {"zeroGradient": L.BC_ZEROGRADIENT, "fixedValue": L.BC_FIXEDVALUE, "slip": L.BC_SLIP, "fixedGradient": L.BC_QGDFLUX,
        "qhdFlux": L.BC_QGDFLUX, "qhdFluxCoupled": L.BC_QHDFLUX, "none": L.BC_NONE}
@@ -218,6 +219,20 @@ class QHDFoamCase:
     def step(self, n=1):
         L.check(L.lib.qgd_qhd_case_step(self._h, int(n)), "qgd_qhd_case_step")
 
+    # ---- adjustTimeStep [QHDCourantNo.H L37-57, setDeltaT-QGDQHD.H L41-61] (include/qgd_amd.h) ----
+    def set_time_control(self, adjust=True, max_co=1.0, max_delta_t=GREAT, c_tau=0.75):
+        """readTimeControls.H: from the next step on, every step sets deltaT by the Courant number of its fluxes (adjust=False: the fixed
+        deltaT of the options again).  Any time between steps; not on a sharded device, not with step_phase."""
+        L.check(L.lib.qgd_qhd_case_set_time_control(self._h, 1 if adjust else 0, float(max_co), float(max_delta_t), float(c_tau)),
+                "qgd_qhd_case_set_time_control")
+
+    def time_info(self):
+        """time, the deltaT in force, the Courant number its control saw (deltaT before it x maxUnfByH), maxUnfByH = max |Unf|/hQGDf
+        of the last step's fluxes, min tauQGDf, whether the control is on, steps"""
+        a = (C.c_double * 8)()
+        L.check(L.lib.qgd_qhd_case_time_info(self._h, a), "qgd_qhd_case_time_info")
+        return dict(time=a[0], deltaT=a[1], CoNum=a[2], maxUnfByH=a[3], minTau=a[4], adjustTimeStep=bool(a[5]), steps=int(a[6]))
+
     def field(self, name):
         if name == "faceTerms":   # the four net face terms of the U (3) and T equations by face label, after a step: (4, nFaces)
             out = np.zeros((4, self.mesh.nFaces))
@@ -225,7 +240,7 @@ class QHDFoamCase:
             return out
         base = name[:-len(".boundary")] if name.endswith(".boundary") else name
         nc = 3 if base == "U" else 1
-        n = self.mesh.nBoundaryFaces if name.endswith(".boundary") else (self.mesh.nFaces if base in ("phi", "phiu", "phiwo", "tauQGDf")
+        n = self.mesh.nBoundaryFaces if name.endswith(".boundary") else (self.mesh.nFaces if base in ("phi", "phiu", "phiwo", "tauQGDf", "hQGDf")
                                                                          else self.mesh.nCells)
         out = np.zeros((n, nc) if nc > 1 else (n,))
         if n:
